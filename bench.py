@@ -1,7 +1,16 @@
 #!/usr/bin/env python
 """Headline benchmark: Mpixels/s of the fused grain -> 33^3 LUT -> colour match -> unsharp chain at 4K.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          # N=1: plain python; N>1: launched by torchrun
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]     # N=1: plain python; N>1: launched by torchrun
+
+A plain run sets up, warms up, times the K steps of the headline leg, writes its outputs when --dump-outputs is given, and prints
+the line.  Everything else described below -- the output check, the fast colour-match policy, the timing of the reference-frame
+statistics alone, the live PMC passes, the `configs` legs, the device-resident graph leg, the host-fed rates, the CPU baseline, the
+fp64 statistics leg at N > 1 and the shader-clock sampling -- runs only with --full (the --no-* options still switch parts of it off).
+
+`--dump-outputs DIR` writes what the timed steps left in rank 0's output batch after the last step, as float32 .npy files (~22 MB in
+all): `output_sample` = the elements at a fixed, seeded set of 2^22 flat indices of the whole batch, `output_first_rows` /
+`output_last_rows` = the first / last 64 rows of the first / last frame.  Inputs are seeded, so equal arguments give equal inputs.
 
 Workload (BASELINE.json metric / configs[4] per-GPU shard): every rank holds `--frames` (default 256) synthetic
 4K fp32 RGB frames resident in HBM (generated on device, never touched by the host), chain = Fast Film Grain
@@ -30,6 +39,7 @@ timed next to it and reported under `fast_variant`, never as `value`.
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -78,11 +88,17 @@ def parse_args():
                                                               "workload only)")
     ap.add_argument("--no-fp64-leg", action="store_true", help="N > 1: skip the second headline leg with the fp64 statistics policy (the one whose reference-frame "
                                                                "statistics cross the RCCL all-reduce inside the timed steps)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also run every check and measurement beyond the headline figure (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write rank 0's output of the last timed step to DIR/<name>.npy (float32)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def self_launch(args):
-    """`python bench.py --gpus N` outside torchrun: become `torch.distributed.run --nproc-per-node N bench.py ...`."""
+    """`python bench.py --gpus N` outside torchrun: run `torch.distributed.run --nproc-per-node N bench.py ...` as a child process and exit
+    with its status (a child, not exec: this process has already opened the GPU to count the devices)."""
     if args.gpus <= 1 or "WORLD_SIZE" in os.environ:
         return
     n_vis = torch.cuda.device_count()
@@ -99,7 +115,9 @@ def self_launch(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execvpe(sys.executable, cmd, env)
+    import subprocess
+    rc = subprocess.run(cmd, env=env).returncode
+    raise SystemExit(128 - rc if rc < 0 else rc)        # killed by signal s: the shell's status 128 + s (SIGABRT 134, SIGSEGV 139)
 
 
 def make_frames(n, H, W, dev, seed, dist, first_frame=None):
@@ -339,6 +357,24 @@ def output_digests(out, chunk):
     return [hashlib.sha256(out[f:f + chunk].cpu().numpy().tobytes()).hexdigest() for f in range(0, out.shape[0], chunk)]
 
 
+DUMP_SAMPLE = 1 << 22           # elements of the seeded sample (16 MB in fp32): a 4K batch is far over the 64 MB a dump may hold
+DUMP_ROWS = 64
+
+
+def dump_outputs(out, dump_dir):
+    """--dump-outputs: a fixed, seeded sample of the elements of the whole batch `out` (the indices depend on its size only) and the first /
+    last DUMP_ROWS rows of its first / last frame, as float32 .npy files."""
+    import numpy as np
+    os.makedirs(dump_dir, exist_ok=True)
+    flat = out.view(-1)
+    if flat.numel() > DUMP_SAMPLE:
+        idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(20261016)).sort().values
+        flat = flat[idx.to(out.device)]
+    arrays = {"output_sample": flat, "output_first_rows": out[0, :DUMP_ROWS], "output_last_rows": out[-1, -DUMP_ROWS:]}
+    for name, a in arrays.items():
+        np.save(os.path.join(dump_dir, name + ".npy"), a.to(torch.float32).cpu().numpy())
+
+
 class Ctx:
     """What every leg needs: the package modules, the rank geometry, the LUT."""
     pass
@@ -436,9 +472,10 @@ ALGO_BPP = {"stats": 12, "apply": 24, "tstats": 12}         # SURVEY.md section 
 
 
 def run_workload(C, args, workload, pixel_dist, frames, steps, warmup, *, cm_stats=None, verify=True, digest=False, fast_variant=False,
-                 time_reference_stats=False, cube_name=None):
+                 time_reference_stats=False, cube_name=None, dump_dir=None):
     """One leg: `frames` synthetic frames of `workload` resident in HBM on every rank, `warmup` untimed + `steps` timed steps bracketed
-    by barrier + synchronize, MAX over ranks.  Returns the measurements and frees its buffers."""
+    by barrier + synchronize, MAX over ranks; the shader clock is sampled during them with --full.  Returns the measurements and frees
+    its buffers."""
     ops, sharding, dist = C.ops, C.sharding, C.dist
     rank, world, dev = C.rank, C.world, C.dev
     H, W, stages = WORKLOADS[workload]
@@ -501,13 +538,14 @@ def run_workload(C, args, workload, pixel_dist, frames, steps, warmup, *, cm_sta
             step(**kw)
         barrier()
         ev = []
-        with ClockSampler() as cs:
+        cs = ClockSampler() if args.full else None
+        with cs or contextlib.nullcontext():
             t0 = time.perf_counter()
             for _ in range(steps):
                 step(ev, **kw)
             barrier()
             el = time.perf_counter() - t0
-        clocks["last"] = cs.summary() if rank == 0 else None
+        clocks["last"] = cs.summary() if cs is not None and rank == 0 else None
         per_rank = [el / steps * 1e3]
         if dist.is_initialized():
             t = torch.tensor([el], dtype=torch.float64, device=dev)
@@ -521,7 +559,9 @@ def run_workload(C, args, workload, pixel_dist, frames, steps, warmup, *, cm_sta
     elapsed, per_rank_ms, events = timed()
     R = {"clock": clocks.get("last"), "workload": workload, "dist": pixel_dist, "cube": cube_name, "frames": frames, "H": H, "W": W, "stages": stages, "chunk": chunk, "steps": steps, "warmup": warmup,
          "elapsed": elapsed, "per_rank_ms": per_rank_ms, "px_rank": frames * H * W, "cm_stats": cm_stats}
-    # the timed steps' own output, checked and fingerprinted BEFORE anything else overwrites it (never inside the timed region)
+    # the timed steps' own output, written, checked and fingerprinted BEFORE anything else overwrites it (never inside the timed region)
+    if dump_dir is not None and rank == 0:
+        dump_outputs(out, dump_dir)
     R["verify"] = None
     if rank == 0 and verify:
         try:
@@ -751,12 +791,13 @@ def main():
     default_frames = {"grain_lut_1080p": 128, "colormatch_4k": 512}
     frames = args.frames or default_frames.get(args.workload, 256)      # BASELINE.json configs[1..4]
 
-    M = run_workload(C, args, args.workload, args.dist, frames, args.steps, args.warmup, cm_stats=args.cm_stats, verify=not args.no_verify,
-                     digest=args.digest, fast_variant=not args.no_fast_variant, time_reference_stats=True)
+    full = args.full
+    M = run_workload(C, args, args.workload, args.dist, frames, args.steps, args.warmup, cm_stats=args.cm_stats, verify=full and not args.no_verify,
+                     digest=args.digest, fast_variant=full and not args.no_fast_variant, time_reference_stats=full, dump_dir=args.dump_outputs)
     # N > 1: a second headline leg whose reference-frame statistics are the fp64 (n, mean, M2) form -- rows split across the ranks, merged
     # by the RCCL all-reduce INSIDE the timed steps (BASELINE configs[4] names that collective; the default device policy needs none)
     fp64_leg = None
-    if world > 1 and "colormatch" in stages and not args.no_fp64_leg and (args.cm_stats or "device") == "device":
+    if full and world > 1 and "colormatch" in stages and not args.no_fp64_leg and (args.cm_stats or "device") == "device":
         F64 = run_workload(C, args, args.workload, args.dist, frames, args.steps, args.warmup, cm_stats="fp64", verify=not args.no_verify)
         fp64_leg = {"cm_stats": "fp64 (reference-frame rows split across the ranks, (n, mean, M2) merged by two SUM all-reduces over RCCL inside every step)",
                     "value": round(world * F64["px_rank"] * args.steps / F64["elapsed"] / 1e6, 1), "unit": "Mpixels/s",
@@ -776,9 +817,9 @@ def main():
     bytes_per_px_chain = 36 if "colormatch" in stages else 24
 
     # PMC counters of every workload's kernels: live on this box (three rocprofv3 --pmc passes of tools/prof_driver.py in their own
-    # process, right after the timed region), else the committed run of the same command
+    # process, right after the timed region; --full only), else the committed run of the same command
     pmc, pmc_src, pmc_err = {}, None, None
-    if rank == 0 and world == 1 and not args.no_live_traffic:
+    if full and rank == 0 and world == 1 and not args.no_live_traffic:
         try:
             pmc = live_traffic()
             pmc_src = "rocprofv3 --kernel-trace --pmc on this box right after the timed region (separate passes, own process, the same kernels on 16x4K frames)"
@@ -885,7 +926,7 @@ def main():
             line["fp64_stats_leg"] = fp64_leg
     # The other single-GPU BASELINE configs and the second pixel distribution ("report both"), each timed the way
     # the headline is -- every rank would have to take part, so N = 1 only
-    if world == 1 and args.workload == "chain4_4k" and not args.no_configs:
+    if full and world == 1 and args.workload == "chain4_4k" and not args.no_configs:
         n1080 = 128 if args.frames is None else args.frames          # BASELINE's frame counts unless --frames shrinks the run
         legs = [("chain4_4k", "video", frames), ("chain3_4k", "uniform", frames), ("chain3_4k", "video", frames),
                 ("grain_lut_1080p", "uniform", n1080), ("grain_lut_1080p", "video", n1080), ("colormatch_4k", "uniform", 2 * frames)]
@@ -921,7 +962,7 @@ def main():
             cfgs["graph_four_nodes_device_resident"] = {"error": f"{type(exc).__name__}: {exc}"}
         line["configs"] = cfgs
     if rank == 0:
-        if world == 1 and not args.no_host_fed and args.workload == "chain4_4k":
+        if full and world == 1 and not args.no_host_fed and args.workload == "chain4_4k":
             # what a ComfyUI graph sees: CPU tensors in, CPU tensors out, every node call crossing PCIe both ways -- never `value`
             try:
                 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -930,7 +971,7 @@ def main():
                 line["host_fed"] = host_fed.measure(frames=16, reps=5, warmup=4)       # (torch's host / device pools of this process settle after 3 calls per row)
             except Exception as exc:
                 line["host_fed"] = {"error": f"{type(exc).__name__}: {exc}"}
-        if not args.no_cpu_baseline:
+        if full and not args.no_cpu_baseline:
             # rank 0 only, any N (the other ranks wait at the final barrier; the process group's timeout covers it)
             try:
                 line["cpu_baseline"] = cpu_baseline(stages, args.cpu_frames if H > 1080 else 4 * args.cpu_frames, H, W, lut_cpu, per_node=True)

@@ -465,7 +465,7 @@ def test_bench_two_rank_flow_on_one_gpu_with_gloo(dev):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--frames", "8", "--steps", "1", "--warmup", "1",
-                        "--cpu-frames", "1"], capture_output=True, text=True, env=env, timeout=900)
+                        "--cpu-frames", "1", "--full"], capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -2380,7 +2380,7 @@ def test_colour_match_4k_at_bench_geometry_is_the_device_oracle(ops, dev):
 
 
 def test_bench_verifies_its_own_output(dev):
-    """bench.py --verify (on by default): after the timed steps the first and the last RNG chunk of `out` are re-derived with the
+    """bench.py --full (the output check is on by default there): after the timed steps the first and the last RNG chunk of `out` are re-derived with the
     stand-alone operators and with the oracle composition; the JSON line says so."""
     import json
     import subprocess
@@ -2389,7 +2389,7 @@ def test_bench_verifies_its_own_output(dev):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--frames", "8", "--steps", "1", "--warmup", "1", "--no-cpu-baseline",
-                        "--no-live-traffic", "--no-fast-variant", "--digest", "--no-host-fed"], capture_output=True, text=True, env=env, timeout=1200)
+                        "--no-live-traffic", "--no-fast-variant", "--digest", "--no-host-fed", "--full"], capture_output=True, text=True, env=env, timeout=1200)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert line["verified"] is True, line["verify"]

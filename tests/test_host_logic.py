@@ -132,24 +132,32 @@ def test_cube_writer_roundtrip_and_errors(pkg, tmp_path):
             cube.parse_cube_file(str(p))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/LUTS"), reason="reference assets not present")
-def test_cube_parser_on_shipped_reference_assets(pkg):
+def test_cube_parser_on_shipped_reference_assets(pkg, tmp_path):
+    """The reference's 12 shipped cube files (tests/golden/reference_luts/, gzip of the files as shipped), parsed by the pack and the oracle."""
+    import gzip
     from comfyui_vrgamedevgirl_amd import cube
-    for name in sorted(os.listdir("/root/reference/LUTS")):
-        if name.endswith(".cube"):
-            a = cube.parse_cube_file(os.path.join("/root/reference/LUTS", name))
-            b = R.parse_cube_file(os.path.join("/root/reference/LUTS", name))
-            assert torch.equal(a["lut"], b["lut"]) and torch.equal(a["domain_min"], b["domain_min"]), name
+    src = os.path.join(GOLDEN, "reference_luts")
+    names = sorted(n[:-3] for n in os.listdir(src) if n.endswith(".cube.gz"))
+    assert len(names) == 12
+    for name in names:
+        path = tmp_path / name
+        with gzip.open(os.path.join(src, name + ".gz"), "rb") as fh:
+            path.write_bytes(fh.read())
+        a = cube.parse_cube_file(str(path))
+        b = R.parse_cube_file(str(path))
+        assert torch.equal(a["lut"], b["lut"]) and torch.equal(a["domain_min"], b["domain_min"]), name
 
 
 def test_palette_lut_matches_reference_generator(pkg):
-    from oracle import reference_loader as RL
-    if not RL.reference_available():
-        pytest.skip("reference not present")
+    """The reference's _build_palette_lut on three palettes, recorded from a live run of it (tests/golden/reference_nodes.*)."""
+    import json
     from comfyui_vrgamedevgirl_amd import cube
-    iv = RL.load_iv_adjustments()
-    for colors, n in (("#0b1d51, #1f6aa5, #f3d27a", 8), ("red", 9), ("teal, orange", 11)):
-        assert torch.equal(cube.build_palette_lut(colors, n), iv._build_palette_lut(colors, n))
+    z = np.load(os.path.join(GOLDEN, "reference_nodes.npz"))
+    with open(os.path.join(GOLDEN, "reference_nodes.json")) as fh:
+        cases = json.load(fh)["palette"]
+    assert [(c["colors"], c["n"]) for c in cases] == [("#0b1d51, #1f6aa5, #f3d27a", 8), ("red", 9), ("teal, orange", 11)]
+    for i, c in enumerate(cases):
+        assert torch.equal(cube.build_palette_lut(c["colors"], c["n"]), torch.from_numpy(z[f"palette.{i}"])), c
 
 
 def test_frame_groups(pkg):
@@ -402,3 +410,35 @@ def test_bench_issue_cost_roofline_and_clock_sampler_without_a_gpu(pkg):
     with bench.ClockSampler() as cs:
         pass
     assert cs.summary() is None or "sclk_mhz_median" in cs.summary()
+
+
+def test_bench_dump_outputs_and_step_counts_without_a_gpu(pkg, tmp_path):
+    """bench.py --dump-outputs writes float32 .npy files whose sample indices depend on the batch size only (equal runs, equal files), within
+    64 MB at the headline's 4K x 256 frames; --steps below 1 and a negative --warmup are refused."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("_bench_for_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    argv, sys.argv = sys.argv, ["bench.py"]
+    try:
+        spec.loader.exec_module(bench)
+        assert (bench.DUMP_SAMPLE + 2 * bench.DUMP_ROWS * 3840 * 3) * 4 <= 64 << 20
+        bench.DUMP_SAMPLE = 1000                  # (this test's own copy of the module) the sampled form on a small batch
+        out = torch.rand(3, 70, 40, 3, generator=torch.Generator().manual_seed(1))
+        dumps = []
+        for d in ("a", "b"):
+            bench.dump_outputs(out, str(tmp_path / d))
+            dumps.append({n: np.load(tmp_path / d / f"{n}.npy") for n in ("output_sample", "output_first_rows", "output_last_rows")})
+        for n, a in dumps[0].items():
+            assert a.dtype == np.float32 and np.array_equal(a, dumps[1][n]), n
+        assert np.array_equal(dumps[0]["output_first_rows"], out[0, :bench.DUMP_ROWS].numpy())
+        assert np.array_equal(dumps[0]["output_last_rows"], out[-1, -bench.DUMP_ROWS:].numpy())
+        assert dumps[0]["output_sample"].shape == (1000,) and np.isin(dumps[0]["output_sample"], out.numpy()).all()
+        sys.argv = ["bench.py", "--steps", "7", "--warmup", "0"]
+        args = bench.parse_args()
+        assert (args.steps, args.warmup, args.full, args.dump_outputs) == (7, 0, False, None)
+        for bad in (["--steps", "0"], ["--warmup", "-1"]):
+            sys.argv = ["bench.py", *bad]
+            with pytest.raises(SystemExit):
+                bench.parse_args()
+    finally:
+        sys.argv = argv

@@ -179,32 +179,40 @@ def test_lab_restated_self_consistency():
     assert R.kornia_rgb_to_lab(torch.zeros(1, 3, 1, 1)).abs().max() == 0
 
 
-@pytest.mark.skipif(not RL.reference_available(), reason="reference checkout (third-party LUT assets) not present")
-def test_shipped_lut_assets_by_digest():
+def test_shipped_lut_assets_by_digest(tmp_path):
+    """The reference's 12 shipped cube files (tests/golden/reference_luts/, gzip of the files as shipped) against the recorded digests."""
+    import gzip
     with open(os.path.join(GOLDEN, "shipped_lut_digests.json")) as fh:
         meta = json.load(fh)
     g = torch.Generator().manual_seed(meta["probe_seed"])
     probe = torch.rand(*meta["probe_shape"], generator=g) * meta["probe_affine"][0] + meta["probe_affine"][1]
-    luts_dir = os.path.join(RL.REFERENCE_ROOT, "LUTS")
     assert len(meta["luts"]) == 12
     for name, want in meta["luts"].items():
-        lut = R.parse_cube_file(os.path.join(luts_dir, name))
+        path = tmp_path / name
+        with gzip.open(os.path.join(GOLDEN, "reference_luts", name + ".gz"), "rb") as fh:
+            path.write_bytes(fh.read())
+        lut = R.parse_cube_file(str(path))
         assert lut["size"] == want["size"]
         assert hashlib.sha256(lut["lut"].numpy().tobytes()).hexdigest() == want["lut_sha256"], name
         out = R.apply_cube_lut(probe, lut["lut"], lut["domain_min"], lut["domain_max"])
         assert hashlib.sha256(out.numpy().tobytes()).hexdigest() == want["out_sha256"], name
 
 
-@pytest.mark.skipif(not RL.reference_available(), reason="reference checkout not present")
+def _reference_nodes():
+    """tests/golden/reference_nodes.*: what the reference's node classes returned on these tests' seeded inputs (oracle/make_golden.py)."""
+    with open(os.path.join(GOLDEN, "reference_nodes.json")) as fh:
+        return _npz("reference_nodes.npz"), json.load(fh)
+
+
 def test_restatement_against_live_reference_random_shapes():
-    nodes = RL.load_nodes()
-    g = torch.Generator().manual_seed(77)
-    for shape in ((1, 3, 5, 3), (2, 17, 9, 3), (1, 32, 48, 3)):
-        x = torch.rand(*shape, generator=g) * 1.2 - 0.1
+    """The three sharpen nodes of the reference on random shapes, recorded from a live run of its node classes."""
+    z, _ = _reference_nodes()
+    for i in range(3):
+        x = _t(z[f"sharpen{i}.x"])
         for s, gpu in ((0.5, False), (2.5, True)):
-            assert torch.equal(R.unsharp(x, s, gpu).contiguous(), nodes.FastUnsharpSharpen().apply_unsharp(x, s, gpu)[0].contiguous())
-            assert torch.equal(R.laplacian(x, s, gpu).contiguous(), nodes.FastLaplacianSharpen().apply_laplacian(x, s, gpu)[0].contiguous())
-            assert torch.equal(R.sobel(x, s, gpu).contiguous(), nodes.FastSobelSharpen().apply_sobel(x, s, gpu)[0].contiguous())
+            assert torch.equal(R.unsharp(x, s, gpu).contiguous(), _t(z[f"sharpen{i}.unsharp.{s}.{int(gpu)}"])), (i, s, gpu)
+            assert torch.equal(R.laplacian(x, s, gpu).contiguous(), _t(z[f"sharpen{i}.laplacian.{s}.{int(gpu)}"])), (i, s, gpu)
+            assert torch.equal(R.sobel(x, s, gpu).contiguous(), _t(z[f"sharpen{i}.sobel.{s}.{int(gpu)}"])), (i, s, gpu)
 
 
 # ------------------------------------------------------------------ 13-slider Adjust (section 8f rank 2)
@@ -278,17 +286,14 @@ def test_opening_match_restatement_against_reference_fixtures():
             assert R.opening_match_weight(k, 24.0, m["strength"], m["fade_seconds"]) == want, (name, k)
 
 
-@pytest.mark.skipif(not RL.reference_available(), reason="reference checkout not present")
 def test_opening_match_against_live_reference():
-    pytest.importorskip("PIL")
-    import tempfile
-    g = np.random.default_rng(3)
-    ref = g.integers(0, 256, (21, 18, 3), dtype=np.uint8)
-    tgt = (g.integers(0, 256, (17, 23, 3)) * 0.4 + 90).astype(np.uint8)
-    with tempfile.TemporaryDirectory() as d:
-        out = RL.opening_color_match_reference(ref, tgt, d, 0.5, 3.0)
-    scales, offsets = R.opening_match_terms(R.image_stat_rgb(ref), R.image_stat_rgb(tgt))
-    assert scales == out["scales"] and offsets == out["offsets"] and R.opening_match_cube_text(scales, offsets) == out["cube_text"]
+    """The reference's opening colour match (strength 0.5, fade 3 s) on a seeded pair of frames, recorded from a live run of its statements:
+    scales and offsets exactly, the cube text by SHA-256."""
+    z, meta = _reference_nodes()
+    out = meta["opening"]
+    scales, offsets = R.opening_match_terms(R.image_stat_rgb(z["opening.ref"]), R.image_stat_rgb(z["opening.tgt"]))
+    assert scales == out["scales"] and offsets == out["offsets"]
+    assert hashlib.sha256(R.opening_match_cube_text(scales, offsets).encode()).hexdigest() == out["cube_sha256"]
 
 
 def test_lab_restatement_known_answers_from_colour_science():
@@ -314,18 +319,16 @@ def test_lab_restatement_known_answers_from_colour_science():
     assert (back - rgb).abs().max().item() < 1e-5
 
 
-@pytest.mark.skipif(not RL.reference_available(), reason="reference checkout not present")
 def test_baseline_config_1_oracle_equals_reference_node_on_cpu():
     """BASELINE.json configs[0] on the reference's own CPU path: same seed, same mt19937 noise -> the restatement and the
-    reference node agree bit for bit on the 512x512 frame."""
-    nodes = RL.load_nodes()
+    reference node agree bit for bit on the 512x512 frame (the node's output recorded by the SHA-256 of its fp32 bytes)."""
+    _, meta = _reference_nodes()
     torch.manual_seed(0)
     x = torch.rand(1, 512, 512, 3)
-    torch.manual_seed(1)
-    want = nodes.FastFilmGrain().apply_grain(x, 0.04, 0.5, 4)[0]
+    assert hashlib.sha256(x.numpy().tobytes()).hexdigest() == meta["grain_512"]["input_sha256"]
     torch.manual_seed(1)
     got = R.fast_film_grain(x, 0.04, 0.5, 4)
-    assert torch.equal(got, want)
+    assert hashlib.sha256(got.contiguous().numpy().tobytes()).hexdigest() == meta["grain_512"]["out_sha256"]
 
 
 def test_ffmpeg_style_lut3d_restatement_properties():
