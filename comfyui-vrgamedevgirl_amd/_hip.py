@@ -23,6 +23,7 @@ STENCIL_UNSHARP, STENCIL_LAPLACIAN, STENCIL_SOBEL = 0, 1, 2
 STAGE_GRAIN, STAGE_LUT, STAGE_COLORMATCH, STAGE_SHARPEN, STAGE_FROM_LAB = 1, 2, 4, 8, 16
 CM_MATH_DEVICE, CM_MATH_FAST = 0, 1
 ADJUST_DIV_IEEE, ADJUST_DIV_DEVICE = 0, 1
+RESIZE_BICUBIC, RESIZE_BILINEAR, RESIZE_AREA, RESIZE_NEAREST = 0, 1, 2, 3
 ABI_VERSION = 8
 
 
@@ -107,6 +108,8 @@ _SIGNATURES = {
     "vrg_chain_stats_lab_f32": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.POINTER(ChainDesc), _P, _P, _P]),
     "vrg_noise_f32": (C.c_int, [_P, C.c_int64, C.c_int64, C.POINTER(NoiseDesc), _P]),
     "vrg_selfcheck_pow_f32": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P]),
+    "vrg_resize_f32": (C.c_int, [_P, _P, C.c_int64] + [C.c_int32] * 13 + [C.c_int32, _P]),
+    "vrg_restore_f32": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64] + [C.c_int32] * 13 + [C.c_int32, C.c_int32, C.c_float, C.c_float, _P]),
 }
 
 # include/vrgdg_hip_debug.h: self-tests and probes -- for the test suite and the measurement tools, not part of the drop-in boundary

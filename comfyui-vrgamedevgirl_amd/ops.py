@@ -512,6 +512,136 @@ def stencil3x3(images: torch.Tensor, op: str, strength: float, zero_border: bool
 
 
 # ------------------------------------------------------------------------------------------------
+# frame resize / restore (Video Enhance: VRGDG_VideoEnhanceNodes.py:54-106, 394-419)
+# ------------------------------------------------------------------------------------------------
+
+FIT_STRETCH, FIT_CROP, FIT_LETTERBOX = "Stretch to dimensions", "Crop to fill", "Fit with letterbox (preserve all)"
+#: the widget strings of `resize_method` -> F.interpolate mode; anything else is bicubic, as in the reference (:45-51)
+INTERPOLATION = {"Nearest": "nearest", "Bilinear": "bilinear", "Bicubic (recommended)": "bicubic", "Area": "area"}
+RESIZE_METHODS = {"bicubic": 0, "bilinear": 1, "area": 2, "nearest": 3}       # include/vrgdg_hip.h, enum vrg_resize_method
+
+
+def interpolation_mode(resize_method) -> str:
+    return INTERPOLATION.get(str(resize_method), "bicubic")
+
+
+@dataclass(frozen=True)
+class ResizeGeometry:
+    """What one launch does: the `src` rectangle (x0, y0, w, h) of every input frame is resampled to the size of the `dst` rectangle and
+    lands at its position in the [out_h, out_w] output frame; output pixels outside `dst` are zero (letterbox bars), and the part of `dst`
+    outside the output frame is not produced (crop to fill: its resample positions are those of the whole scaled image)."""
+    out_h: int
+    out_w: int
+    src: tuple
+    dst: tuple
+
+
+def resize_geometry(in_h: int, in_w: int, target_width, target_height, fit_mode) -> ResizeGeometry:
+    """The integers of _resize_batch (:57-85), computed as the reference computes them (Python's round and //)."""
+    source_height, source_width = int(in_h), int(in_w)
+    target_width, target_height = int(target_width), int(target_height)
+    src = (0, 0, source_width, source_height)
+    if fit_mode == FIT_STRETCH:
+        return ResizeGeometry(target_height, target_width, src, (0, 0, target_width, target_height))
+    ratios = (target_width / source_width, target_height / source_height)
+    scale = max(ratios) if fit_mode == FIT_CROP else min(ratios)
+    scaled_width = max(1, int(round(source_width * scale)))
+    scaled_height = max(1, int(round(source_height * scale)))
+    if fit_mode == FIT_CROP:
+        left = max(0, (scaled_width - target_width) // 2)
+        top = max(0, (scaled_height - target_height) // 2)
+        return ResizeGeometry(min(target_height, scaled_height - top), min(target_width, scaled_width - left), src,
+                              (-left, -top, scaled_width, scaled_height))
+    pad_left = max(0, (target_width - scaled_width) // 2)
+    pad_right = max(0, target_width - scaled_width - pad_left)
+    pad_top = max(0, (target_height - scaled_height) // 2)
+    pad_bottom = max(0, target_height - scaled_height - pad_top)
+    return ResizeGeometry(scaled_height + pad_top + pad_bottom, scaled_width + pad_left + pad_right, src,
+                          (pad_left, pad_top, scaled_width, scaled_height))
+
+
+def restore_geometry(work_h: int, work_w: int, source_width, source_height, fit_mode) -> ResizeGeometry:
+    """The integers of _restore_batch (:89-106): the letterbox content rectangle is cut out again, then everything is a stretch."""
+    working_height, working_width = int(work_h), int(work_w)
+    source_width, source_height = int(source_width), int(source_height)
+    dst = (0, 0, source_width, source_height)
+    if fit_mode != FIT_LETTERBOX:
+        return ResizeGeometry(source_height, source_width, (0, 0, working_width, working_height), dst)
+    scale = min(working_width / source_width, working_height / source_height)
+    content_width = min(working_width, max(1, int(round(source_width * scale))))
+    content_height = min(working_height, max(1, int(round(source_height * scale))))
+    left = max(0, (working_width - content_width) // 2)
+    top = max(0, (working_height - content_height) // 2)
+    return ResizeGeometry(source_height, source_width, (left, top, content_width, content_height), dst)
+
+
+def _check_resize_source(t: torch.Tensor, name: str) -> torch.Tensor:
+    t = _check_frames(t, name)
+    if t.shape[0] < 1:
+        raise ValueError("Video Enhance requires a non-empty IMAGE batch.")
+    if t.shape[-1] < 3 or t.shape[1] < 1 or t.shape[2] < 1:
+        raise ValueError(f"{name} must have at least one pixel and 3 channels, got {tuple(t.shape)}")
+    return t
+
+
+def _geometry_args(x: torch.Tensor, g: ResizeGeometry):
+    if g.out_h < 1 or g.out_w < 1:
+        raise ValueError(f"resize to {g.out_w} x {g.out_h}: the target must have at least one pixel")
+    return (int(x.shape[1]), int(x.shape[2]), int(x.shape[3]), *g.src, g.out_h, g.out_w, *g.dst)
+
+
+@_on_device
+def resize_geometry_frames(images: torch.Tensor, geometry: ResizeGeometry, resize_method, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """RGB of `images` ([F, H, W, C >= 3]) resampled as `geometry` says, clamped to [0, 1]: [F, out_h, out_w, 3].  One launch."""
+    x = _check_resize_source(images, "images")
+    shape = (int(x.shape[0]), geometry.out_h, geometry.out_w, 3)
+    args = _geometry_args(x, geometry)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
+        raise ValueError(f"out must be a contiguous float32 tensor shaped {shape} on the frames' device")
+    _hip.check(_hip.lib().vrg_resize_f32(_hip.ptr(x), _hip.ptr(out), shape[0], *args, RESIZE_METHODS[interpolation_mode(resize_method)],
+                                        _hip.current_stream()), "vrg_resize_f32")
+    return out
+
+
+def resize_frames(images: torch.Tensor, target_width, target_height, fit_mode, resize_method, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """_resize_batch (:54-86) on device frames: stretch, crop to fill or letterbox to the target size."""
+    x = _check_resize_source(images, "images")
+    return resize_geometry_frames(x, resize_geometry(x.shape[1], x.shape[2], target_width, target_height, fit_mode), resize_method, out)
+
+
+@_on_device
+def restore_frames(work: torch.Tensor, originals: torch.Tensor, source_width, source_height, fit_mode, resize_method, strength: float,
+                   frame_count: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """VRGDGVideoEnhanceRestoreOriginal.restore (:404-419) in one pass over the originals: the working-resolution frames `work` go back to
+    the source size (_restore_batch), are blended over the RGB of the first min(frame_count, len(work)) `originals` as
+    o * (1 - strength) + restored * strength, and everything -- further channels and the unmatched tail frames of the originals
+    included -- is clamped to [0, 1].  Shaped like `originals`."""
+    w = _check_resize_source(work, "work")
+    o = _check_frames(originals, "originals")
+    if o.device != w.device:
+        raise RuntimeError(f"originals live on {o.device}, the working frames on {w.device}")
+    if o.shape[-1] < 3:
+        raise ValueError(f"originals must have at least 3 channels, got {o.shape[-1]}")
+    g = restore_geometry(w.shape[1], w.shape[2], source_width, source_height, fit_mode)
+    if (g.out_h, g.out_w) != (int(o.shape[1]), int(o.shape[2])):
+        raise ValueError(f"originals are {int(o.shape[2])} x {int(o.shape[1])}, the restore target is {g.out_w} x {g.out_h}")
+    frames = int(o.shape[0])
+    usable = min(frames if frame_count is None else int(frame_count), int(w.shape[0]))
+    if usable > frames:
+        raise ValueError(f"{usable} restored frames for {frames} original frames")
+    out = _out_like(o, out)
+    if o.numel() == 0:
+        return out
+    strength = float(strength)
+    _hip.check(_hip.lib().vrg_restore_f32(_hip.ptr(w), _hip.ptr(o), _hip.ptr(out), max(0, usable), frames, *_geometry_args(w, g),
+                                         int(o.shape[3]), RESIZE_METHODS[interpolation_mode(resize_method)], _f32(strength),
+                                         _f32(1.0 - strength), _hip.current_stream()), "vrg_restore_f32")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # 13-slider Adjust (video routes)
 # ------------------------------------------------------------------------------------------------
 

@@ -313,6 +313,37 @@ int vrg_adjust_u8(const uint8_t* in, uint8_t* out, float* tmp, int64_t frames, i
                   const vrg_adjust_desc* desc, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Frame resize and the Video Enhance restore.  Replaces _resize_batch / _restore_batch (VRGDG_VideoEnhanceNodes.py:54-106) and
+ * the blend of VRGDGVideoEnhanceRestoreOriginal.restore (:404-419).
+ * Arithmetic: torch's CPU kernels behind F.interpolate in their plain one-rounding-per-operation form (what
+ * ATEN_CPU_CAPABILITY=default executes), fp32 throughout: bicubic (A = -0.75) and bilinear with align_corners = False, area
+ * (adaptive average pooling) and nearest (csrc/vrg_resize_math.hpp states each rule).  torch's AVX2 / AVX-512 builds differ from that
+ * form -- and so from these kernels -- by a few ulp(1.0) in most elements.
+ * ------------------------------------------------------------------------------------------- */
+enum vrg_resize_method { VRG_RESIZE_BICUBIC = 0, VRG_RESIZE_BILINEAR = 1, VRG_RESIZE_AREA = 2, VRG_RESIZE_NEAREST = 3 };
+
+/* The source rectangle (src_x0, src_y0, src_w, src_h) of the RGB of every [in_h][in_w][in_channels >= 3] frame is resampled to
+ * dst_w x dst_h and written at (dst_x0, dst_y0) of the [out_h][out_w][3] output frame, clamped to [0, 1]; the rest of the output is
+ * zero.  The source rectangle lies inside the input frame.  The destination rectangle may hang over the output frame (negative
+ * offsets, or a size past the frame): only its part inside is produced, at the resample positions of the whole rectangle -- stretch
+ * is dst = the frame, crop to fill a dst larger than the frame, letterbox a dst inside it, the letterbox undo a src rectangle.  The
+ * caller computes the rectangles (the reference does so with Python's round() and //).  in != out. */
+int vrg_resize_f32(const float* in, float* out, int64_t frames, int32_t in_h, int32_t in_w, int32_t in_channels,
+                   int32_t src_x0, int32_t src_y0, int32_t src_w, int32_t src_h, int32_t out_h, int32_t out_w,
+                   int32_t dst_x0, int32_t dst_y0, int32_t dst_w, int32_t dst_h, int32_t method, void* stream);
+
+/* The fused restore: `work` = work_frames working-resolution frames, `originals` and `out` = frames [out_h][out_w][channels >= 3]
+ * frames.  For frame f < min(work_frames, frames):
+ *     out.rgb = clamp(fl(fl(originals.rgb * one_minus_strength) + fl(clamp(resampled, 0, 1) * strength)), 0, 1)
+ * with `resampled` as vrg_resize_f32 produces it for the same geometry, further channels = clamp(originals, 0, 1); the remaining
+ * frames = clamp(originals, 0, 1).  one_minus_strength = (float)(1.0 - strength) formed in double by the caller.  `out` aliases
+ * neither input. */
+int vrg_restore_f32(const float* work, const float* originals, float* out, int64_t work_frames, int64_t frames,
+                    int32_t in_h, int32_t in_w, int32_t in_channels, int32_t src_x0, int32_t src_y0, int32_t src_w, int32_t src_h,
+                    int32_t out_h, int32_t out_w, int32_t dst_x0, int32_t dst_y0, int32_t dst_w, int32_t dst_h,
+                    int32_t channels, int32_t method, float strength, float one_minus_strength, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Introspection
  * ------------------------------------------------------------------------------------------- */
 int vrg_abi_version(void);
