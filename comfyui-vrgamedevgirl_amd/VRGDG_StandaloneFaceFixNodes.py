@@ -1,0 +1,164 @@
+"""Face Fix composite on the MI355X: `VRGDGFaceFixComposite` and `VRGDGFaceFixCompositeOpaque` of the reference's
+VRGDG_StandaloneFaceFixNodes.py with the same names, widget specs, tooltips, messages and log lines; the pixels come from
+csrc/vrg_composite.hip (ops.composite_frames).
+
+The reference composites frame by frame in Python (about twenty eager ops, a host synchronisation and a boolean gather per frame, a full
+clone of the originals); here the whole batch is two small measuring launches and one pass over the output, and whether a frame's colour
+match applies (at least 16 pixels with alpha > 0.35) is decided on the device.  CPU originals (what ComfyUI hands a node) stream through
+the host-fed pipeline of _devices in pieces along the frame axis, the much smaller work frames are uploaded once ahead; device tensors are
+processed where they are.  Inputs are never written.  The repaired count is computed on the host from the entries.
+
+What is NOT here: detection and tracking (Prepare / Collect nodes, cv2), the landmark-aligned composite (cv2 warp),
+and the registration in the package's NODE_CLASS_MAPPINGS: INTEGRATION.md shows the two lines.  The nodes are eager.
+
+Refused with a ValueError, because the reference fails on them rather than defines them: a box that does not lie inside its frame (shape
+mismatch in the reference), an empty box in VRGDGFaceFixComposite, and channel counts other than 3 or 4.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import ops
+from ._devices import compute_device, intermediate_device, stream_frames_with_masks
+
+FACE_FIX_CONTEXT = "VRGDG_FACE_FIX_CONTEXT"
+
+
+def _log(message):
+    print(f"[VRGDG Face Fix] {message}", flush=True)
+
+
+class _Plan:
+    """What a composite call works on, read from the node's inputs once: the context's original frames and entries, the index of the
+    first work frame that belongs to source frame 0, how many source frames have a work frame at all, and the frame-count difference
+    the reference reports (source frames minus the work frames left after the offset; more than 7 either way is refused)."""
+
+    def __init__(self, work, context):
+        self.work, self.originals, self.entries = work, context["original_frames"], context["entries"]
+        self.offset = int(context.get("ltx_frame_offset") or 0)
+        self.work_frames, self.sources = int(work.shape[0]), len(self.entries)
+        left_after_offset = self.work_frames - self.offset if self.work_frames > self.offset else 0
+        self.delta = self.sources - left_after_offset
+        self.usable = self.sources if self.sources < left_after_offset else left_after_offset
+
+    def refuse_if_counts_differ(self):
+        if not -7 <= self.delta <= 7:
+            raise ValueError(f"LTX returned {self.work_frames} frames for {self.sources} source frames.")
+
+    def repaired(self, counts) -> int:
+        return sum(1 for entry in self.entries[:self.usable] if counts(entry))
+
+
+def _composite(plan, rule, color_match):
+    """(frames, masks) wherever the originals live."""
+    work, originals, entries, offset = plan.work, plan.originals, plan.entries, plan.offset
+    n_work, n_orig = plan.work_frames, int(originals.shape[0])
+    ops.composite_channels(rule, originals.shape[3], work.shape[3])
+    rows = ops.face_fix_entries(entries, n_work, offset, n_orig)
+    ops.composite_table(rows, rule, color_match, originals.shape[1], originals.shape[2])        # refuses before anything is uploaded
+    if originals.is_cuda or n_orig == 0 or intermediate_device().type != "cpu":
+        dev = originals.device if originals.is_cuda else compute_device()
+        with torch.cuda.device(dev):
+            out, masks = ops.composite_frames(originals.to(dev, torch.float32), work.to(dev, torch.float32), rows, rule, color_match)
+        if not originals.is_cuda:
+            out, masks = out.to(intermediate_device()), masks.to(intermediate_device())
+        return out, masks
+    # host-fed: the originals (24 B per pixel up and down) stream through the staging pipeline, the work frames are uploaded once
+    dev = compute_device()
+    with torch.cuda.device(dev):
+        work_dev = work.to(dev, torch.float32)
+    if originals.dtype != torch.float32:
+        originals = originals.float()
+
+    def piece(gpu_originals, first_frame):
+        last = first_frame + int(gpu_originals.shape[0])
+        return ops.composite_frames(gpu_originals, work_dev, ops.face_fix_entries(entries, n_work, offset, n_orig, first_frame, last), rule,
+                                    color_match)
+
+    return stream_frames_with_masks(originals, piece)
+
+
+class VRGDGFaceFixComposite:
+    @classmethod
+    def INPUT_TYPES(cls):
+        return {"required": {
+            "ltx_face_frames": ("IMAGE", {"tooltip": "Connect the final IMAGE batch from the LTX VAE Decode node. Do not connect source crops or anchor images here."}),
+            "face_fix_context": (FACE_FIX_CONTEXT, {"tooltip": "Connect Collect LTX Inputs: face_fix_context. It supplies original full-resolution frames, crop rectangles, and no-face safety decisions."}),
+            "feather_pixels": ("INT", {"default": 18, "min": 0, "max": 256, "tooltip": "Softens the boundary where each repaired face crop meets the original frame. Higher values create a wider, smoother transition; too high may weaken facial detail. Lower values are sharper but can reveal a visible edge. Recommended starting value: 18."}),
+            "color_match": ("FLOAT", {"default": 0.65, "min": 0.0, "max": 1.0, "step": 0.05, "tooltip": "Shifts the repaired crop's average color toward the original face region before blending. 0 disables matching; 1 applies the full measured correction. Increase for lighting/color seams, decrease if skin tone becomes dull or unstable. Recommended: 0.65."}),
+        }}
+
+    RETURN_TYPES = ("IMAGE", "MASK", "INT")
+    RETURN_NAMES = ("repaired_video_frames", "applied_face_mask", "repaired_frame_count")
+    RETURN_TOOLTIPS = (
+        "Original full-resolution video frame batch with safe repaired faces composited in. Connect to VHS Video Combine images.",
+        "Per-frame grayscale mask showing exactly where and how strongly Face Fix was applied. Optional diagnostic output.",
+        "Number of frames that received a nonzero repaired-face composite. Optional diagnostic output.",
+    )
+    FUNCTION = "composite"
+    CATEGORY = "VRGameDevGirl/Face Fix"
+    DESCRIPTION = "Feathers LTX face frames back into the original video frames; no-face and short LTX tail frames remain unchanged."
+
+    def composite(self, ltx_face_frames, face_fix_context, feather_pixels, color_match):
+        plan = _Plan(ltx_face_frames, face_fix_context)
+        _log(
+            f"Composite started. Job={face_fix_context.get('job_id', 'unknown')}; "
+            f"source_frames={plan.sources}, LTX_frames={plan.work_frames}, delta={plan.delta}, "
+            f"feather={feather_pixels}, color_match={color_match:.2f}."
+        )
+        plan.refuse_if_counts_differ()
+        # a frame is repaired when its entry has a box and a positive strength (a missing strength is 0)
+        repaired = plan.repaired(lambda entry: bool(entry.get("box")) and float(entry.get("strength", 0.0)) > 0)
+        output, masks = _composite(plan, ops.CompositeRule("radial", feather=feather_pixels), color_match)
+        _log(
+            f"Composite finished: repaired={repaired}, unchanged={plan.sources - repaired}, "
+            f"preserved_LTX_tail={plan.delta if plan.delta > 0 else 0}."
+        )
+        return output, masks, repaired
+
+
+class VRGDGFaceFixCompositeOpaque:
+    """Composite the generated crop at full opacity inside a feathered edge."""
+
+    @classmethod
+    def INPUT_TYPES(cls):
+        return {"required": {
+            "ltx_face_frames": ("IMAGE", {"tooltip": "The complete decoded LTX face-video batch."}),
+            "face_fix_context": (FACE_FIX_CONTEXT, {"tooltip": "Tracked crop boxes and original frames from Face Fix Prepare."}),
+            "feather_pixels": ("INT", {"default": 6, "min": 0, "max": 128, "tooltip": "Feather only the outer crop boundary. The face interior remains fully opaque."}),
+        }}
+
+    RETURN_TYPES = ("IMAGE", "MASK", "INT")
+    RETURN_NAMES = ("repaired_video_frames", "applied_face_mask", "repaired_frame_count")
+    FUNCTION = "composite"
+    CATEGORY = "VRGameDevGirl/Face Fix"
+    DESCRIPTION = "Fully replaces every tracked face crop; only the outside boundary is feathered."
+
+    def composite(self, ltx_face_frames, face_fix_context, feather_pixels):
+        plan = _Plan(ltx_face_frames, face_fix_context)
+        plan.refuse_if_counts_differ()
+        feather = int(feather_pixels) if int(feather_pixels) > 0 else 0
+
+        def has_area(entry):                                # the opaque node ignores the strength; an empty box is skipped
+            box = entry.get("box")
+            if not box:
+                return False
+            left, top, right, bottom = (int(v) for v in box)
+            return right > left and bottom > top
+
+        repaired = plan.repaired(has_area)
+        output, masks = _composite(plan, ops.CompositeRule("opaque", feather=feather), 0.0)
+        _log(f"Opaque composite finished: repaired={repaired}, unchanged={plan.sources - repaired}, feather={feather}.")
+        return output, masks, repaired
+
+
+NODE_CLASS_MAPPINGS = {
+    "VRGDGFaceFixComposite": VRGDGFaceFixComposite,
+    "VRGDGFaceFixCompositeOpaque": VRGDGFaceFixCompositeOpaque,
+}
+
+
+NODE_DISPLAY_NAME_MAPPINGS = {
+    "VRGDGFaceFixComposite": "Face Fix - Composite Repaired Video",
+    "VRGDGFaceFixCompositeOpaque": "Face Fix - Composite Opaque Full Face",
+}

@@ -943,6 +943,29 @@ def stream_frames(images: torch.Tensor, fn, multiple_of: int = 1, out_dtype=None
     return _stream_frames_on(devices, fns, images, multiple_of, out_dtype)
 
 
+def stream_frames_with_masks(originals, piece):
+    """stream_frames for a pass with a second, one-channel result: `piece(gpu_frames, first_frame) -> (frames, masks)`.  The
+    masks go to a page-locked host tensor (when it fits PIN_LIMIT_BYTES) with a copy that does not hold the host, so the next
+    piece's upload is queued behind this piece's kernels as for the frames; the copies are awaited once, at the end."""
+    shape = tuple(originals.shape[:3])
+    pinned, masks = _result_buffer(shape, torch.float32, 4 * shape[0] * shape[1] * shape[2])
+    in_flight = []
+
+    def fn(gpu_frames, first_frame):
+        out, mask = piece(gpu_frames, first_frame)
+        masks[first_frame:first_frame + int(mask.shape[0])].copy_(mask, non_blocking=pinned)
+        if pinned:
+            done = torch.cuda.Event()
+            done.record()
+            in_flight.append((done, mask))                 # the device mask lives until its copy has finished
+        return out
+
+    frames = stream_frames(originals, fn)
+    for done, _ in in_flight:
+        done.synchronize()
+    return frames, masks
+
+
 #: Pageable input frames: "ring" = this pack copies them into a page-locked ring with several host threads (vrg_host_copy) and uploads
 #: from there asynchronously; "runtime" = the HIP runtime's own pageable copy, which starts only when everything queued on the device
 #: has drained -- upload, kernels and download then run one after the other (profiles/r04_host_fed_timeline_runtime_pageable.json).

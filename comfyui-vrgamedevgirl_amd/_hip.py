@@ -24,6 +24,9 @@ STAGE_GRAIN, STAGE_LUT, STAGE_COLORMATCH, STAGE_SHARPEN, STAGE_FROM_LAB = 1, 2, 
 CM_MATH_DEVICE, CM_MATH_FAST = 0, 1
 ADJUST_DIV_IEEE, ADJUST_DIV_DEVICE = 0, 1
 RESIZE_BICUBIC, RESIZE_BILINEAR, RESIZE_AREA, RESIZE_NEAREST = 0, 1, 2, 3
+COMPOSITE_NONE, COMPOSITE_ELLIPSE, COMPOSITE_RECTANGLE, COMPOSITE_RADIAL, COMPOSITE_OPAQUE = 0, 1, 2, 3, 4
+COMPOSITE_CLAMP_CROP, COMPOSITE_MATCH, COMPOSITE_STEP, COMPOSITE_USER_MASK, COMPOSITE_RAW_COPY = 1, 2, 4, 8, 16
+COMPOSITE_STATS_WORDS = 16
 ABI_VERSION = 8
 
 
@@ -58,6 +61,15 @@ class AdjustDesc(C.Structure):
                 ("has_fade", C.c_int32), ("fade_mul", C.c_float), ("fade_add", C.c_float),
                 ("has_vignette", C.c_int32), ("vignette", C.c_float),
                 ("div_mode", C.c_int32)]
+
+
+class CompositeDesc(C.Structure):
+    """vrg_composite_desc"""
+    _fields_ = [("rule", C.c_int32), ("flags", C.c_int32),
+                ("original_index", C.c_int32), ("crop_index", C.c_int32), ("mask_index", C.c_int32),
+                ("left", C.c_int32), ("top", C.c_int32), ("box_w", C.c_int32), ("box_h", C.c_int32),
+                ("paste_w", C.c_int32), ("paste_h", C.c_int32),
+                ("match_strength", C.c_float), ("threshold", C.c_float), ("p", C.c_float * 7)]
 
 
 _F3 = C.c_float * 3
@@ -110,6 +122,9 @@ _SIGNATURES = {
     "vrg_selfcheck_pow_f32": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P]),
     "vrg_resize_f32": (C.c_int, [_P, _P, C.c_int64] + [C.c_int32] * 13 + [C.c_int32, _P]),
     "vrg_restore_f32": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64] + [C.c_int32] * 13 + [C.c_int32, C.c_int32, C.c_float, C.c_float, _P]),
+    "vrg_composite_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "vrg_composite_stats_f32": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int64] + [C.c_int64] * 4 + [C.c_int32] * 10 + [_P, _P, _P]),
+    "vrg_composite_apply_f32": (C.c_int, [_P, _P, _P, _P, _P, _P, _P] + [C.c_int64] * 4 + [C.c_int32] * 10 + [_P]),
 }
 
 # include/vrgdg_hip_debug.h: self-tests and probes -- for the test suite and the measurement tools, not part of the drop-in boundary

@@ -642,6 +642,234 @@ def restore_frames(work: torch.Tensor, originals: torch.Tensor, source_width, so
 
 
 # ------------------------------------------------------------------------------------------------
+# feathered crop composite (Image Paste Back: VRGDG_ImagePasteBack.py:11-41, 209-262; Face Fix composite and its opaque twin:
+# VRGDG_StandaloneFaceFixNodes.py:811-854, 874-919)
+# ------------------------------------------------------------------------------------------------
+
+COMPOSITE_RULES = {"ellipse": _hip.COMPOSITE_ELLIPSE, "rectangle": _hip.COMPOSITE_RECTANGLE, "radial": _hip.COMPOSITE_RADIAL,
+                   "opaque": _hip.COMPOSITE_OPAQUE}
+PASTE_BACK_THRESHOLD, FACE_FIX_THRESHOLD = 0.25, 0.35
+
+
+@dataclass(frozen=True)
+class CompositeRule:
+    """Which alpha the composite uses and its widgets: kind "ellipse" / "rectangle" (Paste Back: `inset`, `feather`), "radial" (Face Fix:
+    `feather`, alpha times the entry's strength) or "opaque" (Face Fix Opaque: `feather` = the edge width)."""
+    kind: str
+    feather: float = 0
+    inset: float = 0
+
+
+def _linspace_step(n: int) -> float:
+    """torch.linspace(-1, 1, n) in fp32: (1 - -1) / (n - 1), one fp32 division (csrc/vrg_composite_math.hpp cp_linspace)"""
+    return float(np.float32(2.0) / np.float32(n - 1)) if n > 1 else 0.0
+
+
+def composite_table(entries, rule: CompositeRule, color_match, height: int, width: int):
+    """The descriptor table of one composite call, from Python numbers exactly as the reference computes its rectangles and constants.
+    `entries`: one dict per OUTPUT frame -- "original", "crop" (frame indices), optional "mask" (frame of the user mask), "box" =
+    (left, top, right, bottom) or None (frame returned clamped, mask zero), "strength" (radial: the alpha factor).  Returns
+    (ctypes array of _hip.CompositeDesc, list of the frames to measure, largest pasted region in pixels)."""
+    if rule.kind not in COMPOSITE_RULES:
+        raise ValueError(f"composite rule must be one of {sorted(COMPOSITE_RULES)}, got {rule.kind!r}")
+    height, width = int(height), int(width)
+    paste = rule.kind in ("ellipse", "rectangle")
+    color_match = float(color_match)
+    table = (_hip.CompositeDesc * max(1, len(entries)))()
+    match, max_pixels = [], 0
+    for f, entry in enumerate(entries):
+        d = table[f]
+        d.rule, d.original_index, d.crop_index, d.mask_index = _hip.COMPOSITE_NONE, int(entry["original"]), int(entry.get("crop", 0)), -1
+        box = entry.get("box")
+        if not box:
+            continue
+        left, top, right, bottom = (int(v) for v in box)
+        box_w, box_h = right - left, bottom - top
+        if paste:
+            # paste_back (:215-230): the rectangle is cut at the right / bottom edge; a negative corner would be Python's negative slicing
+            if box_w <= 0 or box_h <= 0:
+                raise ValueError(f"Invalid crop rectangle in CROP_DATA: {tuple(box)!r}")
+            if left < 0 or top < 0:
+                raise ValueError(f"CROP_DATA {tuple(box)!r} has a negative corner: the reference slices from the far edge there, which is not "
+                                 "a defined paste; refused")
+            left, top = min(left, width), min(top, height)
+            paste_w, paste_h = min(left + box_w, width) - left, min(top + box_h, height) - top
+            if paste_w <= 0 or paste_h <= 0:
+                d.flags = _hip.COMPOSITE_RAW_COPY                       # :233-236: the original is returned as it is, not clamped
+                continue
+            inset = max(0.0, min(float(rule.inset), (min(box_w, box_h) - 1) / 2.0))
+            if rule.kind == "ellipse":
+                cx, cy = (box_w - 1) / 2.0, (box_h - 1) / 2.0
+                rx, ry = max(0.5, cx - inset), max(0.5, cy - inset)
+                consts = (cx, cy, rx, ry, min(rx, ry))
+            else:
+                consts = (inset, box_w - 1 - inset, box_h - 1 - inset, 0.0, 0.0)
+            step = rule.feather <= 0
+            consts += (1.0 if step else float(rule.feather),)
+            flags = _hip.COMPOSITE_STEP if step else 0
+            if entry.get("mask") is not None:
+                flags |= _hip.COMPOSITE_USER_MASK
+                d.mask_index = int(entry["mask"])
+            threshold = PASTE_BACK_THRESHOLD
+        else:
+            if rule.kind == "radial" and float(entry.get("strength", 0.0)) <= 0:
+                continue                                                # the no-face decision comes first (:830): whatever the box says
+            if box_w <= 0 or box_h <= 0:
+                if rule.kind == "opaque":
+                    continue                                            # the opaque node skips an empty box (:897)
+                raise ValueError(f"Face Fix box {tuple(box)!r} is empty: the reference fails on it; refused")
+            if left < 0 or top < 0 or right > width or bottom > height:
+                raise ValueError(f"Face Fix box {tuple(box)!r} does not lie inside the {width} x {height} frame: the reference fails on a "
+                                 "shape mismatch there; refused")
+            paste_w, paste_h = box_w, box_h
+            flags = _hip.COMPOSITE_CLAMP_CROP
+            if rule.kind == "radial":
+                strength = float(entry.get("strength", 0.0))
+                feather_scale = max(1.0, float(rule.feather) / max(1.0, min(box_w, box_h) / 2.0))
+                consts = (_linspace_step(box_w), _linspace_step(box_h), feather_scale, strength)
+            else:
+                feather = max(0, int(rule.feather))
+                edge = min(1.0, (2.0 * feather) / max(1.0, float(min(box_w, box_h))))
+                if edge <= 0:
+                    flags |= _hip.COMPOSITE_STEP
+                consts = (_linspace_step(box_w), _linspace_step(box_h), edge if edge > 0 else 1.0)
+            threshold = FACE_FIX_THRESHOLD
+        if color_match > 0 and rule.kind != "opaque":
+            flags |= _hip.COMPOSITE_MATCH
+            match.append(f)
+        d.rule, d.flags = COMPOSITE_RULES[rule.kind], flags
+        d.left, d.top, d.box_w, d.box_h, d.paste_w, d.paste_h = left, top, box_w, box_h, paste_w, paste_h
+        d.match_strength, d.threshold = _f32(color_match), _f32(threshold)
+        for i, v in enumerate(consts):
+            d.p[i] = _f32(v)
+        max_pixels = max(max_pixels, paste_w * paste_h)
+    return table, match, max_pixels
+
+
+def paste_back_entries(n_originals: int, n_crops: int, n_masks: int, box) -> list:
+    """The output frames of paste_back (:221-225, _batch_item): as many as the longest input, each reading frame min(index, n - 1) of the
+    shorter ones.  `box` = (x, y, right_edge, bottom_edge) of CROP_DATA; n_masks = 0 without a user mask."""
+    frames = max(int(n_originals), int(n_crops), int(n_masks) if n_masks else 1)
+    return [{"original": min(i, n_originals - 1), "crop": min(i, n_crops - 1), "mask": min(i, n_masks - 1) if n_masks else None,
+             "box": tuple(int(v) for v in box)} for i in range(frames)]
+
+
+def face_fix_entries(entries, n_work: int, offset: int, n_originals: int, first_frame: int = 0, last_frame: Optional[int] = None) -> list:
+    """The output frames [first_frame, last_frame) of the Face Fix composites (:826-834, :887-899): source frame i takes work frame
+    i + offset while i < usable = min(len(entries), max(0, n_work - offset)); everything else is returned clamped.  "original" counts
+    from first_frame (the frames may be a piece of the batch), "strength" as the reference reads it (missing = 0)."""
+    usable = min(len(entries), max(0, int(n_work) - int(offset)))
+    last_frame = int(n_originals) if last_frame is None else int(last_frame)
+    rows = []
+    for i in range(int(first_frame), last_frame):
+        box = entries[i].get("box") if i < usable else None
+        rows.append({"original": i - int(first_frame), "crop": i + int(offset) if box else 0, "box": tuple(box) if box else None,
+                     "strength": float(entries[i].get("strength", 0.0)) if box else 0.0})
+    return rows
+
+
+def composite_channels(rule: CompositeRule, original_channels: int, crop_channels: int) -> int:
+    """How many channels are composited: Paste Back blends the channels both images have (:241, :255), the Face Fix nodes RGB."""
+    if int(original_channels) not in (3, 4):
+        raise ValueError(f"the composite is defined for 3 or 4 channels, the originals have {int(original_channels)}; refused")
+    if int(crop_channels) not in (3, 4):
+        raise ValueError(f"the composite is defined for 3 or 4 channels, the crop has {int(crop_channels)}; refused")
+    return min(int(original_channels), int(crop_channels)) if rule.kind in ("ellipse", "rectangle") else 3
+
+
+def _composite_prepare(originals, crops, entries, rule, color_match, user_mask):
+    o = _check_frames(originals, "originals")
+    c = _check_frames(crops, "crops")
+    if c.device != o.device:
+        raise RuntimeError(f"crops live on {c.device}, the originals on {o.device}")
+    if o.shape[0] < 1 or c.shape[0] < 1 or min(o.shape[1], o.shape[2], c.shape[1], c.shape[2]) < 1:
+        raise ValueError("the composite needs at least one original and one crop frame of at least one pixel")
+    nc = composite_channels(rule, o.shape[3], c.shape[3])
+    mask_h = mask_w = mask_stride = n_mask = 0
+    m = None
+    if user_mask is not None:
+        m = user_mask
+        if not isinstance(m, torch.Tensor) or m.ndim not in (3, 4) or m.dtype != torch.float32 or m.device != o.device:
+            raise ValueError("user_mask must be a float32 [frames, height, width] (or [..., channels]) tensor on the originals' device")
+        m = m if m.is_contiguous() else m.contiguous()
+        n_mask, mask_h, mask_w = int(m.shape[0]), int(m.shape[1]), int(m.shape[2])
+        mask_stride = int(m.shape[3]) if m.ndim == 4 else 1
+        if min(n_mask, mask_h, mask_w, mask_stride) < 1:
+            raise ValueError("user_mask must not be empty")
+    table, match, max_pixels = composite_table(entries, rule, color_match, o.shape[1], o.shape[2])
+    frames = len(entries)
+    for f in range(frames):
+        d = table[f]
+        if not 0 <= d.original_index < o.shape[0] or not 0 <= d.crop_index < c.shape[0]:
+            raise ValueError(f"entry {f} names original {d.original_index} / crop {d.crop_index} of {int(o.shape[0])} / {int(c.shape[0])}")
+        if d.flags & _hip.COMPOSITE_USER_MASK and not 0 <= d.mask_index < n_mask:
+            raise ValueError(f"entry {f} names frame {d.mask_index} of a user mask of {n_mask}")
+    # one upload: the records, then the list of frames to measure
+    raw = bytes(memoryview(table))[:frames * C.sizeof(_hip.CompositeDesc)] + np.asarray(match, dtype=np.int32).tobytes()
+    dev_table = torch.frombuffer(bytearray(raw) or bytearray(4), dtype=torch.uint8).to(o.device)
+    geom = (frames, int(o.shape[0]), int(c.shape[0]), n_mask, int(c.shape[1]), int(c.shape[2]), int(c.shape[3]), int(o.shape[1]),
+            int(o.shape[2]), int(o.shape[3]), mask_h, mask_w, mask_stride, nc)
+    stats = torch.zeros((max(frames, 1), _hip.COMPOSITE_STATS_WORDS), dtype=torch.int32, device=o.device)
+    return o, c, m, dev_table, match, max_pixels, geom, stats
+
+
+def _composite_measure(o, c, m, dev_table, match, max_pixels, geom, stats):
+    if not match:
+        return
+    lib = _hip.lib()
+    scratch = torch.empty(int(lib.vrg_composite_scratch_bytes(len(match), max_pixels)), dtype=torch.uint8, device=o.device)
+    match_ptr = C.c_void_p(dev_table.data_ptr() + geom[0] * C.sizeof(_hip.CompositeDesc))
+    _hip.check(lib.vrg_composite_stats_f32(_hip.ptr(c), _hip.ptr(o), _hip.ptr(m) if m is not None else None, _hip.ptr(dev_table), match_ptr,
+                                           len(match), max_pixels, *geom, _hip.ptr(scratch), _hip.ptr(stats), _hip.current_stream()),
+               "vrg_composite_stats_f32")
+
+
+def _stats_record(stats: torch.Tensor, frames: int) -> dict:
+    words = stats[:frames]
+    f32 = words.view(torch.float32)
+    return {"count": words[:, 0], "matched": words[:, 1], "crop_mean": f32[:, 2:6], "original_mean": f32[:, 6:10], "shift": f32[:, 10:14]}
+
+
+@_on_device
+def composite_stats(originals: torch.Tensor, crops: torch.Tensor, entries, rule: CompositeRule, color_match, user_mask=None) -> dict:
+    """What the colour match of composite_frames measures, per output frame, as device tensors: "count" (selected pixels, int32),
+    "matched" (count >= 16), "crop_mean" / "original_mean" ([frames, 4] fp32, fp64-accumulated) and "shift".  Zero for frames that are not
+    measured (no box, strength 0, the opaque rule)."""
+    prepared = _composite_prepare(originals, crops, entries, rule, color_match, user_mask)
+    _composite_measure(*prepared)
+    return _stats_record(prepared[-1], len(entries))
+
+
+@_on_device
+def composite_frames(originals: torch.Tensor, crops: torch.Tensor, entries, rule: CompositeRule, color_match=0.0, user_mask=None,
+                     out: Optional[torch.Tensor] = None, mask_out: Optional[torch.Tensor] = None):
+    """The feathered crop composite on device frames: for every entry (see composite_table) the crop is bicubic-resized to its box, blended
+    over the original under the rule's alpha (times the bilinear-resized, clamped `user_mask`), after the mean-shift colour match when
+    color_match > 0 and at least 16 pixels have alpha above the threshold -- decided on the device, no host synchronisation.  Returns
+    (frames [len(entries), H, W, C] clamped to [0, 1], masks [len(entries), H, W]).  Two measuring launches (only for frames that ask for
+    a match) and one pass over the output."""
+    o, c, m, dev_table, match, max_pixels, geom, stats = _composite_prepare(originals, crops, entries, rule, color_match, user_mask)
+    frames = len(entries)
+    shape = (frames, int(o.shape[1]), int(o.shape[2]), int(o.shape[3]))
+    for name, t, want in (("out", out, shape), ("mask_out", mask_out, shape[:3])):
+        if t is not None and (tuple(t.shape) != want or t.dtype != torch.float32 or not t.is_contiguous() or t.device != o.device):
+            raise ValueError(f"{name} must be a contiguous float32 tensor shaped {want} on the frames' device")
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=o.device)
+    if mask_out is None:
+        mask_out = torch.empty(shape[:3], dtype=torch.float32, device=o.device)
+    if out.data_ptr() in (o.data_ptr(), c.data_ptr()):
+        raise ValueError("out must not be an input")
+    if frames == 0:
+        return out, mask_out
+    _composite_measure(o, c, m, dev_table, match, max_pixels, geom, stats)
+    _hip.check(_hip.lib().vrg_composite_apply_f32(_hip.ptr(c), _hip.ptr(o), _hip.ptr(m) if m is not None else None, _hip.ptr(dev_table),
+                                                 _hip.ptr(stats), _hip.ptr(out), _hip.ptr(mask_out), *geom, _hip.current_stream()),
+               "vrg_composite_apply_f32")
+    return out, mask_out
+
+
+# ------------------------------------------------------------------------------------------------
 # 13-slider Adjust (video routes)
 # ------------------------------------------------------------------------------------------------
 

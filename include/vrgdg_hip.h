@@ -344,6 +344,69 @@ int vrg_restore_f32(const float* work, const float* originals, float* out, int64
                     int32_t channels, int32_t method, float strength, float one_minus_strength, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Feathered crop composite.  Replaces the per-frame loops of VRGDG_ImagePasteBack.paste_back (VRGDG_ImagePasteBack.py:224-260),
+ * VRGDGFaceFixComposite.composite and VRGDGFaceFixCompositeOpaque.composite (VRGDG_StandaloneFaceFixNodes.py:827-849, 891-916):
+ * a crop / work frame is bicubic-resized to a box of the frame, an analytic alpha (x an optional bilinear-resized user mask) is
+ * formed, the crop is optionally shifted towards the mean colour of the frame under the alpha (measured on the device), blended in,
+ * and the whole frame clamped.  csrc/vrg_composite_math.hpp states each rule.
+ * ------------------------------------------------------------------------------------------- */
+enum vrg_composite_rule {
+    VRG_COMPOSITE_NONE = 0,        /* no box: out = clamp(original, 0, 1) (or the original itself: VRG_COMPOSITE_RAW_COPY), mask = 0 */
+    VRG_COMPOSITE_ELLIPSE = 1,     /* Paste Back: p = cx, cy, rx, ry, min(rx, ry), feather */
+    VRG_COMPOSITE_RECTANGLE = 2,   /* Paste Back: p = inset, width - 1 - inset, height - 1 - inset, -, -, feather */
+    VRG_COMPOSITE_RADIAL = 3,      /* Face Fix: p = linspace step x, step y, feather_scale, entry strength */
+    VRG_COMPOSITE_OPAQUE = 4       /* Face Fix Opaque: p = linspace step x, step y, edge */
+};
+enum vrg_composite_flags {
+    VRG_COMPOSITE_CLAMP_CROP = 1,  /* clamp the resampled crop to [0, 1] before anything else (Face Fix) */
+    VRG_COMPOSITE_MATCH = 2,       /* colour match requested (strength > 0): the frame is measured by vrg_composite_stats_f32 */
+    VRG_COMPOSITE_STEP = 4,        /* feather <= 0 / edge <= 0: alpha is the 0 / 1 step */
+    VRG_COMPOSITE_USER_MASK = 8,   /* multiply the resized, clamped user mask in */
+    VRG_COMPOSITE_RAW_COPY = 16    /* with VRG_COMPOSITE_NONE: out = original as it is, not clamped (Paste Back with the rectangle outside the frame) */
+};
+/* One OUTPUT frame.  The box (left, top, box_w x box_h) is the resample target; paste_w x paste_h is its part inside the frame
+ * (the box may hang over the right / bottom edge; left, top >= 0).  All constants are fp32 roundings of the reference's Python
+ * doubles, formed by the caller. */
+typedef struct vrg_composite_desc {
+    int32_t rule, flags;
+    int32_t original_index, crop_index, mask_index;   /* frames of `originals`, `crops`, `user_mask` this output frame reads */
+    int32_t left, top, box_w, box_h, paste_w, paste_h;
+    float match_strength;                              /* (float)color_match */
+    float threshold;                                   /* selected = alpha > threshold: 0.25 Paste Back, 0.35 Face Fix */
+    float p[7];
+} vrg_composite_desc;
+
+/* Bytes of `scratch` for vrg_composite_stats_f32 measuring `frames` frames whose pasted regions hold at most `max_box_pixels`. */
+int64_t vrg_composite_scratch_bytes(int64_t frames, int64_t max_box_pixels);
+
+/* Measures the `n_match` output frames listed in `match_frames` (device, int32, ascending): over the pixels of the pasted region
+ * with alpha > threshold, the selected count and the fp64-accumulated means of the resampled crop and of the original under it.
+ * Writes for each listed frame f the record stats[f] of 16 32-bit words: [0] count (int32), [1] matched = count >= 16 (int32),
+ * [2..5] crop means, [6..9] original means, [10..13] shift = fl(fl(original mean - crop mean) * match_strength) (fp32; channels
+ * past `match_channels` and everything of an unmatched frame's shift are 0), [14..15] 0.  Records of other frames are not touched.
+ * Partial sums are combined in a fixed order: the same inputs give the same bits on every run.  `desc`: device, one record per
+ * output frame.  crops [.][crop_h][crop_w][crop_channels], originals [.][height][width][channels], user_mask (or NULL)
+ * [.][mask_h][mask_w] with `mask_stride` floats between mask pixels; match_channels (3 or 4) <= both channel counts.  `frames` = records in `desc`
+ * and `stats`; a record whose indices or box do not fit the stated frame counts and sizes is treated as VRG_COMPOSITE_NONE. */
+int vrg_composite_stats_f32(const float* crops, const float* originals, const float* user_mask, const vrg_composite_desc* desc,
+                            const int32_t* match_frames, int64_t n_match, int64_t max_box_pixels,
+                            int64_t frames, int64_t original_frames, int64_t crop_frames, int64_t mask_frames,
+                            int32_t crop_h, int32_t crop_w, int32_t crop_channels, int32_t height, int32_t width, int32_t channels,
+                            int32_t mask_h, int32_t mask_w, int32_t mask_stride, int32_t match_channels,
+                            void* scratch, void* stats, void* stream);
+
+/* One pass over `frames` output frames [height][width][channels] and their masks [height][width]: outside the frame's box
+ * out = clamp(original, 0, 1), mask = 0; inside, the first match_channels channels are
+ *     clamp(fl(fl(original * fl(1 - alpha)) + fl(crop' * alpha)), 0, 1),  crop' = matched ? clamp(crop + shift, 0, 1) : crop
+ * with `matched` and `shift` from stats[f] when the frame has VRG_COMPOSITE_MATCH, further channels clamp(original), mask = alpha.
+ * `out` aliases no input.  channels is 3 or 4. */
+int vrg_composite_apply_f32(const float* crops, const float* originals, const float* user_mask, const vrg_composite_desc* desc,
+                            const void* stats, float* out, float* mask_out,
+                            int64_t frames, int64_t original_frames, int64_t crop_frames, int64_t mask_frames,
+                            int32_t crop_h, int32_t crop_w, int32_t crop_channels, int32_t height, int32_t width, int32_t channels,
+                            int32_t mask_h, int32_t mask_w, int32_t mask_stride, int32_t match_channels, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Introspection
  * ------------------------------------------------------------------------------------------- */
 int vrg_abi_version(void);
