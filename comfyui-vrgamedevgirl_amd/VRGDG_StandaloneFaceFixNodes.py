@@ -1,6 +1,13 @@
-"""Face Fix composite on the MI355X: `VRGDGFaceFixComposite` and `VRGDGFaceFixCompositeOpaque` of the reference's
-VRGDG_StandaloneFaceFixNodes.py with the same names, widget specs, tooltips, messages and log lines; the pixels come from
-csrc/vrg_composite.hip (ops.composite_frames).
+"""Face Fix on the MI355X: the crop sequence of the reference's Prepare nodes and its two composite nodes.
+
+`VRGDGFaceFixComposite` and `VRGDGFaceFixCompositeOpaque` of the reference's VRGDG_StandaloneFaceFixNodes.py with the same names, widget
+specs, tooltips, messages and log lines; the pixels come from csrc/vrg_composite.hip (ops.composite_frames).
+
+`face_crop_sequence` is the outgoing half: the video and its tracked face boxes (the `entries` a Prepare node builds) become the
+512 x 512 face video that LTX repairs and the composites paste back.  The reference crops frame by frame (slice, permute, bicubic
+F.interpolate, permute, clamp), fills the frames without a face with copies, prefixes copies of the first crop and stacks the list; here
+the whole batch -- crops, filled holes, prefix -- is one launch of csrc/vrg_crop.hip (ops.crop_frames), and of CPU frames only the boxes
+are uploaded (ops.crop_frames_host).
 
 The reference composites frame by frame in Python (about twenty eager ops, a host synchronisation and a boolean gather per frame, a full
 clone of the originals); here the whole batch is two small measuring launches and one pass over the output, and whether a frame's colour
@@ -8,11 +15,14 @@ match applies (at least 16 pixels with alpha > 0.35) is decided on the device.  
 the host-fed pipeline of _devices in pieces along the frame axis, the much smaller work frames are uploaded once ahead; device tensors are
 processed where they are.  Inputs are never written.  The repaired count is computed on the host from the entries.
 
-What is NOT here: detection and tracking (Prepare / Collect nodes, cv2), the landmark-aligned composite (cv2 warp),
-and the registration in the package's NODE_CLASS_MAPPINGS: INTEGRATION.md shows the two lines.  The nodes are eager.
+What is NOT here: detection and tracking (cv2 DNN, candidate choice, cut scoring, anchor selection and the anchor
+PNG dump) and with them the Prepare / Collect node classes -- a Prepare node calls face_crop_sequence once after its detection loop,
+INTEGRATION.md shows the lines; the landmark-aligned composite (cv2 warp); and the registration in the package's NODE_CLASS_MAPPINGS:
+INTEGRATION.md shows the two lines.  The nodes are eager.
 
 Refused with a ValueError, because the reference fails on them rather than defines them: a box that does not lie inside its frame (shape
-mismatch in the reference), an empty box in VRGDGFaceFixComposite, and channel counts other than 3 or 4.
+mismatch in the reference's composite, a smaller crop than the box in its Prepare), an empty box in VRGDGFaceFixComposite and in the crop
+sequence, and channel counts other than 3 or 4 in the composites.
 """
 from __future__ import annotations
 
@@ -26,6 +36,27 @@ FACE_FIX_CONTEXT = "VRGDG_FACE_FIX_CONTEXT"
 
 def _log(message):
     print(f"[VRGDG Face Fix] {message}", flush=True)
+
+
+def face_crop_sequence(video_frames, entries, *, per_shot=False, anchors=None):
+    """The crop / fill / prefix / stack / anchor-gather lines of VRGDGFaceFixPrepare.prepare (per_shot=False) and
+    VRGDGFaceFixPrepareShotAware.prepare (per_shot=True: holes take the first crop of their entry's "shot_id").  `entries`: one dict per
+    video frame, "box" = (left, top, right, bottom) or None.  Returns (crop_batch [ltx_offset + frames, 512, 512, 3], anchor_batch =
+    crop_batch[ltx_offset:][anchors] or None, ltx_offset) -- the context fields "entries", "original_frames" and "ltx_frame_offset" of
+    the reference go with it unchanged to the composite nodes.  Device frames are cropped where they are and the batch stays there; of CPU
+    frames only the boxes are uploaded, the batch comes back on the intermediate device.  `video_frames` is never written."""
+    if not isinstance(video_frames, torch.Tensor) or video_frames.ndim != 4 or video_frames.shape[0] < 1:
+        raise ValueError("Face Fix Prepare requires a non-empty IMAGE batch from a video loader.")
+    count, height, width = (int(v) for v in video_frames.shape[:3])
+    plan = ops.crop_sequence_plan(entries, count, height, width, per_shot=per_shot)        # refuses before anything is uploaded
+    if video_frames.is_cuda:
+        crop_batch = ops.crop_frames(video_frames.to(torch.float32), plan)
+    else:
+        crop_batch = ops.crop_frames_host(video_frames, plan)
+    anchor_batch = None
+    if anchors is not None:
+        anchor_batch = crop_batch[plan.ltx_offset:][torch.tensor([int(a) for a in anchors], device=crop_batch.device, dtype=torch.long)]
+    return crop_batch, anchor_batch, plan.ltx_offset
 
 
 class _Plan:

@@ -72,6 +72,12 @@ class CompositeDesc(C.Structure):
                 ("match_strength", C.c_float), ("threshold", C.c_float), ("p", C.c_float * 7)]
 
 
+class CropDesc(C.Structure):
+    """vrg_crop_desc"""
+    _fields_ = [("src_offset", C.c_int64), ("row_pitch", C.c_int32), ("pixel_stride", C.c_int32),
+                ("box_w", C.c_int32), ("box_h", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 _F3 = C.c_float * 3
 _P = C.c_void_p
 _SIGNATURES = {
@@ -125,6 +131,7 @@ _SIGNATURES = {
     "vrg_composite_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "vrg_composite_stats_f32": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int64] + [C.c_int64] * 4 + [C.c_int32] * 10 + [_P, _P, _P]),
     "vrg_composite_apply_f32": (C.c_int, [_P, _P, _P, _P, _P, _P, _P] + [C.c_int64] * 4 + [C.c_int32] * 10 + [_P]),
+    "vrg_crop_resize_f32": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
 }
 
 # include/vrgdg_hip_debug.h: self-tests and probes -- for the test suite and the measurement tools, not part of the drop-in boundary

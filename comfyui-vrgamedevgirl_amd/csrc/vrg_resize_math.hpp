@@ -155,4 +155,11 @@ VRG_HD void rs_pixel(const ResizeGeom& g, int32_t method, int32_t ox, int32_t oy
     }
 }
 
+// A box crop (csrc/vrg_crop.hip: the Face Fix work frames) is rs_pixel on a view: the box [box_h][box_w] is the whole input frame AND the
+// source rectangle -- so the taps are clamped to the box, not to the frame it was cut from, as F.interpolate sees the sliced view -- and
+// the size_h x size_w output frame is the whole destination.  `load(y, x, c)` then takes box coordinates.
+VRG_HD ResizeGeom rs_box_geom(int32_t box_w, int32_t box_h, int32_t channels, int32_t size_w, int32_t size_h) {
+    return ResizeGeom{box_h, box_w, channels, 0, 0, box_w, box_h, size_h, size_w, 0, 0, size_w, size_h};
+}
+
 }  // namespace vrg

@@ -13,6 +13,7 @@ from __future__ import annotations
 import ctypes as C
 import functools
 import math
+import operator
 import os
 import threading
 from dataclasses import dataclass
@@ -867,6 +868,199 @@ def composite_frames(originals: torch.Tensor, crops: torch.Tensor, entries, rule
                                                  _hip.ptr(stats), _hip.ptr(out), _hip.ptr(mask_out), *geom, _hip.current_stream()),
                "vrg_composite_apply_f32")
     return out, mask_out
+
+
+# ------------------------------------------------------------------------------------------------
+# Face Fix crop sequence (both Prepare nodes: VRGDG_StandaloneFaceFixNodes.py:320-351, 387-389, 486-516, 537-539)
+# ------------------------------------------------------------------------------------------------
+
+CROP_SIZE = (512, 512)           # the reference's F.interpolate(size=(512, 512))
+_CROP_DESC = np.dtype([("src_offset", "<i8"), ("row_pitch", "<i4"), ("pixel_stride", "<i4"), ("box_w", "<i4"), ("box_h", "<i4"),
+                       ("reserved", "<i4", (2,))])
+assert _CROP_DESC.itemsize == C.sizeof(_hip.CropDesc)
+
+
+@dataclass(frozen=True)
+class CropPlan:
+    """Which rectangle every OUTPUT frame of the crop sequence is resampled from: `sources[k]` = (source frame, (left, top, right,
+    bottom)) for output frame k, the `ltx_offset` prefix frames first; `frames`, `height`, `width`: the video the plan was made for."""
+    frames: int
+    height: int
+    width: int
+    ltx_offset: int
+    sources: tuple
+
+    @property
+    def count(self) -> int:
+        return len(self.sources)
+
+
+def _crop_box(box, index: int, height: int, width: int):
+    try:
+        values = tuple(box)
+        if len(values) != 4:
+            raise TypeError
+        left, top, right, bottom = (operator.index(v) for v in values)
+    except TypeError:
+        raise ValueError(f"Face Fix box {box!r} of frame {index} is not four integers (left, top, right, bottom); refused") from None
+    if right <= left or bottom <= top:
+        raise ValueError(f"Face Fix box {(left, top, right, bottom)!r} of frame {index} is empty: the reference fails on it; refused")
+    if left < 0 or top < 0 or right > width or bottom > height:
+        raise ValueError(f"Face Fix box {(left, top, right, bottom)!r} of frame {index} does not lie inside the {width} x {height} frame: "
+                         "the reference crops less than the box there; refused")
+    return left, top, right, bottom
+
+
+def crop_sequence_plan(entries, frames: int, height: int, width: int, *, per_shot: bool = False) -> CropPlan:
+    """Which output frame of the Face Fix crop sequence reads which (source frame, box) -- the list work of both Prepare nodes without
+    the pixels.  An entry has a crop when entry["box"] is truthy.  A frame without one takes the last crop before it, leading ones the
+    first crop of the video (:333-342); with per_shot the first crop of its entry["shot_id"], a shot without any the first crop of the
+    video (:501-511).  (-(frames - 1)) % 8 copies of output frame 0 go in front (:348-351): `ltx_offset`.  Pure Python."""
+    frames, height, width = int(frames), int(height), int(width)
+    entries = list(entries)
+    if len(entries) != frames:
+        raise ValueError(f"{len(entries)} Face Fix entries for {frames} video frames; refused")
+    own = [(i, _crop_box(entry["box"], i, height, width)) if entry.get("box") else None for i, entry in enumerate(entries)]
+    valid = [s for s in own if s is not None]
+    if not valid:
+        raise ValueError("No face was detected in the video. Lower confidence or minimum face pixels.")
+    filled = list(own)
+    if per_shot:
+        first_of_shot = {}
+        for entry, s in zip(entries, own):
+            if s is not None:
+                first_of_shot.setdefault(entry["shot_id"], s)
+        for i, entry in enumerate(entries):
+            if filled[i] is None:
+                filled[i] = first_of_shot.get(entry["shot_id"], valid[0])
+    else:
+        last = valid[0]
+        for i in range(frames):
+            if filled[i] is None:
+                filled[i] = last
+            else:
+                last = filled[i]
+    ltx_offset = (-(frames - 1)) % 8
+    return CropPlan(frames, height, width, ltx_offset, tuple([filled[0]] * ltx_offset + filled))
+
+
+def _crop_size(size):
+    size_h, size_w = (int(v) for v in size)
+    if size_h < 1 or size_w < 1:
+        raise ValueError(f"crop size {size!r}: the work frames must have at least one pixel")
+    return size_h, size_w
+
+
+@_on_device
+def crop_resize(source: torch.Tensor, records, size=CROP_SIZE, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One launch of vrg_crop_resize_f32: `source` = any contiguous float32 device tensor, `records` = one (src_offset, row_pitch,
+    pixel_stride, box_w, box_h) per output frame, in floats from the start of `source` (include/vrgdg_hip.h, vrg_crop_desc).  Every record
+    is checked against the size of `source` here: one that reaches outside is a ValueError, nothing is launched.  Returns
+    [len(records), size_h, size_w, 3], clamped to [0, 1]."""
+    if not isinstance(source, torch.Tensor) or source.dtype != torch.float32 or not source.is_contiguous():
+        raise ValueError("source must be a contiguous float32 tensor")
+    if not source.is_cuda:
+        raise RuntimeError("source must live on the GPU (ops.* are device-resident; crop_frames_host packs CPU frames)")
+    size_h, size_w = _crop_size(size)
+    table = np.zeros(len(records), dtype=_CROP_DESC)
+    if len(records):
+        rec = np.asarray(records, dtype=np.int64).reshape(len(records), 5)
+        offset, pitch, stride, box_w, box_h = (rec[:, k] for k in range(5))
+        if (box_w < 1).any() or (box_h < 1).any() or (stride < 3).any() or (pitch < 0).any() or (offset < 0).any() or (rec[:, 1:] > 0x7fffffff).any():
+            raise ValueError("crop record with an empty box, a pixel stride below 3 or a negative offset / pitch; refused")
+        last = offset + (box_h - 1) * pitch + (box_w - 1) * stride + 3
+        bad = np.nonzero((last > source.numel()) | (box_w * stride > 0x7fffffff))[0]
+        if bad.size:
+            k = int(bad[0])
+            raise ValueError(f"crop record {k} {tuple(int(v) for v in rec[k])} reaches float {int(last[k])} of a source of {source.numel()}; refused")
+        for k, name in enumerate(("src_offset", "row_pitch", "pixel_stride", "box_w", "box_h")):
+            table[name] = rec[:, k]
+    shape = (len(records), size_h, size_w, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=source.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != source.device:
+        raise ValueError(f"out must be a contiguous float32 tensor shaped {shape} on the frames' device")
+    if len(records) == 0:
+        return out
+    if out.data_ptr() == source.data_ptr():
+        raise ValueError("out must not be the source")
+    dev_table = torch.from_numpy(table.view(np.uint8)).to(source.device)
+    _hip.check(_hip.lib().vrg_crop_resize_f32(_hip.ptr(source), source.numel(), _hip.ptr(out), _hip.ptr(dev_table), len(records), size_h, size_w,
+                                             _hip.current_stream()), "vrg_crop_resize_f32")
+    return out
+
+
+def _check_crop_plan(plan: CropPlan, shape):
+    if not isinstance(plan, CropPlan):
+        raise ValueError("plan must come from crop_sequence_plan")
+    if (int(shape[0]), int(shape[1]), int(shape[2])) != (plan.frames, plan.height, plan.width):
+        raise ValueError(f"the plan was made for {plan.frames} frames of {plan.width} x {plan.height}, the video has {int(shape[0])} of "
+                         f"{int(shape[2])} x {int(shape[1])}")
+    if int(shape[3]) < 3:
+        raise ValueError(f"frames must have at least 3 channels, got {int(shape[3])}")
+
+
+def crop_frames(frames: torch.Tensor, plan: CropPlan, size=CROP_SIZE, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The Face Fix crop sequence of device-resident `frames` ([F, H, W, C >= 3] float32, never written): output frame k is the box
+    plan.sources[k] bicubic-resampled to `size` and clamped -- crops, filled holes and the LTX prefix in one launch, no intermediate.
+    Returns [plan.ltx_offset + F, size_h, size_w, 3] on the frames' device."""
+    x = _check_frames(frames, "frames")
+    _check_crop_plan(plan, x.shape)
+    h, w, c = int(x.shape[1]), int(x.shape[2]), int(x.shape[3])
+    records = [(((f * h + top) * w + left) * c, w * c, c, right - left, bottom - top) for f, (left, top, right, bottom) in plan.sources]
+    return crop_resize(x, records, size, out)
+
+
+def crop_frames_host(frames_cpu: torch.Tensor, plan: CropPlan, size=CROP_SIZE) -> torch.Tensor:
+    """crop_frames for CPU frames: only the boxes cross to the GPU.  Every DISTINCT (frame, box) of the plan is packed once as
+    [box_h][box_w][3] float32 into a page-locked buffer (a strided torch copy per box), uploaded, and the records point into the pack;
+    whole frames are never uploaded.  A pack above VRGDG_PIN_LIMIT_GB goes through in pieces along the output-frame axis.  The batch is
+    returned on intermediate_device()."""
+    from . import _devices
+    if not isinstance(frames_cpu, torch.Tensor) or frames_cpu.ndim != 4 or frames_cpu.is_cuda:
+        raise ValueError("frames_cpu must be a CPU [frames, height, width, channels] tensor")
+    _check_crop_plan(plan, frames_cpu.shape)
+    size_h, size_w = _crop_size(size)
+    dev = _devices.compute_device()
+    pin = _devices.PIN_LIMIT_BYTES > 0
+    limit = (_devices.PIN_LIMIT_BYTES if pin else _devices.STAGE_BYTES) // 4                   # floats per piece
+    with torch.cuda.device(dev):
+        out = torch.empty((plan.count, size_h, size_w, 3), dtype=torch.float32, device=dev)
+        first = 0
+        while first < plan.count:
+            # the output frames [first, stop) whose distinct boxes fit one pack (one box alone always goes)
+            where, floats, stop = {}, 0, first
+            while stop < plan.count:
+                src = plan.sources[stop]
+                if src not in where:
+                    left, top, right, bottom = src[1]
+                    n = (right - left) * (bottom - top) * 3
+                    if where and floats + n > limit:
+                        break
+                    where[src] = floats
+                    floats += n
+                stop += 1
+            pack = None
+            if pin:
+                try:
+                    pack = torch.empty(floats, dtype=torch.float32, pin_memory=True)
+                except RuntimeError:                  # the host refused to page-lock that much: pageable pack
+                    pack = None
+            if pack is None:
+                pack = torch.empty(floats, dtype=torch.float32)
+            for (f, (left, top, right, bottom)), at in where.items():
+                bw, bh = right - left, bottom - top
+                pack[at:at + bh * bw * 3].view(bh, bw, 3).copy_(frames_cpu[f, top:bottom, left:right, :3])
+            records = [(where[s], (s[1][2] - s[1][0]) * 3, 3, s[1][2] - s[1][0], s[1][3] - s[1][1]) for s in plan.sources[first:stop]]
+            crop_resize(pack.to(dev, non_blocking=True), records, (size_h, size_w), out[first:stop])
+            torch.cuda.current_stream().synchronize()  # the pack is reused by the allocator once it is dropped
+            first = stop
+    return out.to(_devices.intermediate_device())
+
+
+def crop_host_bytes(plan: CropPlan) -> int:
+    """Bytes crop_frames_host uploads for `plan`: its distinct boxes as float32 RGB."""
+    return sum((r - l) * (b - t) * 12 for _, (l, t, r, b) in set(plan.sources))
 
 
 # ------------------------------------------------------------------------------------------------

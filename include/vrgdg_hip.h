@@ -407,6 +407,30 @@ int vrg_composite_apply_f32(const float* crops, const float* originals, const fl
                             int32_t mask_h, int32_t mask_w, int32_t mask_stride, int32_t match_channels, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Face Fix crop sequence.  Replaces the per-frame crop (slice, permute, F.interpolate bicubic, permute, clamp), the hole filling, the
+ * LTX prefix and the torch.stack of VRGDGFaceFixPrepare.prepare and VRGDGFaceFixPrepareShotAware.prepare
+ * (VRGDG_StandaloneFaceFixNodes.py:320-351, 387-389, 486-516, 537-539): one launch produces the whole 512 x 512 work batch.
+ * ------------------------------------------------------------------------------------------- */
+/* One OUTPUT frame: the rectangle of RGB(+) pixels it is resampled from.  A rectangle inside device-resident frames [F][H][W][C] is
+ * src_offset = ((f*H + top)*W + left)*C, row_pitch = W*C, pixel_stride = C; a rectangle packed on its own [box_h][box_w][3] is
+ * row_pitch = box_w*3, pixel_stride = 3.  Records may repeat (a hole re-reads another frame's rectangle): equal records give output
+ * frames that are equal bit for bit. */
+typedef struct vrg_crop_desc {
+    int64_t src_offset;      /* floats from `in` to the rectangle's first value */
+    int32_t row_pitch;       /* floats between rows of the rectangle */
+    int32_t pixel_stride;    /* floats between pixels: the source's channel count (>= 3); the first three are read */
+    int32_t box_w, box_h;    /* >= 1 */
+    int32_t reserved[2];     /* 0 */
+} vrg_crop_desc;
+
+/* out = [n_out][size_h][size_w][3]; frame f = clamp(bicubic(rectangle of desc[f] -> size_h x size_w), 0, 1) in the arithmetic of
+ * vrg_resize_f32 with the rectangle as the resampled view (taps clamped to the rectangle, not to the frame around it).  `desc`: device,
+ * n_out records.  `in_floats`: the floats readable from `in`; a record whose rectangle does not lie inside them (or with a size < 1, a
+ * pixel stride < 3, a negative offset or pitch) is never read: its frame is written as zeros.  The caller checks its table on the host. */
+int vrg_crop_resize_f32(const float* in, int64_t in_floats, float* out, const vrg_crop_desc* desc, int64_t n_out,
+                        int32_t size_h, int32_t size_w, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Introspection
  * ------------------------------------------------------------------------------------------- */
 int vrg_abi_version(void);
