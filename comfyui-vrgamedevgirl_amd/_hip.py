@@ -132,6 +132,10 @@ _SIGNATURES = {
     "vrg_composite_stats_f32": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int64] + [C.c_int64] * 4 + [C.c_int32] * 10 + [_P, _P, _P]),
     "vrg_composite_apply_f32": (C.c_int, [_P, _P, _P, _P, _P, _P, _P] + [C.c_int64] * 4 + [C.c_int32] * 10 + [_P]),
     "vrg_crop_resize_f32": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
+    "vrg_lanczos4_taps": (C.c_int, [C.c_int32] * 4 + [_P]),
+    "vrg_lanczos4_u8": (C.c_int, [_P, _P, C.c_int64] + [C.c_int32] * 4 + [_P, _P]),
+    "vrg_upscale_sharpen_grain_u8": (C.c_int, [_P, _P, C.c_int64] + [C.c_int32] * 4 + [_P, C.c_float, C.c_int32, C.c_float, C.c_float, C.c_float,
+                                               C.POINTER(NoiseDesc), _P]),
 }
 
 # include/vrgdg_hip_debug.h: self-tests and probes -- for the test suite and the measurement tools, not part of the drop-in boundary

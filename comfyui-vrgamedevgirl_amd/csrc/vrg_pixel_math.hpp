@@ -526,6 +526,18 @@ VRG_HD float stencil_value(int op, const float p[3][3], float strength, int zero
     if (op == 1) return laplacian_value(p, strength, zero_border);
     return sobel_value(p, strength, zero_border);
 }
+// The stand-alone enhancer's byte pipeline on one byte whose taps are already / 255: unsharp (p = the 3 x 3 window of this byte's channel, borders
+// applied) -> per-frame-seeded grain -> * 255 clip truncate.  Shared by k_sharpen_grain_u8, k_sharpen_grain_u8_any (csrc/vrg_pointwise.hip)
+// and the fused upscale (csrc/vrg_lanczos.hip); SHARP / GRAIN off
+// leave the step out as ops.sharpen_then_seeded_grain does.  `channel`: 0 = R .. 2 = B (byte j of a B,G,R pixel is channel 2 - j).
+template <bool SHARP, bool GRAIN>
+VRG_HD uint8_t sharpen_grain_byte(const float p[3][3], float strength, int zero_border, float n_own, float n_green, int channel, float I,
+                                  float S, float T) {
+    const float x = SHARP ? stencil_value(0, p, strength, zero_border) : p[1][1];
+    const float res = GRAIN ? grain_element(x, n_own, n_green, channel, I, S, T) : x;
+    return u8_from_unit(res);
+}
+
 // The three channels of a pixel whose taps are in [0, 1] or NaN (the colour transfer's output): the same values with the three clamps behind
 // one NaN test (clamp01_3) and the unsharp mean without its Inf pass-through
 VRG_HD void stencil_value3_unit(int op, const float p[3][3][3], float strength, int zero_border, float o[3]) {

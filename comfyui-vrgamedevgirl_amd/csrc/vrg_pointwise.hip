@@ -480,11 +480,9 @@ __global__ __launch_bounds__(256) void k_sharpen_grain_u8(const uint32_t* __rest
                 p[r][1] = o[r][kk];
                 p[r][2] = kk < 1 ? o[r][kk < 1 ? kk + 3 : 0] : nr[r][kk >= 1 ? kk - 1 : 0];
             }
-            const float x = stencil_value(0, p, strength, ZERO ? 1 : 0);
             const float n_own = sn[ii][4 + t4 + kk + 2 - 2 * jj];     // element 3 p + 2 - jj of byte 3 p + jj
             const float n_green = sn[ii][4 + t4 + kk + 1 - jj];       // element 3 p + 1
-            const float res = grain_element(x, n_own, n_green, 2 - jj, I, S, T);
-            packed |= (uint32_t)u8_from_unit(res) << (8 * kk);
+            packed |= (uint32_t)sharpen_grain_byte<true, true>(p, strength, ZERO ? 1 : 0, n_own, n_green, 2 - jj, I, S, T) << (8 * kk);
             jj = (jj == 2) ? 0 : jj + 1;
         }
         if (v < nvec) fout[v] = packed;
@@ -645,11 +643,9 @@ __global__ __launch_bounds__(256) void k_sharpen_grain_u8_any(const uint8_t* __r
                     p[2][j] = bot[kk] ? (ZERO ? 0.0f : p[1][j]) : p[2][j];
                 }
             }
-            const float x = stencil_value(0, p, strength, ZERO ? 1 : 0);
             const float n_own = sn[ii][4 + t4 + kk + 2 - 2 * jj];     // element 3 p + 2 - jj of byte 3 p + jj
             const float n_green = sn[ii][4 + t4 + kk + 1 - jj];       // element 3 p + 1
-            const float res = grain_element(x, n_own, n_green, 2 - jj, I, S, T);
-            packed |= (uint32_t)u8_from_unit(res) << (8 * kk);
+            packed |= (uint32_t)sharpen_grain_byte<true, true>(p, strength, ZERO ? 1 : 0, n_own, n_green, 2 - jj, I, S, T) << (8 * kk);
             jj = (jj == 2) ? 0 : jj + 1;
         }
         uint8_t* dst = out + fbase + (int64_t)q.a0;

@@ -384,6 +384,114 @@ def _sharpen_then_seeded_grain_u8(frames_bgr, sharpen_strength, zero_border, gra
     return out
 
 
+# ---------------------------------------------------------------------------------------------
+# The stand-alone enhancer's upscale (cv2.resize(..., INTER_LANCZOS4) on decoded bytes, reference
+# VRGDG_StandaloneVideoEnhancerNodes.py:213-230) and the upscale fused into sharpen -> grain
+# ---------------------------------------------------------------------------------------------
+LANCZOS_TAP_BYTES = 20          # one record of the table: int32 s, eight int16 weights (csrc/vrg_lanczos_math.hpp: LzTap)
+_lanczos_lock = threading.Lock()
+_lanczos_host_lib = None
+_lanczos_tables: dict = {}      # (in_h, in_w, out_h, out_w, device) -> the uploaded table
+
+
+def lanczos4_taps(in_h: int, in_w: int, out_h: int, out_w: int) -> np.ndarray:
+    """The table of the two Lanczos kernels, made on the host (no GPU needed): ``out_w`` column records then ``out_h`` row records as a
+    structured array with fields ``s`` (floor of the source coordinate; the taps are s - 3 .. s + 4, clamped) and ``w`` (eight int16)."""
+    global _lanczos_host_lib
+    in_h, in_w, out_h, out_w = int(in_h), int(in_w), int(out_h), int(out_w)
+    if min(in_h, in_w, out_h, out_w) < 1:
+        raise ValueError("lanczos4_taps: sizes must be at least 1")
+    if _lanczos_host_lib is None:
+        with _lanczos_lock:
+            if _lanczos_host_lib is None:
+                _lanczos_host_lib = _hip.load_library()
+    table = np.zeros(out_w + out_h, dtype=np.dtype([("s", "<i4"), ("w", "<i2", (8,))]))
+    assert table.dtype.itemsize == LANCZOS_TAP_BYTES
+    _hip.check(_lanczos_host_lib.vrg_lanczos4_taps(in_h, in_w, out_h, out_w, C.c_void_p(table.ctypes.data)), "vrg_lanczos4_taps")
+    return table
+
+
+def _lanczos_table(in_h, in_w, out_h, out_w, device) -> torch.Tensor:
+    key = (in_h, in_w, out_h, out_w, str(device))
+    t = _lanczos_tables.get(key)
+    if t is None:
+        host = torch.from_numpy(lanczos4_taps(in_h, in_w, out_h, out_w).view(np.uint8).copy())
+        t = host.to(device)
+        with _lanczos_lock:
+            if len(_lanczos_tables) >= 64:          # a handful of geometries per job; never grows without bound
+                _lanczos_tables.clear()
+            _lanczos_tables[key] = t
+    return t
+
+
+def _lanczos_sizes(x, out_w, out_h):
+    out_w, out_h = int(out_w), int(out_h)
+    if out_w < 1 or out_h < 1:
+        raise ValueError("resize: output width and height must be at least 1")
+    if x.shape[1] < 1 or x.shape[2] < 1:
+        raise ValueError("resize: frames must be at least 1 x 1")
+    return out_w, out_h
+
+
+@_on_device
+def resize_frames_u8(frames_u8: torch.Tensor, out_w: int, out_h: int) -> torch.Tensor:
+    """``cv2.resize(frame, (out_w, out_h), interpolation=cv2.INTER_LANCZOS4)`` on every frame of a ``[F,H,W,3]`` uint8 batch on the GPU
+    (vrg_lanczos4_u8; the arithmetic is the restatement of csrc/vrg_lanczos_math.hpp).  Equal sizes hand the input back untouched, as the
+    reference's _resize_frames does."""
+    x = _check_frames(frames_u8, "frames", channels=3, dtype=torch.uint8)
+    out_w, out_h = _lanczos_sizes(x, out_w, out_h)
+    F, H, W, _ = x.shape
+    if (W, H) == (out_w, out_h):
+        return frames_u8
+    out = torch.empty((F, out_h, out_w, 3), dtype=torch.uint8, device=x.device)
+    if F == 0:
+        return out
+    taps = _lanczos_table(H, W, out_h, out_w, x.device)
+    _hip.check(_hip.lib().vrg_lanczos4_u8(_hip.ptr(x), _hip.ptr(out), F, H, W, out_h, out_w, _hip.ptr(taps), _hip.current_stream()),
+               "vrg_lanczos4_u8")
+    return out
+
+
+@_on_device
+def upscale_sharpen_then_seeded_grain(frames_u8: torch.Tensor, out_w: int, out_h: int, strength: float, use_gpu: bool, intensity: float,
+                                      saturation_mix: float, seed: int, frame_start: int = 0) -> torch.Tensor:
+    """``sharpen_then_seeded_grain(resize_frames_u8(frames, out_w, out_h), ...)`` byte for byte, in ONE launch
+    (vrg_upscale_sharpen_grain_u8): the upscaled frames never go to memory.  ``use_gpu`` selects the border of the unsharp as in the
+    reference (True: avg_pool2d's zero padding, False: the numpy path's replicated edge).  Wherever the fused kernel refuses (vertical
+    ratios below about 0.9), and for equal sizes, the two launches run."""
+    x = _check_frames(frames_u8, "frames", channels=3, dtype=torch.uint8)
+    out_w, out_h = _lanczos_sizes(x, out_w, out_h)
+    F, H, W, _ = x.shape
+
+    def two_launches():
+        return sharpen_then_seeded_grain(resize_frames_u8(x, out_w, out_h), strength, bool(use_gpu), intensity, saturation_mix, seed, frame_start)
+
+    if (W, H) == (out_w, out_h) or F == 0:
+        return two_launches()
+    fe_in, fe_out = H * W * 3, out_h * out_w * 3
+    grain = intensity > 0
+    I32, S32, T32 = _f32(intensity), _f32(saturation_mix), _f32(1.0 - saturation_mix)
+    out = torch.empty((F, out_h, out_w, 3), dtype=torch.uint8, device=x.device)
+    taps = _lanczos_table(H, W, out_h, out_w, x.device)
+    lib = _hip.lib()
+    first = int(seed) + int(frame_start)
+    f = 0
+    while f < F:   # split where the 31-bit mask wraps (practically never)
+        s0 = (first + f) & 0x7FFFFFFF
+        run = min(F - f, 0x80000000 - s0)
+        d = NoisePlan(1, rng.per_frame_seeded(fe_out, s0, x.device)).desc() if grain else None
+        st = lib.vrg_upscale_sharpen_grain_u8(C.c_void_p(x.data_ptr() + f * fe_in), C.c_void_p(out.data_ptr() + f * fe_out), run, H, W, out_h, out_w,
+                                              _hip.ptr(taps), _f32(max(strength, 0.0)), _hip.BORDER_ZERO if use_gpu else _hip.BORDER_REPLICATE,
+                                              I32 if grain else 0.0, S32, T32, C.byref(d) if grain else None, _hip.current_stream())
+        if st == _hip.VRG_ERR_UNSUPPORTED:
+            if f != 0:
+                raise RuntimeError("vrg_upscale_sharpen_grain_u8 refused a later run of a batch it had accepted")
+            return two_launches()
+        _hip.check(st, "vrg_upscale_sharpen_grain_u8")
+        f += run
+    return out
+
+
 @_on_device
 def film_grain_injected(images: torch.Tensor, noise: torch.Tensor, grain_intensity: float, saturation_mix: float) -> torch.Tensor:
     """Grain arithmetic with caller-supplied N(0,1) noise (same shape): the noise-injection parity form."""

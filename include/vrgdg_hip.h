@@ -431,6 +431,29 @@ int vrg_crop_resize_f32(const float* in, int64_t in_floats, float* out, const vr
                         int32_t size_h, int32_t size_w, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The stand-alone enhancer's upscale: cv2.resize(frame, (out_w, out_h), interpolation=INTER_LANCZOS4) on decoded uint8 B,G,R frames
+ * (VRGDG_StandaloneVideoEnhancerNodes.py:213-230), restated in csrc/vrg_lanczos_math.hpp: an 8 x 8-tap separable filter with 11-bit
+ * integer weights, int32 sums, one rounding at the end -- integer arithmetic, the same bytes on every machine.
+ *
+ * vrg_lanczos4_taps fills, ON THE HOST, the table both kernels read: out_w column records then out_h row records of 20 bytes each
+ * (int32 s = floor of the source coordinate, then the eight int16 weights of taps s - 3 .. s + 4).  The caller keeps one table per
+ * geometry and uploads it; `taps` of the two launches below is that table in device memory, 4-byte aligned.
+ *
+ * vrg_lanczos4_u8: [frames][in_h][in_w][3] -> [frames][out_h][out_w][3], any sizes >= 1, any ratio (a downscale uses the same eight
+ * taps, no antialiasing, as cv2 does), any alignment.  in != out; `in` is never written.
+ *
+ * vrg_upscale_sharpen_grain_u8 = vrg_sharpen_grain_u8(vrg_lanczos4_u8(in)) byte for byte, in one launch: the upscaled frame never goes
+ * to memory.  strength <= 0 leaves the unsharp out, intensity <= 0 the grain (`noise` may then be null), as the two-launch route of the
+ * Python layer does.  Borders and noise are those of the OUTPUT frame.  VRG_ERR_UNSUPPORTED (the caller runs the two entry points)
+ * when an output tile of 34 rows needs more than 44 source rows (vertical ratios below about 0.9) or chunk_frames != 1. */
+int vrg_lanczos4_taps(int32_t in_h, int32_t in_w, int32_t out_h, int32_t out_w, void* taps_host);
+int vrg_lanczos4_u8(const uint8_t* in, uint8_t* out, int64_t frames, int32_t in_h, int32_t in_w, int32_t out_h, int32_t out_w,
+                    const void* taps, void* stream);
+int vrg_upscale_sharpen_grain_u8(const uint8_t* in, uint8_t* out, int64_t frames, int32_t in_h, int32_t in_w, int32_t out_h,
+                                 int32_t out_w, const void* taps, float strength, int32_t border, float intensity, float sat,
+                                 float one_minus_sat, const vrg_noise_desc* noise, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Introspection
  * ------------------------------------------------------------------------------------------- */
 int vrg_abi_version(void);
