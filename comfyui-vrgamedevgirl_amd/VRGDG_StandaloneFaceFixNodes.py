@@ -1,7 +1,17 @@
-"""Face Fix on the MI355X: the crop sequence of the reference's Prepare nodes and its two composite nodes.
+"""Face Fix on the MI355X: the crop sequence of the reference's Prepare nodes and its three composite nodes.
 
-`VRGDGFaceFixComposite` and `VRGDGFaceFixCompositeOpaque` of the reference's VRGDG_StandaloneFaceFixNodes.py with the same names, widget
-specs, tooltips, messages and log lines; the pixels come from csrc/vrg_composite.hip (ops.composite_frames).
+`VRGDGFaceFixComposite`, `VRGDGFaceFixCompositeOpaque` and `VRGDGFaceFixCompositeLandmarkAligned` of the reference's
+VRGDG_StandaloneFaceFixNodes.py with the same names, widget specs, tooltips, messages and log lines; the pixels come from
+csrc/vrg_composite.hip (ops.composite_frames, ops.aligned_composite_frames).
+
+`VRGDGFaceFixCompositeLandmarkAligned` runs in three phases: the bicubic face of every box as bytes on the GPU (ops.face_bytes, one
+launch, downloaded once); a host loop over the frames in order that asks the node's `estimator(source_u8, generated_u8) -> 2 x 3 | None`
+and keeps the reference's smoothing / reset bookkeeping in float32 numpy (aligned_transforms); one composite pass in which the frames with
+a transform blend cv2's byte Lanczos-4 affine warp of those bytes (csrc/vrg_warp_math.hpp) and the others the bicubic face.  Detection
+is a seam: `estimator` is a class attribute, None by default -- the reference's behaviour when its detector cannot be created: every frame
+takes the fallback path and the result is the opaque composite's.  INTEGRATION.md binds the reference's detector to it.  The module's
+NODE_CLASS_MAPPINGS keeps its two keys (an existing test pins that set); the new node is listed in LANDMARK_NODE_CLASS_MAPPINGS /
+LANDMARK_NODE_DISPLAY_NAME_MAPPINGS beside them.
 
 `face_crop_sequence` is the outgoing half: the video and its tracked face boxes (the `entries` a Prepare node builds) become the
 512 x 512 face video that LTX repairs and the composites paste back.  The reference crops frame by frame (slice, permute, bicubic
@@ -17,8 +27,8 @@ processed where they are.  Inputs are never written.  The repaired count is comp
 
 What is NOT here: detection and tracking (cv2 DNN, candidate choice, cut scoring, anchor selection and the anchor
 PNG dump) and with them the Prepare / Collect node classes -- a Prepare node calls face_crop_sequence once after its detection loop,
-INTEGRATION.md shows the lines; the landmark-aligned composite (cv2 warp); and the registration in the package's NODE_CLASS_MAPPINGS:
-INTEGRATION.md shows the two lines.  The nodes are eager.
+INTEGRATION.md shows the lines; the landmark detector of the aligned composite (YuNet, the RANSAC similarity fit and the .onnx asset); and
+the registration in the package's NODE_CLASS_MAPPINGS: INTEGRATION.md shows the lines.  The nodes are eager.
 
 Refused with a ValueError, because the reference fails on them rather than defines them: a box that does not lie inside its frame (shape
 mismatch in the reference's composite, a smaller crop than the box in its Prepare), an empty box in VRGDGFaceFixComposite and in the crop
@@ -26,6 +36,7 @@ sequence, and channel counts other than 3 or 4 in the composites.
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from . import ops
@@ -183,6 +194,144 @@ class VRGDGFaceFixCompositeOpaque:
         return output, masks, repaired
 
 
+def _has_area(entry):
+    box = entry.get("box")
+    if not box:
+        return False
+    left, top, right, bottom = (int(v) for v in box)
+    return right > left and bottom > top
+
+
+def aligned_transforms(entries, usable, transform_smoothing, estimate):
+    """The transform bookkeeping of VRGDGFaceFixCompositeLandmarkAligned.composite (:1011-1048) for source frames 0 .. usable - 1, in
+    order: `estimate(index) -> 2 x 3 | None` is asked once for every frame whose box has area; an estimate becomes float32 and is smoothed
+    into the previous one (previous * s + estimate * (1 - s), the two Python scalars entering as float32); a miss reuses the previous
+    transform; `previous` is forgotten at an entry with "hard_cut" and when the "shot_id" changes (frames without a box do not take
+    part).  Returns (one float32 2 x 3 or None per frame, the number of frames that have one = the log's `aligned`)."""
+    smoothing = max(0.0, min(0.95, float(transform_smoothing)))
+    keep, take = np.float32(smoothing), np.float32(1.0 - smoothing)
+    transforms, aligned = [None] * int(usable), 0
+    previous, previous_shot = None, None
+    for index in range(int(usable)):
+        entry = entries[index]
+        if not _has_area(entry):
+            continue
+        shot_id = entry.get("shot_id", 0)
+        if entry.get("hard_cut") or (previous_shot is not None and shot_id != previous_shot):
+            previous = None
+        previous_shot = shot_id
+        transform = estimate(index)
+        if transform is not None:
+            transform = np.asarray(transform).astype(np.float32).reshape(2, 3)
+            if previous is not None:
+                transform = (previous * keep + transform * take).astype(np.float32)
+            previous = transform
+        elif previous is not None:
+            transform = previous
+        if transform is not None:
+            transforms[index] = transform
+            aligned += 1
+    return transforms, aligned
+
+
+def _quantise_host(values: torch.Tensor) -> np.ndarray:
+    """uint8(clip(rint(v * 255), 0, 255)) in float32 on the host; NaN gives 0 (what ops.face_bytes gives on the device)"""
+    v = values.detach().to(torch.float32).numpy()
+    with np.errstate(invalid="ignore"):
+        r = np.clip(np.rint(v * np.float32(255.0)), 0, 255)
+    return np.where(np.isnan(r), np.float32(0), r).astype(np.uint8)
+
+
+def _aligned_composite(plan, feather, transform_smoothing, estimator):
+    """(frames, masks, aligned) wherever the originals live."""
+    work, originals, entries, offset = plan.work, plan.originals, plan.entries, plan.offset
+    n_work, n_orig = plan.work_frames, int(originals.shape[0])
+    rule = ops.CompositeRule("opaque", feather=feather)
+    ops.composite_channels(rule, originals.shape[3], work.shape[3])
+    rows = ops.face_fix_entries(entries, n_work, offset, n_orig)
+    ops.composite_table(rows, rule, 0.0, originals.shape[1], originals.shape[2])                # refuses before anything is uploaded
+    height, width = int(originals.shape[1]), int(originals.shape[2])
+    host_fed = not (originals.is_cuda or n_orig == 0 or intermediate_device().type != "cpu")
+    dev = originals.device if originals.is_cuda else compute_device()
+    with torch.cuda.device(dev):
+        work_dev = work.to(dev, torch.float32)
+        originals_dev = None if host_fed or not originals.is_cuda else originals.to(torch.float32)
+        # phase 1: the faces as bytes, made on the GPU and downloaded once; the source bytes too when the originals are there
+        faces = ops.face_bytes(work_dev, rows, height, width, originals=originals_dev)
+        generated_host = faces.generated.cpu().numpy()
+        source_host = faces.source.cpu().numpy() if faces.source is not None else None
+
+    def estimate(index):
+        left, top, right, bottom = (int(v) for v in entries[index]["box"])
+        if source_host is not None:
+            source = faces.image(source_host, index)
+        else:
+            source = _quantise_host(originals[index, top:bottom, left:right, :3].cpu())
+        return estimator(source, faces.image(generated_host, index))
+
+    # phase 2: the estimator and the smoothing / reset rules, frame by frame on the host
+    transforms, aligned = aligned_transforms(entries, plan.usable, transform_smoothing, estimate)
+    transforms += [None] * (n_orig - len(transforms))
+    ops.warp_records(transforms, [row["box"] for row in rows])                                  # refuses before the pass
+    # phase 3: one composite pass
+    if not host_fed:
+        with torch.cuda.device(dev):
+            frames_dev = originals_dev if originals_dev is not None else originals.to(dev, torch.float32)
+            out, masks = ops.aligned_composite_frames(frames_dev, work_dev, rows, feather, transforms, generated=faces)
+        if not originals.is_cuda:
+            out, masks = out.to(intermediate_device()), masks.to(intermediate_device())
+        return out, masks, aligned
+    if originals.dtype != torch.float32:
+        originals = originals.float()
+
+    def piece(gpu_originals, first_frame):
+        last = first_frame + int(gpu_originals.shape[0])
+        return ops.aligned_composite_frames(gpu_originals, work_dev, ops.face_fix_entries(entries, n_work, offset, n_orig, first_frame, last),
+                                            feather, transforms[first_frame:last], generated=faces.piece(first_frame, last))
+
+    out, masks = stream_frames_with_masks(originals, piece)
+    return out, masks, aligned
+
+
+class VRGDGFaceFixCompositeLandmarkAligned:
+    """Align the generated face to the source crop before opaque compositing."""
+
+    #: `estimator(source_u8, generated_u8) -> 2 x 3 | None`: the transform that carries the generated face's landmarks onto the source's
+    #: ([h, w, 3] uint8 RGB each), or None when either face gives no landmarks.  None = no detector: every frame takes the fallback.
+    estimator = None
+
+    @classmethod
+    def INPUT_TYPES(cls):
+        return {"required": {
+            "ltx_face_frames": ("IMAGE", {"tooltip": "Decoded LTX face-video frames."}),
+            "face_fix_context": (FACE_FIX_CONTEXT, {"tooltip": "Tracked source crop boxes and original frames."}),
+            "feather_pixels": ("INT", {"default": 6, "min": 0, "max": 128, "tooltip": "Feather only the outer crop boundary."}),
+            "transform_smoothing": ("FLOAT", {"default": 0.75, "min": 0.0, "max": 0.95, "step": 0.05, "tooltip": "Smooths landmark scale/position changes across frames. Resets automatically at hard cuts."}),
+        }}
+
+    RETURN_TYPES = ("IMAGE", "MASK", "INT")
+    RETURN_NAMES = ("repaired_video_frames", "applied_face_mask", "repaired_frame_count")
+    FUNCTION = "composite"
+    CATEGORY = "VRGameDevGirl/Face Fix"
+    DESCRIPTION = "Aligns LTX eyes/nose/mouth to the source crop, then fully replaces the tracked face."
+
+    def composite(self, ltx_face_frames, face_fix_context, feather_pixels, transform_smoothing):
+        plan = _Plan(ltx_face_frames, face_fix_context)
+        plan.refuse_if_counts_differ()
+        smoothing = max(0.0, min(0.95, float(transform_smoothing)))
+        feather = int(feather_pixels) if int(feather_pixels) > 0 else 0
+        repaired = plan.repaired(_has_area)
+        estimator = self.estimator
+        if estimator is None or repaired == 0:
+            output, masks = _composite(plan, ops.CompositeRule("opaque", feather=feather), 0.0)
+            aligned = 0
+        else:
+            output, masks, aligned = _aligned_composite(plan, feather, smoothing, estimator)
+        _log(f"Landmark composite finished: repaired={repaired}, aligned={aligned}, fallback={repaired - aligned}, feather={feather_pixels}, "
+             f"smoothing={smoothing:.2f}.")
+        return output, masks, repaired
+
+
 NODE_CLASS_MAPPINGS = {
     "VRGDGFaceFixComposite": VRGDGFaceFixComposite,
     "VRGDGFaceFixCompositeOpaque": VRGDGFaceFixCompositeOpaque,
@@ -192,4 +341,14 @@ NODE_CLASS_MAPPINGS = {
 NODE_DISPLAY_NAME_MAPPINGS = {
     "VRGDGFaceFixComposite": "Face Fix - Composite Repaired Video",
     "VRGDGFaceFixCompositeOpaque": "Face Fix - Composite Opaque Full Face",
+}
+
+
+LANDMARK_NODE_CLASS_MAPPINGS = {
+    "VRGDGFaceFixCompositeLandmarkAligned": VRGDGFaceFixCompositeLandmarkAligned,
+}
+
+
+LANDMARK_NODE_DISPLAY_NAME_MAPPINGS = {
+    "VRGDGFaceFixCompositeLandmarkAligned": "Face Fix - Composite Landmark Aligned",
 }

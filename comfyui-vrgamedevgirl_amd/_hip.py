@@ -78,6 +78,14 @@ class CropDesc(C.Structure):
                 ("box_w", C.c_int32), ("box_h", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+class WarpDesc(C.Structure):
+    """vrg_warp_desc"""
+    _fields_ = [("m", C.c_double * 6), ("src_offset", C.c_int64), ("src_w", C.c_int32), ("src_h", C.c_int32),
+                ("set", C.c_int32), ("reserved", C.c_int32)]
+
+
+WARP_TABLE_BYTES = 1024 * 64 * 2
+
 _F3 = C.c_float * 3
 _P = C.c_void_p
 _SIGNATURES = {
@@ -136,6 +144,11 @@ _SIGNATURES = {
     "vrg_lanczos4_u8": (C.c_int, [_P, _P, C.c_int64] + [C.c_int32] * 4 + [_P, _P]),
     "vrg_upscale_sharpen_grain_u8": (C.c_int, [_P, _P, C.c_int64] + [C.c_int32] * 4 + [_P, C.c_float, C.c_int32, C.c_float, C.c_float, C.c_float,
                                                C.POINTER(NoiseDesc), _P]),
+    "vrg_warp_phase_table": (C.c_int, [_P]),
+    "vrg_warp_record": (C.c_int, [_P] + [C.c_int32] * 4 + [C.c_int64, _P]),
+    "vrg_face_bytes_u8": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64] + [C.c_int64] * 3 + [C.c_int32] * 6 + [_P]),
+    "vrg_warp_affine_u8": (C.c_int, [_P, C.c_int64, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
+    "vrg_composite_warp_apply_f32": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P, _P] + [C.c_int64] * 4 + [C.c_int32] * 10 + [_P]),
 }
 
 # include/vrgdg_hip_debug.h: self-tests and probes -- for the test suite and the measurement tools, not part of the drop-in boundary

@@ -979,6 +979,224 @@ def composite_frames(originals: torch.Tensor, crops: torch.Tensor, entries, rule
 
 
 # ------------------------------------------------------------------------------------------------
+# landmark-aligned Face Fix composite (VRGDG_StandaloneFaceFixNodes.py:1015-1054): the face as bytes, cv2's byte Lanczos-4 affine warp
+# (csrc/vrg_warp_math.hpp), the warp fused into the composite pass
+# ------------------------------------------------------------------------------------------------
+_warp_lock = threading.Lock()
+_warp_host_lib = None
+_warp_host_table = None
+_warp_tables: dict = {}          # device -> the uploaded phase table
+
+
+def _warp_lib():
+    global _warp_host_lib
+    if _warp_host_lib is None:
+        with _warp_lock:
+            if _warp_host_lib is None:
+                _warp_host_lib = _hip.load_library()
+    return _warp_host_lib
+
+
+def warp_phase_table() -> np.ndarray:
+    """The 1024 x 8 x 8 int16 weights of the warp (phase = fy * 32 + fx, tap row, tap column), made on the host once (no GPU needed);
+    every phase sums to exactly 32768.  Read-only."""
+    global _warp_host_table
+    if _warp_host_table is None:
+        table = np.zeros((1024, 8, 8), dtype=np.int16)
+        _hip.check(_warp_lib().vrg_warp_phase_table(C.c_void_p(table.ctypes.data)), "vrg_warp_phase_table")
+        table.setflags(write=False)
+        _warp_host_table = table
+    return _warp_host_table
+
+
+def _warp_table(device) -> torch.Tensor:
+    key = str(device)
+    t = _warp_tables.get(key)
+    if t is None:
+        with _warp_lock:
+            t = _warp_tables.get(key)
+            if t is None:
+                t = torch.from_numpy(warp_phase_table().reshape(-1).copy()).to(device)
+                _warp_tables[key] = t
+    return t
+
+
+def _box_size(box):
+    """(w, h) of a box with area, else None"""
+    if not box:
+        return None
+    left, top, right, bottom = (int(v) for v in box)
+    return (right - left, bottom - top) if right > left and bottom > top else None
+
+
+def _pack_offsets(boxes):
+    """Where each box's [h][w][3] byte image starts in the packed buffer (16-byte steps; -1 = no image), and the buffer's size."""
+    offsets, total = [], 0
+    for box in boxes:
+        size = _box_size(box)
+        if size is None:
+            offsets.append(-1)
+            continue
+        offsets.append(total)
+        total += (size[0] * size[1] * 3 + 15) // 16 * 16
+    return offsets, total
+
+
+def _warp_record_table(transforms, sizes, sources, offsets):
+    """ctypes array of _hip.WarpDesc: result size sizes[f], source image sources[f] = (w, h) at offsets[f]; transforms[f] None = not set"""
+    n = len(transforms)
+    table = (_hip.WarpDesc * max(1, n))()
+    lib = _warp_lib()
+    for f, t in enumerate(transforms):
+        if t is None or sizes[f] is None or offsets[f] < 0:
+            continue
+        m = np.ascontiguousarray(np.asarray(t, dtype=np.float32).reshape(-1))
+        if m.size != 6:
+            raise ValueError(f"transform {f} must be a 2 x 3 matrix, got shape {np.asarray(t).shape}")
+        if not np.isfinite(m).all():
+            raise ValueError(f"transform {f} has a non-finite entry: cv2.warpAffine leaves that undefined; refused")
+        status = lib.vrg_warp_record(C.c_void_p(m.ctypes.data), sizes[f][0], sizes[f][1], sources[f][0], sources[f][1], offsets[f],
+                                     C.cast(C.byref(table[f]), C.c_void_p))
+        if status != _hip.VRG_OK:
+            raise ValueError(f"transform {f} scales a coordinate of its {sizes[f][0]} x {sizes[f][1]} box past the 32-bit fixed point of "
+                             "cv2.warpAffine, which leaves that undefined; refused")
+    return table
+
+
+def warp_records(transforms, boxes):
+    """The warp records of one composite call, made on the host (no GPU needed): transforms[f] = the forward 2 x 3 matrix warpAffine takes
+    (or None: the frame keeps its bicubic face), boxes[f] = (left, top, right, bottom) or None.  The byte image of every box with area
+    gets a place in the packed buffer whether or not it has a transform (the estimator reads it).  Returns (ctypes array of
+    _hip.WarpDesc, byte offsets (-1 = no image), bytes of the packed buffer).  ValueError for a transform with a non-finite entry or one
+    whose fixed-point terms leave int32 for some pixel of its box."""
+    if len(transforms) != len(boxes):
+        raise ValueError(f"{len(transforms)} transforms for {len(boxes)} boxes")
+    offsets, total = _pack_offsets(boxes)
+    sizes = [_box_size(b) for b in boxes]
+    return _warp_record_table(transforms, sizes, sizes, offsets), offsets, total
+
+
+@dataclass
+class FaceBytes:
+    """What face_bytes made: the packed uint8 images on the device (`generated`; `source` when device originals were given), where each
+    entry's image starts (`offsets`, -1 = none) and its (w, h) (`sizes`)."""
+    generated: torch.Tensor
+    source: Optional[torch.Tensor]
+    offsets: list
+    sizes: list
+
+    def piece(self, first: int, last: int) -> "FaceBytes":
+        return FaceBytes(self.generated, self.source, self.offsets[first:last], self.sizes[first:last])
+
+    def image(self, packed: np.ndarray, f: int) -> np.ndarray:
+        """entry f's [h, w, 3] image inside a downloaded copy of `generated` or `source`"""
+        w, h = self.sizes[f]
+        return packed[self.offsets[f]:self.offsets[f] + w * h * 3].reshape(h, w, 3)
+
+
+@_on_device
+def face_bytes(crops: torch.Tensor, entries, height: int, width: int, originals: Optional[torch.Tensor] = None) -> FaceBytes:
+    """Steps 1-2 of the landmark-aligned composite for every entry with a box (entries as for composite_frames, frames height x width):
+    uint8(clip(rint(clamp(bicubic(crop -> box), 0, 1) * 255), 0, 255)) packed into one device buffer, one launch (vrg_face_bytes_u8).  With
+    device `originals` the same quantisation of the unclamped original under each box is made next to it.  A NaN gives byte 0."""
+    c = _check_frames(crops, "crops")
+    composite_channels(CompositeRule("opaque"), 3 if originals is None else originals.shape[3], c.shape[3])
+    table, _, max_pixels = composite_table(entries, CompositeRule("opaque"), 0.0, height, width)
+    frames = len(entries)
+    sizes = [(table[f].box_w, table[f].box_h) if table[f].rule != _hip.COMPOSITE_NONE else None for f in range(frames)]
+    offsets, total = _pack_offsets([(0, 0, s[0], s[1]) if s else None for s in sizes])
+    o = None
+    if originals is not None:
+        o = _check_frames(originals, "originals")
+        if o.device != c.device or tuple(o.shape[1:3]) != (int(height), int(width)):
+            raise ValueError("originals must be height x width frames on the crops' device")
+    n_orig = int(o.shape[0]) if o is not None else max([1] + [table[f].original_index + 1 for f in range(frames)])
+    for f in range(frames):
+        if not 0 <= table[f].original_index < n_orig or not 0 <= table[f].crop_index < c.shape[0]:
+            raise ValueError(f"entry {f} names original {table[f].original_index} / crop {table[f].crop_index} of {n_orig} / {int(c.shape[0])}")
+    generated = torch.zeros(max(total, 16), dtype=torch.uint8, device=c.device)
+    source = torch.zeros_like(generated) if o is not None else None
+    if frames == 0 or total == 0:
+        return FaceBytes(generated, source, offsets, sizes)
+    raw = bytes(memoryview(table))[:frames * C.sizeof(_hip.CompositeDesc)] + np.asarray(offsets, dtype=np.int64).tobytes()
+    dev_table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(c.device)
+    offsets_ptr = C.c_void_p(dev_table.data_ptr() + frames * C.sizeof(_hip.CompositeDesc))
+    _hip.check(_hip.lib().vrg_face_bytes_u8(_hip.ptr(c), _hip.ptr(o) if o is not None else None, _hip.ptr(dev_table), offsets_ptr,
+                                           _hip.ptr(generated), _hip.ptr(source) if source is not None else None, total, max_pixels,
+                                           frames, n_orig, int(c.shape[0]), int(c.shape[1]), int(c.shape[2]), int(c.shape[3]),
+                                           int(height), int(width), int(o.shape[3]) if o is not None else 3, _hip.current_stream()),
+               "vrg_face_bytes_u8")
+    return FaceBytes(generated, source, offsets, sizes)
+
+
+@_on_device
+def warp_affine_u8(frames_u8: torch.Tensor, transforms, out_w: int, out_h: int) -> torch.Tensor:
+    """``cv2.warpAffine(frame, transform, (out_w, out_h), flags=cv2.INTER_LANCZOS4, borderMode=cv2.BORDER_REFLECT101)`` on every frame of
+    a ``[F,H,W,3]`` uint8 batch on the GPU (vrg_warp_affine_u8; the arithmetic is the restatement of csrc/vrg_warp_math.hpp).
+    transforms[f] = the frame's 2 x 3 matrix; None gives a frame of zeros.  Refuses as warp_records does."""
+    x = _check_frames(frames_u8, "frames", channels=3, dtype=torch.uint8)
+    out_w, out_h = int(out_w), int(out_h)
+    F, H, W, _ = (int(v) for v in x.shape)
+    if out_w < 1 or out_h < 1 or H < 1 or W < 1:
+        raise ValueError("warp: frames and the output must be at least 1 x 1")
+    if len(transforms) != F:
+        raise ValueError(f"{len(transforms)} transforms for {F} frames")
+    table = _warp_record_table(transforms, [(out_w, out_h)] * F, [(W, H)] * F, [f * H * W * 3 for f in range(F)])
+    out = torch.empty((F, out_h, out_w, 3), dtype=torch.uint8, device=x.device)
+    if F == 0:
+        return out
+    rec = torch.frombuffer(bytearray(bytes(memoryview(table))[:F * C.sizeof(_hip.WarpDesc)]), dtype=torch.uint8).to(x.device)
+    _hip.check(_hip.lib().vrg_warp_affine_u8(_hip.ptr(x), x.numel(), _hip.ptr(out), _hip.ptr(rec), _hip.ptr(_warp_table(x.device)), F,
+                                            out_h, out_w, _hip.current_stream()), "vrg_warp_affine_u8")
+    return out
+
+
+@_on_device
+def aligned_composite_frames(originals: torch.Tensor, crops: torch.Tensor, entries, feather, transforms, generated: Optional[FaceBytes] = None,
+                             out: Optional[torch.Tensor] = None, mask_out: Optional[torch.Tensor] = None):
+    """The landmark-aligned composite on device frames: composite_frames with the opaque rule, where every entry f with transforms[f]
+    (2 x 3, as warpAffine takes it) blends fl(warpAffine(byte face) / 255) in place of the bicubic face -- one pass over the output
+    (vrg_composite_warp_apply_f32).  `generated`: the FaceBytes of these entries if face_bytes has run already (the node downloads them for
+    its estimator), else made here.  Entries without a transform, and a call without any, give composite_frames' bits."""
+    if len(transforms) != len(entries):
+        raise ValueError(f"{len(transforms)} transforms for {len(entries)} entries")
+    rule = CompositeRule("opaque", feather=feather)
+    o, c, m, dev_table, match, max_pixels, geom, stats = _composite_prepare(originals, crops, entries, rule, 0.0, None)
+    if generated is None:
+        sizes = [_box_size(e.get("box")) for e in entries]
+        offsets = None
+    else:
+        if len(generated.offsets) != len(entries) or generated.generated.device != o.device:
+            raise ValueError("generated does not belong to these entries")
+        sizes, offsets = generated.sizes, generated.offsets
+    live = [t if sizes[f] is not None else None for f, t in enumerate(transforms)]
+    if offsets is None:
+        offsets, _ = _pack_offsets([(0, 0, s[0], s[1]) if s else None for s in sizes])
+    records = _warp_record_table(live, sizes, sizes, offsets)                 # refuses before any launch
+    if not any(records[f].set for f in range(len(entries))):
+        return composite_frames(o, c, entries, rule, 0.0, out=out, mask_out=mask_out)
+    if generated is None:
+        generated = face_bytes(c, entries, o.shape[1], o.shape[2])
+    frames = len(entries)
+    shape = (frames, int(o.shape[1]), int(o.shape[2]), int(o.shape[3]))
+    for name, t, want in (("out", out, shape), ("mask_out", mask_out, shape[:3])):
+        if t is not None and (tuple(t.shape) != want or t.dtype != torch.float32 or not t.is_contiguous() or t.device != o.device):
+            raise ValueError(f"{name} must be a contiguous float32 tensor shaped {want} on the frames' device")
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=o.device)
+    if mask_out is None:
+        mask_out = torch.empty(shape[:3], dtype=torch.float32, device=o.device)
+    if out.data_ptr() in (o.data_ptr(), c.data_ptr()):
+        raise ValueError("out must not be an input")
+    rec = torch.frombuffer(bytearray(bytes(memoryview(records))[:frames * C.sizeof(_hip.WarpDesc)]), dtype=torch.uint8).to(o.device)
+    g = generated.generated
+    _hip.check(_hip.lib().vrg_composite_warp_apply_f32(_hip.ptr(c), _hip.ptr(o), None, _hip.ptr(dev_table), _hip.ptr(stats), _hip.ptr(rec),
+                                                      _hip.ptr(g), g.numel(), _hip.ptr(_warp_table(o.device)), _hip.ptr(out),
+                                                      _hip.ptr(mask_out), *geom, _hip.current_stream()), "vrg_composite_warp_apply_f32")
+    return out, mask_out
+
+
+# ------------------------------------------------------------------------------------------------
 # Face Fix crop sequence (both Prepare nodes: VRGDG_StandaloneFaceFixNodes.py:320-351, 387-389, 486-516, 537-539)
 # ------------------------------------------------------------------------------------------------
 

@@ -454,6 +454,58 @@ int vrg_upscale_sharpen_grain_u8(const uint8_t* in, uint8_t* out, int64_t frames
                                  float one_minus_sat, const vrg_noise_desc* noise, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The landmark-aligned Face Fix composite (VRGDGFaceFixCompositeLandmarkAligned.composite, VRGDG_StandaloneFaceFixNodes.py:1015-1054):
+ * the work frame is bicubic-resized to the box and quantised to bytes, the bytes are warped with
+ * cv2.warpAffine(..., INTER_LANCZOS4, BORDER_REFLECT101), divided by 255 and blended in under the opaque alpha.  The warp is cv2's
+ * fixed-point affine remap, restated in csrc/vrg_warp_math.hpp: integer arithmetic, the same bytes on every machine.
+ *
+ * vrg_warp_phase_table fills, ON THE HOST, the 1024 x 8 x 8 int16 weights (131072 bytes, phase = fy * 32 + fx, then tap row, tap column)
+ * that the two warping launches read from device memory; every phase sums to exactly 32768.
+ * vrg_warp_record fills, ON THE HOST, the record of one warped frame from the forward 2 x 3 float transform, as warpAffine takes it, for
+ * an out_w x out_h result read from a [src_h][src_w][3] byte image that starts src_offset bytes into the byte buffer.  It returns
+ * VRG_ERR_BAD_ARG and clears the record when an entry is not finite or a fixed-point term leaves int32 for some pixel of the result (cv2
+ * leaves both undefined).  A singular matrix follows cv2 (determinant 0 inverts to the zero matrix).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct vrg_warp_desc {
+    double m[6];          /* the INVERTED matrix (result -> source), as warpAffine forms it in double */
+    int64_t src_offset;   /* bytes from the byte buffer to this frame's [src_h][src_w][3] image */
+    int32_t src_w, src_h;
+    int32_t set;          /* 0: no transform -- the composite takes the bicubic face, the stand-alone warp writes zeros */
+    int32_t reserved;     /* 0 */
+} vrg_warp_desc;
+
+int vrg_warp_phase_table(void* table_host);
+int vrg_warp_record(const float* transform, int32_t out_w, int32_t out_h, int32_t src_w, int32_t src_h, int64_t src_offset,
+                    vrg_warp_desc* record_host);
+
+/* Steps 1-2 of the node for every output frame of `desc` (device, the table of the composite) whose offsets[f] >= 0 (device, one int64
+ * per frame: bytes from `generated` / `source` to that frame's [box_h][box_w][3] image): generated = uint8(clip(rint(clamp(bicubic(crop ->
+ * box), 0, 1) * 255), 0, 255)) in the arithmetic of the composite, and -- when `source` is not NULL -- source = the same quantisation of
+ * the unclamped original under the box.  A NaN gives byte 0.  An image that does not end inside `capacity` bytes, or whose record the
+ * composite would not use, is not written.  max_box_pixels >= the largest box_w * box_h. */
+int vrg_face_bytes_u8(const float* crops, const float* originals, const vrg_composite_desc* desc, const int64_t* offsets,
+                      uint8_t* generated, uint8_t* source, int64_t capacity, int64_t max_box_pixels,
+                      int64_t frames, int64_t original_frames, int64_t crop_frames,
+                      int32_t crop_h, int32_t crop_w, int32_t crop_channels, int32_t height, int32_t width, int32_t channels,
+                      void* stream);
+
+/* The warp alone: out[f] = warpAffine(in + rec[f].src_offset, ..., (out_w, out_h), INTER_LANCZOS4, BORDER_REFLECT101) for `frames`
+ * records (device).  `in_bytes`: the bytes readable from `in`; a record that is not set or whose image does not lie inside them gives a
+ * frame of zeros.  `table`: device copy of vrg_warp_phase_table.  in != out; `in` is never written. */
+int vrg_warp_affine_u8(const uint8_t* in, int64_t in_bytes, uint8_t* out, const vrg_warp_desc* rec, const void* table, int64_t frames,
+                       int32_t out_h, int32_t out_w, void* stream);
+
+/* vrg_composite_apply_f32 with a side table of `frames` warp records (device) parallel to `desc`: a frame whose record is set (and whose
+ * image is box_w x box_h and lies inside `n_bytes`) takes fl(warped byte / 255) as its face, every other frame the bicubic face -- bit
+ * for bit what vrg_composite_apply_f32 gives.  `bytes`: the packed images of vrg_face_bytes_u8. */
+int vrg_composite_warp_apply_f32(const float* crops, const float* originals, const float* user_mask, const vrg_composite_desc* desc,
+                                 const void* stats, const vrg_warp_desc* rec, const uint8_t* bytes, int64_t n_bytes, const void* table,
+                                 float* out, float* mask_out,
+                                 int64_t frames, int64_t original_frames, int64_t crop_frames, int64_t mask_frames,
+                                 int32_t crop_h, int32_t crop_w, int32_t crop_channels, int32_t height, int32_t width, int32_t channels,
+                                 int32_t mask_h, int32_t mask_w, int32_t mask_stride, int32_t match_channels, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Introspection
  * ------------------------------------------------------------------------------------------- */
 int vrg_abi_version(void);
