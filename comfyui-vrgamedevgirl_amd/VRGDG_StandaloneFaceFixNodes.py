@@ -25,16 +25,28 @@ match applies (at least 16 pixels with alpha > 0.35) is decided on the device.  
 the host-fed pipeline of _devices in pieces along the frame axis, the much smaller work frames are uploaded once ahead; device tensors are
 processed where they are.  Inputs are never written.  The repaired count is computed on the host from the entries.
 
-What is NOT here: detection and tracking (cv2 DNN, candidate choice, cut scoring, anchor selection and the anchor
-PNG dump) and with them the Prepare / Collect node classes -- a Prepare node calls face_crop_sequence once after its detection loop,
-INTEGRATION.md shows the lines; the landmark detector of the aligned composite (YuNet, the RANSAC similarity fit and the .onnx asset); and
+`shot_cut_scores` / `shot_boundaries` are the hard-cut detection of the two shot-aware Prepare nodes (`_cut_score`, :421-435, called per
+frame at :457): a whole-frame reduction that depends on nothing but the video, so it runs for the whole batch before the detection loop.
+Every frame is quantised to bytes and reduced to cv2's 64 x 64 INTER_AREA thumbnail in one launch of csrc/vrg_cut.hip (the frame is
+read once, 12 B per pixel); two small launches turn the thumbnails into hue / saturation histograms and into four exact integers per
+consecutive pair, and the host finishes the score in double (cut_scores_from_sums).  CPU frames go up through the staging pipeline of
+_devices; nothing but 32 bytes per pair comes back.  The `shot_id` values are what face_crop_sequence(..., per_shot=True) consumes.
+
+What is NOT here: detection and tracking (cv2 DNN, candidate choice, anchor selection and the anchor PNG dump) and
+with them the Prepare / Collect node classes -- a shot-aware Prepare node calls shot_boundaries once before its detection loop and
+face_crop_sequence once after it, INTEGRATION.md shows the lines; the landmark detector of the aligned composite (YuNet, the RANSAC similarity fit and the .onnx asset); and
 the registration in the package's NODE_CLASS_MAPPINGS: INTEGRATION.md shows the lines.  The nodes are eager.
 
 Refused with a ValueError, because the reference fails on them rather than defines them: a box that does not lie inside its frame (shape
 mismatch in the reference's composite, a smaller crop than the box in its Prepare), an empty box in VRGDGFaceFixComposite and in the crop
-sequence, and channel counts other than 3 or 4 in the composites.
+sequence, and channel counts other than 3 or 4 in the composites.  The cut score refuses frames with a side below 64 px (cv2's INTER_AREA
+takes another, bilinear-like route there: out of scope), batches that are not [frames, height, width, channels], empty batches and fewer
+than 3 channels.
 """
 from __future__ import annotations
+
+import math
+import sys
 
 import numpy as np
 import torch
@@ -68,6 +80,65 @@ def face_crop_sequence(video_frames, entries, *, per_shot=False, anchors=None):
     if anchors is not None:
         anchor_batch = crop_batch[plan.ltx_offset:][torch.tensor([int(a) for a in anchors], device=crop_batch.device, dtype=torch.long)]
     return crop_batch, anchor_batch, plan.ltx_offset
+
+
+_THUMB_VALUES = 64 * 64 * 3         # bytes of one thumbnail
+_HIST_TOTAL = 64 * 64               # every histogram sums to the pixels of a thumbnail
+_HIST_BINS = 32 * 32
+
+
+def cut_scores_from_sums(sums) -> np.ndarray:
+    """The host half of the cut score: `sums` = int [pairs, 4] rows (D, S11, S22, S12) of ops.cut_pair_sums -> float64 [pairs + 1] with
+    score[0] = 0.0 and score[i] = what `_cut_score(frame i - 1, frame i)` returns:
+      mean_delta = D / (255 * 12288)
+      corr       = compareHist(.., HISTCMP_CORREL) of the two L2-normalised histograms.  The correlation does not change under the
+                   normalisation, so it is (1024 S12 - 4096^2) / sqrt((1024 S11 - 4096^2) (1024 S22 - 4096^2)) from exact integers; cv2's
+                   `|denom| > DBL_EPSILON` test (1.0 where it fails) is evaluated on the normalised values it sees
+      score      = max(mean_delta, (1 - corr) / 2)"""
+    rows = [[int(v) for v in row] for row in np.asarray(sums).reshape(-1, 4).tolist()]
+    scores = np.zeros(len(rows) + 1, dtype=np.float64)
+    square = _HIST_TOTAL * _HIST_TOTAL
+    for i, (d, s11, s22, s12) in enumerate(rows):
+        mean_delta = d / (255.0 * _THUMB_VALUES)
+        var1, var2, cov = _HIST_BINS * s11 - square, _HIST_BINS * s22 - square, _HIST_BINS * s12 - square
+        denom_normalised = (var1 / (_HIST_BINS * s11)) * (var2 / (_HIST_BINS * s22)) if s11 > 0 and s22 > 0 else 0.0
+        corr = cov / math.sqrt(var1 * var2) if abs(denom_normalised) > sys.float_info.epsilon else 1.0
+        scores[i + 1] = max(mean_delta, (1.0 - corr) * 0.5)
+    return scores
+
+
+def boundaries_from_scores(scores, cut_sensitivity):
+    """The rule of VRGDGFaceFixPrepareShotAware.prepare (:457-459): hard_cut[i] = i > 0 and score[i] >= float(cut_sensitivity); shot_id
+    starts at 0 and increments at every hard cut.  Returns (hard_cut: list[bool], shot_id: list[int])."""
+    threshold = float(cut_sensitivity)
+    hard_cut, shot_id, shot = [], [], 0
+    for index, score in enumerate(scores):
+        cut = index > 0 and float(score) >= threshold
+        if cut:
+            shot += 1
+        hard_cut.append(bool(cut))
+        shot_id.append(shot)
+    return hard_cut, shot_id
+
+
+def shot_cut_scores(video_frames) -> np.ndarray:
+    """float64 [frames]: score[0] = 0.0, score[i] = the reference's `_cut_score` of frames i - 1 and i (each quantised as :456 does).
+    Device frames are reduced where they are; CPU frames stream up in pieces.  `video_frames` is never written."""
+    if not isinstance(video_frames, torch.Tensor) or video_frames.ndim != 4 or video_frames.shape[0] < 1:
+        raise ValueError("Shot-aware Face Fix Prepare requires a non-empty video batch.")
+    if video_frames.is_cuda:
+        thumbs = ops.cut_thumbnails(video_frames.to(torch.float32))
+    else:
+        thumbs = ops.cut_thumbnails_host(video_frames)
+    if thumbs.shape[0] < 2:
+        return np.zeros(int(thumbs.shape[0]), dtype=np.float64)
+    return cut_scores_from_sums(ops.cut_pair_sums(thumbs).cpu().numpy())
+
+
+def shot_boundaries(video_frames, cut_sensitivity):
+    """(hard_cut: list[bool], shot_id: list[int]) of the video, one per frame: what the loop of VRGDGFaceFixPrepareShotAware.prepare and
+    VRGDGFaceFixPrepareVideoShotAware.prepare derives frame by frame, computed before it for the whole batch."""
+    return boundaries_from_scores(shot_cut_scores(video_frames), cut_sensitivity)
 
 
 class _Plan:

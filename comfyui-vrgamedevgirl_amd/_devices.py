@@ -966,6 +966,49 @@ def stream_frames_with_masks(originals, piece):
     return frames, masks
 
 
+def upload_frames(images: torch.Tensor, fn) -> None:
+    """The upload half of the pipeline alone, for a pass whose result stays on the device: ``fn(gpu_frames, first_frame)`` is called
+    for every piece of a CPU-resident batch on the caller's stream of the compute device, with the upload of the next piece (through
+    the page-locked ring when the frames are pageable) queued under it; at most PIPE_DEPTH pieces are in HBM at a time.  Returns when
+    every piece has run.  `images` is never written."""
+    images = materialise(images).contiguous()
+    F = int(images.shape[0])
+    frame_bytes = images.element_size()
+    for d in images.shape[1:]:
+        frame_bytes *= int(d)
+    if F == 0 or frame_bytes == 0:
+        return
+    dev = compute_device()
+    per = piece_frames(F, frame_bytes)
+    with torch.cuda.device(dev), _STAGING.lock:
+        h2d, _d2h, _own = _STAGING.side_streams(dev, 0)
+        compute = torch.cuda.current_stream(dev)
+        stage_in = PAGEABLE_UPLOAD == "ring" and images.device.type == "cpu" and not images.is_pinned()
+        ring = _UploadRing(_STAGING, 0) if stage_in else None
+        ran = []
+        for i, s in enumerate(range(0, F, per)):
+            e = min(F, s + per)
+            if len(ran) == PIPE_DEPTH:          # bounds the device memory in flight
+                ran.pop(0).synchronize()
+            if stage_in:
+                gpu_in, up = ring.upload(images[s:e], dev, h2d)
+            else:
+                with torch.cuda.stream(h2d):
+                    gpu_in = images[s:e].to(dev, non_blocking=True)
+                    up = _event()
+                    up.record(h2d)
+            compute.wait_event(up)
+            fn(gpu_in, s)
+            gpu_in.record_stream(compute)
+            done = _event()
+            done.record(compute)
+            ran.append(done)
+        for done in ran:
+            done.synchronize()
+        if ring is not None:
+            ring.drain()
+
+
 #: Pageable input frames: "ring" = this pack copies them into a page-locked ring with several host threads (vrg_host_copy) and uploads
 #: from there asynchronously; "runtime" = the HIP runtime's own pageable copy, which starts only when everything queued on the device
 #: has drained -- upload, kernels and download then run one after the other (profiles/r04_host_fed_timeline_runtime_pageable.json).

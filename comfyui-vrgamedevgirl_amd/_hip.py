@@ -149,6 +149,10 @@ _SIGNATURES = {
     "vrg_face_bytes_u8": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64] + [C.c_int64] * 3 + [C.c_int32] * 6 + [_P]),
     "vrg_warp_affine_u8": (C.c_int, [_P, C.c_int64, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
     "vrg_composite_warp_apply_f32": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P, _P] + [C.c_int64] * 4 + [C.c_int32] * 10 + [_P]),
+    "vrg_area_taps": (C.c_int, [C.c_int32, C.c_int32, _P]),
+    "vrg_cut_thumbs_f32": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "vrg_cut_hist_u8": (C.c_int, [_P, _P, C.c_int64, _P]),
+    "vrg_cut_pair_sums": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
 }
 
 # include/vrgdg_hip_debug.h: self-tests and probes -- for the test suite and the measurement tools, not part of the drop-in boundary

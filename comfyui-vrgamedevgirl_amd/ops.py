@@ -1390,6 +1390,125 @@ def crop_host_bytes(plan: CropPlan) -> int:
 
 
 # ------------------------------------------------------------------------------------------------
+# The hard-cut score of the shot-aware Face Fix Prepare nodes (reference VRGDG_StandaloneFaceFixNodes.py:421-435, :456): 64 x 64
+# INTER_AREA thumbnails of the quantised frames, their hue / saturation histograms, four integers per consecutive pair
+# ------------------------------------------------------------------------------------------------
+CUT_THUMB = 64                  # the thumbnail is 64 x 64 x 3 bytes
+AREA_CELL = np.dtype([("first", "<i4"), ("count", "<i4"), ("w_first", "<f4"), ("w_mid", "<f4"), ("w_last", "<f4")])      # csrc/vrg_area_math.hpp: AreaCell
+_area_tables: dict = {}         # (height, width, device) -> the uploaded table
+
+
+def _check_cut_shape(shape):
+    """The refusals of the cut score, before anything is uploaded."""
+    if len(shape) != 4:
+        raise ValueError("cut score: frames must be a [frames, height, width, channels] batch")
+    if int(shape[3]) < 3:
+        raise ValueError(f"cut score: frames must have at least 3 channels, got {int(shape[3])}")
+    if int(shape[1]) < CUT_THUMB or int(shape[2]) < CUT_THUMB:
+        raise ValueError(f"cut score: {int(shape[2])} x {int(shape[1])} frames have a side below {CUT_THUMB} px; cv2's INTER_AREA takes "
+                         "another, bilinear-like route there, which is out of scope; refused")
+
+
+def area_taps(in_h: int, in_w: int) -> np.ndarray:
+    """The table of the thumbnail kernel, made on the host (no GPU needed): 64 column cells then 64 row cells (AREA_CELL records: the
+    taps of output index d are the source samples first .. first + count - 1, the first weighs w_first, the last w_last, the others w_mid)."""
+    global _lanczos_host_lib
+    in_h, in_w = int(in_h), int(in_w)
+    if min(in_h, in_w) < CUT_THUMB:
+        raise ValueError(f"area_taps: sides must be at least {CUT_THUMB}")
+    if _lanczos_host_lib is None:
+        with _lanczos_lock:
+            if _lanczos_host_lib is None:
+                _lanczos_host_lib = _hip.load_library()
+    table = np.zeros(2 * CUT_THUMB, dtype=AREA_CELL)
+    _hip.check(_lanczos_host_lib.vrg_area_taps(in_h, in_w, C.c_void_p(table.ctypes.data)), "vrg_area_taps")
+    return table
+
+
+def _area_table(in_h, in_w, device) -> torch.Tensor:
+    key = (in_h, in_w, str(device))
+    t = _area_tables.get(key)
+    if t is None:
+        t = torch.from_numpy(area_taps(in_h, in_w).view(np.uint8).copy()).to(device)
+        with _lanczos_lock:
+            if len(_area_tables) >= 64:
+                _area_tables.clear()
+            _area_tables[key] = t
+    return t
+
+
+@_on_device
+def cut_thumbnails(frames: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``cv2.resize(rgb, (64, 64), interpolation=cv2.INTER_AREA)`` of ``rgb = (frame[..., :3].clamp(0, 1) * 255).round().astype(uint8)`` for
+    every frame of a device-resident ``[F, H, W, C >= 3]`` fp32 batch (never written), in one launch of vrg_cut_thumbs_f32.  Returns
+    ``[F, 64, 64, 3]`` uint8 on the frames' device."""
+    if isinstance(frames, torch.Tensor):
+        _check_cut_shape(frames.shape)
+    x = _check_frames(frames, "frames")
+    F, H, W, Cn = (int(v) for v in x.shape)
+    if Cn > 4:
+        x = x[..., :3].contiguous()
+        Cn = 3
+    shape = (F, CUT_THUMB, CUT_THUMB, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=x.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != x.device:
+        raise ValueError(f"out must be a contiguous uint8 tensor shaped {shape} on the frames' device")
+    if F == 0:
+        return out
+    taps = _area_table(H, W, x.device)
+    _hip.check(_hip.lib().vrg_cut_thumbs_f32(_hip.ptr(x), _hip.ptr(out), F, H, W, Cn, _hip.ptr(taps), _hip.current_stream()), "vrg_cut_thumbs_f32")
+    return out
+
+
+def cut_thumbnails_host(frames_cpu: torch.Tensor) -> torch.Tensor:
+    """cut_thumbnails for CPU frames: they go up through the staging pipeline of _devices in pieces along the frame axis (page-locked
+    ring, upload of piece i + 1 under the kernel of piece i); nothing comes back -- the ``[F, 64, 64, 3]`` thumbnails stay on the compute
+    device for the pair pass."""
+    from . import _devices
+    if not isinstance(frames_cpu, torch.Tensor) or frames_cpu.is_cuda:
+        raise ValueError("frames_cpu must be a CPU [frames, height, width, channels] tensor")
+    _check_cut_shape(frames_cpu.shape)
+    if frames_cpu.dtype != torch.float32:
+        frames_cpu = frames_cpu.float()
+    dev = _devices.compute_device()
+    with torch.cuda.device(dev):
+        out = torch.empty((int(frames_cpu.shape[0]), CUT_THUMB, CUT_THUMB, 3), dtype=torch.uint8, device=dev)
+        _devices.upload_frames(frames_cpu, lambda gpu, first: cut_thumbnails(gpu, out=out[first:first + int(gpu.shape[0])]))
+    return out
+
+
+@_on_device
+def cut_histograms(thumbs: torch.Tensor) -> torch.Tensor:
+    """``calcHist([cvtColor(thumb, COLOR_RGB2HSV)], [0, 1], None, [32, 32], [0, 180, 0, 256])`` as int32 ``[F, 1024]`` (vrg_cut_hist_u8)."""
+    t = _check_frames(thumbs, "thumbs", channels=3, dtype=torch.uint8)
+    if tuple(t.shape[1:3]) != (CUT_THUMB, CUT_THUMB):
+        raise ValueError(f"thumbs must be [frames, {CUT_THUMB}, {CUT_THUMB}, 3] uint8")
+    hist = torch.empty((int(t.shape[0]), 1024), dtype=torch.int32, device=t.device)
+    if t.shape[0]:
+        _hip.check(_hip.lib().vrg_cut_hist_u8(_hip.ptr(t), _hip.ptr(hist), int(t.shape[0]), _hip.current_stream()), "vrg_cut_hist_u8")
+    return hist
+
+
+@_on_device
+def cut_pair_sums(thumbs: torch.Tensor, hist: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int64 ``[F - 1, 4]`` = (D, S11, S22, S12) of every consecutive pair of thumbnails: D = sum |a - b| over the 12288 bytes, the S the
+    sums of squares and products of the two histograms (cut_histograms, computed here when not given).  Exact integers: the score made
+    of them does not depend on how the frames were cut into launches."""
+    t = _check_frames(thumbs, "thumbs", channels=3, dtype=torch.uint8)
+    if hist is None:
+        hist = cut_histograms(t)
+    F = int(t.shape[0])
+    hist = _check_side(hist, "hist", t, shape_tail=(1024,), dtype=torch.int32)
+    if int(hist.shape[0]) != F:
+        raise ValueError(f"{int(hist.shape[0])} histograms for {F} thumbnails")
+    sums = torch.empty((max(F - 1, 0), 4), dtype=torch.int64, device=t.device)
+    if F > 1:
+        _hip.check(_hip.lib().vrg_cut_pair_sums(_hip.ptr(t), _hip.ptr(hist), _hip.ptr(sums), F, _hip.current_stream()), "vrg_cut_pair_sums")
+    return sums
+
+
+# ------------------------------------------------------------------------------------------------
 # 13-slider Adjust (video routes)
 # ------------------------------------------------------------------------------------------------
 

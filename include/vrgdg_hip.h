@@ -506,6 +506,29 @@ int vrg_composite_warp_apply_f32(const float* crops, const float* originals, con
                                  int32_t mask_h, int32_t mask_w, int32_t mask_stride, int32_t match_channels, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The hard-cut score of the shot-aware Face Fix Prepare nodes (VRGDGFaceFixPrepareShotAware._cut_score,
+ * VRGDG_StandaloneFaceFixNodes.py:421-435, with the quantisation of :456), restated in csrc/vrg_area_math.hpp: frames are quantised to
+ * bytes, reduced to 64 x 64 thumbnails as cv2.resize(..., (64, 64), INTER_AREA) does for sides >= 64 (fp32 sums in cv2's order, or its
+ * integer fast path when both ratios are integers), turned into 32 x 32 hue / saturation histograms (cvtColor's fixed-point RGB2HSV), and
+ * every consecutive pair gives four exact integers from which the host finishes the score in double.
+ *
+ * vrg_area_taps fills, ON THE HOST, the table the thumbnail kernel reads: 64 column cells then 64 row cells of 20 bytes each (int32 first
+ * source sample, int32 count, then the fp32 weights of the first, the middle and the last tap).  `taps` below is that table in device
+ * memory, 4-byte aligned.
+ *
+ * vrg_cut_thumbs_f32: [frames][height][width][channels] fp32 -> [frames][64][64][3] bytes in one launch; height, width >= 64 (a smaller
+ * side is VRG_ERR_BAD_ARG: cv2 takes another route there), channels 3 or 4 (the fourth is ignored), `in` 4-byte aligned and never written.
+ * vrg_cut_hist_u8: [frames][64][64][3] bytes -> int32 [frames][1024] (bin = hue bin * 32 + saturation bin).
+ * vrg_cut_pair_sums: int64 [frames - 1][4] = (sum |a - b| over the bytes, sum ha^2, sum hb^2, sum ha * hb) of thumbnails / histograms
+ * (i, i + 1); fewer than two frames write nothing.
+ * ------------------------------------------------------------------------------------------- */
+int vrg_area_taps(int32_t in_h, int32_t in_w, void* taps_host);
+int vrg_cut_thumbs_f32(const float* in, uint8_t* out, int64_t frames, int32_t height, int32_t width, int32_t channels, const void* taps,
+                       void* stream);
+int vrg_cut_hist_u8(const uint8_t* thumbs, int32_t* hist, int64_t frames, void* stream);
+int vrg_cut_pair_sums(const uint8_t* thumbs, const int32_t* hist, int64_t* sums, int64_t frames, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Introspection
  * ------------------------------------------------------------------------------------------- */
 int vrg_abi_version(void);
