@@ -1,0 +1,341 @@
+"""The pixels of the AI Video Builder's Face Fix (VRGDG_FaceFix.py of the reference: the routes /vrgdg/face_fix/prepare and
+/vrgdg/face_fix/finalize) on the GPU, on decoded uint8 B,G,R frames.
+
+``crop_frames``       what ``prepare_face_fix`` does per tracked frame (:473-476): the square box cut out of the frame and
+                      ``cv2.resize(crop, (enhance_size, enhance_size), INTER_LANCZOS4)`` -- one launch for a batch of boxes of any sizes.
+``composite_frames``  the loop body of ``finalize_face_fix`` (:937-957): the repaired frame resized to its box, ``_soft_ellipse_mask``,
+                      ``_color_match``, the fp32 blend under ``alpha * composite_strength`` and the paste into a copy of the original --
+                      four launches for a batch, no host round trip in between.
+
+Device-resident inputs stay on the device; CPU inputs (a uint8 tensor, a list of numpy frames) are uploaded whole and the result is
+downloaded whole (the staging helpers of VRGDG_LUTVideoTools).  Detection, tracking, PNG / video I/O, manifests, ffmpeg and the aiohttp
+routes are out of scope.  The arithmetic is csrc/vrg_facefix_math.hpp; the library is reached through ``_hip`` only.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import threading
+
+import numpy as np
+import torch
+
+from . import _hip
+from ._devices import compute_device
+
+NODE_CLASS_MAPPINGS = {}
+NODE_DISPLAY_NAME_MAPPINGS = {}
+
+DEFAULT_FEATHER = 18
+DEFAULT_COLOR_MATCH = 0.65
+_TAP = np.dtype([("s", "<i4"), ("w", "<i2", (8,))])
+_BOX_DESC = np.dtype([("frame", "<i4"), ("left", "<i4"), ("top", "<i4"), ("box_w", "<i4"), ("box_h", "<i4"), ("reserved", "<i4"),
+                      ("taps_offset", "<i8")])
+_MASK_DESC = np.dtype([("width", "<i4"), ("height", "<i4"), ("span_offset", "<i8"), ("mask_offset", "<i8")])
+_FF_DESC = np.dtype([("enhanced_index", "<i4"), ("left", "<i4"), ("top", "<i4"), ("box_w", "<i4"), ("box_h", "<i4"), ("strength", "<f4"),
+                     ("mask_offset", "<i8"), ("taps_offset", "<i8"), ("bytes_offset", "<i8")])
+assert _BOX_DESC.itemsize == C.sizeof(_hip.FaceFixBoxDesc) and _MASK_DESC.itemsize == C.sizeof(_hip.FaceFixMaskDesc)
+assert _FF_DESC.itemsize == C.sizeof(_hip.FaceFixDesc)
+
+_lock = threading.Lock()
+_host_lib = None
+
+
+def _host():
+    """the library for its HOST table functions (no GPU needed)"""
+    global _host_lib
+    if _host_lib is None:
+        with _lock:
+            if _host_lib is None:
+                _host_lib = _hip.load_library()
+    return _host_lib
+
+
+# ------------------------------------------------------------------------------------------------
+# host integers
+# ------------------------------------------------------------------------------------------------
+def _square_crop_box(face_box, width, height, padding):
+    """(left, top, right, bottom) of the square around a tracked face (:207-226): the larger side of the face grown by ``padding`` on both
+    sides, no larger than the frame, rounded half to even, pushed back inside the frame."""
+    x, y, face_w, face_h = face_box
+    side = min(max(face_w, face_h) * (1.0 + 2.0 * max(0.0, padding)), width, height)
+    left = int(round(x + face_w / 2.0 - side / 2.0))
+    top = int(round(y + face_h / 2.0 - side / 2.0))
+    right, bottom = left + int(round(side)), top + int(round(side))
+    if left < 0:
+        left, right = 0, right - left
+    if top < 0:
+        top, bottom = 0, bottom - top
+    if right > width:
+        left, right = left - (right - width), width
+    if bottom > height:
+        top, bottom = top - (bottom - height), height
+    return (max(0, left), max(0, top), min(width, right), min(height, bottom))
+
+
+def settings_from_payload(payload) -> dict:
+    """``feather`` and ``color_match`` as finalize_face_fix reads them (:930-931): a missing or zero value falls back to the default
+    (the reference's ``or``), then the clamp."""
+    return {"feather": max(0, min(256, int(payload.get("feather") or DEFAULT_FEATHER))),
+            "color_match": max(0.0, min(1.0, float(payload.get("color_match") or DEFAULT_COLOR_MATCH)))}
+
+
+def ellipse_spans(width: int, height: int) -> np.ndarray:
+    """[height, 2] int32: the filled pixels x0 .. x1 of every row of the mask's ellipse (x0 > x1: none); host only"""
+    width, height = int(width), int(height)
+    if width < 1 or height < 1:
+        raise ValueError("ellipse_spans: width and height must be at least 1")
+    spans = np.zeros((height, 2), dtype=np.int32)
+    _hip.check(_host().vrg_ff_ellipse_spans(width, height, C.c_void_p(spans.ctypes.data)), "vrg_ff_ellipse_spans")
+    return spans
+
+
+def gauss_taps(feather: int) -> int:
+    return max(3, 4 * int(feather) + 1)
+
+
+def gauss_coeffs(feather: int) -> np.ndarray:
+    """the fp32 coefficients of the mask's GaussianBlur for 0 <= feather <= 256; host only"""
+    feather = int(feather)
+    if not 0 <= feather <= 256:
+        raise ValueError("gauss_coeffs: feather must lie in 0 .. 256")
+    coeffs = np.zeros(gauss_taps(feather), dtype=np.float32)
+    _hip.check(_host().vrg_ff_gauss_coeffs(feather, C.c_void_p(coeffs.ctypes.data)), "vrg_ff_gauss_coeffs")
+    return coeffs
+
+
+def _lanczos_taps(in_h, in_w, out_h, out_w) -> np.ndarray:
+    table = np.zeros(out_w + out_h, dtype=_TAP)
+    _hip.check(_host().vrg_lanczos4_taps(in_h, in_w, out_h, out_w, C.c_void_p(table.ctypes.data)), "vrg_lanczos4_taps")
+    return table
+
+
+# ------------------------------------------------------------------------------------------------
+# frames in, frames out
+# ------------------------------------------------------------------------------------------------
+def _frames_in(frames, name):
+    """-> (uint8 [F,H,W,3] on the GPU, a function that hands a GPU batch back in the caller's form)"""
+    from .VRGDG_LUTVideoTools import _stack_frames, _unstack_frames
+    from .VRGDG_StandaloneVideoEnhancerNodes import DecodedFrames
+    if isinstance(frames, DecodedFrames):
+        return _check(frames.u8, name), DecodedFrames
+    if isinstance(frames, torch.Tensor):
+        x = _check(frames, name)
+        if x.is_cuda:
+            return x, lambda t: t
+        if x.shape[0] == 0:
+            return x.to(compute_device()), lambda t: t.cpu()
+        return _stack_frames(list(x.numpy())), lambda t: torch.from_numpy(np.stack(_unstack_frames(t))) if t.shape[0] else t.cpu()
+    arrays = list(frames)
+    if not arrays:
+        raise ValueError(f"{name} must not be empty")
+    return _stack_frames(arrays), lambda t: _unstack_frames(t) if t.shape[0] else []
+
+
+def _peek(frames, name):
+    """(frames, height, width) of a batch in any of the accepted forms, checked before anything is uploaded"""
+    t = getattr(frames, "u8", frames)
+    if isinstance(t, torch.Tensor):
+        _check(t, name)
+        return int(t.shape[0]), int(t.shape[1]), int(t.shape[2])
+    arrays = [np.asarray(f) for f in frames]
+    if not arrays:
+        raise ValueError(f"{name} must not be empty")
+    for a in arrays:
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[-1] != 3 or a.shape != arrays[0].shape:
+            raise ValueError(f"{name} must be HxWx3 uint8 arrays of one size")
+    return len(arrays), int(arrays[0].shape[0]), int(arrays[0].shape[1])
+
+
+def _check(t, name):
+    if t.ndim != 4 or t.shape[-1] != 3 or t.dtype != torch.uint8:
+        raise ValueError(f"{name} must be [frames, height, width, 3] uint8")
+    if t.shape[1] < 1 or t.shape[2] < 1:
+        raise ValueError(f"{name} must be at least 1 x 1")
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def _boxes(crop_boxes, frames, height, width):
+    """one (left, top, w, h) or None per frame; a box without pixels raises the reference's ValueError (:947-948)"""
+    boxes = list(crop_boxes)
+    if len(boxes) != frames:
+        raise ValueError(f"crop_boxes must hold one box (or None) per frame: {len(boxes)} for {frames} frames")
+    out = []
+    for index, box in enumerate(boxes):
+        if box is None:
+            out.append(None)
+            continue
+        left, top, right, bottom = (int(v) for v in box)
+        w, h = right - left, bottom - top
+        if w <= 0 or h <= 0:
+            raise ValueError(f"Invalid crop box for frame {index}.")
+        if left < 0 or top < 0 or right > width or bottom > height:
+            raise ValueError(f"crop box of frame {index} does not lie inside the {width} x {height} frame")
+        out.append((left, top, w, h))
+    return out
+
+
+def _upload(array: np.ndarray, device) -> torch.Tensor:
+    return torch.from_numpy(np.ascontiguousarray(array).view(np.uint8).reshape(-1).copy()).to(device)
+
+
+def _tap_tables(sizes, in_size_of, out_size_of):
+    """the concatenated Lanczos records of the distinct sizes: -> (table, {size: offset in records})"""
+    offsets, parts, total = {}, [], 0
+    for size in sizes:
+        if size in offsets:
+            continue
+        (ih, iw), (oh, ow) = in_size_of(size), out_size_of(size)
+        offsets[size] = total
+        parts.append(_lanczos_taps(ih, iw, oh, ow))
+        total += ow + oh
+    return (np.concatenate(parts) if parts else np.zeros(1, dtype=_TAP)), offsets
+
+
+def crop_frames(frames_u8, crop_boxes, enhance_size):
+    """``cv2.resize(frame[top:bottom, left:right], (enhance_size, enhance_size), INTER_LANCZOS4)`` for every frame that has a box
+    (``crop_boxes``: one (left, top, right, bottom) or None per frame) -> ``[n, S, S, 3]`` uint8 in the order of the frames, in the form
+    the frames came in (CUDA tensor, CPU tensor, list of numpy frames, DecodedFrames)."""
+    size = int(enhance_size)
+    if size < 1:
+        raise ValueError("enhance_size must be at least 1")
+    boxes = _boxes(crop_boxes, *_peek(frames_u8, "frames"))
+    x, back = _frames_in(frames_u8, "frames")
+    F, H, W, _ = x.shape
+    used = [(f, b) for f, b in enumerate(boxes) if b is not None]
+    with torch.cuda.device(x.device):
+        out = torch.empty((len(used), size, size, 3), dtype=torch.uint8, device=x.device)
+        if used:
+            table, offsets = _tap_tables([(b[3], b[2]) for _, b in used], lambda s: s, lambda s: (size, size))
+            desc = np.zeros(len(used), dtype=_BOX_DESC)
+            for i, (f, (left, top, w, h)) in enumerate(used):
+                desc[i] = (f, left, top, w, h, 0, offsets[(h, w)])
+            taps, dev_desc = _upload(table, x.device), _upload(desc, x.device)
+            _hip.check(_hip.lib().vrg_lanczos4_boxes_u8(_hip.ptr(x), F, H, W, _hip.ptr(out), _hip.ptr(dev_desc), len(used), size, size,
+                                                        _hip.ptr(taps), len(table), _hip.current_stream()), "vrg_lanczos4_boxes_u8")
+        return back(out)
+
+
+def _mask_tables(sizes, feather):
+    """spans, mask records and the packed offsets of the distinct (w, h): -> (spans, records, {(w, h): offset in floats}, floats, largest)"""
+    offsets, spans, records, total, rows, largest = {}, [], [], 0, 0, 0
+    for w, h in sizes:
+        if (w, h) in offsets:
+            continue
+        offsets[(w, h)] = total
+        spans.append(ellipse_spans(w, h))
+        records.append((w, h, rows, total))
+        rows += h
+        total += w * h
+        largest = max(largest, w * h)
+    return np.concatenate(spans), np.array(records, dtype=_MASK_DESC), offsets, total, largest
+
+
+def _run_masks(spans, records, total, largest, feather, device):
+    """the launches of vrg_ff_masks_f32 -> the packed masks on the device"""
+    masks = torch.empty(max(total, 1), dtype=torch.float32, device=device)
+    n_coeffs = gauss_taps(feather) if feather > 0 else 0
+    coeffs = _upload(gauss_coeffs(feather), device) if n_coeffs else None
+    scratch = torch.empty_like(masks) if n_coeffs else None
+    dev_spans, dev_records = _upload(spans, device), _upload(records, device)
+    _hip.check(_hip.lib().vrg_ff_masks_f32(_hip.ptr(dev_spans), len(spans), _hip.ptr(coeffs) if n_coeffs else None, n_coeffs,
+                                           _hip.ptr(dev_records), len(records), largest, _hip.ptr(scratch) if n_coeffs else None,
+                                           _hip.ptr(masks), total, _hip.current_stream()), "vrg_ff_masks_f32")
+    return masks
+
+
+def _soft_ellipse_mask(width, height, feather) -> np.ndarray:
+    """``_soft_ellipse_mask(width, height, feather)`` of the reference (:880-894) as a float32 ``[height, width]`` array, made on the GPU"""
+    width, height, feather = int(width), int(height), max(0, int(feather))
+    if width < 1 or height < 1:
+        raise ValueError("mask width and height must be at least 1")
+    if feather > 256:
+        raise ValueError("feather must not exceed 256")
+    device = compute_device()
+    with torch.cuda.device(device):
+        spans, records, _, total, largest = _mask_tables([(width, height)], feather)
+        return _run_masks(spans, records, total, largest, feather, device).cpu().numpy().reshape(height, width)
+
+
+def _strengths(strengths, frames):
+    values = [float(strengths)] * frames if isinstance(strengths, (int, float)) else [float(v) for v in strengths]
+    if len(values) != frames:
+        raise ValueError(f"strengths must hold one value per frame: {len(values)} for {frames} frames")
+    return [max(0.0, min(1.0, v)) for v in values]
+
+
+def composite_frames(originals_u8, enhanced_u8, crop_boxes, strengths, feather=DEFAULT_FEATHER, color_match=DEFAULT_COLOR_MATCH):
+    """The loop body of ``finalize_face_fix`` for a batch: ``enhanced_u8`` (one frame per box in the order of the frames, or one per
+    original frame) resized to its box, colour matched, blended under the soft ellipse times ``strengths[f]`` and pasted into a copy of
+    ``originals_u8``, which is never written.  Frames without a box or with strength <= 0 come back unchanged.  The result has the shape
+    and the form of ``originals_u8``."""
+    feather = max(0, min(256, int(feather)))
+    color_match = max(0.0, min(1.0, float(color_match)))
+    boxes = _boxes(crop_boxes, *_peek(originals_u8, "originals"))
+    strength = _strengths(strengths, len(boxes))
+    x, back = _frames_in(originals_u8, "originals")
+    F, H, W, _ = x.shape
+    n_boxes = sum(b is not None for b in boxes)
+    if n_boxes == 0 and (enhanced_u8 is None or len(enhanced_u8) == 0):
+        e = torch.zeros((1, 1, 1, 3), dtype=torch.uint8, device=x.device)
+    else:
+        e, _ = _frames_in(enhanced_u8, "enhanced")
+        if e.device != x.device:
+            e = e.to(x.device)
+    if e.shape[0] not in (n_boxes, F) and n_boxes:
+        raise ValueError(f"enhanced must hold one frame per box ({n_boxes}) or per original frame ({F}), got {e.shape[0]}")
+    per_box = e.shape[0] == n_boxes
+    with torch.cuda.device(x.device):
+        if F == 0:
+            return back(torch.empty_like(x))
+        plan = CompositePlan(x, e, boxes, strength, per_box, feather, color_match)
+        plan.run_masks()
+        plan.run_resize_stats()
+        return back(plan.run_composite())
+
+
+class CompositePlan:
+    """The tables and buffers of one ``composite_frames`` call on device batches, and its three steps (``composite_frames`` runs them in
+    order; tools/bench_facefix_builder.py times each).  ``boxes``: (left, top, w, h) or None per frame; ``strength``: clamped, per frame."""
+
+    def __init__(self, x, e, boxes, strength, per_box, feather, color_match):
+        self.x, self.e, self.feather, self.color_match = x, e, feather, color_match
+        F, EH, EW = int(x.shape[0]), int(e.shape[1]), int(e.shape[2])
+        desc = np.zeros(F, dtype=_FF_DESC)
+        active, k = [], 0
+        for f, box in enumerate(boxes):
+            if box is None:
+                continue
+            index, k = (k if per_box else f), k + 1
+            if strength[f] > 0.0:
+                active.append((f, index, box))
+        sizes = [(b[2], b[3]) for _, _, b in active] or [(1, 1)]
+        self.spans, self.records, mask_offsets, self.mask_floats, self.largest = _mask_tables(sizes, feather)
+        table, tap_offsets = _tap_tables([(b[3], b[2]) for _, _, b in active], lambda s: (EH, EW), lambda s: s)
+        capacity = 0
+        for f, index, (left, top, w, h) in active:
+            desc[f] = (index, left, top, w, h, strength[f], mask_offsets[(w, h)], tap_offsets[(h, w)], capacity)
+            capacity += w * h * 3
+        self.capacity, self.n_taps, self.active = capacity, len(table), len(active)
+        self.taps, self.desc = _upload(table, x.device), _upload(desc, x.device)
+        self.face = torch.empty(max(capacity, 1), dtype=torch.uint8, device=x.device)
+        self.stats = torch.empty(F * _hip.FACEFIX_STATS_WORDS, dtype=torch.int64, device=x.device)
+        self.out = torch.empty_like(x)
+        self.masks = None
+
+    def run_masks(self):
+        self.masks = _run_masks(self.spans, self.records, self.mask_floats, self.largest, self.feather, self.x.device)
+
+    def run_resize_stats(self):
+        x, e = self.x, self.e
+        _hip.check(_hip.lib().vrg_ff_resize_stats_u8(_hip.ptr(x), _hip.ptr(e), _hip.ptr(self.masks), self.mask_floats, _hip.ptr(self.desc),
+                                                     _hip.ptr(self.taps), self.n_taps, _hip.ptr(self.face), self.capacity, _hip.ptr(self.stats),
+                                                     int(x.shape[0]), int(e.shape[0]), int(x.shape[1]), int(x.shape[2]), int(e.shape[1]),
+                                                     int(e.shape[2]), self.largest if self.active else 0, self.color_match,
+                                                     _hip.current_stream()), "vrg_ff_resize_stats_u8")
+
+    def run_composite(self):
+        x = self.x
+        _hip.check(_hip.lib().vrg_ff_composite_u8(_hip.ptr(x), _hip.ptr(self.masks), self.mask_floats, _hip.ptr(self.desc), _hip.ptr(self.face),
+                                                  self.capacity, _hip.ptr(self.stats), _hip.ptr(self.out), int(x.shape[0]), int(x.shape[1]),
+                                                  int(x.shape[2]), _hip.current_stream()), "vrg_ff_composite_u8")
+        return self.out

@@ -86,6 +86,26 @@ class WarpDesc(C.Structure):
 
 WARP_TABLE_BYTES = 1024 * 64 * 2
 
+
+class FaceFixBoxDesc(C.Structure):
+    """vrg_ff_box_desc"""
+    _fields_ = [("frame", C.c_int32), ("left", C.c_int32), ("top", C.c_int32), ("box_w", C.c_int32), ("box_h", C.c_int32),
+                ("reserved", C.c_int32), ("taps_offset", C.c_int64)]
+
+
+class FaceFixMaskDesc(C.Structure):
+    """vrg_ff_mask_desc"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("span_offset", C.c_int64), ("mask_offset", C.c_int64)]
+
+
+class FaceFixDesc(C.Structure):
+    """vrg_ff_desc"""
+    _fields_ = [("enhanced_index", C.c_int32), ("left", C.c_int32), ("top", C.c_int32), ("box_w", C.c_int32), ("box_h", C.c_int32),
+                ("strength", C.c_float), ("mask_offset", C.c_int64), ("taps_offset", C.c_int64), ("bytes_offset", C.c_int64)]
+
+
+FACEFIX_STATS_WORDS = 12        # uint64 per frame (csrc/vrg_facefix_math.hpp: FF_STATS_WORDS)
+
 _F3 = C.c_float * 3
 _P = C.c_void_p
 _SIGNATURES = {
@@ -153,6 +173,13 @@ _SIGNATURES = {
     "vrg_cut_thumbs_f32": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "vrg_cut_hist_u8": (C.c_int, [_P, _P, C.c_int64, _P]),
     "vrg_cut_pair_sums": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
+    "vrg_ff_ellipse_spans": (C.c_int, [C.c_int32, C.c_int32, _P]),
+    "vrg_ff_gauss_coeffs": (C.c_int, [C.c_int32, _P]),
+    "vrg_lanczos4_boxes_u8": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64, _P]),
+    "vrg_ff_masks_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int32, _P, C.c_int64, C.c_int64, _P, _P, C.c_int64, _P]),
+    "vrg_ff_resize_stats_u8": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int64] + [C.c_int32] * 4 +
+                               [C.c_int64, C.c_float, _P]),
+    "vrg_ff_composite_u8": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
 }
 
 # include/vrgdg_hip_debug.h: self-tests and probes -- for the test suite and the measurement tools, not part of the drop-in boundary

@@ -1,0 +1,363 @@
+// vrg_facefix.hip -- the pixels of the AI Video Builder's Face Fix (reference VRGDG_FaceFix.py: prepare_face_fix :473-476,
+// finalize_face_fix :937-957) on decoded B,G,R bytes.  gfx950 only.  Arithmetic: csrc/vrg_facefix_math.hpp, csrc/vrg_lanczos_math.hpp.
+//
+// Shape of the work.  A job is a batch of byte frames and one square box per frame, a few per cent of a 4K frame up to all of its height.
+//   k_lanczos4_boxes     prepare: one launch, blockIdx.y = the output frame, so its record (source frame, box, where its Lanczos records
+//                        start) is wave-uniform; one thread = one output pixel straight from the definition (lz_pixel: 64 byte taps per
+//                        channel out of L1 / L2, clamped to the BOX).  The box sizes differ per frame, so the tiles of k_lanczos4_tile
+//                        (one geometry per launch) do not apply.
+//   k_ff_mask_h / _v     the soft-ellipse masks, one per distinct (w, h) of the batch: the 0 / 1 spans blurred through a scratch plane.
+//                        The horizontal pass adds the coefficients of the taps inside the row's span; the vertical pass reads the plane
+//                        column-wise (consecutive lanes, consecutive floats).
+//   k_ff_resize_stats    finalize, first half: the repaired frame resized to its box (lz_pixel again) into a packed byte scratch, and in
+//                        the same launch the selected count and six byte sums of the frame: lane values -> wave butterfly -> LDS -> one
+//                        64-bit integer atomic per sum and workgroup (integer addition: the same bits in any order).
+//   k_ff_finish          the means and shifts of every frame, on the device: the host never waits.
+//   k_ff_composite       finalize, second half: ONE pass over the output batch as a flat run of bytes, 16 per thread.  A piece that
+//                        misses the box (nearly all of a frame) is one 16-byte non-temporal load and store; a piece that touches it is
+//                        rebuilt byte by byte in registers; pieces that cross a frame boundary or are not 16-byte aligned go byte by byte.
+#include "vrg_common.hpp"
+#include "vrg_facefix_math.hpp"
+#include "vrg_lanczos_math.hpp"
+
+namespace vrg {
+
+typedef uint32_t ffu4 __attribute__((ext_vector_type(4)));
+
+struct FfGeom {
+    int64_t frames, enhanced_frames, mask_floats, n_taps, capacity;
+    int32_t H, W, enh_h, enh_w;
+};
+
+__device__ __forceinline__ bool ff_box_ok(const vrg_ff_box_desc& d, int64_t in_frames, int32_t H, int32_t W, int64_t n_taps, int32_t out_h,
+                                          int32_t out_w) {
+    if (d.frame < 0 || d.frame >= in_frames || d.left < 0 || d.top < 0 || d.box_w < 1 || d.box_h < 1) return false;
+    if ((int64_t)d.left + d.box_w > W || (int64_t)d.top + d.box_h > H) return false;
+    return d.taps_offset >= 0 && d.taps_offset <= n_taps && (int64_t)out_w + out_h <= n_taps - d.taps_offset;
+}
+
+// the record of the composite: `resized` = the checks of the passes that read the resize source as well
+__device__ __forceinline__ bool ff_desc_ok(const vrg_ff_desc& d, const FfGeom& g, bool resized) {
+    if (!(d.strength > 0.0f) || d.left < 0 || d.top < 0 || d.box_w < 1 || d.box_h < 1) return false;
+    if ((int64_t)d.left + d.box_w > g.W || (int64_t)d.top + d.box_h > g.H) return false;
+    const int64_t px = (int64_t)d.box_w * d.box_h;
+    if (d.mask_offset < 0 || d.mask_offset > g.mask_floats || px > g.mask_floats - d.mask_offset) return false;
+    if (d.bytes_offset < 0 || d.bytes_offset > g.capacity || px * 3 > g.capacity - d.bytes_offset) return false;
+    if (!resized) return true;
+    if (d.enhanced_index < 0 || d.enhanced_index >= g.enhanced_frames) return false;
+    return d.taps_offset >= 0 && d.taps_offset <= g.n_taps && (int64_t)d.box_w + d.box_h <= g.n_taps - d.taps_offset;
+}
+
+__global__ __launch_bounds__(256) void k_lanczos4_boxes(const uint8_t* __restrict__ in, int64_t in_frames, int32_t H, int32_t W,
+                                                         uint8_t* __restrict__ out, const vrg_ff_box_desc* __restrict__ desc, int32_t out_h,
+                                                         int32_t out_w, const LzTap* __restrict__ taps, int64_t n_taps) {
+    const int32_t n = out_h * out_w;
+    const int32_t p = (int32_t)(blockIdx.x * 256 + threadIdx.x);
+    if (p >= n) return;
+    const vrg_ff_box_desc d = desc[blockIdx.y];                          // wave-uniform
+    uint8_t* dst = out + ((int64_t)blockIdx.y * n + p) * 3;
+    uint8_t o[3] = {0, 0, 0};
+    if (ff_box_ok(d, in_frames, H, W, n_taps, out_h, out_w)) {
+        const int32_t y = p / out_w, x = p - y * out_w;
+        const uint8_t* box = in + (((int64_t)d.frame * H + d.top) * W + d.left) * 3;
+        const LzTap cx = taps[d.taps_offset + x], ry = taps[d.taps_offset + out_w + y];
+        lz_pixel(cx, ry, d.box_w, d.box_h, [&](int32_t sy, int32_t sx, int c) { return box[((int64_t)sy * W + sx) * 3 + c]; }, o);
+    }
+    dst[0] = o[0]; dst[1] = o[1]; dst[2] = o[2];
+}
+
+__device__ __forceinline__ bool ff_mask_ok(const vrg_ff_mask_desc& d, int64_t n_spans, int64_t mask_floats) {
+    if (d.width < 1 || d.height < 1 || d.span_offset < 0 || d.span_offset > n_spans || d.height > n_spans - d.span_offset) return false;
+    return d.mask_offset >= 0 && d.mask_offset <= mask_floats && (int64_t)d.width * d.height <= mask_floats - d.mask_offset;
+}
+
+// n == 0: the 0 / 1 spans go straight to `plane` (the masks); otherwise the horizontal plane (the scratch)
+__global__ __launch_bounds__(256) void k_ff_mask_h(const FfSpan* __restrict__ spans, int64_t n_spans, const float* __restrict__ coeffs, int32_t n,
+                                                    const vrg_ff_mask_desc* __restrict__ desc, float* __restrict__ plane, int64_t mask_floats) {
+    const vrg_ff_mask_desc d = desc[blockIdx.y];
+    if (!ff_mask_ok(d, n_spans, mask_floats)) return;
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= (int64_t)d.width * d.height) return;
+    const int32_t y = (int32_t)(p / d.width), x = (int32_t)(p - (int64_t)y * d.width);
+    const FfSpan s = spans[d.span_offset + y];
+    plane[d.mask_offset + p] = n == 0 ? ((x >= s.x0 && x <= s.x1) ? 1.0f : 0.0f) : ff_blur_h(coeffs, n, s, d.width, x);
+}
+
+__global__ __launch_bounds__(256) void k_ff_mask_v(int64_t n_spans, const float* __restrict__ coeffs, int32_t n,
+                                                    const vrg_ff_mask_desc* __restrict__ desc, const float* __restrict__ plane,
+                                                    float* __restrict__ masks, int64_t mask_floats) {
+    const vrg_ff_mask_desc d = desc[blockIdx.y];
+    if (!ff_mask_ok(d, n_spans, mask_floats)) return;
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= (int64_t)d.width * d.height) return;
+    const int32_t y = (int32_t)(p / d.width), x = (int32_t)(p - (int64_t)y * d.width);
+    const float* col = plane + d.mask_offset + x;
+    masks[d.mask_offset + p] = ff_blur_v(coeffs, n, d.height, y, [&](int32_t row) { return col[(int64_t)row * d.width]; });
+}
+
+__global__ __launch_bounds__(256) void k_ff_resize_stats(const uint8_t* __restrict__ originals, const uint8_t* __restrict__ enhanced,
+                                                          const float* __restrict__ masks, const vrg_ff_desc* __restrict__ desc,
+                                                          const LzTap* __restrict__ taps, uint8_t* __restrict__ bytes,
+                                                          unsigned long long* __restrict__ stats, FfGeom g, int64_t f0, int32_t measure) {
+    const int64_t f = f0 + blockIdx.y;
+    const vrg_ff_desc d = desc[f];                                       // wave-uniform
+    if (!ff_desc_ok(d, g, true)) return;                                 // the whole workgroup leaves
+    const int64_t n = (int64_t)d.box_w * d.box_h;
+    if ((int64_t)blockIdx.x * 256 >= n) return;
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    uint32_t acc[FF_STAT_SUMS];
+#pragma unroll
+    for (int i = 0; i < FF_STAT_SUMS; ++i) acc[i] = 0u;
+    if (p < n) {
+        const int32_t dy = (int32_t)(p / d.box_w), dx = (int32_t)(p - (int64_t)dy * d.box_w);
+        const uint8_t* ef = enhanced + (int64_t)d.enhanced_index * g.enh_h * g.enh_w * 3;
+        const LzTap cx = taps[d.taps_offset + dx], ry = taps[d.taps_offset + d.box_w + dy];
+        uint8_t o[3];
+        const int32_t ew = g.enh_w;
+        lz_pixel(cx, ry, g.enh_w, g.enh_h, [&](int32_t sy, int32_t sx, int c) { return ef[((int64_t)sy * ew + sx) * 3 + c]; }, o);
+        uint8_t* dst = bytes + d.bytes_offset + p * 3;
+        dst[0] = o[0]; dst[1] = o[1]; dst[2] = o[2];
+        if (measure && ff_selected(masks[d.mask_offset + p])) {
+            const uint8_t* t = originals + ((f * g.H + d.top + dy) * (int64_t)g.W + d.left + dx) * 3;
+            acc[0] = 1u;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                acc[1 + c] = o[c];
+                acc[4 + c] = t[c];
+            }
+        }
+    }
+    if (!measure) return;                                                // uniform
+#pragma unroll
+    for (int i = 0; i < FF_STAT_SUMS; ++i) {
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) acc[i] += (uint32_t)__shfl_xor((int)acc[i], off, 64);
+    }
+    __shared__ uint32_t part[4][FF_STAT_SUMS];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < FF_STAT_SUMS; ++i) part[wave][i] = acc[i];
+    }
+    __syncthreads();
+    if (threadIdx.x < FF_STAT_SUMS) {
+        const int t = threadIdx.x;
+        const uint32_t s = part[0][t] + part[1][t] + part[2][t] + part[3][t];             // <= 256 * 255
+        if (s) atomicAdd(stats + f * FF_STATS_WORDS + t, (unsigned long long)s);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_ff_finish(unsigned long long* __restrict__ stats, int64_t frames, float color_match) {
+    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (f >= frames) return;
+    unsigned long long* rec = stats + f * FF_STATS_WORDS;
+    uint64_t sums[FF_STAT_SUMS];
+#pragma unroll
+    for (int i = 0; i < FF_STAT_SUMS; ++i) sums[i] = rec[i];
+    float shift[3];
+    const bool matched = ff_shifts(sums, color_match, shift);
+    rec[7] = matched ? 1ull : 0ull;
+    rec[8] = (unsigned long long)f32_bits(shift[0]) | ((unsigned long long)f32_bits(shift[1]) << 32);
+    rec[9] = (unsigned long long)f32_bits(shift[2]);
+}
+
+struct FfFrame {
+    vrg_ff_desc d;
+    bool ok, matched;
+    float shift[3];
+};
+
+__device__ __forceinline__ void ff_frame(FfFrame& fr, const vrg_ff_desc* __restrict__ desc, const unsigned long long* __restrict__ stats,
+                                         const FfGeom& g, int64_t f) {
+    fr.d = desc[f];
+    fr.ok = ff_desc_ok(fr.d, g, false);
+    fr.matched = false;
+    fr.shift[0] = fr.shift[1] = fr.shift[2] = 0.0f;
+}
+
+// the shifts are read only by a thread that touches the box
+__device__ __forceinline__ void ff_frame_stats(FfFrame& fr, const unsigned long long* __restrict__ stats, int64_t f) {
+    const unsigned long long* rec = stats + f * FF_STATS_WORDS;
+    fr.matched = rec[7] != 0ull;
+    const unsigned long long a = rec[8], b = rec[9];
+    fr.shift[0] = f32_from_bits((uint32_t)a);
+    fr.shift[1] = f32_from_bits((uint32_t)(a >> 32));
+    fr.shift[2] = f32_from_bits((uint32_t)b);
+}
+
+// byte r of the frame (value v in the original): what the composite leaves there
+__device__ __forceinline__ uint8_t ff_byte(const FfFrame& fr, const FfGeom& g, const float* __restrict__ masks, const uint8_t* __restrict__ bytes,
+                                           int32_t r, uint8_t v) {
+    const int32_t px = (int32_t)((uint32_t)r / 3u), c = r - px * 3;
+    const int32_t y = (int32_t)((uint32_t)px / (uint32_t)g.W), x = px - y * g.W;
+    const int32_t dx = x - fr.d.left, dy = y - fr.d.top;
+    if (dx < 0 || dx >= fr.d.box_w || dy < 0 || dy >= fr.d.box_h) return v;
+    const int64_t i = (int64_t)dy * fr.d.box_w + dx;
+    uint8_t face = bytes[fr.d.bytes_offset + i * 3 + c];
+    if (fr.matched) face = ff_shift_byte(face, fr.shift[c]);
+    return ff_blend_byte(v, face, masks[fr.d.mask_offset + i], fr.d.strength);
+}
+
+// do bytes r .. r + 15 of a frame touch the box?  (a piece spans at most two rows unless the frame is narrower than six pixels)
+__device__ __forceinline__ bool ff_piece_hits(const vrg_ff_desc& d, int32_t W, int32_t r) {
+    const int32_t pitch = W * 3;
+    const int32_t y0 = (int32_t)((uint32_t)r / (uint32_t)pitch), y1 = (int32_t)((uint32_t)(r + 15) / (uint32_t)pitch);
+    if (y1 < d.top || y0 >= d.top + d.box_h) return false;
+    if (y0 != y1) return true;
+    const int32_t xs = (r - y0 * pitch) / 3, xe = (r + 15 - y0 * pitch) / 3;
+    return xe >= d.left && xs < d.left + d.box_w;
+}
+
+__global__ __launch_bounds__(256) void k_ff_composite(const uint8_t* __restrict__ originals, const float* __restrict__ masks,
+                                                       const vrg_ff_desc* __restrict__ desc, const uint8_t* __restrict__ bytes,
+                                                       const unsigned long long* __restrict__ stats, uint8_t* __restrict__ out, FfGeom g,
+                                                       int64_t frame_bytes, int64_t total, int32_t aligned) {
+    const int64_t b0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 16;
+    if (b0 >= total) return;
+    int64_t f = b0 / frame_bytes;
+    int32_t r = (int32_t)(b0 - f * frame_bytes);
+    FfFrame fr;
+    ff_frame(fr, desc, stats, g, f);
+    const uint8_t* src = originals + b0;
+    uint8_t* dst = out + b0;
+    if (aligned && (int64_t)r + 16 <= frame_bytes) {
+        ffu4 q = __builtin_nontemporal_load(reinterpret_cast<const ffu4*>(src));
+        if (fr.ok && ff_piece_hits(fr.d, g.W, r)) {
+            ff_frame_stats(fr, stats, f);
+            uint32_t w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                const uint8_t v = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
+                const uint8_t n = ff_byte(fr, g, masks, bytes, r + k, v);
+                w[k >> 2] = (w[k >> 2] & ~(0xffu << (8 * (k & 3)))) | ((uint32_t)n << (8 * (k & 3)));
+            }
+            q = ffu4{w[0], w[1], w[2], w[3]};
+        }
+        __builtin_nontemporal_store(q, reinterpret_cast<ffu4*>(dst));
+        return;
+    }
+    if (fr.ok) ff_frame_stats(fr, stats, f);
+    for (int k = 0; k < 16 && b0 + k < total; ++k) {
+        if (r >= frame_bytes) {
+            r = 0;
+            ++f;
+            ff_frame(fr, desc, stats, g, f);
+            if (fr.ok) ff_frame_stats(fr, stats, f);
+        }
+        const uint8_t v = src[k];
+        dst[k] = fr.ok ? ff_byte(fr, g, masks, bytes, r, v) : v;
+        ++r;
+    }
+}
+
+}  // namespace vrg
+
+using namespace vrg;
+
+extern "C" {
+
+int vrg_ff_ellipse_spans(int32_t width, int32_t height, int32_t* spans_host) {
+    if (!spans_host || width < 1 || height < 1) return VRG_ERR_BAD_ARG;
+    ff_ellipse_spans(width, height, reinterpret_cast<FfSpan*>(spans_host));
+    return VRG_OK;
+}
+
+int vrg_ff_gauss_coeffs(int32_t feather, float* coeffs_host) {
+    if (!coeffs_host || feather < 0 || feather > 256) return VRG_ERR_BAD_ARG;
+    ff_gauss_coeffs(feather, coeffs_host);
+    return VRG_OK;
+}
+
+int vrg_lanczos4_boxes_u8(const uint8_t* in, int64_t in_frames, int32_t height, int32_t width, uint8_t* out, const vrg_ff_box_desc* desc,
+                          int64_t n_out, int32_t out_h, int32_t out_w, const void* taps, int64_t n_taps, void* stream) {
+    if (!in || !out || in == out || !desc || !taps || (reinterpret_cast<uintptr_t>(taps) & 3u) != 0 || in_frames < 0 || n_out < 0 || n_taps < 0 ||
+        height < 1 || width < 1 || out_h < 1 || out_w < 1)
+        return VRG_ERR_BAD_ARG;
+    if (n_out == 0) return VRG_OK;
+    if ((int64_t)out_h * out_w * 3 > 0x7fffffffll || (int64_t)height * width * 3 > 0x7fffffffll) return VRG_ERR_UNSUPPORTED;
+    const uint32_t parts = (uint32_t)(((int64_t)out_h * out_w + 255) / 256);
+    const int64_t out_fe = (int64_t)out_h * out_w * 3;
+    for (int64_t f0 = 0; f0 < n_out; f0 += 32768) {
+        const int64_t nf = n_out - f0 < 32768 ? n_out - f0 : 32768;
+        hipLaunchKernelGGL(k_lanczos4_boxes, dim3(parts, (uint32_t)nf), dim3(256), 0, (hipStream_t)stream, in, in_frames, height, width,
+                           out + f0 * out_fe, desc + f0, out_h, out_w, reinterpret_cast<const LzTap*>(taps), n_taps);
+        VRG_CHECK_LAUNCH();
+    }
+    return VRG_OK;
+}
+
+int vrg_ff_masks_f32(const int32_t* spans, int64_t n_spans, const float* coeffs, int32_t n_coeffs, const vrg_ff_mask_desc* desc,
+                     int64_t n_masks, int64_t max_mask_pixels, float* scratch, float* masks, int64_t mask_floats, void* stream) {
+    if (n_masks < 0 || n_spans < 0 || max_mask_pixels < 0 || mask_floats < 0 || n_coeffs < 0 || n_coeffs > 4 * 256 + 1) return VRG_ERR_BAD_ARG;
+    if (n_masks == 0) return VRG_OK;
+    if (!spans || !desc || !masks || (n_coeffs > 0 && (!coeffs || !scratch || scratch == masks || (n_coeffs & 1) == 0))) return VRG_ERR_BAD_ARG;
+    if (max_mask_pixels > 0x7fffffffll) return VRG_ERR_UNSUPPORTED;
+    if (max_mask_pixels == 0) return VRG_OK;
+    const uint32_t parts = (uint32_t)((max_mask_pixels + 255) / 256);
+    hipStream_t st = (hipStream_t)stream;
+    for (int64_t m0 = 0; m0 < n_masks; m0 += 32768) {
+        const int64_t nm = n_masks - m0 < 32768 ? n_masks - m0 : 32768;
+        hipLaunchKernelGGL(k_ff_mask_h, dim3(parts, (uint32_t)nm), dim3(256), 0, st, reinterpret_cast<const FfSpan*>(spans), n_spans, coeffs,
+                           n_coeffs, desc + m0, n_coeffs ? scratch : masks, mask_floats);
+        VRG_CHECK_LAUNCH();
+        if (n_coeffs) {
+            hipLaunchKernelGGL(k_ff_mask_v, dim3(parts, (uint32_t)nm), dim3(256), 0, st, n_spans, coeffs, n_coeffs, desc + m0,
+                               (const float*)scratch, masks, mask_floats);
+            VRG_CHECK_LAUNCH();
+        }
+    }
+    return VRG_OK;
+}
+
+int vrg_ff_resize_stats_u8(const uint8_t* originals, const uint8_t* enhanced, const float* masks, int64_t mask_floats,
+                           const vrg_ff_desc* desc, const void* taps, int64_t n_taps, uint8_t* bytes, int64_t capacity, void* stats,
+                           int64_t frames, int64_t enhanced_frames, int32_t height, int32_t width, int32_t enh_h, int32_t enh_w,
+                           int64_t max_box_pixels, float color_match, void* stream) {
+    if (frames < 0 || enhanced_frames < 0 || mask_floats < 0 || n_taps < 0 || capacity < 0 || max_box_pixels < 0) return VRG_ERR_BAD_ARG;
+    if (frames == 0) return VRG_OK;
+    if (!originals || !enhanced || !masks || !desc || !taps || (reinterpret_cast<uintptr_t>(taps) & 3u) != 0 || !bytes || !stats ||
+        (reinterpret_cast<uintptr_t>(stats) & 7u) != 0 || bytes == originals || bytes == enhanced || height < 1 || width < 1 || enh_h < 1 || enh_w < 1)
+        return VRG_ERR_BAD_ARG;
+    if ((int64_t)height * width * 3 > 0x7fffffffll || (int64_t)enh_h * enh_w * 3 > 0x7fffffffll || max_box_pixels > 0x7fffffffll)
+        return VRG_ERR_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(stats, 0, (size_t)frames * FF_STATS_WORDS * sizeof(uint64_t), st) != hipSuccess) return VRG_ERR_LAUNCH;
+    const FfGeom g{frames, enhanced_frames, mask_floats, n_taps, capacity, height, width, enh_h, enh_w};
+    const int32_t measure = color_match > 0.0f ? 1 : 0;
+    if (max_box_pixels > 0) {
+        const uint32_t parts = (uint32_t)((max_box_pixels + 255) / 256);
+        for (int64_t f0 = 0; f0 < frames; f0 += 32768) {
+            const int64_t nf = frames - f0 < 32768 ? frames - f0 : 32768;
+            hipLaunchKernelGGL(k_ff_resize_stats, dim3(parts, (uint32_t)nf), dim3(256), 0, st, originals, enhanced, masks, desc,
+                               reinterpret_cast<const LzTap*>(taps), bytes, (unsigned long long*)stats, g, f0, measure);
+            VRG_CHECK_LAUNCH();
+        }
+    }
+    if (measure) {
+        hipLaunchKernelGGL(k_ff_finish, dim3((uint32_t)((frames + 255) / 256)), dim3(256), 0, st, (unsigned long long*)stats, frames, color_match);
+        VRG_CHECK_LAUNCH();
+    }
+    return VRG_OK;
+}
+
+int vrg_ff_composite_u8(const uint8_t* originals, const float* masks, int64_t mask_floats, const vrg_ff_desc* desc, const uint8_t* bytes,
+                        int64_t capacity, const void* stats, uint8_t* out, int64_t frames, int32_t height, int32_t width, void* stream) {
+    if (frames < 0 || mask_floats < 0 || capacity < 0) return VRG_ERR_BAD_ARG;
+    if (frames == 0) return VRG_OK;
+    if (!originals || !masks || !desc || !bytes || !stats || (reinterpret_cast<uintptr_t>(stats) & 7u) != 0 || !out || out == originals ||
+        out == bytes || height < 1 || width < 1)
+        return VRG_ERR_BAD_ARG;
+    const int64_t frame_bytes = (int64_t)height * width * 3;
+    if (frame_bytes > 0x7fffffffll - 16) return VRG_ERR_UNSUPPORTED;
+    const int64_t total = frames * frame_bytes;
+    const int64_t blocks = ((total + 15) / 16 + 255) / 256;
+    if (blocks > 0x7fffffffll) return VRG_ERR_UNSUPPORTED;
+    const FfGeom g{frames, 0, mask_floats, 0, capacity, height, width, 0, 0};
+    const int32_t aligned = ((reinterpret_cast<uintptr_t>(originals) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0 ? 1 : 0;
+    hipLaunchKernelGGL(k_ff_composite, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, originals, masks, desc, bytes,
+                       (const unsigned long long*)stats, out, g, frame_bytes, total, aligned);
+    VRG_CHECK_LAUNCH();
+    return VRG_OK;
+}
+
+}  // extern "C"

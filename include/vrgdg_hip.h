@@ -529,6 +529,72 @@ int vrg_cut_hist_u8(const uint8_t* thumbs, int32_t* hist, int64_t frames, void* 
 int vrg_cut_pair_sums(const uint8_t* thumbs, const int32_t* hist, int64_t* sums, int64_t frames, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The AI Video Builder's Face Fix (VRGDG_FaceFix.py of the reference: prepare_face_fix :473-476, finalize_face_fix :937-957) on decoded
+ * uint8 B,G,R frames: square boxes resized with cv2's byte Lanczos-4 to the enhance size; and, on the way back, the repaired frame
+ * resized to its box, colour matched by a mean shift over a soft ellipse and blended into a copy of the original.  Arithmetic:
+ * csrc/vrg_facefix_math.hpp (and csrc/vrg_lanczos_math.hpp for the resize).
+ *
+ * HOST tables.  vrg_ff_ellipse_spans fills `height` records of two int32 (x0, x1: the filled pixels of the row, x0 > x1 = none) -- the
+ * restated cv2.ellipse(..., -1) of _soft_ellipse_mask(width, height, .).  vrg_ff_gauss_coeffs fills the max(3, 4 * feather + 1) fp32
+ * coefficients of its GaussianBlur (0 <= feather <= 256).  The Lanczos records are those of vrg_lanczos4_taps, one set of
+ * out_w + out_h records per distinct (source size -> result size), concatenated by the caller; `n_taps` = records in the table.
+ *
+ * Every table and record below is device memory; a record that names anything outside the stated sizes, or a box that does not lie inside
+ * the frame, is treated as "no box".
+ * ------------------------------------------------------------------------------------------- */
+typedef struct vrg_ff_box_desc {
+    int32_t frame;                     /* frame of `in` the box is cut from */
+    int32_t left, top, box_w, box_h;
+    int32_t reserved;                  /* 0 */
+    int64_t taps_offset;               /* records from `taps` to the out_w + out_h records of (box_h, box_w) -> (out_h, out_w) */
+} vrg_ff_box_desc;
+
+typedef struct vrg_ff_mask_desc {
+    int32_t width, height;
+    int64_t span_offset;               /* records from `spans` to this mask's `height` records */
+    int64_t mask_offset;               /* floats from `masks` (and `scratch`) to this mask's [height][width] plane */
+} vrg_ff_mask_desc;
+
+typedef struct vrg_ff_desc {           /* one OUTPUT frame f: originals[f] with enhanced[enhanced_index] composited into the box */
+    int32_t enhanced_index;
+    int32_t left, top, box_w, box_h;
+    float strength;                    /* composite_strength in (0, 1]; <= 0: the frame is copied */
+    int64_t mask_offset;               /* floats from `masks` to the [box_h][box_w] mask */
+    int64_t taps_offset;               /* records from `taps` to the box_w + box_h records of (enh_h, enh_w) -> (box_h, box_w) */
+    int64_t bytes_offset;              /* bytes from `bytes` to this frame's [box_h][box_w][3] resized face */
+} vrg_ff_desc;
+
+int vrg_ff_ellipse_spans(int32_t width, int32_t height, int32_t* spans_host);
+int vrg_ff_gauss_coeffs(int32_t feather, float* coeffs_host);
+
+/* out[i] = cv2.resize(in[frame][top : top + box_h, left : left + box_w], (out_w, out_h), INTER_LANCZOS4) for n_out records, one launch:
+ * taps clamp to the BOX (cv2 resizes a view).  A box of exactly the output size comes out as a copy of its bytes.  "No box" writes
+ * zeros.  in != out; `in` ([in_frames][height][width][3]) is never written. */
+int vrg_lanczos4_boxes_u8(const uint8_t* in, int64_t in_frames, int32_t height, int32_t width, uint8_t* out, const vrg_ff_box_desc* desc,
+                          int64_t n_out, int32_t out_h, int32_t out_w, const void* taps, int64_t n_taps, void* stream);
+
+/* The soft-ellipse masks of `n_masks` records, packed into `masks` (`mask_floats` floats; `scratch` of the same size holds the horizontal
+ * planes): the 0 / 1 spans blurred horizontally, then vertically, with `n_coeffs` coefficients (BORDER_REFLECT_101), clipped to [0, 1].
+ * n_coeffs == 0 (feather 0; `coeffs` and `scratch` may be NULL): the 0 / 1 spans.  max_mask_pixels >= the largest width * height. */
+int vrg_ff_masks_f32(const int32_t* spans, int64_t n_spans, const float* coeffs, int32_t n_coeffs, const vrg_ff_mask_desc* desc,
+                     int64_t n_masks, int64_t max_mask_pixels, float* scratch, float* masks, int64_t mask_floats, void* stream);
+
+/* For every frame with a box and strength > 0: enhanced[enhanced_index] ([.][enh_h][enh_w][3]) resized to the box into `bytes`
+ * (`capacity` bytes), and -- when color_match > 0 -- into stats[f] (12 uint64 per frame, zeroed here): [0] the count of mask > 0.35,
+ * [1..3] the sums of the resized face's bytes there, [4..6] of the original's, exact integers; then [7] matched = count >= 16 and
+ * [8..9] the three fp32 shifts fl(fl(original mean - face mean) * color_match) and a zero.  max_box_pixels >= the largest box. */
+int vrg_ff_resize_stats_u8(const uint8_t* originals, const uint8_t* enhanced, const float* masks, int64_t mask_floats,
+                           const vrg_ff_desc* desc, const void* taps, int64_t n_taps, uint8_t* bytes, int64_t capacity, void* stats,
+                           int64_t frames, int64_t enhanced_frames, int32_t height, int32_t width, int32_t enh_h, int32_t enh_w,
+                           int64_t max_box_pixels, float color_match, void* stream);
+
+/* One pass over out = [frames][height][width][3]: the original's bytes outside the box (and everywhere for "no box" / strength <= 0);
+ * inside, face' = matched ? trunc(clip(face + shift, 0, 255)) : face and
+ * out = trunc(clip(fl(fl(original * fl(1 - a)) + fl(face' * a)), 0, 255)), a = fl(mask * strength).  out != originals, never written. */
+int vrg_ff_composite_u8(const uint8_t* originals, const float* masks, int64_t mask_floats, const vrg_ff_desc* desc, const uint8_t* bytes,
+                        int64_t capacity, const void* stats, uint8_t* out, int64_t frames, int32_t height, int32_t width, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Introspection
  * ------------------------------------------------------------------------------------------- */
 int vrg_abi_version(void);
