@@ -7,9 +7,16 @@
                       ``_color_match``, the fp32 blend under ``alpha * composite_strength`` and the paste into a copy of the original --
                       four launches for a batch, no host round trip in between.
 
+``detection_plan`` / ``detector_blobs`` / ``rotated_frames`` / ``candidates_from_outputs`` / ``detect_with_rotation``
+                      the pixel work in front of the face detector and the host arithmetic behind it (``_detect_with_rotation`` /
+                      ``_detect``, :67-157) with the Builder's rules: mode names off / light / strong, the caller's regions at angle 0 and
+                      ``_initial_regions`` (rounded tiles) at the others, regions with a side below 8 skipped, boxes decoded with
+                      round() and kept when x2 > x and y2 > y.  The implementation is shared with VRGDG_StandaloneFaceFixNodes
+                      (csrc/vrg_detect.hip); the network is a seam (``forward``), None by default.
+
 Device-resident inputs stay on the device; CPU inputs (a uint8 tensor, a list of numpy frames) are uploaded whole and the result is
-downloaded whole (the staging helpers of VRGDG_LUTVideoTools).  Detection, tracking, PNG / video I/O, manifests, ffmpeg and the aiohttp
-routes are out of scope.  The arithmetic is csrc/vrg_facefix_math.hpp; the library is reached through ``_hip`` only.
+downloaded whole (the staging helpers of VRGDG_LUTVideoTools).  The detector network, tracking, PNG / video I/O, manifests, ffmpeg and the
+aiohttp routes are out of scope.  The arithmetic is csrc/vrg_facefix_math.hpp; the library is reached through ``_hip`` only.
 """
 from __future__ import annotations
 
@@ -339,3 +346,58 @@ class CompositePlan:
                                                   self.capacity, _hip.ptr(self.stats), _hip.ptr(self.out), int(x.shape[0]), int(x.shape[1]),
                                                   int(x.shape[2]), _hip.current_stream()), "vrg_ff_composite_u8")
         return self.out
+
+
+# ------------------------------------------------------------------------------------------------
+# the detector's input and its candidates, with the Builder's rules
+# ------------------------------------------------------------------------------------------------
+def _initial_regions(width, height):
+    """``_initial_regions`` (:54-64): the whole frame and, from 600 x 400 up, four corner tiles of round(0.60 w) x round(0.70 h)"""
+    from .VRGDG_StandaloneFaceFixNodes import scan_regions
+    return scan_regions(width, height, builder=True)
+
+
+def detection_plan(width, height, rotation_assist, regions=None):
+    """VRGDG_StandaloneFaceFixNodes.detection_plan with the Builder's rules: angle 0 scans ``regions`` (None: the initial regions), every
+    other angle the initial regions; ``rotation_assist`` is off / light / strong (None or unknown: light)."""
+    from . import VRGDG_StandaloneFaceFixNodes as nodes
+    return nodes.detection_plan(width, height, rotation_assist, regions=regions, builder=True)
+
+
+def _as_batch(frames_u8):
+    if isinstance(frames_u8, torch.Tensor):
+        return frames_u8
+    from .VRGDG_StandaloneVideoEnhancerNodes import DecodedFrames
+    if isinstance(frames_u8, DecodedFrames):
+        return frames_u8.u8
+    return torch.from_numpy(np.stack([np.asarray(f) for f in frames_u8]))
+
+
+def detector_blobs(frames_u8, plan, frames=None):
+    """fp32 ``[F, A, R, 3, 300, 300]`` blobs of decoded B,G,R frames (a uint8 tensor on the GPU or the CPU, DecodedFrames, or a list of
+    numpy frames); see VRGDG_StandaloneFaceFixNodes.detector_blobs."""
+    from . import VRGDG_StandaloneFaceFixNodes as nodes
+    return nodes.detector_blobs(_as_batch(frames_u8), plan, frames)
+
+
+def rotated_frames(frames_u8, plan, frames=None):
+    """uint8 ``[F, A, H, W, 3]``: the rotated frames the YuNet branch scans"""
+    from . import VRGDG_StandaloneFaceFixNodes as nodes
+    return nodes.rotated_frames(_as_batch(frames_u8), plan, frames)
+
+
+def candidates_from_outputs(plan, outputs, confidence, kind="caffe"):
+    """The candidates of one frame with the Builder's decode (round(), kept when x2 > x and y2 > y; ``_select_tracked`` applies
+    ``minimum_pixels`` later); see VRGDG_StandaloneFaceFixNodes.candidates_from_outputs."""
+    from . import VRGDG_StandaloneFaceFixNodes as nodes
+    if not plan.builder:
+        raise ValueError("candidates_from_outputs: the plan was not made by this module's detection_plan")
+    return nodes.candidates_from_outputs(plan, outputs, confidence, 0, kind=kind)
+
+
+def detect_with_rotation(forward=None, frames_u8=None, confidence=0.5, regions=None, rotation_assist="light", frames=None, chunk_frames=16):
+    """``_detect_with_rotation(net, frame, confidence, regions, rotation_assist)`` for the frames of a decoded batch: one candidate list
+    per frame.  ``forward(blobs) -> [n, 1, K, 7]`` is the network; None (the default) means no detector: no candidates, nothing computed."""
+    from . import VRGDG_StandaloneFaceFixNodes as nodes
+    return nodes.detect_with_rotation(forward, _as_batch(frames_u8), confidence, 0, rotation_assist, regions=regions, builder=True, frames=frames,
+                                      chunk_frames=chunk_frames)

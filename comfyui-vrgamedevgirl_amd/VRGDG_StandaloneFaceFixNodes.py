@@ -141,6 +141,274 @@ def shot_boundaries(video_frames, cut_sensitivity):
     return boundaries_from_scores(shot_cut_scores(video_frames), cut_sensitivity)
 
 
+# ------------------------------------------------------------------------------------------------
+# the detector's input and the candidates made of its output (`_detect_with_rotation` / `_detect`, :95-185)
+# ------------------------------------------------------------------------------------------------
+ROTATION_ANGLES = {"Off (fastest)": [0], "Light: ±15°": [0, -15, 15], "Strong: ±15° and ±30°": [0, -15, 15, -30, 30]}
+BUILDER_ROTATION_ANGLES = {"off": [0], "light": [0, -15, 15], "strong": [0, -15, 15, -30, 30]}
+
+
+def _iou(a, b):
+    ax, ay, aw, ah = a
+    bx, by, bw, bh = b
+    overlap = max(0.0, min(ax + aw, bx + bw) - max(ax, bx)) * max(0.0, min(ay + ah, by + bh) - max(ay, by))
+    union = aw * ah + bw * bh - overlap
+    return overlap / union if union > 0 else 0.0
+
+
+def _suppress(found):
+    """the reference's suppression pass: by falling score (stable), keep what overlaps nothing kept by more than IoU 0.35"""
+    kept = []
+    for item in sorted(found, key=lambda value: value[4], reverse=True):
+        if not any(_iou(item[:4], other[:4]) > 0.35 for other in kept):
+            kept.append(item)
+    return kept
+
+
+def scan_regions(width, height, builder=False):
+    """The regions one (rotated) frame is scanned in: the whole frame and, from 600 x 400 up, four 60 % x 70 % corner tiles -- int(...) in
+    the stand-alone nodes (:98-102), int(round(...)) in the Builder (`_initial_regions`)."""
+    width, height = int(width), int(height)
+    regions = [(0, 0, width, height)]
+    if width >= 600 and height >= 400:
+        if builder:
+            tile_w, tile_h = int(round(width * 0.60)), int(round(height * 0.70))
+        else:
+            tile_w, tile_h = int(width * 0.60), int(height * 0.70)
+        regions += [(0, 0, tile_w, tile_h), (width - tile_w, 0, width, tile_h), (0, height - tile_h, tile_w, height),
+                    (width - tile_w, height - tile_h, width, height)]
+    return regions
+
+
+def rotation_matrices(width, height, angle):
+    """(forward, inverse) 2 x 3 float64 of one angle: cv2.getRotationMatrix2D((width / 2.0, height / 2.0), angle, 1.0) and its
+    cv2.invertAffineTransform -- the same doubles warpAffine forms when it inverts the matrix itself (csrc/vrg_detect_math.hpp)."""
+    radians = float(angle) * math.pi / 180.0
+    a, b = math.cos(radians), math.sin(radians)
+    cx, cy = width / 2.0, height / 2.0
+    m = [a, b, (1.0 - a) * cx - b * cy, -b, a, b * cx + (1.0 - a) * cy]
+    forward = np.array(m, dtype=np.float64).reshape(2, 3)
+    d = m[0] * m[4] - m[1] * m[3]
+    d = 1.0 / d if d != 0.0 else 0.0
+    a11, a22 = m[4] * d, m[0] * d
+    m[0], m[1], m[3], m[4] = a11, m[1] * -d, m[3] * -d, a22
+    b1, b2 = -m[0] * m[2] - m[1] * m[5], -m[3] * m[2] - m[4] * m[5]
+    m[2], m[5] = b1, b2
+    return forward, np.array(m, dtype=np.float64).reshape(2, 3)
+
+
+class DetectionPlan:
+    """What the detector scans in every frame of a width x height video: `angles`; per angle the `forward` and `inverse` matrices (None at
+    angle 0) and the list of `regions` (left, top, right, bottom) of the rotated frame; `transforms` = the [T, 6] inverse doubles of the
+    non-zero angles in order, `transform_index[a]` = its row or -1; `slots` = the largest region count of an angle, `scanned[a][r]` =
+    whether slot r of angle a exists and has both sides >= 8 (the Builder skips smaller regions; the stand-alone nodes do not meet them).
+    `descriptors(frame_indices)` -> ops.DETECT_DESC records in [frame, angle, slot] order of the scanned slots, and their positions."""
+
+    def __init__(self, width, height, angles, regions, builder):
+        self.width, self.height, self.angles, self.builder = int(width), int(height), [int(a) for a in angles], bool(builder)
+        self.regions = [[tuple(int(v) for v in r) for r in per_angle] for per_angle in regions]
+        self.forward, self.inverse, self.transform_index, rows = [], [], [], []
+        for angle in self.angles:
+            if angle == 0:
+                self.forward.append(None)
+                self.inverse.append(None)
+                self.transform_index.append(-1)
+                continue
+            forward, inverse = rotation_matrices(self.width, self.height, angle)
+            self.forward.append(forward)
+            self.inverse.append(inverse)
+            self.transform_index.append(len(rows))
+            rows.append(inverse.reshape(6))
+        self.transforms = np.array(rows, dtype=np.float64).reshape(-1, 6)
+        self.slots = max((len(r) for r in self.regions), default=0)
+        self.scanned = [[(r < len(per_angle) and per_angle[r][2] - per_angle[r][0] >= ops.DETECT_MIN_SIDE and
+                          per_angle[r][3] - per_angle[r][1] >= ops.DETECT_MIN_SIDE) for r in range(self.slots)] for per_angle in self.regions]
+
+    def descriptors(self, frame_indices):
+        frame_indices = [int(f) for f in frame_indices]
+        per_frame = [(a, r) for a in range(len(self.angles)) for r in range(self.slots) if self.scanned[a][r]]
+        desc = np.zeros(len(frame_indices) * len(per_frame), dtype=ops.DETECT_DESC)
+        where = np.zeros(desc.size, dtype=np.int64)
+        k = 0
+        for i, f in enumerate(frame_indices):
+            for a, r in per_frame:
+                left, top, right, bottom = self.regions[a][r]
+                desc[k] = (f, self.transform_index[a], left, top, right, bottom)
+                where[k] = (i * len(self.angles) + a) * self.slots + r
+                k += 1
+        return desc, where
+
+
+def detection_plan(width, height, rotation_assist, regions=None, builder=False):
+    """The scan of `_detect_with_rotation` for width x height frames.  Stand-alone nodes (:146-166): `rotation_assist` is the widget's value
+    (an unknown one scans angle 0 only) and every angle scans scan_regions(width, height).  `builder=True` (VRGDG_FaceFix.py:116-139): the
+    mode names are off / light / strong (None or an unknown one: light), angle 0 scans the caller's `regions` (None: the initial regions)
+    and every other angle the initial regions.  A region must lie inside the frame; one with a side below 8 is not scanned."""
+    width, height = int(width), int(height)
+    if not (1 <= width <= ops.DETECT_MAX_SIDE and 1 <= height <= ops.DETECT_MAX_SIDE):
+        raise ValueError(f"detection_plan: {width} x {height}: sides must lie in 1 .. {ops.DETECT_MAX_SIDE}")
+    if builder:
+        angles = BUILDER_ROTATION_ANGLES.get(str(rotation_assist or "light").lower(), [0, -15, 15])
+    else:
+        angles = ROTATION_ANGLES.get(str(rotation_assist), [0])
+    initial = scan_regions(width, height, builder=builder)
+    own = initial if regions is None else [tuple(int(v) for v in r) for r in regions]
+    for left, top, right, bottom in own:
+        if left < 0 or top < 0 or right > width or bottom > height:
+            raise ValueError(f"detection_plan: region {(left, top, right, bottom)} does not lie inside the {width} x {height} frame")
+    if not builder and min(width, height) < ops.DETECT_MIN_SIDE:
+        raise ValueError(f"detection_plan: {width} x {height} frames have a side below {ops.DETECT_MIN_SIDE} px; refused")
+    return DetectionPlan(width, height, angles, [own if (angle == 0 or not builder) else initial for angle in angles], builder)
+
+
+def _plan_frames(video_frames, plan, frames):
+    if not isinstance(video_frames, torch.Tensor) or video_frames.ndim != 4:
+        raise ValueError("the detector input requires a [frames, height, width, channels] batch")
+    if (int(video_frames.shape[1]), int(video_frames.shape[2])) != (plan.height, plan.width):
+        raise ValueError(f"the plan was made for {plan.width} x {plan.height} frames, the batch is {int(video_frames.shape[2])} x {int(video_frames.shape[1])}")
+    count = int(video_frames.shape[0])
+    indices = list(range(count)) if frames is None else [int(f) for f in frames]
+    for f in indices:
+        if not 0 <= f < count:
+            raise ValueError(f"frame {f} is outside the batch of {count}")
+    return indices
+
+
+def detector_blobs(video_frames, plan, frames=None):
+    """The blobs the Caffe detector is fed for the frames `frames` (None: all) of the batch: fp32 ``[F, A, R, 3, 300, 300]`` (A angles of the
+    plan, R = plan.slots; a slot that is not scanned is zeros) on the compute device, in one launch of csrc/vrg_detect.hip -- the frame is
+    quantised, swapped to B,G,R, rotated, cut and resized where it is read; no rotated frame is written.  `video_frames`: fp32 R,G,B
+    ``[n, H, W, C >= 3]`` as the nodes get it, or uint8 B,G,R ``[n, H, W, 3]`` as the Builder decodes it; GPU or CPU; never written."""
+    indices = _plan_frames(video_frames, plan, frames)
+    desc, where = plan.descriptors(indices)
+    blobs = ops.detect_blobs(video_frames, desc, plan.transforms)
+    shape = (len(indices), len(plan.angles), plan.slots, 3, ops.DETECT_BLOB, ops.DETECT_BLOB)
+    if desc.size == shape[0] * shape[1] * shape[2]:
+        return blobs.view(shape)
+    out = torch.zeros(shape, dtype=torch.float32, device=blobs.device)
+    if desc.size:
+        out.view((-1,) + shape[3:]).index_copy_(0, torch.from_numpy(where).to(blobs.device), blobs)
+    return out
+
+
+def rotated_frames(video_frames, plan, frames=None):
+    """The rotated B,G,R byte frames of the YuNet branch (`detector.detect(region)` reads regions of them): uint8 ``[F, A, H, W, 3]`` on the
+    compute device; angle 0 is the quantised frame itself.  Frames as detector_blobs takes them."""
+    indices = _plan_frames(video_frames, plan, frames)
+    desc = np.array([(f, t) for f in indices for t in plan.transform_index], dtype=ops.DETECT_FRAME_DESC)
+    out = ops.warp_linear_bytes(video_frames, desc, plan.transforms)
+    return out.view(len(indices), len(plan.angles), plan.height, plan.width, 3)
+
+
+def _decode_caffe(rows, region, confidence, minimum_pixels, builder):
+    left, top, right, bottom = region
+    rw, rh = right - left, bottom - top
+    found = []
+    for item in rows:
+        score = float(item[2])
+        if score < confidence:
+            continue
+        if builder:
+            x1 = max(left, left + int(round(float(item[3]) * rw)))
+            y1 = max(top, top + int(round(float(item[4]) * rh)))
+            x2 = min(right, left + int(round(float(item[5]) * rw)))
+            y2 = min(bottom, top + int(round(float(item[6]) * rh)))
+            keep = x2 > x1 and y2 > y1
+        else:
+            x1 = max(left, left + int(float(item[3]) * rw))
+            y1 = max(top, top + int(float(item[4]) * rh))
+            x2 = min(right, left + int(float(item[5]) * rw))
+            y2 = min(bottom, top + int(float(item[6]) * rh))
+            keep = min(x2 - x1, y2 - y1) >= minimum_pixels
+        if keep:
+            found.append((float(x1), float(y1), float(x2 - x1), float(y2 - y1), score))
+    return found
+
+
+def _decode_yunet(faces, region, confidence, minimum_pixels, builder):
+    left, top, right, bottom = region
+    found = []
+    for item in (() if faces is None else faces):
+        score = float(item[-1])
+        if score < confidence:
+            continue
+        x1 = max(left, left + int(round(float(item[0]))))
+        y1 = max(top, top + int(round(float(item[1]))))
+        x2 = min(right, x1 + int(round(float(item[2]))))
+        y2 = min(bottom, y1 + int(round(float(item[3]))))
+        keep = (x2 > x1 and y2 > y1) if builder else min(x2 - x1, y2 - y1) >= minimum_pixels
+        if keep:
+            found.append((float(x1), float(y1), float(x2 - x1), float(y2 - y1), score))
+    return found
+
+
+def candidates_from_outputs(plan, outputs, confidence, minimum_pixels=0, kind="caffe"):
+    """The candidates of ONE frame from what the detector returned for its scanned regions, host arithmetic in double as the reference does
+    it.  `outputs[a][r]`: for kind "caffe" the ``[K, 7]`` rows of ``forward()[0, 0]`` of angle a, slot r (a leading ``[1, 1]`` or ``[1]`` is
+    dropped); for kind "yunet" the faces ``[k, 15]`` (or None) `detector.detect` returned for that region.  A slot that is not scanned is
+    ignored.  Per angle: the box decode (stand-alone: int() truncation, kept when min(w, h) >= minimum_pixels; Builder: round(), kept when
+    x2 > x and y2 > y) and the IoU-0.35 suppression of `_detect`; then for a rotated angle the four corners mapped through the inverse
+    matrix, their bounding box clipped to the frame and the score lowered by |angle| * 0.0001; then the suppression over all angles.
+    Returns [(x, y, w, h, score)] floats."""
+    confidence = float(confidence)
+    width, height = plan.width, plan.height
+    found = []
+    for a, angle in enumerate(plan.angles):
+        per_angle = []
+        for r in range(plan.slots):
+            if not plan.scanned[a][r]:
+                continue
+            rows = outputs[a][r]
+            if kind == "yunet":
+                per_angle += _decode_yunet(rows, plan.regions[a][r], confidence, minimum_pixels, plan.builder)
+            else:
+                rows = np.asarray(rows)
+                per_angle += _decode_caffe(rows.reshape(-1, rows.shape[-1]) if rows.size else (), plan.regions[a][r], confidence, minimum_pixels, plan.builder)
+        inverse = plan.inverse[a]
+        for x, y, w, h, score in _suppress(per_angle):
+            if inverse is None:
+                found.append((x, y, w, h, score))
+                continue
+            corners = np.array([[x, y, 1.0], [x + w, y, 1.0], [x, y + h, 1.0], [x + w, y + h, 1.0]], dtype=np.float64)
+            mapped = corners @ inverse.T
+            x1, y1 = max(0.0, mapped[:, 0].min()), max(0.0, mapped[:, 1].min())
+            x2, y2 = min(float(width), mapped[:, 0].max()), min(float(height), mapped[:, 1].max())
+            if x2 > x1 and y2 > y1:
+                found.append((x1, y1, x2 - x1, y2 - y1, score - abs(angle) * 0.0001))
+    return _suppress(found)
+
+
+def detect_with_rotation(forward=None, video_frames=None, confidence=0.70, minimum_pixels=20, rotation_assist="Light: ±15°", regions=None,
+                         builder=False, frames=None, chunk_frames=16):
+    """`_detect_with_rotation` for the frames `frames` (None: all) of a batch: one candidate list [(x, y, w, h, score)] per frame.
+    `forward(blobs) -> [n, 1, K, 7]` is the network: it gets fp32 ``[n, 3, 300, 300]`` blobs on the compute device and returns, per blob, the
+    rows of cv2.dnn's ``net.forward()[0, 0]`` (a tensor, an array, or a list of n arrays whose row counts K may differ).  It is None by default -- no detector, the state of a machine
+    without cv2's DNN module or the model files: every frame then has no candidates and nothing is computed.  INTEGRATION.md binds the
+    reference's Caffe net to it.  The blobs of `chunk_frames` frames are made in one launch and handed to `forward` together."""
+    if not isinstance(video_frames, torch.Tensor) or video_frames.ndim != 4:
+        raise ValueError("detect_with_rotation requires a [frames, height, width, channels] batch")
+    plan = detection_plan(int(video_frames.shape[2]), int(video_frames.shape[1]), rotation_assist, regions=regions, builder=builder)
+    indices = _plan_frames(video_frames, plan, frames)
+    if forward is None:
+        return [[] for _ in indices]
+    results, step = [], max(1, int(chunk_frames))
+    for s in range(0, len(indices), step):
+        part = indices[s:s + step]
+        blobs = detector_blobs(video_frames, plan, part)
+        flat = blobs.view((-1,) + tuple(blobs.shape[3:]))
+        outputs = forward(flat)
+        if isinstance(outputs, torch.Tensor):
+            outputs = outputs.detach().cpu().numpy()
+        per_blob = list(outputs)                                                   # one [1, K, 7] or [K, 7] per blob; K may differ from blob to blob
+        if len(per_blob) != int(flat.shape[0]):
+            raise ValueError(f"forward returned {len(per_blob)} outputs for {int(flat.shape[0])} blobs")
+        angles, slots = len(plan.angles), plan.slots
+        for i in range(len(part)):
+            results.append(candidates_from_outputs(plan, [[per_blob[(i * angles + a) * slots + r] for r in range(slots)] for a in range(angles)],
+                                                   confidence, minimum_pixels))
+    return results
+
+
 class _Plan:
     """What a composite call works on, read from the node's inputs once: the context's original frames and entries, the index of the
     first work frame that belongs to source frame 0, how many source frames have a work frame at all, and the frame-count difference

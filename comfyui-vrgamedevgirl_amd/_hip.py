@@ -104,6 +104,17 @@ class FaceFixDesc(C.Structure):
                 ("strength", C.c_float), ("mask_offset", C.c_int64), ("taps_offset", C.c_int64), ("bytes_offset", C.c_int64)]
 
 
+class DetectDesc(C.Structure):
+    """vrg_detect_desc"""
+    _fields_ = [("frame", C.c_int32), ("transform", C.c_int32), ("left", C.c_int32), ("top", C.c_int32), ("right", C.c_int32),
+                ("bottom", C.c_int32)]
+
+
+class DetectFrameDesc(C.Structure):
+    """vrg_detect_frame_desc"""
+    _fields_ = [("frame", C.c_int32), ("transform", C.c_int32)]
+
+
 FACEFIX_STATS_WORDS = 12        # uint64 per frame (csrc/vrg_facefix_math.hpp: FF_STATS_WORDS)
 
 _F3 = C.c_float * 3
@@ -180,6 +191,11 @@ _SIGNATURES = {
     "vrg_ff_resize_stats_u8": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int64] + [C.c_int32] * 4 +
                                [C.c_int64, C.c_float, _P]),
     "vrg_ff_composite_u8": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
+    "vrg_linear_taps": (C.c_int, [C.c_int32, C.c_int32, _P, _P]),
+    "vrg_detect_check": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64]),
+    "vrg_detect_blobs_f32": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P, _P]),
+    "vrg_detect_blobs_u8": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P, _P]),
+    "vrg_warp_linear_u8": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P, _P]),
 }
 
 # include/vrgdg_hip_debug.h: self-tests and probes -- for the test suite and the measurement tools, not part of the drop-in boundary

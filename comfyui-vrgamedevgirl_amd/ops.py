@@ -1509,6 +1509,181 @@ def cut_pair_sums(thumbs: torch.Tensor, hist: Optional[torch.Tensor] = None) -> 
 
 
 # ------------------------------------------------------------------------------------------------
+# The input of the Face Fix face detector (reference VRGDG_StandaloneFaceFixNodes.py:95-185, VRGDG_FaceFix.py:67-157): rotated scans and
+# 300 x 300 blobs in one launch (csrc/vrg_detect.hip, arithmetic csrc/vrg_detect_math.hpp)
+# ------------------------------------------------------------------------------------------------
+DETECT_BLOB = 300               # the network's input is 300 x 300
+DETECT_MIN_SIDE = 8             # a region with a smaller side is refused (the Builder skips those)
+DETECT_MAX_SIDE = 32767         # positions of the warp are int16
+DETECT_DESC = np.dtype([("frame", "<i4"), ("transform", "<i4"), ("left", "<i4"), ("top", "<i4"), ("right", "<i4"), ("bottom", "<i4")])
+DETECT_FRAME_DESC = np.dtype([("frame", "<i4"), ("transform", "<i4")])
+assert DETECT_DESC.itemsize == C.sizeof(_hip.DetectDesc) and DETECT_FRAME_DESC.itemsize == C.sizeof(_hip.DetectFrameDesc)
+
+
+def _host_lib():
+    """the library for its HOST table functions (no GPU needed)"""
+    global _lanczos_host_lib
+    if _lanczos_host_lib is None:
+        with _lanczos_lock:
+            if _lanczos_host_lib is None:
+                _lanczos_host_lib = _hip.load_library()
+    return _lanczos_host_lib
+
+
+def linear_taps(n_in: int, n_out: int = DETECT_BLOB) -> dict:
+    """The tables of one axis of ``cv2.resize(..., INTER_LINEAR)`` on bytes from ``n_in`` to ``n_out`` samples, made on the host by
+    vrg_linear_taps (no GPU needed): ``h_ofs`` int32 [n_out] and ``h_coef`` int16 [n_out, 2] for the horizontal pass (sample s and s + 1;
+    at the borders s is 0 or n_in - 1 and the second weight 0), ``v_ofs`` / ``v_coef`` for the vertical pass (s = floor(f), which may be -1
+    or n_in - 1: the two rows are clamped to the axis, the weights stay)."""
+    n_in, n_out = int(n_in), int(n_out)
+    if not (1 <= n_in <= DETECT_MAX_SIDE and 1 <= n_out <= DETECT_MAX_SIDE):
+        raise ValueError(f"linear_taps: sizes must lie in 1 .. {DETECT_MAX_SIDE}")
+    ofs = np.zeros(2 * n_out, dtype=np.int32)
+    coef = np.zeros(4 * n_out, dtype=np.int16)
+    _hip.check(_host_lib().vrg_linear_taps(n_in, n_out, C.c_void_p(ofs.ctypes.data), C.c_void_p(coef.ctypes.data)), "vrg_linear_taps")
+    coef = coef.reshape(2, n_out, 2)
+    return {"h_ofs": ofs[:n_out].copy(), "h_coef": coef[0].copy(), "v_ofs": ofs[n_out:].copy(), "v_coef": coef[1].copy()}
+
+
+def _detect_inputs(frames, descriptors, transforms, dtype, name):
+    """The refusals of the detector input, before anything is uploaded -> (frames [F, H, W, C], descriptor records, [T, 6] doubles)."""
+    if not isinstance(frames, torch.Tensor) or frames.ndim != 4:
+        raise ValueError(f"{name}: frames must be a [frames, height, width, channels] tensor")
+    F, H, W, Cn = (int(v) for v in frames.shape)
+    if frames.dtype == torch.uint8:
+        if Cn != 3:
+            raise ValueError(f"{name}: uint8 frames are decoded B,G,R frames with 3 channels, got {Cn}")
+    elif Cn < 3:
+        raise ValueError(f"{name}: frames must have at least 3 channels, got {Cn}")
+    if H < 1 or W < 1 or H > DETECT_MAX_SIDE or W > DETECT_MAX_SIDE:
+        raise ValueError(f"{name}: {W} x {H} frames: sides must lie in 1 .. {DETECT_MAX_SIDE}")
+    t = np.ascontiguousarray(np.asarray(transforms if transforms is not None else [], dtype=np.float64).reshape(-1, 6))
+    if not np.isfinite(t).all():
+        raise ValueError(f"{name}: transforms must be finite")
+    d = np.asarray(descriptors)
+    if d.dtype != dtype:
+        d = np.array([tuple(int(v) for v in row) for row in np.asarray(descriptors).reshape(-1, len(dtype.names)).tolist()], dtype=dtype)
+    d = np.ascontiguousarray(d.reshape(-1))
+    return d, t, (F, H, W, Cn)
+
+
+def detect_check(descriptors, frames: int, height: int, width: int, transforms: int) -> None:
+    """ValueError when a blob descriptor names a frame or a transform that does not exist, or a region that does not lie inside the frame
+    or has a side below 8 (vrg_detect_check, on the host)."""
+    d = np.ascontiguousarray(descriptors)
+    st = _host_lib().vrg_detect_check(C.c_void_p(d.ctypes.data if d.size else 0), int(d.size), int(frames), int(height), int(width), int(transforms))
+    if st != _hip.VRG_OK:
+        raise ValueError(f"detector input: a descriptor names a frame outside 0 .. {int(frames) - 1}, a transform outside -1 .. {int(transforms) - 1}, "
+                         f"or a region that does not lie inside the {int(width)} x {int(height)} frame with both sides >= {DETECT_MIN_SIDE}")
+
+
+def _detect_run(frames, records, launch, out):
+    """Run `launch(gpu_frames, records of those frames with the frame index rebased, out rows)` over device frames at once or over CPU
+    frames piece by piece through the staging pipeline of _devices; `out` rows are in the order of the records."""
+    if frames.is_cuda:
+        x = frames if frames.is_contiguous() else frames.contiguous()
+        with torch.cuda.device(x.device):
+            launch(x, records, out)
+        return out
+    from . import _devices
+    # only the frames the records name cross PCIe: a run of frames as a view, scattered ones gathered on the host first
+    used = np.unique(records["frame"])
+    if used.size < int(frames.shape[0]):
+        records = records.copy()
+        if int(used[-1]) - int(used[0]) + 1 == used.size:
+            frames = frames[int(used[0]):int(used[-1]) + 1]
+            records["frame"] -= int(used[0])
+        else:
+            frames = frames.index_select(0, torch.from_numpy(used.astype(np.int64)))
+            records["frame"] = np.searchsorted(used, records["frame"]).astype(np.int32)
+    order = np.arange(records.size)
+
+    def piece(gpu, first):
+        last = first + int(gpu.shape[0])
+        pick = order[(records["frame"] >= first) & (records["frame"] < last)]
+        if pick.size == 0:
+            return
+        sub = records[pick].copy()
+        sub["frame"] -= first
+        if int(pick[-1]) - int(pick[0]) + 1 == pick.size and (np.diff(pick) == 1).all():
+            launch(gpu, sub, out[int(pick[0]):int(pick[-1]) + 1])
+        else:                                                                    # records not grouped by frame: gather the rows afterwards
+            tmp = torch.empty((pick.size,) + tuple(out.shape[1:]), dtype=out.dtype, device=out.device)
+            launch(gpu, sub, tmp)
+            out.index_copy_(0, torch.from_numpy(pick).to(out.device), tmp)
+
+    _devices.upload_frames(frames, piece)
+    return out
+
+
+def _upload_records(array: np.ndarray, device) -> torch.Tensor:
+    return torch.from_numpy(np.ascontiguousarray(array).view(np.uint8).reshape(-1).copy()).to(device)
+
+
+def detect_blobs(frames: torch.Tensor, descriptors, transforms) -> torch.Tensor:
+    """``blobFromImage(cv2.resize(rotated[top:bottom, left:right], (300, 300)), 1.0, (300, 300), (104, 177, 123))`` for every descriptor
+    ``(frame, transform, left, top, right, bottom)`` (DETECT_DESC records or rows of six integers), where ``rotated`` is
+    ``cv2.warpAffine(bgr, M, (W, H), INTER_LINEAR, BORDER_REPLICATE)`` of the quantised B,G,R frame for ``transform >= 0`` (``transforms``:
+    ``[T, 6]`` doubles, the INVERTED matrices) and the frame itself for -1 -- one launch of vrg_detect_blobs_f32 / _u8; the rotated frame
+    is never written.  ``frames``: ``[F, H, W, C >= 3]`` fp32 R,G,B (other float types are converted) or ``[F, H, W, 3]`` uint8 B,G,R, on
+    the GPU or on the CPU (of CPU frames those the descriptors name go up through the staging pipeline of _devices in pieces, once); never written.  Returns fp32
+    ``[N, 3, 300, 300]`` on the compute device."""
+    d, t, (F, H, W, Cn) = _detect_inputs(frames, descriptors, transforms, DETECT_DESC, "detect_blobs")
+    detect_check(d, F, H, W, len(t))
+    if frames.dtype not in (torch.uint8, torch.float32):
+        frames = frames.float()
+    from . import _devices
+    dev = frames.device if frames.is_cuda else _devices.compute_device()
+    with torch.cuda.device(dev):
+        out = torch.empty((d.size, 3, DETECT_BLOB, DETECT_BLOB), dtype=torch.float32, device=dev)
+        if d.size == 0:
+            return out
+        tr = torch.from_numpy(t.copy()).to(dev) if len(t) else None
+
+        def launch(x, records, rows):
+            rec = _upload_records(records, x.device)
+            n, h, w, c = (int(v) for v in x.shape)
+            if x.dtype == torch.uint8:
+                st = _hip.lib().vrg_detect_blobs_u8(_hip.ptr(x), n, h, w, _hip.ptr(tr) if tr is not None else None, len(t), _hip.ptr(rec), records.size,
+                                                    _hip.ptr(rows), _hip.current_stream())
+            else:
+                st = _hip.lib().vrg_detect_blobs_f32(_hip.ptr(x), n, h, w, c, _hip.ptr(tr) if tr is not None else None, len(t), _hip.ptr(rec),
+                                                     records.size, _hip.ptr(rows), _hip.current_stream())
+            _hip.check(st, "vrg_detect_blobs")
+            rec.record_stream(torch.cuda.current_stream())
+
+        return _detect_run(frames, d, launch, out)
+
+
+def warp_linear_bytes(frames: torch.Tensor, descriptors, transforms) -> torch.Tensor:
+    """``cv2.warpAffine(bgr, M, (W, H), flags=INTER_LINEAR, borderMode=BORDER_REPLICATE)`` of the quantised B,G,R frame for every descriptor
+    ``(frame, transform)`` (-1: the B,G,R bytes of the frame itself) -> uint8 ``[N, H, W, 3]`` on the compute device (vrg_warp_linear_u8).
+    Frames and transforms as detect_blobs takes them; never written."""
+    d, t, (F, H, W, Cn) = _detect_inputs(frames, descriptors, transforms, DETECT_FRAME_DESC, "warp_linear_bytes")
+    if d.size and (int(d["frame"].min()) < 0 or int(d["frame"].max()) >= F or int(d["transform"].min()) < -1 or int(d["transform"].max()) >= len(t)):
+        raise ValueError(f"warp_linear_bytes: a descriptor names a frame outside 0 .. {F - 1} or a transform outside -1 .. {len(t) - 1}")
+    if frames.dtype not in (torch.uint8, torch.float32):
+        frames = frames.float()
+    from . import _devices
+    dev = frames.device if frames.is_cuda else _devices.compute_device()
+    with torch.cuda.device(dev):
+        out = torch.empty((d.size, H, W, 3), dtype=torch.uint8, device=dev)
+        if d.size == 0:
+            return out
+        tr = torch.from_numpy(t.copy()).to(dev) if len(t) else None
+
+        def launch(x, records, rows):
+            rec = _upload_records(records, x.device)
+            n, h, w, c = (int(v) for v in x.shape)
+            st = _hip.lib().vrg_warp_linear_u8(_hip.ptr(x), 0 if x.dtype == torch.uint8 else c, n, h, w, _hip.ptr(tr) if tr is not None else None,
+                                               len(t), _hip.ptr(rec), records.size, _hip.ptr(rows), _hip.current_stream())
+            _hip.check(st, "vrg_warp_linear_u8")
+            rec.record_stream(torch.cuda.current_stream())
+
+        return _detect_run(frames, d, launch, out)
+
+
+# ------------------------------------------------------------------------------------------------
 # 13-slider Adjust (video routes)
 # ------------------------------------------------------------------------------------------------
 

@@ -595,6 +595,51 @@ int vrg_ff_composite_u8(const uint8_t* originals, const float* masks, int64_t ma
                         int64_t capacity, const void* stats, uint8_t* out, int64_t frames, int32_t height, int32_t width, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The input of the Face Fix face detector (`_detect_with_rotation` / `_detect`, VRGDG_StandaloneFaceFixNodes.py:95-185 and
+ * VRGDG_FaceFix.py:67-157 of the reference), restated in csrc/vrg_detect_math.hpp: frames quantised to B,G,R bytes, rotated about the frame
+ * centre (cv2.warpAffine, INTER_LINEAR, BORDER_REPLICATE, the classic fixed-point path), cut into regions, each resized to 300 x 300
+ * (cv2.resize, INTER_LINEAR on bytes) and made a blob (fp32 [3][300][300], byte - (104, 177, 123)).  The network itself is not here.
+ *
+ * Frames are [n_frames][height][width][channels >= 3] fp32 R,G,B (channels beyond 3 are ignored) or [n_frames][height][width][3] uint8
+ * B,G,R; height, width <= 32767.  `transforms`: n_transforms x 6 doubles (device, 8-byte aligned), each the INVERTED 2 x 3 matrix
+ * (result -> source) as warpAffine forms it in double; the host makes them (trigonometry in libm).  Descriptors are device memory; one
+ * that names a frame, a transform or a region outside what the call states writes zeros.  vrg_detect_check refuses such descriptors ON
+ * THE HOST (VRG_ERR_BAD_ARG): a region must lie inside the frame with both sides >= 8.  n_blobs / n_out == 0 succeeds without a launch.
+ * Frames are never written.
+ *
+ * vrg_linear_taps fills, ON THE HOST, the tables of one axis of cv2.resize(INTER_LINEAR, 8U) from n_in to n_out samples: ofs = 2 * n_out
+ * int32, coef = 4 * n_out int16.  First the horizontal rule (ofs[d] = s in 0 .. n_in - 1, coef[2d], coef[2d + 1] the weights of S[s] and
+ * S[s + 1]), then, n_out entries on, the vertical rule (ofs = floor(f), which may be -1 or n_in - 1: the two rows are clamped).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct vrg_detect_desc {       /* one blob */
+    int32_t frame;
+    int32_t transform;                 /* index into `transforms`, -1: the frame as it is */
+    int32_t left, top, right, bottom;  /* the region of the (rotated) frame */
+} vrg_detect_desc;
+
+typedef struct vrg_detect_frame_desc { /* one rotated frame */
+    int32_t frame;
+    int32_t transform;                 /* -1: the quantised B,G,R frame itself */
+} vrg_detect_frame_desc;
+
+int vrg_linear_taps(int32_t n_in, int32_t n_out, int32_t* ofs_host, int16_t* coef_host);
+int vrg_detect_check(const vrg_detect_desc* desc_host, int64_t n_desc, int64_t n_frames, int32_t height, int32_t width,
+                     int64_t n_transforms);
+
+/* out[i] = blob(resize(warp(frame)[top:bottom, left:right], (300, 300))) for n_blobs descriptors in ONE launch: fp32
+ * [n_blobs][3][300][300].  The rotated frame is never written: a value reads 4 source pixels without a transform, 16 with one. */
+int vrg_detect_blobs_f32(const float* frames, int64_t n_frames, int32_t height, int32_t width, int32_t channels, const double* transforms,
+                         int64_t n_transforms, const vrg_detect_desc* desc, int64_t n_blobs, float* out, void* stream);
+int vrg_detect_blobs_u8(const uint8_t* frames, int64_t n_frames, int32_t height, int32_t width, const double* transforms,
+                        int64_t n_transforms, const vrg_detect_desc* desc, int64_t n_blobs, float* out, void* stream);
+
+/* The rotated B,G,R byte frames themselves, [n_out][height][width][3] (what the YuNet branch hands its detector).  f32_channels == 0:
+ * `frames` are uint8 B,G,R; >= 3: fp32 R,G,B with that many channels.  16-byte stores where a frame of `out` starts on a 16-byte
+ * boundary. */
+int vrg_warp_linear_u8(const void* frames, int32_t f32_channels, int64_t n_frames, int32_t height, int32_t width, const double* transforms,
+                       int64_t n_transforms, const vrg_detect_frame_desc* desc, int64_t n_out, uint8_t* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Introspection
  * ------------------------------------------------------------------------------------------- */
 int vrg_abi_version(void);
