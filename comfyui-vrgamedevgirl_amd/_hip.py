@@ -115,6 +115,27 @@ class DetectFrameDesc(C.Structure):
     _fields_ = [("frame", C.c_int32), ("transform", C.c_int32)]
 
 
+class PilResizeDesc(C.Structure):
+    """vrg_pil_resize_desc"""
+    _fields_ = [("src_offset", C.c_int64), ("dst_offset", C.c_int64), ("tmp_offset", C.c_int64), ("h_table", C.c_int64), ("v_table", C.c_int64),
+                ("in_w", C.c_int32), ("in_h", C.c_int32), ("out_w", C.c_int32), ("out_h", C.c_int32), ("h_ksize", C.c_int32),
+                ("v_ksize", C.c_int32)]
+
+
+class PilMaskDesc(C.Structure):
+    """vrg_pil_mask_desc"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("radius", C.c_int32), ("ww", C.c_uint32), ("fw", C.c_uint32),
+                ("reserved", C.c_int32), ("span_offset", C.c_int64), ("mask_offset", C.c_int64)]
+
+
+class PilBoxDesc(C.Structure):
+    """vrg_pil_box_desc"""
+    _fields_ = [("left", C.c_int32), ("top", C.c_int32), ("box_w", C.c_int32), ("box_h", C.c_int32), ("color_match", C.c_int32),
+                ("reserved", C.c_int32), ("mask_offset", C.c_int64), ("rep_offset", C.c_int64)]
+
+
+PIL_STATS_WORDS = 12            # uint32 per frame (csrc/vrg_pil_math.hpp: PIL_STATS_WORDS)
+PIL_MAX_LINE = 8192             # the longest mask row / column (csrc/vrg_pil_math.hpp: PIL_MAX_LINE)
 FACEFIX_STATS_WORDS = 12        # uint64 per frame (csrc/vrg_facefix_math.hpp: FF_STATS_WORDS)
 
 _F3 = C.c_float * 3
@@ -191,6 +212,13 @@ _SIGNATURES = {
     "vrg_ff_resize_stats_u8": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int64] + [C.c_int32] * 4 +
                                [C.c_int64, C.c_float, _P]),
     "vrg_ff_composite_u8": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
+    "vrg_pil_lanczos_ksize": (C.c_int32, [C.c_int32, C.c_int32]),
+    "vrg_pil_lanczos_table": (C.c_int, [C.c_int32, C.c_int32, _P, _P]),
+    "vrg_pil_box_parameters": (C.c_int, [C.c_float, _P]),
+    "vrg_pil_resize_u8": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int64, _P]),
+    "vrg_pil_mask_u8": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P]),
+    "vrg_np_masked_means_f32": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_float, _P]),
+    "vrg_pil_paste_u8": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
     "vrg_linear_taps": (C.c_int, [C.c_int32, C.c_int32, _P, _P]),
     "vrg_detect_check": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64]),
     "vrg_detect_blobs_f32": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P, _P]),

@@ -1,0 +1,476 @@
+// vrg_farface.hip -- the pixels of the far-face repair composite (reference scripts/far_face_repair_backend.py: composite :339-371) on
+// decoded bytes: Pillow's LANCZOS resize, its GaussianBlur of the soft-ellipse mask, numpy's fp32 mean shift and Image.paste under an L
+// mask, each byte for byte.  gfx950 only.  Arithmetic: csrc/vrg_pil_math.hpp.
+//
+// Shape of the work.  A job is a batch of byte frames, at most one box per frame, and one repaired crop (of any size) per box.
+//   k_pil_resize_h / _v   Image.resize: blockIdx.y = the output image, so its record is wave-uniform; one thread = one pixel of the pass,
+//                         its taps and bounds out of the host-made integer tables.  The horizontal pass writes the rounded byte image the
+//                         vertical pass reads (`tmp`); a pass whose size does not change is skipped.
+//   k_pil_mask_h / _v     the masks, one per distinct (w, h, feather): one workgroup = one row (then one column) held in LDS through its
+//                         three box passes; every pass is a block-wide prefix sum and then one independent pixel per lane
+//                         (pil_box_pixel) -- nothing walks along a line.
+//   k_np_means            numpy's sequential fp32 means: one workgroup per frame walks its box in chunks of NP_CHUNK pixels; a lane folds
+//                         NP_RUN consecutive pixels into six maps, the maps are reduced pairwise in order through LDS, and the chunk is
+//                         applied at once unless a sum would reach its next power of two -- then one lane per sum walks the chunk with
+//                         real fp32 adds.
+//   k_pil_paste           ONE pass over the output batch as a flat run of bytes, 16 per thread: a piece that misses the box is one 16-byte
+//                         non-temporal load and store, a piece that touches it is rebuilt byte by byte (the mover of vrg_ff_composite_u8).
+#include "vrg_common.hpp"
+#include "vrg_pil_math.hpp"
+
+namespace vrg {
+
+typedef uint32_t pfu4 __attribute__((ext_vector_type(4)));
+
+struct PilResizeGeom {
+    int64_t src_bytes, table_ints, tmp_bytes, dst_bytes;
+    int32_t C;
+};
+
+__device__ __forceinline__ bool pil_span_fits(int64_t offset, int64_t need, int64_t size) {
+    return offset >= 0 && offset <= size && need <= size - offset;
+}
+
+__device__ __forceinline__ bool pil_resize_ok(const vrg_pil_resize_desc& d, const PilResizeGeom& g) {
+    if (d.in_w < 1 || d.in_h < 1 || d.out_w < 1 || d.out_h < 1) return false;
+    const bool hp = d.in_w != d.out_w, vp = d.in_h != d.out_h;
+    if (!pil_span_fits(d.src_offset, (int64_t)d.in_h * d.in_w * g.C, g.src_bytes)) return false;
+    if (!pil_span_fits(d.dst_offset, (int64_t)d.out_h * d.out_w * g.C, g.dst_bytes)) return false;
+    if (hp && (d.h_ksize < 1 || !pil_span_fits(d.h_table, (int64_t)d.out_w * (2 + d.h_ksize), g.table_ints))) return false;
+    if (vp && (d.v_ksize < 1 || !pil_span_fits(d.v_table, (int64_t)d.out_h * (2 + d.v_ksize), g.table_ints))) return false;
+    if (hp && vp && !pil_span_fits(d.tmp_offset, (int64_t)d.in_h * d.out_w * g.C, g.tmp_bytes)) return false;
+    return true;
+}
+
+// the bounds of output index i of a table of n_out records, checked against the n_in sources
+__device__ __forceinline__ bool pil_bounds(const int32_t* __restrict__ table, int32_t i, int32_t ksize, int32_t n_in, int32_t& first, int32_t& n) {
+    first = table[2 * i];
+    n = table[2 * i + 1];
+    return first >= 0 && n >= 0 && n <= ksize && first <= n_in - n;
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void k_pil_resize_h(const uint8_t* __restrict__ src, const vrg_pil_resize_desc* __restrict__ desc,
+                                                       const int32_t* __restrict__ tables, uint8_t* __restrict__ tmp, uint8_t* __restrict__ dst,
+                                                       PilResizeGeom g) {
+    const vrg_pil_resize_desc d = desc[blockIdx.y];                      // wave-uniform
+    if (!pil_resize_ok(d, g) || d.in_w == d.out_w) return;
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= (int64_t)d.in_h * d.out_w) return;
+    const int32_t y = (int32_t)(p / d.out_w), x = (int32_t)(p - (int64_t)y * d.out_w);
+    const int32_t* table = tables + d.h_table;
+    uint8_t* out = (d.in_h != d.out_h ? tmp + d.tmp_offset : dst + d.dst_offset) + p * C;
+    uint8_t o[C];
+    int32_t first, n;
+    if (pil_bounds(table, x, d.h_ksize, d.in_w, first, n)) {
+        const uint8_t* row = src + d.src_offset + ((int64_t)y * d.in_w + first) * C;
+        pil_taps<C>(table + 2 * (int64_t)d.out_w + (int64_t)x * d.h_ksize, n, [&](int32_t i, int c) { return row[i * C + c]; }, o);
+    } else {
+        for (int c = 0; c < C; ++c) o[c] = 0;
+    }
+    for (int c = 0; c < C; ++c) out[c] = o[c];
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void k_pil_resize_v(const uint8_t* __restrict__ src, const vrg_pil_resize_desc* __restrict__ desc,
+                                                       const int32_t* __restrict__ tables, const uint8_t* __restrict__ tmp,
+                                                       uint8_t* __restrict__ dst, PilResizeGeom g) {
+    const vrg_pil_resize_desc d = desc[blockIdx.y];
+    if (!pil_resize_ok(d, g)) return;
+    const bool hp = d.in_w != d.out_w, vp = d.in_h != d.out_h;
+    if (hp && !vp) return;                                               // the horizontal pass wrote the result
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= (int64_t)d.out_h * d.out_w) return;
+    const uint8_t* from = hp ? tmp + d.tmp_offset : src + d.src_offset;  // [in_h][out_w][C]
+    uint8_t* out = dst + d.dst_offset + p * C;
+    uint8_t o[C];
+    if (!vp) {                                                           // the size itself: a copy
+        for (int c = 0; c < C; ++c) o[c] = from[p * C + c];
+    } else {
+        const int32_t y = (int32_t)(p / d.out_w), x = (int32_t)(p - (int64_t)y * d.out_w);
+        const int32_t* table = tables + d.v_table;
+        int32_t first, n;
+        if (pil_bounds(table, y, d.v_ksize, d.in_h, first, n)) {
+            const uint8_t* col = from + ((int64_t)first * d.out_w + x) * C;
+            const int64_t pitch = (int64_t)d.out_w * C;
+            pil_taps<C>(table + 2 * (int64_t)d.out_h + (int64_t)y * d.v_ksize, n, [&](int32_t i, int c) { return col[i * pitch + c]; }, o);
+        } else {
+            for (int c = 0; c < C; ++c) o[c] = 0;
+        }
+    }
+    for (int c = 0; c < C; ++c) out[c] = o[c];
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// masks
+// ---------------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool pil_mask_ok(const vrg_pil_mask_desc& d, int64_t n_spans, int64_t mask_bytes) {
+    if (d.width < 1 || d.height < 1 || d.width > PIL_MAX_LINE || d.height > PIL_MAX_LINE || d.radius > (1 << 20)) return false;
+    return pil_span_fits(d.span_offset, d.height, n_spans) && pil_span_fits(d.mask_offset, (int64_t)d.width * d.height, mask_bytes);
+}
+
+struct PilLineLds {
+    uint32_t pre[PIL_MAX_LINE + 1];
+    uint8_t line[2][PIL_MAX_LINE];
+    uint32_t wave_total[4];
+};
+
+// three box passes over the n bytes of s.line[0], all 256 threads; the result is in s.line[1] (3 is odd); ends synchronised
+__device__ __forceinline__ void pil_blur_line(PilLineLds& s, int32_t n, const PilBox& b) {
+    const int32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int32_t per = (n + 255) / 256, i0 = t * per, i1 = i0 + per < n ? i0 + per : n;
+    for (int pass = 0; pass < 3; ++pass) {
+        const uint8_t* in = s.line[pass & 1];
+        uint8_t* out = s.line[(pass & 1) ^ 1];
+        uint32_t own = 0;
+        for (int32_t i = i0; i < i1; ++i) own += in[i];
+        uint32_t scan = own;                                             // inclusive over the wave
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t v = (uint32_t)__shfl_up((int)scan, off, 64);
+            if (lane >= off) scan += v;
+        }
+        if (lane == 63) s.wave_total[wave] = scan;
+        __syncthreads();
+        uint32_t run = scan - own;
+        for (int w = 0; w < wave; ++w) run += s.wave_total[w];
+        if (t == 0) s.pre[0] = 0u;
+        for (int32_t i = i0; i < i1; ++i) {
+            run += in[i];
+            s.pre[i + 1] = run;
+        }
+        __syncthreads();
+        for (int32_t x = t; x < n; x += 256)
+            out[x] = pil_box_pixel(x, n, b, [&](int32_t i) { return s.pre[i]; }, [&](int32_t i) { return in[i]; });
+        __syncthreads();
+    }
+}
+
+// rows: the spans, blurred along x into `scratch`; radius < 0: the 0 / 255 spans straight into `masks`
+__global__ __launch_bounds__(256) void k_pil_mask_h(const PilSpan* __restrict__ spans, int64_t n_spans, const vrg_pil_mask_desc* __restrict__ desc,
+                                                     uint8_t* __restrict__ scratch, uint8_t* __restrict__ masks, int64_t mask_bytes) {
+    __shared__ PilLineLds s;
+    const vrg_pil_mask_desc d = desc[blockIdx.y];
+    if (!pil_mask_ok(d, n_spans, mask_bytes) || (int32_t)blockIdx.x >= d.height) return;     // uniform
+    const int32_t y = (int32_t)blockIdx.x, n = d.width;
+    const PilSpan sp = spans[d.span_offset + y];
+    uint8_t* row = (d.radius < 0 ? masks : scratch) + d.mask_offset + (int64_t)y * n;
+    if (d.radius < 0) {
+        for (int32_t x = threadIdx.x; x < n; x += 256) row[x] = (x >= sp.x0 && x <= sp.x1) ? 255 : 0;
+        return;
+    }
+    for (int32_t x = threadIdx.x; x < n; x += 256) s.line[0][x] = (x >= sp.x0 && x <= sp.x1) ? 255 : 0;
+    __syncthreads();
+    const PilBox b{d.radius, d.ww, d.fw};
+    pil_blur_line(s, n, b);
+    for (int32_t x = threadIdx.x; x < n; x += 256) row[x] = s.line[1][x];
+}
+
+// columns: `plane` blurred along y into `masks`
+__global__ __launch_bounds__(256) void k_pil_mask_v(int64_t n_spans, const vrg_pil_mask_desc* __restrict__ desc, const uint8_t* __restrict__ plane,
+                                                     uint8_t* __restrict__ masks, int64_t mask_bytes) {
+    __shared__ PilLineLds s;
+    const vrg_pil_mask_desc d = desc[blockIdx.y];
+    if (!pil_mask_ok(d, n_spans, mask_bytes) || d.radius < 0 || (int32_t)blockIdx.x >= d.width) return;
+    const int32_t x = (int32_t)blockIdx.x, n = d.height;
+    const uint8_t* col = plane + d.mask_offset + x;
+    for (int32_t y = threadIdx.x; y < n; y += 256) s.line[0][y] = col[(int64_t)y * d.width];
+    __syncthreads();
+    const PilBox b{d.radius, d.ww, d.fw};
+    pil_blur_line(s, n, b);
+    uint8_t* to = masks + d.mask_offset + x;
+    for (int32_t y = threadIdx.x; y < n; y += 256) to[(int64_t)y * d.width] = s.line[1][y];
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// means and paste
+// ---------------------------------------------------------------------------------------------------------------------------------
+struct PilGeom {
+    int64_t frames, rep_bytes, mask_bytes;
+    int32_t H, W;
+};
+
+__device__ __forceinline__ bool pil_box_ok(const vrg_pil_box_desc& d, const PilGeom& g) {
+    if (d.left < 0 || d.top < 0 || d.box_w < 1 || d.box_h < 1) return false;
+    if ((int64_t)d.left + d.box_w > g.W || (int64_t)d.top + d.box_h > g.H) return false;
+    const int64_t px = (int64_t)d.box_w * d.box_h;
+    return pil_span_fits(d.mask_offset, px, g.mask_bytes) && pil_span_fits(d.rep_offset, px * 3, g.rep_bytes);
+}
+
+__global__ __launch_bounds__(256) void k_np_means(const uint8_t* __restrict__ originals, const uint8_t* __restrict__ repaired,
+                                                   const uint8_t* __restrict__ masks, const vrg_pil_box_desc* __restrict__ desc,
+                                                   uint32_t* __restrict__ stats, PilGeom g, float strength) {
+    __shared__ uint8_t stage[6][NP_CHUNK];                               // the chunk's values (0 where not selected), for the walk
+    __shared__ NpMap maps[256][6];
+    __shared__ uint64_t acc[6];
+    __shared__ uint32_t counts[4];
+    const int64_t f = blockIdx.x;
+    const int32_t t = threadIdx.x;
+    const vrg_pil_box_desc d = desc[f];                                  // uniform
+    uint32_t* rec = stats + f * PIL_STATS_WORDS;
+    if (!pil_box_ok(d, g) || !d.color_match) {
+        if (t < PIL_STATS_WORDS) rec[t] = 0u;
+        return;
+    }
+    const int64_t n = (int64_t)d.box_w * d.box_h;
+    const uint8_t* frame = originals + ((f * g.H + d.top) * (int64_t)g.W + d.left) * 3;
+    const uint8_t* rep = repaired + d.rep_offset;
+    const uint8_t* mask = masks + d.mask_offset;
+    if (t < 6) acc[t] = 0ull;
+    uint32_t count = 0;
+    __syncthreads();
+    for (int64_t base = 0; base < n; base += NP_CHUNK) {
+        uint32_t sh[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) sh[k] = np_ulp_shift(acc[k]);
+        NpMap m[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) m[k].d[0] = m[k].d[1] = 0u;
+#pragma unroll
+        for (int e = 0; e < NP_RUN; ++e) {
+            const int32_t i = t * NP_RUN + e;
+            const int64_t p = base + i;
+            uint8_t v[6] = {0, 0, 0, 0, 0, 0};
+            if (p < n && mask[p] >= PIL_SELECT_FROM) {
+                const int32_t dy = (int32_t)(p / d.box_w), dx = (int32_t)(p - (int64_t)dy * d.box_w);
+                const uint8_t* o = frame + ((int64_t)dy * g.W + dx) * 3;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    v[c] = o[c];
+                    v[3 + c] = rep[p * 3 + c];
+                }
+                ++count;
+            }
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                stage[k][i] = v[k];
+                np_map_push(m[k], v[k], sh[k]);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 6; ++k) maps[t][k] = m[k];
+        __syncthreads();
+        for (int s = 1; s < 256; s <<= 1) {                              // in order: (t) then (t + s)
+            if ((t & (2 * s - 1)) == 0) {
+#pragma unroll
+                for (int k = 0; k < 6; ++k) maps[t][k] = np_map_then(maps[t][k], maps[t + s][k], sh[k]);
+            }
+            __syncthreads();
+        }
+        if (t < 6) {
+            uint64_t a = acc[t];
+            const uint32_t mine = np_ulp_shift(a);
+            if (!np_apply(a, maps[0][t], mine)) {
+                const int32_t len = (int32_t)(n - base < NP_CHUNK ? n - base : NP_CHUNK);
+                a = np_walk(a, stage[t], len, 1);
+            }
+            acc[t] = a;
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) count += (uint32_t)__shfl_xor((int)count, off, 64);
+    if ((t & 63) == 0) counts[t >> 6] = count;
+    __syncthreads();
+    if (t == 0) {
+        uint64_t sums[6];
+        for (int k = 0; k < 6; ++k) sums[k] = acc[k];
+        uint32_t out[PIL_STATS_WORDS];
+        np_finish(counts[0] + counts[1] + counts[2] + counts[3], sums, strength, out);
+        for (int i = 0; i < PIL_STATS_WORDS; ++i) rec[i] = out[i];
+    }
+}
+
+struct PilFrame {
+    vrg_pil_box_desc d;
+    bool ok, matched;
+    float shift[3];
+};
+
+__device__ __forceinline__ void pil_frame(PilFrame& fr, const vrg_pil_box_desc* __restrict__ desc, const PilGeom& g, int64_t f) {
+    fr.d = desc[f];
+    fr.ok = pil_box_ok(fr.d, g);
+    fr.matched = false;
+    fr.shift[0] = fr.shift[1] = fr.shift[2] = 0.0f;
+}
+
+// the shifts are read only by a thread that touches the box
+__device__ __forceinline__ void pil_frame_stats(PilFrame& fr, const uint32_t* __restrict__ stats, int64_t f) {
+    if (!fr.d.color_match) return;
+    const uint32_t* rec = stats + f * PIL_STATS_WORDS;
+    fr.matched = rec[10] != 0u;
+    for (int c = 0; c < 3; ++c) fr.shift[c] = f32_from_bits(rec[7 + c]);
+}
+
+// byte r of the frame (value v in the original): what the paste leaves there
+__device__ __forceinline__ uint8_t pil_byte(const PilFrame& fr, const PilGeom& g, const uint8_t* __restrict__ masks,
+                                            const uint8_t* __restrict__ repaired, int32_t r, uint8_t v) {
+    const int32_t px = (int32_t)((uint32_t)r / 3u), c = r - px * 3;
+    const int32_t y = (int32_t)((uint32_t)px / (uint32_t)g.W), x = px - y * g.W;
+    const int32_t dx = x - fr.d.left, dy = y - fr.d.top;
+    if (dx < 0 || dx >= fr.d.box_w || dy < 0 || dy >= fr.d.box_h) return v;
+    const int64_t i = (int64_t)dy * fr.d.box_w + dx;
+    uint8_t face = repaired[fr.d.rep_offset + i * 3 + c];
+    if (fr.matched) face = pil_shift_byte(face, fr.shift[c]);
+    return pil_paste_byte(v, face, masks[fr.d.mask_offset + i]);
+}
+
+// do bytes r .. r + 15 of a frame touch the box?
+__device__ __forceinline__ bool pil_piece_hits(const vrg_pil_box_desc& d, int32_t W, int32_t r) {
+    const int32_t pitch = W * 3;
+    const int32_t y0 = (int32_t)((uint32_t)r / (uint32_t)pitch), y1 = (int32_t)((uint32_t)(r + 15) / (uint32_t)pitch);
+    if (y1 < d.top || y0 >= d.top + d.box_h) return false;
+    if (y0 != y1) return true;
+    const int32_t xs = (r - y0 * pitch) / 3, xe = (r + 15 - y0 * pitch) / 3;
+    return xe >= d.left && xs < d.left + d.box_w;
+}
+
+__global__ __launch_bounds__(256) void k_pil_paste(const uint8_t* __restrict__ originals, const uint8_t* __restrict__ repaired,
+                                                    const uint8_t* __restrict__ masks, const vrg_pil_box_desc* __restrict__ desc,
+                                                    const uint32_t* __restrict__ stats, uint8_t* __restrict__ out, PilGeom g,
+                                                    int64_t frame_bytes, int64_t total, int32_t aligned) {
+    const int64_t b0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 16;
+    if (b0 >= total) return;
+    int64_t f = b0 / frame_bytes;
+    int32_t r = (int32_t)(b0 - f * frame_bytes);
+    PilFrame fr;
+    pil_frame(fr, desc, g, f);
+    const uint8_t* src = originals + b0;
+    uint8_t* dst = out + b0;
+    if (aligned && (int64_t)r + 16 <= frame_bytes) {
+        pfu4 q = __builtin_nontemporal_load(reinterpret_cast<const pfu4*>(src));
+        if (fr.ok && pil_piece_hits(fr.d, g.W, r)) {
+            pil_frame_stats(fr, stats, f);
+            uint32_t w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                const uint8_t v = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
+                const uint8_t nv = pil_byte(fr, g, masks, repaired, r + k, v);
+                w[k >> 2] = (w[k >> 2] & ~(0xffu << (8 * (k & 3)))) | ((uint32_t)nv << (8 * (k & 3)));
+            }
+            q = pfu4{w[0], w[1], w[2], w[3]};
+        }
+        __builtin_nontemporal_store(q, reinterpret_cast<pfu4*>(dst));
+        return;
+    }
+    if (fr.ok) pil_frame_stats(fr, stats, f);
+    for (int k = 0; k < 16 && b0 + k < total; ++k) {
+        if (r >= frame_bytes) {
+            r = 0;
+            ++f;
+            pil_frame(fr, desc, g, f);
+            if (fr.ok) pil_frame_stats(fr, stats, f);
+        }
+        const uint8_t v = src[k];
+        dst[k] = fr.ok ? pil_byte(fr, g, masks, repaired, r, v) : v;
+        ++r;
+    }
+}
+
+}  // namespace vrg
+
+using namespace vrg;
+
+extern "C" {
+
+int32_t vrg_pil_lanczos_ksize(int32_t n_in, int32_t n_out) { return (n_in < 1 || n_out < 1) ? 0 : pil_lanczos_ksize(n_in, n_out); }
+
+int vrg_pil_lanczos_table(int32_t n_in, int32_t n_out, int32_t* bounds_host, int32_t* weights_host) {
+    if (!bounds_host || !weights_host || n_in < 1 || n_out < 1) return VRG_ERR_BAD_ARG;
+    pil_lanczos_table(n_in, n_out, bounds_host, weights_host);
+    return VRG_OK;
+}
+
+int vrg_pil_box_parameters(float sigma, int32_t* out_host) {
+    if (!out_host || !(sigma > 0.0f) || !(sigma <= 4096.0f)) return VRG_ERR_BAD_ARG;
+    const PilBox b = pil_box_parameters(sigma);
+    out_host[0] = b.r;
+    out_host[1] = (int32_t)b.ww;
+    out_host[2] = (int32_t)b.fw;
+    return VRG_OK;
+}
+
+int vrg_pil_resize_u8(const uint8_t* src, int64_t src_bytes, const vrg_pil_resize_desc* desc, int64_t n_out, int32_t channels,
+                      const int32_t* tables, int64_t table_ints, uint8_t* tmp, int64_t tmp_bytes, uint8_t* dst, int64_t dst_bytes,
+                      int64_t max_pixels, void* stream) {
+    if ((channels != 1 && channels != 3) || n_out < 0 || src_bytes < 0 || table_ints < 0 || tmp_bytes < 0 || dst_bytes < 0 || max_pixels < 0)
+        return VRG_ERR_BAD_ARG;
+    if (n_out == 0 || max_pixels == 0) return VRG_OK;
+    if (!src || !desc || !dst || dst == src || (table_ints > 0 && !tables) || (tmp_bytes > 0 && (!tmp || tmp == src || tmp == dst)))
+        return VRG_ERR_BAD_ARG;
+    if (max_pixels > 0x7fffffffll) return VRG_ERR_UNSUPPORTED;
+    const uint32_t parts = (uint32_t)((max_pixels + 255) / 256);
+    const PilResizeGeom g{src_bytes, table_ints, tmp_bytes, dst_bytes, channels};
+    hipStream_t st = (hipStream_t)stream;
+    for (int64_t i0 = 0; i0 < n_out; i0 += 32768) {
+        const uint32_t ni = (uint32_t)(n_out - i0 < 32768 ? n_out - i0 : 32768);
+        if (channels == 3) {
+            hipLaunchKernelGGL(k_pil_resize_h<3>, dim3(parts, ni), dim3(256), 0, st, src, desc + i0, tables, tmp, dst, g);
+            VRG_CHECK_LAUNCH();
+            hipLaunchKernelGGL(k_pil_resize_v<3>, dim3(parts, ni), dim3(256), 0, st, src, desc + i0, tables, (const uint8_t*)tmp, dst, g);
+        } else {
+            hipLaunchKernelGGL(k_pil_resize_h<1>, dim3(parts, ni), dim3(256), 0, st, src, desc + i0, tables, tmp, dst, g);
+            VRG_CHECK_LAUNCH();
+            hipLaunchKernelGGL(k_pil_resize_v<1>, dim3(parts, ni), dim3(256), 0, st, src, desc + i0, tables, (const uint8_t*)tmp, dst, g);
+        }
+        VRG_CHECK_LAUNCH();
+    }
+    return VRG_OK;
+}
+
+int vrg_pil_mask_u8(const int32_t* spans, int64_t n_spans, const vrg_pil_mask_desc* desc, int64_t n_masks, int32_t max_width,
+                    int32_t max_height, uint8_t* scratch, uint8_t* masks, int64_t mask_bytes, void* stream) {
+    if (n_masks < 0 || n_spans < 0 || mask_bytes < 0 || max_width < 0 || max_height < 0) return VRG_ERR_BAD_ARG;
+    if (n_masks == 0 || max_width == 0 || max_height == 0) return VRG_OK;
+    if (!spans || !desc || !masks || !scratch || scratch == masks) return VRG_ERR_BAD_ARG;
+    if (max_width > PIL_MAX_LINE || max_height > PIL_MAX_LINE) return VRG_ERR_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    for (int64_t m0 = 0; m0 < n_masks; m0 += 32768) {
+        const uint32_t nm = (uint32_t)(n_masks - m0 < 32768 ? n_masks - m0 : 32768);
+        // a record without a blur (radius < 0) writes its spans to `masks` in the first launch and sits out the second
+        hipLaunchKernelGGL(k_pil_mask_h, dim3((uint32_t)max_height, nm), dim3(256), 0, st, reinterpret_cast<const PilSpan*>(spans), n_spans,
+                           desc + m0, scratch, masks, mask_bytes);
+        VRG_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_pil_mask_v, dim3((uint32_t)max_width, nm), dim3(256), 0, st, n_spans, desc + m0, (const uint8_t*)scratch, masks,
+                           mask_bytes);
+        VRG_CHECK_LAUNCH();
+    }
+    return VRG_OK;
+}
+
+int vrg_np_masked_means_f32(const uint8_t* originals, const uint8_t* repaired, int64_t rep_bytes, const uint8_t* masks, int64_t mask_bytes,
+                            const vrg_pil_box_desc* desc, uint32_t* stats, int64_t frames, int32_t height, int32_t width, float strength,
+                            void* stream) {
+    if (frames < 0 || rep_bytes < 0 || mask_bytes < 0) return VRG_ERR_BAD_ARG;
+    if (frames == 0) return VRG_OK;
+    if (!originals || !repaired || !masks || !desc || !stats || (reinterpret_cast<uintptr_t>(stats) & 3u) != 0 || height < 1 || width < 1)
+        return VRG_ERR_BAD_ARG;
+    if ((int64_t)height * width * 3 > 0x7fffffffll || frames > 0x7fffffffll) return VRG_ERR_UNSUPPORTED;
+    const PilGeom g{frames, rep_bytes, mask_bytes, height, width};
+    hipLaunchKernelGGL(k_np_means, dim3((uint32_t)frames), dim3(256), 0, (hipStream_t)stream, originals, repaired, masks, desc, stats, g, strength);
+    VRG_CHECK_LAUNCH();
+    return VRG_OK;
+}
+
+int vrg_pil_paste_u8(const uint8_t* originals, const uint8_t* repaired, int64_t rep_bytes, const uint8_t* masks, int64_t mask_bytes,
+                     const vrg_pil_box_desc* desc, const uint32_t* stats, uint8_t* out, int64_t frames, int32_t height, int32_t width,
+                     void* stream) {
+    if (frames < 0 || rep_bytes < 0 || mask_bytes < 0) return VRG_ERR_BAD_ARG;
+    if (frames == 0) return VRG_OK;
+    if (!originals || !repaired || !masks || !desc || !stats || (reinterpret_cast<uintptr_t>(stats) & 3u) != 0 || !out || out == originals ||
+        out == repaired || height < 1 || width < 1)
+        return VRG_ERR_BAD_ARG;
+    const int64_t frame_bytes = (int64_t)height * width * 3;
+    if (frame_bytes > 0x7fffffffll - 16) return VRG_ERR_UNSUPPORTED;
+    const int64_t total = frames * frame_bytes;
+    const int64_t blocks = ((total + 15) / 16 + 255) / 256;
+    if (blocks > 0x7fffffffll) return VRG_ERR_UNSUPPORTED;
+    const PilGeom g{frames, rep_bytes, mask_bytes, height, width};
+    const int32_t aligned = ((reinterpret_cast<uintptr_t>(originals) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0 ? 1 : 0;
+    hipLaunchKernelGGL(k_pil_paste, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, originals, repaired, masks, desc, stats, out, g,
+                       frame_bytes, total, aligned);
+    VRG_CHECK_LAUNCH();
+    return VRG_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,438 @@
+"""The pixels of the far-face repair backend (scripts/far_face_repair_backend.py of the reference) on the GPU, on decoded uint8 frames,
+under the reference's names.
+
+``expanded_square_crop`` / ``choose_face``   the host arithmetic of ``prepare`` (:154-199), unchanged.
+``crop_frames``                              ``image.crop(box)`` per marked frame (:287): the crops, of their own sizes.
+``soft_face_mask``                           :202-211 -- ``ImageDraw.ellipse`` (the outline is taken from Pillow on the host, two integers
+                                             per row, cached per size) and ``ImageFilter.GaussianBlur`` (six byte box passes on the GPU).
+``color_match_repaired``                     :214-224 -- the mean shift with numpy's sequential fp32 means over ``mask >= 64``.
+``composite_frames``                         the loop body of ``composite`` (:349-366) for a batch: every repaired crop resized to its box
+                                             with Pillow's LANCZOS, the mask, the optional colour match and ``Image.paste`` into a copy of
+                                             the frame -- a handful of launches for the batch, no host round trip in between.
+``pil_lanczos_resize``                       ``Image.resize(size, Image.Resampling.LANCZOS)`` for a batch of RGB or L images of any sizes.
+
+Every step equals Pillow / numpy byte for byte (csrc/vrg_pil_math.hpp).  The channel order is the caller's: the arithmetic treats the three
+channels alike.  Device-resident inputs stay on the device; CPU inputs are uploaded whole and the result comes back in the form the frames
+came in.  Detection, PNG / video I/O, manifests, ``contact_sheet`` and ``rebuild_video`` are out of scope.  The library is reached through
+``_hip`` only; Pillow is needed for the ellipse outline alone.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import functools
+import math
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from . import _hip
+from ._devices import compute_device
+from .VRGDG_FaceFix import _boxes, _frames_in, _host, _peek, _upload
+
+NODE_CLASS_MAPPINGS = {}
+NODE_DISPLAY_NAME_MAPPINGS = {}
+
+DEFAULT_FEATHER = 18
+COLOR_MATCH_STRENGTH = 0.65
+MAX_FEATHER = 4096
+
+FaceBox = namedtuple("FaceBox", "x y w h score")
+
+_RESIZE_DESC = np.dtype([("src_offset", "<i8"), ("dst_offset", "<i8"), ("tmp_offset", "<i8"), ("h_table", "<i8"), ("v_table", "<i8"),
+                         ("in_w", "<i4"), ("in_h", "<i4"), ("out_w", "<i4"), ("out_h", "<i4"), ("h_ksize", "<i4"), ("v_ksize", "<i4")])
+_MASK_DESC = np.dtype([("width", "<i4"), ("height", "<i4"), ("radius", "<i4"), ("ww", "<u4"), ("fw", "<u4"), ("reserved", "<i4"),
+                       ("span_offset", "<i8"), ("mask_offset", "<i8")])
+_BOX_DESC = np.dtype([("left", "<i4"), ("top", "<i4"), ("box_w", "<i4"), ("box_h", "<i4"), ("color_match", "<i4"), ("reserved", "<i4"),
+                      ("mask_offset", "<i8"), ("rep_offset", "<i8")])
+assert _RESIZE_DESC.itemsize == C.sizeof(_hip.PilResizeDesc) and _MASK_DESC.itemsize == C.sizeof(_hip.PilMaskDesc)
+assert _BOX_DESC.itemsize == C.sizeof(_hip.PilBoxDesc)
+
+
+# ------------------------------------------------------------------------------------------------
+# host arithmetic of `prepare`
+# ------------------------------------------------------------------------------------------------
+def choose_face(faces, width, height, mode):
+    """the face ``prepare`` keeps (:154-169): the largest, slightly favouring the centre, or (mode "center") the most central"""
+    if not faces:
+        return None
+    center_x, center_y = width / 2.0, height / 2.0
+
+    def score(face):
+        area = face.w * face.h
+        dist = math.hypot((face.x + face.w / 2.0 - center_x) / width, (face.y + face.h / 2.0 - center_y) / height)
+        return -dist if mode == "center" else area - dist * area * 0.15
+
+    return max(faces, key=score)
+
+
+def expanded_square_crop(face, image_width, image_height, padding):
+    """(left, top, right, bottom) of the padded square around a face (:172-199), at least 32 px, pushed back inside the image"""
+    cx, cy = face.x + face.w / 2.0, face.y + face.h / 2.0
+    side = max(max(face.w, face.h) * float(padding), 32.0)
+    left, top = int(round(cx - side / 2.0)), int(round(cy - side / 2.0))
+    right, bottom = int(round(cx + side / 2.0)), int(round(cy + side / 2.0))
+    if left < 0:
+        left, right = 0, right - left
+    if top < 0:
+        top, bottom = 0, bottom - top
+    if right > image_width:
+        left, right = left - (right - image_width), image_width
+    if bottom > image_height:
+        top, bottom = top - (bottom - image_height), image_height
+    left, top = max(0, left), max(0, top)
+    return left, top, min(image_width, max(left + 1, right)), min(image_height, max(top + 1, bottom))
+
+
+# ------------------------------------------------------------------------------------------------
+# host tables
+# ------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=512)
+def lanczos_table(n_in: int, n_out: int):
+    """(ksize, one axis table as the kernels read it: bounds [n_out, 2] then weights [n_out, ksize], int32); host only"""
+    if n_in < 1 or n_out < 1:
+        raise ValueError("lanczos_table: sizes must be at least 1")
+    ksize = int(_host().vrg_pil_lanczos_ksize(n_in, n_out))
+    table = np.zeros(n_out * (2 + ksize), dtype=np.int32)
+    bounds, weights = table[:2 * n_out], table[2 * n_out:]
+    _hip.check(_host().vrg_pil_lanczos_table(n_in, n_out, C.c_void_p(bounds.ctypes.data), C.c_void_p(weights.ctypes.data)), "vrg_pil_lanczos_table")
+    table.setflags(write=False)
+    return ksize, table
+
+
+@functools.lru_cache(maxsize=64)
+def box_parameters(feather: int):
+    """(radius, ww, fw) of one box pass of ``GaussianBlur(radius=float(feather))``; host only"""
+    out = np.zeros(3, dtype=np.int32)
+    _hip.check(_host().vrg_pil_box_parameters(float(feather), C.c_void_p(out.ctypes.data)), "vrg_pil_box_parameters")
+    return int(out[0]), int(out.view(np.uint32)[1]), int(out.view(np.uint32)[2])
+
+
+@functools.lru_cache(maxsize=512)
+def ellipse_spans(width: int, height: int, shrink: float = 0.12) -> np.ndarray:
+    """[height, 2] int32: the first and last column ``ImageDraw.ellipse`` sets in every row of the mask (first > last: none) -- from
+    Pillow itself; every row of the outline is one run"""
+    from PIL import Image, ImageDraw
+    if width < 1 or height < 1:
+        raise ValueError("ellipse_spans: width and height must be at least 1")
+    inset_x, inset_y = int(round(width * shrink)), int(round(height * shrink))
+    mask = Image.new("L", (width, height), 0)
+    ImageDraw.Draw(mask).ellipse((inset_x, inset_y, width - inset_x, height - inset_y), fill=255)
+    plane = np.asarray(mask) != 0
+    any_set = plane.any(axis=1)
+    first = plane.argmax(axis=1)
+    last = width - 1 - plane[:, ::-1].argmax(axis=1)
+    if int(plane.sum()) != int((last - first + 1)[any_set].sum()):
+        raise RuntimeError("ellipse_spans: a row of Pillow's ellipse is not one run")
+    spans = np.where(any_set[:, None], np.stack([first, last], axis=1), np.array([[1, 0]])).astype(np.int32)
+    spans.setflags(write=False)
+    return spans
+
+
+# ------------------------------------------------------------------------------------------------
+# images in, images out
+# ------------------------------------------------------------------------------------------------
+def _image_list(images, name, channels=None):
+    """-> (a list of uint8 [h, w, c] / [h, w] tensors or arrays, c) of a batch given as a tensor or a sequence"""
+    items = list(images) if not isinstance(images, (torch.Tensor, np.ndarray)) else [images[i] for i in range(images.shape[0])]
+    c = channels
+    for item in items:
+        if item is None:
+            continue
+        dtype_ok = item.dtype == (torch.uint8 if isinstance(item, torch.Tensor) else np.uint8)
+        k = 1 if item.ndim == 2 else int(item.shape[-1]) if item.ndim == 3 else 0
+        if not dtype_ok or k not in (1, 3) or (item.ndim == 3 and k == 1 and channels is None):
+            raise ValueError(f"{name} must be uint8 images of shape [h, w, 3] or [h, w]")
+        if c is None:
+            c = k
+        if k != c:
+            raise ValueError(f"{name} must be uint8 images of {c} channel(s), got {k}")
+        if item.shape[0] < 1 or item.shape[1] < 1:
+            raise ValueError(f"{name} must not hold an empty image")
+    return items, c
+
+
+def _pack(items, device):
+    """the bytes of the images back to back on the device -> (buffer, [offset per image])"""
+    offsets, total = [], 0
+    for item in items:
+        offsets.append(total)
+        total += int(np.prod(item.shape))
+    if all(isinstance(i, torch.Tensor) and i.is_cuda for i in items) and items:
+        buf = torch.cat([i.to(device).contiguous().reshape(-1) for i in items])
+    elif items:
+        buf = torch.from_numpy(np.concatenate([np.ascontiguousarray(i.cpu().numpy() if isinstance(i, torch.Tensor) else i).reshape(-1)
+                                               for i in items])).to(device)
+    else:
+        buf = torch.zeros(1, dtype=torch.uint8, device=device)
+    return buf, offsets
+
+
+class ResizePlan:
+    """``Image.resize(out_size, LANCZOS)`` of a packed batch: sizes[i] = (in_w, in_h, out_w, out_h) -> ``dst`` and ``offsets``"""
+
+    def __init__(self, src, src_offsets, sizes, channels, device):
+        self.src, self.channels = src, channels
+        desc = np.zeros(len(sizes), dtype=_RESIZE_DESC)
+        tables, table_at, n_ints, dst_bytes, tmp_bytes, self.max_pixels = [], {}, 0, 0, 0, 0
+        self.offsets = []
+        for i, (iw, ih, ow, oh) in enumerate(sizes):
+            at, ks = [0, 0], [0, 0]
+            for axis, (n_in, n_out) in enumerate(((iw, ow), (ih, oh))):
+                if n_in == n_out:
+                    continue
+                if (n_in, n_out) not in table_at:
+                    ksize, table = lanczos_table(n_in, n_out)
+                    table_at[(n_in, n_out)] = (n_ints, ksize)
+                    tables.append(table)
+                    n_ints += len(table)
+                at[axis], ks[axis] = table_at[(n_in, n_out)]
+            desc[i] = (src_offsets[i], dst_bytes, tmp_bytes, at[0], at[1], iw, ih, ow, oh, ks[0], ks[1])
+            self.offsets.append(dst_bytes)
+            dst_bytes += ow * oh * channels
+            if iw != ow and ih != oh:
+                tmp_bytes += ih * ow * channels
+            self.max_pixels = max(self.max_pixels, ih * ow, oh * ow)
+        self.n, self.n_ints, self.dst_bytes, self.tmp_bytes = len(sizes), n_ints, dst_bytes, tmp_bytes
+        self.tables = _upload(np.concatenate(tables) if tables else np.zeros(1, np.int32), device)
+        self.desc = _upload(desc, device) if len(sizes) else None
+        self.dst = torch.empty(max(dst_bytes, 1), dtype=torch.uint8, device=device)
+        self.tmp = torch.empty(max(tmp_bytes, 1), dtype=torch.uint8, device=device)
+
+    def run(self):
+        if self.n:
+            _hip.check(_hip.lib().vrg_pil_resize_u8(_hip.ptr(self.src), self.src.numel(), _hip.ptr(self.desc), self.n, self.channels,
+                                                    _hip.ptr(self.tables), self.n_ints, _hip.ptr(self.tmp), self.tmp_bytes, _hip.ptr(self.dst),
+                                                    self.dst_bytes, self.max_pixels, _hip.current_stream()), "vrg_pil_resize_u8")
+        return self.dst
+
+
+def pil_lanczos_resize(images_u8, size):
+    """``Image.resize(size, Image.Resampling.LANCZOS)`` (size = (width, height)) of every image of a batch: a uint8 tensor [n, h, w, 3] /
+    [n, h, w] or a sequence of [h, w, 3] / [h, w] images of any sizes -> [n, height, width(, 3)] uint8, on the GPU for a CUDA tensor or a
+    sequence of them, else on the CPU (a list of arrays for a sequence of arrays)."""
+    width, height = int(size[0]), int(size[1])
+    if width < 1 or height < 1:
+        raise ValueError("size must be at least 1 x 1")
+    items, c = _image_list(images_u8, "images")
+    flat = bool(items) and items[0].ndim == 2
+    shape = (len(items), height, width) + (() if flat else (c or 3,))
+    on_device = isinstance(images_u8, torch.Tensor) and images_u8.is_cuda or (bool(items) and all(isinstance(i, torch.Tensor) and i.is_cuda for i in items))
+    device = items[0].device if on_device and items else compute_device()
+    if not items:
+        return torch.empty(shape, dtype=torch.uint8)
+    with torch.cuda.device(device):
+        src, offsets = _pack(items, device)
+        plan = ResizePlan(src, offsets, [(int(i.shape[1]), int(i.shape[0]), width, height) for i in items], c, device)
+        out = plan.run()[:plan.dst_bytes].reshape(shape)
+        if on_device:
+            return out
+        out = out.cpu()
+        return out if isinstance(images_u8, torch.Tensor) or isinstance(items[0], torch.Tensor) else list(out.numpy())
+
+
+def crop_frames(frames_u8, crop_boxes):
+    """``image.crop((left, top, right, bottom))`` for every frame that has a box (``crop_boxes``: one box or None per frame): the crops in
+    the order of the frames, each of its own size -- CUDA tensors for CUDA frames, CPU tensors for a CPU tensor, arrays for arrays."""
+    frames, height, width = _peek(frames_u8, "frames")
+    boxes = _boxes(crop_boxes, frames, height, width)
+    t = getattr(frames_u8, "u8", frames_u8)
+    out = []
+    for f, box in enumerate(boxes):
+        if box is None:
+            continue
+        left, top, w, h = box
+        crop = t[f][top:top + h, left:left + w]
+        out.append(crop.clone() if isinstance(crop, torch.Tensor) else np.array(crop, copy=True))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
+# masks
+# ------------------------------------------------------------------------------------------------
+def _check_feather(feather):
+    feather = int(feather)
+    if feather > MAX_FEATHER:
+        raise ValueError(f"feather must not exceed {MAX_FEATHER}")
+    return feather
+
+
+class MaskPlan:
+    """the soft-ellipse masks of the distinct (w, h) of a batch, packed -> ``masks`` and ``offsets[(w, h)]``"""
+
+    def __init__(self, sizes, feather, device, shrink=0.12):
+        self.offsets, spans, records, total, rows = {}, [], [], 0, 0
+        radius, ww, fw = box_parameters(feather) if feather > 0 else (-1, 0, 0)
+        for w, h in sizes:
+            if (w, h) in self.offsets:
+                continue
+            if w > _hip.PIL_MAX_LINE or h > _hip.PIL_MAX_LINE:
+                raise ValueError(f"a mask of {w} x {h} exceeds {_hip.PIL_MAX_LINE} pixels a side")
+            self.offsets[(w, h)] = total
+            spans.append(ellipse_spans(w, h, shrink))
+            records.append((w, h, radius, ww, fw, 0, rows, total))
+            rows += h
+            total += w * h
+        self.n, self.total, self.rows = len(records), total, rows
+        self.max_w, self.max_h = max([r[0] for r in records] or [0]), max([r[1] for r in records] or [0])
+        self.spans = _upload(np.concatenate(spans) if spans else np.zeros((1, 2), np.int32), device)
+        self.records = _upload(np.array(records, dtype=_MASK_DESC), device) if records else None
+        self.masks = torch.empty(max(total, 1), dtype=torch.uint8, device=device)
+        self.scratch = torch.empty(max(total, 1), dtype=torch.uint8, device=device)
+
+    def run(self):
+        if self.n:
+            _hip.check(_hip.lib().vrg_pil_mask_u8(_hip.ptr(self.spans), self.rows, _hip.ptr(self.records), self.n, self.max_w, self.max_h,
+                                                  _hip.ptr(self.scratch), _hip.ptr(self.masks), self.total, _hip.current_stream()),
+                       "vrg_pil_mask_u8")
+        return self.masks
+
+
+def soft_face_mask(size, feather, shrink=0.12) -> np.ndarray:
+    """``soft_face_mask(size, feather, shrink)`` of the reference (:202-211) as a uint8 ``[height, width]`` array, made on the GPU"""
+    width, height = int(size[0]), int(size[1])
+    if width < 1 or height < 1:
+        raise ValueError("mask width and height must be at least 1")
+    feather = _check_feather(feather)
+    device = compute_device()
+    with torch.cuda.device(device):
+        plan = MaskPlan([(width, height)], feather, device, float(shrink))
+        return plan.run()[:width * height].cpu().numpy().reshape(height, width)
+
+
+# ------------------------------------------------------------------------------------------------
+# the composite
+# ------------------------------------------------------------------------------------------------
+def _per_box(values, boxes, name):
+    """the entries of `values` that belong to the frames with a box: one per box, or one per frame (None allowed where there is no box)"""
+    n_boxes = sum(b is not None for b in boxes)
+    items = list(values) if not isinstance(values, (torch.Tensor, np.ndarray)) else [values[i] for i in range(values.shape[0])]
+    if len(items) == n_boxes:
+        picked = items
+    elif len(items) == len(boxes):
+        picked = [v for v, b in zip(items, boxes) if b is not None]
+    else:
+        raise ValueError(f"{name} must hold one image per box ({n_boxes}) or per frame ({len(boxes)}), got {len(items)}")
+    if any(v is None for v in picked):
+        raise ValueError(f"{name} has no image for a frame that has a box")
+    return picked
+
+
+class CompositePlan:
+    """The tables and buffers of one ``composite_frames`` call on a device batch, and its steps (``composite_frames`` runs them in order;
+    tools/bench_far_face.py times each).  ``boxes``: (left, top, w, h) or None per frame; ``repaired`` / ``masks``: one image per box."""
+
+    def __init__(self, x, boxes, repaired, feather, color_match, masks=None):
+        device = x.device
+        self.x, self.color_match = x, bool(color_match)
+        used = [(f, b) for f, b in enumerate(boxes) if b is not None]
+        src, offsets = _pack(repaired, device)
+        self.resize = ResizePlan(src, offsets, [(int(r.shape[1]), int(r.shape[0]), b[2], b[3]) for r, (_, b) in zip(repaired, used)], 3, device)
+        if feather >= 0:
+            self.mask_plan, self.mask_resize = MaskPlan([(b[2], b[3]) for _, b in used], feather, device), None
+            mask_offsets = [self.mask_plan.offsets[(b[2], b[3])] for _, b in used]
+            self.mask_bytes = self.mask_plan.total
+        else:
+            msrc, moffsets = _pack(masks, device)
+            self.mask_plan = None
+            self.mask_resize = ResizePlan(msrc, moffsets, [(int(m.shape[1]), int(m.shape[0]), b[2], b[3]) for m, (_, b) in zip(masks, used)], 1,
+                                          device)
+            mask_offsets, self.mask_bytes = self.mask_resize.offsets, self.mask_resize.dst_bytes
+        desc = np.zeros(int(x.shape[0]), dtype=_BOX_DESC)
+        for k, (f, (left, top, w, h)) in enumerate(used):
+            desc[f] = (left, top, w, h, int(self.color_match), 0, mask_offsets[k], self.resize.offsets[k])
+        self.desc = _upload(desc, device)
+        self.stats = torch.zeros(int(x.shape[0]) * _hip.PIL_STATS_WORDS, dtype=torch.int32, device=device)
+        self.out = torch.empty_like(x)
+        self.rep = self.masks = None
+
+    def run_resize(self):
+        self.rep = self.resize.run()
+
+    def run_masks(self):
+        self.masks = self.mask_plan.run() if self.mask_plan is not None else self.mask_resize.run()
+
+    def _args(self):
+        x = self.x
+        return (_hip.ptr(x), _hip.ptr(self.rep), self.resize.dst_bytes, _hip.ptr(self.masks), self.mask_bytes, _hip.ptr(self.desc),
+                _hip.ptr(self.stats))
+
+    def run_means(self):
+        x = self.x
+        if self.color_match:
+            _hip.check(_hip.lib().vrg_np_masked_means_f32(*self._args(), int(x.shape[0]), int(x.shape[1]), int(x.shape[2]), COLOR_MATCH_STRENGTH,
+                                                          _hip.current_stream()), "vrg_np_masked_means_f32")
+
+    def run_paste(self):
+        x = self.x
+        _hip.check(_hip.lib().vrg_pil_paste_u8(*self._args(), _hip.ptr(self.out), int(x.shape[0]), int(x.shape[1]), int(x.shape[2]),
+                                               _hip.current_stream()), "vrg_pil_paste_u8")
+        return self.out
+
+
+def _prepare(originals_u8, repaired, crop_boxes, feather, masks):
+    feather = _check_feather(feather)
+    boxes = _boxes(crop_boxes, *_peek(originals_u8, "originals"))
+    rep, _ = _image_list(_per_box(repaired, boxes, "repaired"), "repaired", 3)
+    if any(r.ndim != 3 for r in rep):
+        raise ValueError("repaired must be uint8 images of shape [h, w, 3]")
+    mk = None
+    if feather < 0:
+        if masks is None:
+            raise ValueError("feather < 0 keeps the saved masks: masks must be given")
+        mk, _ = _image_list(_per_box(masks, boxes, "masks"), "masks", 1)
+        mk = [m[:, :, 0] if m.ndim == 3 else m for m in mk]
+    return feather, boxes, rep, mk
+
+
+def composite_frames(originals_u8, repaired, crop_boxes, feather=DEFAULT_FEATHER, color_match=False, masks=None):
+    """The loop body of ``composite`` for a batch: ``repaired`` (one RGB crop of any size per box in the order of the frames, or one entry
+    per frame) resized to its box with LANCZOS, colour matched if asked, and pasted under the mask into a copy of ``originals_u8``, which is
+    never written.  ``feather >= 0`` makes a fresh soft ellipse per box (0: unblurred); ``feather < 0`` keeps ``masks`` (uint8 [h, w] images
+    of any sizes, one per box), LANCZOS-resized as L.  Frames without a box come back unchanged.  The result has the shape and the form of
+    ``originals_u8`` (CUDA tensor, CPU tensor, list of numpy frames)."""
+    feather, boxes, rep, mk = _prepare(originals_u8, repaired, crop_boxes, feather, masks)
+    x, back = _frames_in(originals_u8, "originals")
+    with torch.cuda.device(x.device):
+        if x.shape[0] == 0:
+            return back(torch.empty_like(x))
+        plan = CompositePlan(x, boxes, rep, feather, color_match, mk)
+        plan.run_resize()
+        plan.run_masks()
+        plan.run_means()
+        return back(plan.run_paste())
+
+
+def color_match_repaired(original, repaired, mask) -> np.ndarray:
+    """``color_match_repaired(original, repaired, mask)`` of the reference (:214-224) on uint8 arrays of one size ([h, w, 3], [h, w, 3],
+    [h, w]) -> the adjusted [h, w, 3] array (the repaired bytes themselves when fewer than 16 pixels are selected), made on the GPU"""
+    original, repaired, mask = (np.ascontiguousarray(a) for a in (original, repaired, mask))
+    if original.dtype != np.uint8 or original.ndim != 3 or original.shape[2] != 3 or repaired.shape != original.shape or \
+            repaired.dtype != np.uint8 or mask.dtype != np.uint8 or mask.shape != original.shape[:2]:
+        raise ValueError("color_match_repaired: original and repaired must be [h, w, 3] uint8 of one size, mask [h, w] uint8")
+    h, w = mask.shape
+    device = compute_device()
+    with torch.cuda.device(device):
+        # the shift alone: pasted under a mask of 255 everywhere the result is the shifted crop
+        plan = CompositePlan(torch.from_numpy(original[None]).to(device), [(0, 0, w, h)], [repaired], -1, True, [mask])
+        plan.run_resize()
+        plan.run_masks()
+        plan.run_means()
+        plan.masks = torch.full_like(plan.masks, 255)
+        return plan.run_paste()[0].cpu().numpy()
+
+
+def masked_means(original, repaired, mask) -> dict:
+    """the record of the means kernel for one box (arrays as for ``color_match_repaired``): count, original_mean, repaired_mean, shift
+    (float32 [3] each) and matched"""
+    original, repaired, mask = (np.ascontiguousarray(a) for a in (original, repaired, mask))
+    h, w = mask.shape
+    device = compute_device()
+    with torch.cuda.device(device):
+        plan = CompositePlan(torch.from_numpy(original[None]).to(device), [(0, 0, w, h)], [repaired], -1, True, [mask])
+        plan.run_resize()
+        plan.run_masks()
+        plan.run_means()
+        rec = plan.stats.cpu().numpy().view(np.uint32)[:_hip.PIL_STATS_WORDS]
+    return {"count": int(rec[0]), "original_mean": rec[1:4].view(np.float32).copy(), "repaired_mean": rec[4:7].view(np.float32).copy(),
+            "shift": rec[7:10].view(np.float32).copy(), "matched": bool(rec[10])}

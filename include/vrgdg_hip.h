@@ -669,6 +669,77 @@ int vrg_selfcheck_pow_f32(const float* in, float* out, int64_t n, int32_t site, 
 
 
 /* ---------------------------------------------------------------------------------------------
+ * Far-face repair composite on decoded bytes (reference: scripts/far_face_repair_backend.py composite :339-371): every repaired crop
+ * resized to its box with Pillow's LANCZOS, a soft-ellipse mask (ImageDraw.ellipse + GaussianBlur), an optional mean shift with numpy's
+ * sequential fp32 means, and Image.paste under the mask into a copy of the frame.  Arithmetic: csrc/vrg_pil_math.hpp, pinned byte for
+ * byte against Pillow itself.
+ *
+ * HOST tables.  vrg_pil_lanczos_ksize gives the taps per output index of one axis `n_in` -> `n_out` (0: a size below 1);
+ * vrg_pil_lanczos_table fills bounds[n_out][2] (first source index, tap count) and weights[n_out][ksize] (22-bit fixed point, zero beyond
+ * the count).  On the device one axis table is these two arrays back to back: n_out * (2 + ksize) int32.  vrg_pil_box_parameters fills
+ * out[3] = radius, ww, fw (the last two uint32) of one box pass of GaussianBlur(radius = sigma), 0 < sigma <= 4096.
+ *
+ * Every table and record below is device memory; a record that names anything outside the stated sizes, or a box that does not lie inside
+ * the frame, is treated as "no box" / "no image".
+ * ------------------------------------------------------------------------------------------- */
+typedef struct vrg_pil_resize_desc {   /* one OUTPUT image: src[in_h][in_w][C] -> dst[out_h][out_w][C] */
+    int64_t src_offset, dst_offset;    /* bytes from `src` / `dst` */
+    int64_t tmp_offset;                /* bytes from `tmp` to the [in_h][out_w][C] image of the horizontal pass (read when both passes run) */
+    int64_t h_table, v_table;          /* int32 from `tables` to the axis table in_w -> out_w / in_h -> out_h (read when the sizes differ) */
+    int32_t in_w, in_h, out_w, out_h;
+    int32_t h_ksize, v_ksize;
+} vrg_pil_resize_desc;
+
+typedef struct vrg_pil_mask_desc {
+    int32_t width, height;             /* each at most 8192 */
+    int32_t radius;                    /* of a box pass; < 0: no blur, the mask is the 0 / 255 spans */
+    uint32_t ww, fw;
+    int32_t reserved;                  /* 0 */
+    int64_t span_offset;               /* records (two int32: first and last set column) from `spans` to this mask's `height` rows */
+    int64_t mask_offset;               /* bytes from `masks` (and `scratch`) to this mask's [height][width] plane */
+} vrg_pil_mask_desc;
+
+typedef struct vrg_pil_box_desc {      /* one OUTPUT frame f */
+    int32_t left, top, box_w, box_h;   /* box_w < 1: no box, the frame is copied */
+    int32_t color_match;               /* != 0: the mean shift of color_match_repaired */
+    int32_t reserved;                  /* 0 */
+    int64_t mask_offset;               /* bytes from `masks` to the [box_h][box_w] mask */
+    int64_t rep_offset;                /* bytes from `repaired` to the [box_h][box_w][3] resized crop */
+} vrg_pil_box_desc;
+
+int32_t vrg_pil_lanczos_ksize(int32_t n_in, int32_t n_out);
+int vrg_pil_lanczos_table(int32_t n_in, int32_t n_out, int32_t* bounds_host, int32_t* weights_host);
+int vrg_pil_box_parameters(float sigma, int32_t* out_host);
+
+/* dst image i = Image.resize((out_w, out_h), LANCZOS) of src image i for n_out records (sources of any sizes, packed in `src`), channels =
+ * 3 (RGB) or 1 (L): the horizontal byte pass into `tmp`, then the vertical one; a pass whose size does not change is skipped, both: a copy.
+ * max_pixels >= the largest in_h * out_w and out_h * out_w.  `src` is never written; src, tmp and dst are distinct. */
+int vrg_pil_resize_u8(const uint8_t* src, int64_t src_bytes, const vrg_pil_resize_desc* desc, int64_t n_out, int32_t channels,
+                      const int32_t* tables, int64_t table_ints, uint8_t* tmp, int64_t tmp_bytes, uint8_t* dst, int64_t dst_bytes,
+                      int64_t max_pixels, void* stream);
+
+/* The masks of `n_masks` records, packed into `masks` (`mask_bytes` bytes; `scratch` of the same size holds the row passes): the 0 / 255
+ * spans through three box passes along the rows, then three along the columns, each rounded to bytes, from integer prefix sums.
+ * max_width / max_height >= the largest of the records. */
+int vrg_pil_mask_u8(const int32_t* spans, int64_t n_spans, const vrg_pil_mask_desc* desc, int64_t n_masks, int32_t max_width,
+                    int32_t max_height, uint8_t* scratch, uint8_t* masks, int64_t mask_bytes, void* stream);
+
+/* stats[f] (12 uint32 per frame) for every frame with a box and color_match != 0 (all zero otherwise): [0] the count of mask >= 64,
+ * [1..3] numpy's fp32 means of the original's box there (the sequential fp32 sum in row-major order / the count), [4..6] those of the
+ * resized crop, [7..9] the shifts fl(fl(original mean - crop mean) * strength), [10] matched = count >= 16, [11] 0; fp32 as bit patterns. */
+int vrg_np_masked_means_f32(const uint8_t* originals, const uint8_t* repaired, int64_t rep_bytes, const uint8_t* masks, int64_t mask_bytes,
+                            const vrg_pil_box_desc* desc, uint32_t* stats, int64_t frames, int32_t height, int32_t width, float strength,
+                            void* stream);
+
+/* One pass over out = [frames][height][width][3]: the original's bytes outside the box (and everywhere for "no box"); inside,
+ * r' = matched ? trunc(clip(fl(r + shift), 0, 255)) : r and t = o (255 - m) + r' m + 128, out = ((t >> 8) + t) >> 8.  out != originals,
+ * which is never written. */
+int vrg_pil_paste_u8(const uint8_t* originals, const uint8_t* repaired, int64_t rep_bytes, const uint8_t* masks, int64_t mask_bytes,
+                     const vrg_pil_box_desc* desc, const uint32_t* stats, uint8_t* out, int64_t frames, int32_t height, int32_t width,
+                     void* stream);
+
+
+/* ---------------------------------------------------------------------------------------------
  * Host side of the node path (reference: nodes.py:50, 61-66 -- CPU tensors in, `images.to(device)` per batch)
  * ------------------------------------------------------------------------------------------- */
 /* memcpy of `bytes` from `src` to `dst` (host pointers, not overlapping) split over `threads` host threads (0 = 8; at most 64; parts of
