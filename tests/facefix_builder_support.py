@@ -289,18 +289,19 @@ def reflect101(index, n):
 
 
 def blur(plane, coeffs):
-    """horizontal then vertical, sums in the dtype of `coeffs` (float32: the specification; float64: the yardstick), taps in index order"""
+    """horizontal then vertical, sums in the dtype of `coeffs` (float32: the specification; float64: the yardstick), taps in index order;
+    `plane` is [h, w] or a stack [..., h, w] of planes of one size"""
     dt = coeffs.dtype.type
     src = np.asarray(plane, dtype=dt)
-    h, w = src.shape
+    h, w = src.shape[-2:]
     n = len(coeffs)
     r = (n - 1) // 2
-    hor = np.zeros((h, w), dtype=dt)
+    hor = np.zeros(src.shape, dtype=dt)
     for i in range(n):
-        hor = hor + coeffs[i] * src[:, reflect101(np.arange(w) + i - r, w)]
-    ver = np.zeros((h, w), dtype=dt)
+        hor = hor + coeffs[i] * src[..., reflect101(np.arange(w) + i - r, w)]
+    ver = np.zeros(src.shape, dtype=dt)
     for j in range(n):
-        ver = ver + coeffs[j] * hor[reflect101(np.arange(h) + j - r, h), :]
+        ver = ver + coeffs[j] * hor[..., reflect101(np.arange(h) + j - r, h), :]
     return ver
 
 
@@ -376,6 +377,25 @@ def crops(frames, boxes, size):
         left, top, right, bottom = box
         out.append(np.asarray(LS.restated(np.ascontiguousarray(frames[f:f + 1, top:bottom, left:right]), size, size))[0])
     return np.stack(out) if out else np.zeros((0, size, size, 3), dtype=np.uint8)
+
+
+# ---- the byte mover: the geometry sweep of far_face_support.MOVER_CASES for k_ff_composite ------------------------------------------------
+MOVER_ENHANCED = (9, 7)                  # (h, w) of every repaired frame of the sweep: unlike every box, so each is resized
+MOVER_SETTINGS = ((0, 0.0), (0, 0.65), (1, 0.0), (1, 0.65))                  # (feather, color_match)
+
+
+def mover_inputs(name):
+    """-> (originals, enhanced [one per box], boxes, strengths) of a case of the sweep: strengths 1.0 and 0.65 in turn, and 0.0 (the frame
+    must come back untouched although it has a box) on the last frame of the first case"""
+    import far_face_support as S
+    F, H, W, boxes = S.MOVER_CASES[name]
+    originals = S.mover_originals(name)
+    n = sum(b is not None for b in boxes)
+    enhanced = make_frames("random", (n,) + MOVER_ENHANCED + (3,), 8500 + sorted(S.MOVER_CASES).index(name))
+    strengths = [(1.0, 0.65)[f % 2] for f in range(F)]
+    if name == "a_1x1":
+        strengths[-1] = 0.0
+    return originals, enhanced, boxes, strengths
 
 
 # ---- the header on the host ---------------------------------------------------------------------------------------------------------------

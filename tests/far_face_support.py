@@ -383,3 +383,132 @@ def steered_inputs(k):
         flat[pick] = (flat[pick].astype(np.int16) + (1 if k > 0 else -1)).astype(np.uint8)
     frame[top:bottom, left:right, 0] = plane
     return frame[None], [rep], [np.full((400, 400), 255, np.uint8)]
+
+
+# ------------------------------------------------------------------------------------------------
+# the byte movers (k_pil_paste of csrc/vrg_farface.hip, k_ff_composite of csrc/vrg_facefix.hip): one geometry sweep for both, and a model
+# of how the kernels split the flat batch into 16-byte pieces.  The model restates the geometry; it calls no kernel.
+# ------------------------------------------------------------------------------------------------
+PIECE = 16
+MOVER_OFFSETS = (0, 1, 4)                                                    # where the batch starts in its device buffer, in bytes
+
+
+def _d_boxes(k):
+    """case d: an interior 6 x 5 box per frame whose `left` is 4 k + f, so that the four cases take every value 0 .. 15"""
+    return [(4 * k + f, 9 + 3 * f, 4 * k + f + 6, 14 + 3 * f) for f in range(4)]
+
+
+# name -> (F, H, W, one (left, top, right, bottom) or None per frame)
+MOVER_CASES = {
+    # one 16-byte piece crosses five seams; the records alternate box / no box
+    "a_1x1": (5, 1, 1, [(0, 0, 1, 1), None, (0, 0, 1, 1), None, (0, 0, 1, 1)]),
+    # pitch 15 < 16: every piece spans two or three rows; 315 bytes leave a tail of 11
+    "b_7x5": (3, 7, 5, [(0, 0, 5, 7), (4, 6, 5, 7), None]),
+    # box edges against the frame edges: the four corners, a single column at x = 10, a single row at y = 8
+    "c_corners": (3, 9, 11, [(7, 0, 11, 4), (0, 0, 4, 3), (0, 6, 3, 9)]),
+    "c_lines": (3, 9, 11, [(8, 5, 11, 9), (10, 0, 11, 9), (0, 8, 11, 9)]),
+    # 3663 bytes per frame, pitch 111: the box's first byte lands on every offset within a piece
+    "d_left0": (4, 33, 37, _d_boxes(0)),
+    "d_left4": (4, 33, 37, _d_boxes(1)),
+    "d_left8": (4, 33, 37, _d_boxes(2)),
+    "d_left12": (4, 33, 37, _d_boxes(3)),
+    # 2115 pixels: more than one chunk of the means and no multiple of it, beside a box of width 1
+    "d_47x45": (3, 64, 48, [(0, 10, 47, 55), (5, 3, 6, 43), None]),
+    # the seam-free size of the older tests: the control
+    "e_96x128": (2, 96, 128, [(30, 20, 70, 60), None]),
+}
+
+
+def mover_originals(name):
+    F, H, W, _ = MOVER_CASES[name]
+    rng = np.random.Generator(np.random.PCG64(8000 + sorted(MOVER_CASES).index(name)))
+    return rng.integers(0, 256, size=(F, H, W, 3), dtype=np.uint8)
+
+
+def mover_inputs(name, other_sizes=False):
+    """-> (originals, repaired crops, saved masks, boxes) of a case for the far-face paste: crops and masks of the box's own size (the
+    resize is then a copy and the paste sees arbitrary mask bytes), the mask's first row forced to 0 and its last to 255;
+    `other_sizes`: crops and masks of sizes unlike their boxes"""
+    F, H, W, boxes = MOVER_CASES[name]
+    seed = 8100 + 10 * sorted(MOVER_CASES).index(name)
+    repaired, masks = [], []
+    for f, box in enumerate(boxes):
+        if box is None:
+            continue
+        w, h = box[2] - box[0], box[3] - box[1]
+        cw, ch = (w + 3 + f, max(1, h - 2)) if other_sizes else (w, h)
+        repaired.append(random_image(seed + f, ch, cw))
+        m = random_image(seed + 5 + f, ch, cw, 0, 1, 256)
+        if ch > 1:
+            m[0], m[-1] = 0, 255
+        masks.append(m)
+    return mover_originals(name), repaired, masks, boxes
+
+
+def first_difference(got, want):
+    """(number of differing bytes, the first differing (frame, y, x, c) or None) of two [F, H, W, 3] batches"""
+    diff = np.argwhere(np.asarray(got) != np.asarray(want))
+    return len(diff), (tuple(int(v) for v in diff[0]) if len(diff) else None)
+
+
+def piece_hits(box, W, r):
+    """`pil_piece_hits` / `ff_piece_hits` restated: may bytes r .. r + 15 of a frame touch the (left, top, right, bottom) box?"""
+    left, top, right, bottom = box
+    pitch = W * 3
+    y0, y1 = r // pitch, (r + 15) // pitch
+    if y1 < top or y0 >= bottom:
+        return False
+    if y0 != y1:
+        return True
+    xs, xe = (r - y0 * pitch) // 3, (r + 15 - y0 * pitch) // 3
+    return xe >= left and xs < right
+
+
+def classify_pieces(name):
+    """One record per 16-byte piece of the flat batch of a case, as the movers see it when the batch lies on the 16-byte grid:
+    seams (frame boundaries inside the piece), tail (the batch ends inside it), walk (the kernel goes byte by byte: seams or tail),
+    rows (1 or more, of an in-frame piece, from y0 to y1), asked (the `*_piece_hits` answer for an in-frame piece whose frame has a box, else None),
+    touches (a byte of the piece lies in a box), first_col / last_col (a byte in the box's first / last column),
+    ends_before / starts_after (a one-row piece inside the box's rows that ends one byte before the box / starts one byte after it),
+    later_box_touched / later_frame_without_box (of a seam-crossing piece: a frame it enters has a box it touches / has no box)."""
+    F, H, W, boxes = MOVER_CASES[name]
+    pitch, fb = W * 3, H * W * 3
+    total = F * fb
+    b = np.arange(total)
+    f, r = b // fb, b % fb
+    y, x = r // pitch, (r % pitch) // 3
+    has = np.array([bx is not None for bx in boxes])
+    geo = np.array([bx if bx is not None else (0, 0, 0, 0) for bx in boxes])
+    left, top, right, bottom = (geo[f, i] for i in range(4))
+    inside = has[f] & (x >= left) & (x < right) & (y >= top) & (y < bottom)
+    out = []
+    for b0 in range(0, total, PIECE):
+        sl = slice(b0, min(b0 + PIECE, total))
+        f0, r0 = int(f[b0]), int(r[b0])
+        rec = dict(case=name, b0=b0, frame=f0, seams=int(f[sl][-1]) - f0, tail=b0 + PIECE > total)
+        rec["walk"] = r0 + PIECE > fb
+        rec["touches"] = bool(inside[sl].any())
+        rec["first_col"] = bool((inside[sl] & (x[sl] == left[sl])).any())
+        rec["last_col"] = bool((inside[sl] & (x[sl] == right[sl] - 1)).any())
+        rec["rows"] = rec["asked"] = None
+        rec["ends_before"] = rec["starts_after"] = False
+        if not rec["walk"]:
+            y0, y1 = r0 // pitch, (r0 + 15) // pitch
+            rec["rows"], rec["y0"], rec["y1"] = y1 - y0 + 1, y0, y1
+            if boxes[f0] is not None:
+                bl, bt, br, bb = boxes[f0]
+                rec["asked"] = piece_hits(boxes[f0], W, r0)
+                if y0 == y1 and bt <= y0 < bb:
+                    rec["ends_before"] = r0 + 15 - y0 * pitch == bl * 3 - 1
+                    rec["starts_after"] = r0 - y0 * pitch == br * 3
+        later = sorted(set(int(v) for v in f[sl]) - {f0})
+        rec["later_box_touched"] = any(bool((inside[sl] & (f[sl] == g)).any()) for g in later)
+        rec["later_frame_without_box"] = any(boxes[g] is None for g in later)
+        out.append(rec)
+    return out
+
+
+def box_first_byte_offsets(name):
+    """where in its 16-byte piece the first byte of every box of a case lies"""
+    F, H, W, boxes = MOVER_CASES[name]
+    return [(f * H * W * 3 + (bx[1] * W + bx[0]) * 3) % PIECE for f, bx in enumerate(boxes) if bx is not None]
