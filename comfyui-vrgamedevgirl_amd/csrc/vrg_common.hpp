@@ -18,13 +18,34 @@
     defined(VRG_NO_FLAT_STENCIL) || defined(VRG_APPLY_FORCE_GENERAL) || defined(VRG_ABLATE_GATHER) || defined(VRG_NO_DIVT_FASTPATH))
 #error "comfyui-vrgamedevgirl_amd: tuning / ablation macros are not build options of the product sources (see the note above this line)"
 #endif
-#include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/vrgdg_hip.h"
 #include "../../include/vrgdg_hip_debug.h"
 #include "vrg_pixel_math.hpp"
 
+namespace vrg {
+
+// Host and device, and all that a plain host compiler sees of this header (tests/host_math).
+// Records name their data by offset into buffers that kernels read through raw pointers: do `need` elements from `offset` lie inside `size`?
+VRG_HD bool span_fits(int64_t offset, int64_t need, int64_t size) { return offset >= 0 && offset <= size && need <= size - offset; }
+
+// blockIdx.y / blockIdx.z take one record each, at most this many per launch
+constexpr int64_t LAUNCH_RECORDS = 32768;
+
+// launch(first, count) for consecutive chunks of [0, n), each at most LAUNCH_RECORDS long; stops at the first return that is not VRG_OK
+template <class Launch>
+inline int launch_chunks(int64_t n, Launch launch) {
+    for (int64_t first = 0; first < n; first += LAUNCH_RECORDS) {
+        const int rc = launch(first, n - first < LAUNCH_RECORDS ? n - first : LAUNCH_RECORDS);
+        if (rc != VRG_OK) return rc;
+    }
+    return VRG_OK;
+}
+
+}  // namespace vrg
+
+#if defined(__HIPCC__) || defined(__HIP__)
 namespace vrg {
 
 // one RGB pixel; 4-byte aligned so that a load/store is a single global_*_dwordx3
@@ -180,4 +201,22 @@ inline LutParams make_lut(const float* cells, int n, const float dmin[3], const 
         if (e_ != hipSuccess) return VRG_ERR_LAUNCH;         \
     } while (0)
 
+// The sums of a 256-thread workgroup: acc[i] of every lane -> the 64-lane xor butterfly -> part[wave][i], synchronised.  Every thread of the
+// workgroup must call it; the caller adds the four wave partials of a sum in the order it needs.
+template <class T, int N>
+__device__ __forceinline__ void block_sum_4waves(T (&acc)[N], T (&part)[4][N]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) acc[i] += __shfl_xor(acc[i], off, 64);
+    }
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) part[wave][i] = acc[i];
+    }
+    __syncthreads();
+}
+
 }  // namespace vrg
+#endif

@@ -96,18 +96,8 @@ __global__ __launch_bounds__(256) void k_composite_stats(const float* __restrict
         }
     }
     // every thread of the workgroup arrives here
-#pragma unroll
-    for (int i = 0; i < CP_PART_DOUBLES; ++i) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) acc[i] += __shfl_xor(acc[i], off, 64);
-    }
     __shared__ double part[4][CP_PART_DOUBLES];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 0) {
-#pragma unroll
-        for (int i = 0; i < CP_PART_DOUBLES; ++i) part[wave][i] = acc[i];
-    }
-    __syncthreads();
+    block_sum_4waves(acc, part);
     if (threadIdx.x < CP_PART_DOUBLES) {
         const int t = threadIdx.x;
         scratch[(m * parts + blockIdx.x) * CP_PART_DOUBLES + t] = ((part[0][t] + part[1][t]) + part[2][t]) + part[3][t];
@@ -148,8 +138,8 @@ struct WarpSrc {
 
 // a record is used only if its image lies inside the byte buffer
 __device__ __forceinline__ bool wp_rec_ok(const vrg_warp_desc& r, int64_t n_bytes) {
-    if (!r.set || r.src_w < 1 || r.src_h < 1 || r.src_offset < 0) return false;
-    return r.src_offset <= n_bytes && (int64_t)r.src_w * r.src_h * 3 <= n_bytes - r.src_offset;
+    if (!r.set || r.src_w < 1 || r.src_h < 1) return false;
+    return span_fits(r.src_offset, (int64_t)r.src_w * r.src_h * 3, n_bytes);
 }
 
 // the warped byte pixel (x, y) of a record's image; the weights of the phase are read row by row, eight int16 = 16 bytes at a time
@@ -272,7 +262,7 @@ __global__ __launch_bounds__(256) void k_face_bytes(const float* __restrict__ cr
     const vrg_composite_desc d = desc[f];
     if (!cp_desc_ok(d, g, false) || d.paste_w != d.box_w || d.paste_h != d.box_h) return;
     const int64_t n = (int64_t)d.box_w * d.box_h;
-    if (off > capacity || n * 3 > capacity - off) return;
+    if (!span_fits(off, n * 3, capacity)) return;
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= n) return;
     const int32_t dy = (int32_t)((uint32_t)p / (uint32_t)d.box_w), dx = (int32_t)p - dy * d.box_w;
@@ -350,8 +340,7 @@ extern "C" int vrg_composite_stats_f32(const float* crops, const float* original
     if (!composite_geom_supported(g, user_mask) || max_box_pixels > 0x7fffffff) return VRG_ERR_UNSUPPORTED;
     const int64_t parts = composite_parts(max_box_pixels);
     hipStream_t st = (hipStream_t)stream;
-    for (int64_t m0 = 0; m0 < n_match; m0 += 32768) {
-        const int64_t nm = n_match - m0 < 32768 ? n_match - m0 : 32768;
+    return launch_chunks(n_match, [&](int64_t m0, int64_t nm) {
         double* sc = (double*)scratch + m0 * parts * CP_PART_DOUBLES;
         hipLaunchKernelGGL(k_composite_stats, dim3((uint32_t)parts, (uint32_t)nm), dim3(256), 0, st, crops, originals, user_mask, desc,
                            match_frames + m0, g, (int32_t)parts, sc);
@@ -359,8 +348,8 @@ extern "C" int vrg_composite_stats_f32(const float* crops, const float* original
         hipLaunchKernelGGL(k_composite_stats_final, dim3((uint32_t)nm), dim3(64), 0, st, desc, match_frames + m0, g, (int32_t)parts,
                            (const double*)sc, (uint32_t*)stats);
         VRG_CHECK_LAUNCH();
-    }
-    return VRG_OK;
+        return VRG_OK;
+    });
 }
 
 extern "C" int vrg_composite_apply_f32(const float* crops, const float* originals, const float* user_mask, const vrg_composite_desc* desc,
@@ -447,13 +436,12 @@ extern "C" int vrg_face_bytes_u8(const float* crops, const float* originals, con
     if (max_box_pixels == 0) return VRG_OK;
     const int64_t parts = (max_box_pixels + 255) / 256;
     hipStream_t st = (hipStream_t)stream;
-    for (int64_t f0 = 0; f0 < frames; f0 += 32768) {
-        const int64_t nf = frames - f0 < 32768 ? frames - f0 : 32768;
+    return launch_chunks(frames, [&](int64_t f0, int64_t nf) {
         hipLaunchKernelGGL(k_face_bytes, dim3((uint32_t)parts, (uint32_t)nf), dim3(256), 0, st, crops, originals, desc, offsets, generated, source,
                            capacity, g, f0);
         VRG_CHECK_LAUNCH();
-    }
-    return VRG_OK;
+        return VRG_OK;
+    });
 }
 
 extern "C" int vrg_warp_affine_u8(const uint8_t* in, int64_t in_bytes, uint8_t* out, const vrg_warp_desc* rec, const void* table, int64_t frames,
@@ -466,10 +454,9 @@ extern "C" int vrg_warp_affine_u8(const uint8_t* in, int64_t in_bytes, uint8_t* 
     const int64_t parts = (px + 255) / 256;
     hipStream_t st = (hipStream_t)stream;
     const WarpSrc ws{rec, in, in_bytes, (const int16_t*)table};
-    for (int64_t f0 = 0; f0 < frames; f0 += 32768) {
-        const int64_t nf = frames - f0 < 32768 ? frames - f0 : 32768;
+    return launch_chunks(frames, [&](int64_t f0, int64_t nf) {
         hipLaunchKernelGGL(k_warp_affine, dim3((uint32_t)parts, (uint32_t)nf), dim3(256), 0, st, ws, out, out_h, out_w, f0);
         VRG_CHECK_LAUNCH();
-    }
-    return VRG_OK;
+        return VRG_OK;
+    });
 }

@@ -115,11 +115,10 @@ extern "C" int vrg_crop_resize_f32(const float* in, int64_t in_floats, float* ou
     const uint32_t bx = (uint32_t)((size_w + 255) / 256), by = (uint32_t)((size_h + CROP_ROWS - 1) / CROP_ROWS);
     if (by > 65535u) return VRG_ERR_UNSUPPORTED;
     const int64_t out_fe = (int64_t)size_h * size_w * 3;
-    for (int64_t f0 = 0; f0 < n_out; f0 += 32768) {
-        const int64_t nf = n_out - f0 < 32768 ? n_out - f0 : 32768;
+    return launch_chunks(n_out, [&](int64_t f0, int64_t nf) {
         hipLaunchKernelGGL(k_crop_resize, dim3(bx, by, (uint32_t)nf), dim3(256), 0, (hipStream_t)stream, in, in_floats, out + f0 * out_fe,
                            desc + f0, size_h, size_w);
         VRG_CHECK_LAUNCH();
-    }
-    return VRG_OK;
+        return VRG_OK;
+    });
 }

@@ -15,14 +15,13 @@
 //   k_ff_finish          the means and shifts of every frame, on the device: the host never waits.
 //   k_ff_composite       finalize, second half: ONE pass over the output batch as a flat run of bytes, 16 per thread.  A piece that
 //                        misses the box (nearly all of a frame) is one 16-byte non-temporal load and store; a piece that touches it is
-//                        rebuilt byte by byte in registers; pieces that cross a frame boundary or are not 16-byte aligned go byte by byte.
-#include "vrg_common.hpp"
+//                        rebuilt byte by byte in registers; pieces that cross a frame boundary or are not 16-byte aligned go byte by byte
+//                        (move_bytes of csrc/vrg_byte_mover.hpp, shared with the far-face paste).
+#include "vrg_byte_mover.hpp"
 #include "vrg_facefix_math.hpp"
 #include "vrg_lanczos_math.hpp"
 
 namespace vrg {
-
-typedef uint32_t ffu4 __attribute__((ext_vector_type(4)));
 
 struct FfGeom {
     int64_t frames, enhanced_frames, mask_floats, n_taps, capacity;
@@ -33,7 +32,7 @@ __device__ __forceinline__ bool ff_box_ok(const vrg_ff_box_desc& d, int64_t in_f
                                           int32_t out_w) {
     if (d.frame < 0 || d.frame >= in_frames || d.left < 0 || d.top < 0 || d.box_w < 1 || d.box_h < 1) return false;
     if ((int64_t)d.left + d.box_w > W || (int64_t)d.top + d.box_h > H) return false;
-    return d.taps_offset >= 0 && d.taps_offset <= n_taps && (int64_t)out_w + out_h <= n_taps - d.taps_offset;
+    return span_fits(d.taps_offset, (int64_t)out_w + out_h, n_taps);
 }
 
 // the record of the composite: `resized` = the checks of the passes that read the resize source as well
@@ -41,11 +40,10 @@ __device__ __forceinline__ bool ff_desc_ok(const vrg_ff_desc& d, const FfGeom& g
     if (!(d.strength > 0.0f) || d.left < 0 || d.top < 0 || d.box_w < 1 || d.box_h < 1) return false;
     if ((int64_t)d.left + d.box_w > g.W || (int64_t)d.top + d.box_h > g.H) return false;
     const int64_t px = (int64_t)d.box_w * d.box_h;
-    if (d.mask_offset < 0 || d.mask_offset > g.mask_floats || px > g.mask_floats - d.mask_offset) return false;
-    if (d.bytes_offset < 0 || d.bytes_offset > g.capacity || px * 3 > g.capacity - d.bytes_offset) return false;
+    if (!span_fits(d.mask_offset, px, g.mask_floats) || !span_fits(d.bytes_offset, px * 3, g.capacity)) return false;
     if (!resized) return true;
     if (d.enhanced_index < 0 || d.enhanced_index >= g.enhanced_frames) return false;
-    return d.taps_offset >= 0 && d.taps_offset <= g.n_taps && (int64_t)d.box_w + d.box_h <= g.n_taps - d.taps_offset;
+    return span_fits(d.taps_offset, (int64_t)d.box_w + d.box_h, g.n_taps);
 }
 
 __global__ __launch_bounds__(256) void k_lanczos4_boxes(const uint8_t* __restrict__ in, int64_t in_frames, int32_t H, int32_t W,
@@ -67,8 +65,8 @@ __global__ __launch_bounds__(256) void k_lanczos4_boxes(const uint8_t* __restric
 }
 
 __device__ __forceinline__ bool ff_mask_ok(const vrg_ff_mask_desc& d, int64_t n_spans, int64_t mask_floats) {
-    if (d.width < 1 || d.height < 1 || d.span_offset < 0 || d.span_offset > n_spans || d.height > n_spans - d.span_offset) return false;
-    return d.mask_offset >= 0 && d.mask_offset <= mask_floats && (int64_t)d.width * d.height <= mask_floats - d.mask_offset;
+    if (d.width < 1 || d.height < 1) return false;
+    return span_fits(d.span_offset, d.height, n_spans) && span_fits(d.mask_offset, (int64_t)d.width * d.height, mask_floats);
 }
 
 // n == 0: the 0 / 1 spans go straight to `plane` (the masks); otherwise the horizontal plane (the scratch)
@@ -128,18 +126,8 @@ __global__ __launch_bounds__(256) void k_ff_resize_stats(const uint8_t* __restri
         }
     }
     if (!measure) return;                                                // uniform
-#pragma unroll
-    for (int i = 0; i < FF_STAT_SUMS; ++i) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) acc[i] += (uint32_t)__shfl_xor((int)acc[i], off, 64);
-    }
     __shared__ uint32_t part[4][FF_STAT_SUMS];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 0) {
-#pragma unroll
-        for (int i = 0; i < FF_STAT_SUMS; ++i) part[wave][i] = acc[i];
-    }
-    __syncthreads();
+    block_sum_4waves(acc, part);
     if (threadIdx.x < FF_STAT_SUMS) {
         const int t = threadIdx.x;
         const uint32_t s = part[0][t] + part[1][t] + part[2][t] + part[3][t];             // <= 256 * 255
@@ -161,93 +149,45 @@ __global__ __launch_bounds__(256) void k_ff_finish(unsigned long long* __restric
     rec[9] = (unsigned long long)f32_bits(shift[2]);
 }
 
-struct FfFrame {
-    vrg_ff_desc d;
-    bool ok, matched;
-    float shift[3];
+// the composite as a policy of move_bytes: the face bytes of the resize scratch, shifted, blended under the float mask and the strength
+struct FfMover {
+    typedef MoverFrame<vrg_ff_desc> Frame;
+    const float* __restrict__ masks;
+    const vrg_ff_desc* __restrict__ desc;
+    const uint8_t* __restrict__ bytes;
+    const unsigned long long* __restrict__ stats;
+    FfGeom g;
+
+    __device__ __forceinline__ void load(Frame& fr, int64_t f) const {
+        fr.d = desc[f];
+        fr.ok = ff_desc_ok(fr.d, g, false);
+        fr.matched = false;
+        fr.shift[0] = fr.shift[1] = fr.shift[2] = 0.0f;
+    }
+    __device__ __forceinline__ void load_stats(Frame& fr, int64_t f) const {
+        const unsigned long long* rec = stats + f * FF_STATS_WORDS;
+        fr.matched = rec[7] != 0ull;
+        const unsigned long long a = rec[8], b = rec[9];
+        fr.shift[0] = f32_from_bits((uint32_t)a);
+        fr.shift[1] = f32_from_bits((uint32_t)(a >> 32));
+        fr.shift[2] = f32_from_bits((uint32_t)b);
+    }
+    __device__ __forceinline__ ByteBox box(const Frame& fr) const { return ByteBox{fr.d.left, fr.d.top, fr.d.box_w, fr.d.box_h, g.W}; }
+    __device__ __forceinline__ uint8_t byte(const Frame& fr, int32_t r, uint8_t v) const {
+        int64_t i;
+        int32_t c;
+        if (!byte_in_box(box(fr), r, i, c)) return v;
+        uint8_t face = bytes[fr.d.bytes_offset + i * 3 + c];
+        if (fr.matched) face = ff_shift_byte(face, fr.shift[c]);
+        return ff_blend_byte(v, face, masks[fr.d.mask_offset + i], fr.d.strength);
+    }
 };
-
-__device__ __forceinline__ void ff_frame(FfFrame& fr, const vrg_ff_desc* __restrict__ desc, const unsigned long long* __restrict__ stats,
-                                         const FfGeom& g, int64_t f) {
-    fr.d = desc[f];
-    fr.ok = ff_desc_ok(fr.d, g, false);
-    fr.matched = false;
-    fr.shift[0] = fr.shift[1] = fr.shift[2] = 0.0f;
-}
-
-// the shifts are read only by a thread that touches the box
-__device__ __forceinline__ void ff_frame_stats(FfFrame& fr, const unsigned long long* __restrict__ stats, int64_t f) {
-    const unsigned long long* rec = stats + f * FF_STATS_WORDS;
-    fr.matched = rec[7] != 0ull;
-    const unsigned long long a = rec[8], b = rec[9];
-    fr.shift[0] = f32_from_bits((uint32_t)a);
-    fr.shift[1] = f32_from_bits((uint32_t)(a >> 32));
-    fr.shift[2] = f32_from_bits((uint32_t)b);
-}
-
-// byte r of the frame (value v in the original): what the composite leaves there
-__device__ __forceinline__ uint8_t ff_byte(const FfFrame& fr, const FfGeom& g, const float* __restrict__ masks, const uint8_t* __restrict__ bytes,
-                                           int32_t r, uint8_t v) {
-    const int32_t px = (int32_t)((uint32_t)r / 3u), c = r - px * 3;
-    const int32_t y = (int32_t)((uint32_t)px / (uint32_t)g.W), x = px - y * g.W;
-    const int32_t dx = x - fr.d.left, dy = y - fr.d.top;
-    if (dx < 0 || dx >= fr.d.box_w || dy < 0 || dy >= fr.d.box_h) return v;
-    const int64_t i = (int64_t)dy * fr.d.box_w + dx;
-    uint8_t face = bytes[fr.d.bytes_offset + i * 3 + c];
-    if (fr.matched) face = ff_shift_byte(face, fr.shift[c]);
-    return ff_blend_byte(v, face, masks[fr.d.mask_offset + i], fr.d.strength);
-}
-
-// do bytes r .. r + 15 of a frame touch the box?  (a piece spans at most two rows unless the frame is narrower than six pixels)
-__device__ __forceinline__ bool ff_piece_hits(const vrg_ff_desc& d, int32_t W, int32_t r) {
-    const int32_t pitch = W * 3;
-    const int32_t y0 = (int32_t)((uint32_t)r / (uint32_t)pitch), y1 = (int32_t)((uint32_t)(r + 15) / (uint32_t)pitch);
-    if (y1 < d.top || y0 >= d.top + d.box_h) return false;
-    if (y0 != y1) return true;
-    const int32_t xs = (r - y0 * pitch) / 3, xe = (r + 15 - y0 * pitch) / 3;
-    return xe >= d.left && xs < d.left + d.box_w;
-}
 
 __global__ __launch_bounds__(256) void k_ff_composite(const uint8_t* __restrict__ originals, const float* __restrict__ masks,
                                                        const vrg_ff_desc* __restrict__ desc, const uint8_t* __restrict__ bytes,
                                                        const unsigned long long* __restrict__ stats, uint8_t* __restrict__ out, FfGeom g,
                                                        int64_t frame_bytes, int64_t total, int32_t aligned) {
-    const int64_t b0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 16;
-    if (b0 >= total) return;
-    int64_t f = b0 / frame_bytes;
-    int32_t r = (int32_t)(b0 - f * frame_bytes);
-    FfFrame fr;
-    ff_frame(fr, desc, stats, g, f);
-    const uint8_t* src = originals + b0;
-    uint8_t* dst = out + b0;
-    if (aligned && (int64_t)r + 16 <= frame_bytes) {
-        ffu4 q = __builtin_nontemporal_load(reinterpret_cast<const ffu4*>(src));
-        if (fr.ok && ff_piece_hits(fr.d, g.W, r)) {
-            ff_frame_stats(fr, stats, f);
-            uint32_t w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-            for (int k = 0; k < 16; ++k) {
-                const uint8_t v = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
-                const uint8_t n = ff_byte(fr, g, masks, bytes, r + k, v);
-                w[k >> 2] = (w[k >> 2] & ~(0xffu << (8 * (k & 3)))) | ((uint32_t)n << (8 * (k & 3)));
-            }
-            q = ffu4{w[0], w[1], w[2], w[3]};
-        }
-        __builtin_nontemporal_store(q, reinterpret_cast<ffu4*>(dst));
-        return;
-    }
-    if (fr.ok) ff_frame_stats(fr, stats, f);
-    for (int k = 0; k < 16 && b0 + k < total; ++k) {
-        if (r >= frame_bytes) {
-            r = 0;
-            ++f;
-            ff_frame(fr, desc, stats, g, f);
-            if (fr.ok) ff_frame_stats(fr, stats, f);
-        }
-        const uint8_t v = src[k];
-        dst[k] = fr.ok ? ff_byte(fr, g, masks, bytes, r, v) : v;
-        ++r;
-    }
+    move_bytes(FfMover{masks, desc, bytes, stats, g}, originals, out, frame_bytes, total, aligned);
 }
 
 }  // namespace vrg
@@ -277,13 +217,12 @@ int vrg_lanczos4_boxes_u8(const uint8_t* in, int64_t in_frames, int32_t height, 
     if ((int64_t)out_h * out_w * 3 > 0x7fffffffll || (int64_t)height * width * 3 > 0x7fffffffll) return VRG_ERR_UNSUPPORTED;
     const uint32_t parts = (uint32_t)(((int64_t)out_h * out_w + 255) / 256);
     const int64_t out_fe = (int64_t)out_h * out_w * 3;
-    for (int64_t f0 = 0; f0 < n_out; f0 += 32768) {
-        const int64_t nf = n_out - f0 < 32768 ? n_out - f0 : 32768;
+    return launch_chunks(n_out, [&](int64_t f0, int64_t nf) {
         hipLaunchKernelGGL(k_lanczos4_boxes, dim3(parts, (uint32_t)nf), dim3(256), 0, (hipStream_t)stream, in, in_frames, height, width,
                            out + f0 * out_fe, desc + f0, out_h, out_w, reinterpret_cast<const LzTap*>(taps), n_taps);
         VRG_CHECK_LAUNCH();
-    }
-    return VRG_OK;
+        return VRG_OK;
+    });
 }
 
 int vrg_ff_masks_f32(const int32_t* spans, int64_t n_spans, const float* coeffs, int32_t n_coeffs, const vrg_ff_mask_desc* desc,
@@ -295,8 +234,7 @@ int vrg_ff_masks_f32(const int32_t* spans, int64_t n_spans, const float* coeffs,
     if (max_mask_pixels == 0) return VRG_OK;
     const uint32_t parts = (uint32_t)((max_mask_pixels + 255) / 256);
     hipStream_t st = (hipStream_t)stream;
-    for (int64_t m0 = 0; m0 < n_masks; m0 += 32768) {
-        const int64_t nm = n_masks - m0 < 32768 ? n_masks - m0 : 32768;
+    return launch_chunks(n_masks, [&](int64_t m0, int64_t nm) {
         hipLaunchKernelGGL(k_ff_mask_h, dim3(parts, (uint32_t)nm), dim3(256), 0, st, reinterpret_cast<const FfSpan*>(spans), n_spans, coeffs,
                            n_coeffs, desc + m0, n_coeffs ? scratch : masks, mask_floats);
         VRG_CHECK_LAUNCH();
@@ -305,8 +243,8 @@ int vrg_ff_masks_f32(const int32_t* spans, int64_t n_spans, const float* coeffs,
                                (const float*)scratch, masks, mask_floats);
             VRG_CHECK_LAUNCH();
         }
-    }
-    return VRG_OK;
+        return VRG_OK;
+    });
 }
 
 int vrg_ff_resize_stats_u8(const uint8_t* originals, const uint8_t* enhanced, const float* masks, int64_t mask_floats,
@@ -326,12 +264,13 @@ int vrg_ff_resize_stats_u8(const uint8_t* originals, const uint8_t* enhanced, co
     const int32_t measure = color_match > 0.0f ? 1 : 0;
     if (max_box_pixels > 0) {
         const uint32_t parts = (uint32_t)((max_box_pixels + 255) / 256);
-        for (int64_t f0 = 0; f0 < frames; f0 += 32768) {
-            const int64_t nf = frames - f0 < 32768 ? frames - f0 : 32768;
+        const int rc = launch_chunks(frames, [&](int64_t f0, int64_t nf) {
             hipLaunchKernelGGL(k_ff_resize_stats, dim3(parts, (uint32_t)nf), dim3(256), 0, st, originals, enhanced, masks, desc,
                                reinterpret_cast<const LzTap*>(taps), bytes, (unsigned long long*)stats, g, f0, measure);
             VRG_CHECK_LAUNCH();
-        }
+            return VRG_OK;
+        });
+        if (rc != VRG_OK) return rc;
     }
     if (measure) {
         hipLaunchKernelGGL(k_ff_finish, dim3((uint32_t)((frames + 255) / 256)), dim3(256), 0, st, (unsigned long long*)stats, frames, color_match);
@@ -347,15 +286,12 @@ int vrg_ff_composite_u8(const uint8_t* originals, const float* masks, int64_t ma
     if (!originals || !masks || !desc || !bytes || !stats || (reinterpret_cast<uintptr_t>(stats) & 7u) != 0 || !out || out == originals ||
         out == bytes || height < 1 || width < 1)
         return VRG_ERR_BAD_ARG;
-    const int64_t frame_bytes = (int64_t)height * width * 3;
-    if (frame_bytes > 0x7fffffffll - 16) return VRG_ERR_UNSUPPORTED;
-    const int64_t total = frames * frame_bytes;
-    const int64_t blocks = ((total + 15) / 16 + 255) / 256;
-    if (blocks > 0x7fffffffll) return VRG_ERR_UNSUPPORTED;
+    ByteMoverLaunch l;
+    const int rc = byte_mover_launch(originals, out, frames, height, width, l);
+    if (rc != VRG_OK) return rc;
     const FfGeom g{frames, 0, mask_floats, 0, capacity, height, width, 0, 0};
-    const int32_t aligned = ((reinterpret_cast<uintptr_t>(originals) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0 ? 1 : 0;
-    hipLaunchKernelGGL(k_ff_composite, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, originals, masks, desc, bytes,
-                       (const unsigned long long*)stats, out, g, frame_bytes, total, aligned);
+    hipLaunchKernelGGL(k_ff_composite, dim3(l.blocks), dim3(256), 0, (hipStream_t)stream, originals, masks, desc, bytes,
+                       (const unsigned long long*)stats, out, g, l.frame_bytes, l.total, l.aligned);
     VRG_CHECK_LAUNCH();
     return VRG_OK;
 }

@@ -14,31 +14,26 @@
 //                         applied at once unless a sum would reach its next power of two -- then one lane per sum walks the chunk with
 //                         real fp32 adds.
 //   k_pil_paste           ONE pass over the output batch as a flat run of bytes, 16 per thread: a piece that misses the box is one 16-byte
-//                         non-temporal load and store, a piece that touches it is rebuilt byte by byte (the mover of vrg_ff_composite_u8).
-#include "vrg_common.hpp"
+//                         non-temporal load and store, a piece that touches it is rebuilt byte by byte (move_bytes of
+//                         csrc/vrg_byte_mover.hpp, shared with vrg_ff_composite_u8).
+#include "vrg_byte_mover.hpp"
 #include "vrg_pil_math.hpp"
 
 namespace vrg {
-
-typedef uint32_t pfu4 __attribute__((ext_vector_type(4)));
 
 struct PilResizeGeom {
     int64_t src_bytes, table_ints, tmp_bytes, dst_bytes;
     int32_t C;
 };
 
-__device__ __forceinline__ bool pil_span_fits(int64_t offset, int64_t need, int64_t size) {
-    return offset >= 0 && offset <= size && need <= size - offset;
-}
-
 __device__ __forceinline__ bool pil_resize_ok(const vrg_pil_resize_desc& d, const PilResizeGeom& g) {
     if (d.in_w < 1 || d.in_h < 1 || d.out_w < 1 || d.out_h < 1) return false;
     const bool hp = d.in_w != d.out_w, vp = d.in_h != d.out_h;
-    if (!pil_span_fits(d.src_offset, (int64_t)d.in_h * d.in_w * g.C, g.src_bytes)) return false;
-    if (!pil_span_fits(d.dst_offset, (int64_t)d.out_h * d.out_w * g.C, g.dst_bytes)) return false;
-    if (hp && (d.h_ksize < 1 || !pil_span_fits(d.h_table, (int64_t)d.out_w * (2 + d.h_ksize), g.table_ints))) return false;
-    if (vp && (d.v_ksize < 1 || !pil_span_fits(d.v_table, (int64_t)d.out_h * (2 + d.v_ksize), g.table_ints))) return false;
-    if (hp && vp && !pil_span_fits(d.tmp_offset, (int64_t)d.in_h * d.out_w * g.C, g.tmp_bytes)) return false;
+    if (!span_fits(d.src_offset, (int64_t)d.in_h * d.in_w * g.C, g.src_bytes)) return false;
+    if (!span_fits(d.dst_offset, (int64_t)d.out_h * d.out_w * g.C, g.dst_bytes)) return false;
+    if (hp && (d.h_ksize < 1 || !span_fits(d.h_table, (int64_t)d.out_w * (2 + d.h_ksize), g.table_ints))) return false;
+    if (vp && (d.v_ksize < 1 || !span_fits(d.v_table, (int64_t)d.out_h * (2 + d.v_ksize), g.table_ints))) return false;
+    if (hp && vp && !span_fits(d.tmp_offset, (int64_t)d.in_h * d.out_w * g.C, g.tmp_bytes)) return false;
     return true;
 }
 
@@ -106,7 +101,7 @@ __global__ __launch_bounds__(256) void k_pil_resize_v(const uint8_t* __restrict_
 // ---------------------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool pil_mask_ok(const vrg_pil_mask_desc& d, int64_t n_spans, int64_t mask_bytes) {
     if (d.width < 1 || d.height < 1 || d.width > PIL_MAX_LINE || d.height > PIL_MAX_LINE || d.radius > (1 << 20)) return false;
-    return pil_span_fits(d.span_offset, d.height, n_spans) && pil_span_fits(d.mask_offset, (int64_t)d.width * d.height, mask_bytes);
+    return span_fits(d.span_offset, d.height, n_spans) && span_fits(d.mask_offset, (int64_t)d.width * d.height, mask_bytes);
 }
 
 struct PilLineLds {
@@ -194,7 +189,7 @@ __device__ __forceinline__ bool pil_box_ok(const vrg_pil_box_desc& d, const PilG
     if (d.left < 0 || d.top < 0 || d.box_w < 1 || d.box_h < 1) return false;
     if ((int64_t)d.left + d.box_w > g.W || (int64_t)d.top + d.box_h > g.H) return false;
     const int64_t px = (int64_t)d.box_w * d.box_h;
-    return pil_span_fits(d.mask_offset, px, g.mask_bytes) && pil_span_fits(d.rep_offset, px * 3, g.rep_bytes);
+    return span_fits(d.mask_offset, px, g.mask_bytes) && span_fits(d.rep_offset, px * 3, g.rep_bytes);
 }
 
 __global__ __launch_bounds__(256) void k_np_means(const uint8_t* __restrict__ originals, const uint8_t* __restrict__ repaired,
@@ -281,90 +276,43 @@ __global__ __launch_bounds__(256) void k_np_means(const uint8_t* __restrict__ or
     }
 }
 
-struct PilFrame {
-    vrg_pil_box_desc d;
-    bool ok, matched;
-    float shift[3];
+// the paste as a policy of move_bytes: the repaired bytes, shifted where the box asked for the colour match, pasted under the byte mask
+struct PilMover {
+    typedef MoverFrame<vrg_pil_box_desc> Frame;
+    const uint8_t* __restrict__ repaired;
+    const uint8_t* __restrict__ masks;
+    const vrg_pil_box_desc* __restrict__ desc;
+    const uint32_t* __restrict__ stats;
+    PilGeom g;
+
+    __device__ __forceinline__ void load(Frame& fr, int64_t f) const {
+        fr.d = desc[f];
+        fr.ok = pil_box_ok(fr.d, g);
+        fr.matched = false;
+        fr.shift[0] = fr.shift[1] = fr.shift[2] = 0.0f;
+    }
+    __device__ __forceinline__ void load_stats(Frame& fr, int64_t f) const {
+        if (!fr.d.color_match) return;
+        const uint32_t* rec = stats + f * PIL_STATS_WORDS;
+        fr.matched = rec[10] != 0u;
+        for (int c = 0; c < 3; ++c) fr.shift[c] = f32_from_bits(rec[7 + c]);
+    }
+    __device__ __forceinline__ ByteBox box(const Frame& fr) const { return ByteBox{fr.d.left, fr.d.top, fr.d.box_w, fr.d.box_h, g.W}; }
+    __device__ __forceinline__ uint8_t byte(const Frame& fr, int32_t r, uint8_t v) const {
+        int64_t i;
+        int32_t c;
+        if (!byte_in_box(box(fr), r, i, c)) return v;
+        uint8_t face = repaired[fr.d.rep_offset + i * 3 + c];
+        if (fr.matched) face = pil_shift_byte(face, fr.shift[c]);
+        return pil_paste_byte(v, face, masks[fr.d.mask_offset + i]);
+    }
 };
-
-__device__ __forceinline__ void pil_frame(PilFrame& fr, const vrg_pil_box_desc* __restrict__ desc, const PilGeom& g, int64_t f) {
-    fr.d = desc[f];
-    fr.ok = pil_box_ok(fr.d, g);
-    fr.matched = false;
-    fr.shift[0] = fr.shift[1] = fr.shift[2] = 0.0f;
-}
-
-// the shifts are read only by a thread that touches the box
-__device__ __forceinline__ void pil_frame_stats(PilFrame& fr, const uint32_t* __restrict__ stats, int64_t f) {
-    if (!fr.d.color_match) return;
-    const uint32_t* rec = stats + f * PIL_STATS_WORDS;
-    fr.matched = rec[10] != 0u;
-    for (int c = 0; c < 3; ++c) fr.shift[c] = f32_from_bits(rec[7 + c]);
-}
-
-// byte r of the frame (value v in the original): what the paste leaves there
-__device__ __forceinline__ uint8_t pil_byte(const PilFrame& fr, const PilGeom& g, const uint8_t* __restrict__ masks,
-                                            const uint8_t* __restrict__ repaired, int32_t r, uint8_t v) {
-    const int32_t px = (int32_t)((uint32_t)r / 3u), c = r - px * 3;
-    const int32_t y = (int32_t)((uint32_t)px / (uint32_t)g.W), x = px - y * g.W;
-    const int32_t dx = x - fr.d.left, dy = y - fr.d.top;
-    if (dx < 0 || dx >= fr.d.box_w || dy < 0 || dy >= fr.d.box_h) return v;
-    const int64_t i = (int64_t)dy * fr.d.box_w + dx;
-    uint8_t face = repaired[fr.d.rep_offset + i * 3 + c];
-    if (fr.matched) face = pil_shift_byte(face, fr.shift[c]);
-    return pil_paste_byte(v, face, masks[fr.d.mask_offset + i]);
-}
-
-// do bytes r .. r + 15 of a frame touch the box?
-__device__ __forceinline__ bool pil_piece_hits(const vrg_pil_box_desc& d, int32_t W, int32_t r) {
-    const int32_t pitch = W * 3;
-    const int32_t y0 = (int32_t)((uint32_t)r / (uint32_t)pitch), y1 = (int32_t)((uint32_t)(r + 15) / (uint32_t)pitch);
-    if (y1 < d.top || y0 >= d.top + d.box_h) return false;
-    if (y0 != y1) return true;
-    const int32_t xs = (r - y0 * pitch) / 3, xe = (r + 15 - y0 * pitch) / 3;
-    return xe >= d.left && xs < d.left + d.box_w;
-}
 
 __global__ __launch_bounds__(256) void k_pil_paste(const uint8_t* __restrict__ originals, const uint8_t* __restrict__ repaired,
                                                     const uint8_t* __restrict__ masks, const vrg_pil_box_desc* __restrict__ desc,
                                                     const uint32_t* __restrict__ stats, uint8_t* __restrict__ out, PilGeom g,
                                                     int64_t frame_bytes, int64_t total, int32_t aligned) {
-    const int64_t b0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 16;
-    if (b0 >= total) return;
-    int64_t f = b0 / frame_bytes;
-    int32_t r = (int32_t)(b0 - f * frame_bytes);
-    PilFrame fr;
-    pil_frame(fr, desc, g, f);
-    const uint8_t* src = originals + b0;
-    uint8_t* dst = out + b0;
-    if (aligned && (int64_t)r + 16 <= frame_bytes) {
-        pfu4 q = __builtin_nontemporal_load(reinterpret_cast<const pfu4*>(src));
-        if (fr.ok && pil_piece_hits(fr.d, g.W, r)) {
-            pil_frame_stats(fr, stats, f);
-            uint32_t w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-            for (int k = 0; k < 16; ++k) {
-                const uint8_t v = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
-                const uint8_t nv = pil_byte(fr, g, masks, repaired, r + k, v);
-                w[k >> 2] = (w[k >> 2] & ~(0xffu << (8 * (k & 3)))) | ((uint32_t)nv << (8 * (k & 3)));
-            }
-            q = pfu4{w[0], w[1], w[2], w[3]};
-        }
-        __builtin_nontemporal_store(q, reinterpret_cast<pfu4*>(dst));
-        return;
-    }
-    if (fr.ok) pil_frame_stats(fr, stats, f);
-    for (int k = 0; k < 16 && b0 + k < total; ++k) {
-        if (r >= frame_bytes) {
-            r = 0;
-            ++f;
-            pil_frame(fr, desc, g, f);
-            if (fr.ok) pil_frame_stats(fr, stats, f);
-        }
-        const uint8_t v = src[k];
-        dst[k] = fr.ok ? pil_byte(fr, g, masks, repaired, r, v) : v;
-        ++r;
-    }
+    move_bytes(PilMover{repaired, masks, desc, stats, g}, originals, out, frame_bytes, total, aligned);
 }
 
 }  // namespace vrg
@@ -402,8 +350,8 @@ int vrg_pil_resize_u8(const uint8_t* src, int64_t src_bytes, const vrg_pil_resiz
     const uint32_t parts = (uint32_t)((max_pixels + 255) / 256);
     const PilResizeGeom g{src_bytes, table_ints, tmp_bytes, dst_bytes, channels};
     hipStream_t st = (hipStream_t)stream;
-    for (int64_t i0 = 0; i0 < n_out; i0 += 32768) {
-        const uint32_t ni = (uint32_t)(n_out - i0 < 32768 ? n_out - i0 : 32768);
+    return launch_chunks(n_out, [&](int64_t i0, int64_t count) {
+        const uint32_t ni = (uint32_t)count;
         if (channels == 3) {
             hipLaunchKernelGGL(k_pil_resize_h<3>, dim3(parts, ni), dim3(256), 0, st, src, desc + i0, tables, tmp, dst, g);
             VRG_CHECK_LAUNCH();
@@ -414,8 +362,8 @@ int vrg_pil_resize_u8(const uint8_t* src, int64_t src_bytes, const vrg_pil_resiz
             hipLaunchKernelGGL(k_pil_resize_v<1>, dim3(parts, ni), dim3(256), 0, st, src, desc + i0, tables, (const uint8_t*)tmp, dst, g);
         }
         VRG_CHECK_LAUNCH();
-    }
-    return VRG_OK;
+        return VRG_OK;
+    });
 }
 
 int vrg_pil_mask_u8(const int32_t* spans, int64_t n_spans, const vrg_pil_mask_desc* desc, int64_t n_masks, int32_t max_width,
@@ -425,8 +373,8 @@ int vrg_pil_mask_u8(const int32_t* spans, int64_t n_spans, const vrg_pil_mask_de
     if (!spans || !desc || !masks || !scratch || scratch == masks) return VRG_ERR_BAD_ARG;
     if (max_width > PIL_MAX_LINE || max_height > PIL_MAX_LINE) return VRG_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
-    for (int64_t m0 = 0; m0 < n_masks; m0 += 32768) {
-        const uint32_t nm = (uint32_t)(n_masks - m0 < 32768 ? n_masks - m0 : 32768);
+    return launch_chunks(n_masks, [&](int64_t m0, int64_t count) {
+        const uint32_t nm = (uint32_t)count;
         // a record without a blur (radius < 0) writes its spans to `masks` in the first launch and sits out the second
         hipLaunchKernelGGL(k_pil_mask_h, dim3((uint32_t)max_height, nm), dim3(256), 0, st, reinterpret_cast<const PilSpan*>(spans), n_spans,
                            desc + m0, scratch, masks, mask_bytes);
@@ -434,8 +382,8 @@ int vrg_pil_mask_u8(const int32_t* spans, int64_t n_spans, const vrg_pil_mask_de
         hipLaunchKernelGGL(k_pil_mask_v, dim3((uint32_t)max_width, nm), dim3(256), 0, st, n_spans, desc + m0, (const uint8_t*)scratch, masks,
                            mask_bytes);
         VRG_CHECK_LAUNCH();
-    }
-    return VRG_OK;
+        return VRG_OK;
+    });
 }
 
 int vrg_np_masked_means_f32(const uint8_t* originals, const uint8_t* repaired, int64_t rep_bytes, const uint8_t* masks, int64_t mask_bytes,
@@ -460,15 +408,12 @@ int vrg_pil_paste_u8(const uint8_t* originals, const uint8_t* repaired, int64_t 
     if (!originals || !repaired || !masks || !desc || !stats || (reinterpret_cast<uintptr_t>(stats) & 3u) != 0 || !out || out == originals ||
         out == repaired || height < 1 || width < 1)
         return VRG_ERR_BAD_ARG;
-    const int64_t frame_bytes = (int64_t)height * width * 3;
-    if (frame_bytes > 0x7fffffffll - 16) return VRG_ERR_UNSUPPORTED;
-    const int64_t total = frames * frame_bytes;
-    const int64_t blocks = ((total + 15) / 16 + 255) / 256;
-    if (blocks > 0x7fffffffll) return VRG_ERR_UNSUPPORTED;
+    ByteMoverLaunch l;
+    const int rc = byte_mover_launch(originals, out, frames, height, width, l);
+    if (rc != VRG_OK) return rc;
     const PilGeom g{frames, rep_bytes, mask_bytes, height, width};
-    const int32_t aligned = ((reinterpret_cast<uintptr_t>(originals) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0 ? 1 : 0;
-    hipLaunchKernelGGL(k_pil_paste, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, originals, repaired, masks, desc, stats, out, g,
-                       frame_bytes, total, aligned);
+    hipLaunchKernelGGL(k_pil_paste, dim3(l.blocks), dim3(256), 0, (hipStream_t)stream, originals, repaired, masks, desc, stats, out, g,
+                       l.frame_bytes, l.total, l.aligned);
     VRG_CHECK_LAUNCH();
     return VRG_OK;
 }

@@ -169,8 +169,7 @@ static int launch_resize(const float* in, float* out, int64_t frames, const Resi
     const uint32_t bx = (uint32_t)((g.out_w + 255) / 256), by = (uint32_t)((g.out_h + RS_ROWS - 1) / RS_ROWS);
     if (by > 65535u) return VRG_ERR_UNSUPPORTED;
     const int64_t in_fe = (int64_t)g.in_h * g.in_w * g.in_c, out_fe = (int64_t)g.out_h * g.out_w * oc;
-    for (int64_t f0 = 0; f0 < frames; f0 += 32768) {
-        const int64_t nf = frames - f0 < 32768 ? frames - f0 : 32768;
+    return launch_chunks(frames, [&](int64_t f0, int64_t nf) {
         const dim3 grid(bx, by, (uint32_t)nf);
         const float* src = in + f0 * in_fe;
         float* dst = out + f0 * out_fe;
@@ -179,8 +178,8 @@ static int launch_resize(const float* in, float* out, int64_t frames, const Resi
         if (method == RS_BICUBIC) hipLaunchKernelGGL((k_resize_bicubic<RESTORE>), grid, dim3(256), 0, st, src, dst, g, rk);
         else hipLaunchKernelGGL((k_resize_direct<RESTORE>), grid, dim3(256), 0, st, src, dst, g, method, rk);
         VRG_CHECK_LAUNCH();
-    }
-    return VRG_OK;
+        return VRG_OK;
+    });
 }
 
 }  // namespace vrg

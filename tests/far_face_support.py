@@ -301,6 +301,7 @@ def bits(x):
 U8P = np.ctypeslib.ndpointer(dtype=np.uint8, flags="C_CONTIGUOUS")
 I32P = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
 U32P = np.ctypeslib.ndpointer(dtype=np.uint32, flags="C_CONTIGUOUS")
+I64P = np.ctypeslib.ndpointer(dtype=np.int64, flags="C_CONTIGUOUS")
 
 
 def build_host_lib(directory):
@@ -317,6 +318,12 @@ def build_host_lib(directory):
     lib.hm_pil_mask.argtypes = [I32P, C.c_int32, C.c_int32, C.c_int32, U8P]
     lib.hm_pil_means.argtypes = [U8P, U8P, U8P, C.c_int64, C.c_int32, U32P]
     lib.hm_pil_paste.argtypes = [U8P, U8P, U8P, C.c_int64, C.c_int32, U32P, U8P]
+    lib.hm_byte_piece_hits.restype = C.c_int32
+    lib.hm_byte_piece_hits.argtypes = [C.c_int32] * 6
+    lib.hm_span_fits.restype = C.c_int32
+    lib.hm_span_fits.argtypes = [C.c_int64] * 3
+    lib.hm_launch_chunks.restype = C.c_int32
+    lib.hm_launch_chunks.argtypes = [C.c_int64, C.c_int32, C.c_int32, I64P, C.c_int32, I32P]
     return lib
 
 
@@ -452,7 +459,8 @@ def first_difference(got, want):
 
 
 def piece_hits(box, W, r):
-    """`pil_piece_hits` / `ff_piece_hits` restated: may bytes r .. r + 15 of a frame touch the (left, top, right, bottom) box?"""
+    """`byte_piece_hits` of csrc/vrg_byte_mover.hpp restated (tests/test_byte_movers_host.py holds the two equal): may bytes r .. r + 15 of a
+    frame touch the (left, top, right, bottom) box?"""
     left, top, right, bottom = box
     pitch = W * 3
     y0, y1 = r // pitch, (r + 15) // pitch
@@ -467,7 +475,7 @@ def piece_hits(box, W, r):
 def classify_pieces(name):
     """One record per 16-byte piece of the flat batch of a case, as the movers see it when the batch lies on the 16-byte grid:
     seams (frame boundaries inside the piece), tail (the batch ends inside it), walk (the kernel goes byte by byte: seams or tail),
-    rows (1 or more, of an in-frame piece, from y0 to y1), asked (the `*_piece_hits` answer for an in-frame piece whose frame has a box, else None),
+    rows (1 or more, of an in-frame piece, from y0 to y1), asked (the `byte_piece_hits` answer for an in-frame piece whose frame has a box, else None),
     touches (a byte of the piece lies in a box), first_col / last_col (a byte in the box's first / last column),
     ends_before / starts_after (a one-row piece inside the box's rows that ends one byte before the box / starts one byte after it),
     later_box_touched / later_frame_without_box (of a seam-crossing piece: a frame it enters has a box it touches / has no box)."""

@@ -2,7 +2,8 @@
 // byte passes of the resize, the box parameters and the six box passes of the mask through prefix sums, numpy's sequential fp32 means in
 // the plain form (np_walk) and in the parallel form the kernel uses (maps of NP_RUN pixels, reduced pairwise per NP_CHUNK), and the paste.
 // Checked against installed Pillow / numpy and the restatement of tests/far_face_support.py (tests/test_far_face_host.py), byte for byte.
-// Never loaded by the package.
+// Also the host side of csrc/vrg_byte_mover.hpp and csrc/vrg_common.hpp: the movers' hit test, span_fits and the chunked launcher
+// (tests/test_byte_movers_host.py).  Never loaded by the package.
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
@@ -12,6 +13,7 @@
 #define VRG_HW_COS_REV(x) cosf((x) * 6.28318530717958647692f)
 #define VRG_HW_EXP2(x) exp2f(x)
 #define VRG_HW_RCP(x) (1.0f / (x))
+#include "vrg_byte_mover.hpp"
 #include "vrg_pil_math.hpp"
 
 using namespace vrg;
@@ -141,6 +143,24 @@ void hm_pil_paste(const uint8_t* original, const uint8_t* repaired, const uint8_
             if (matched) r = pil_shift_byte(r, f32_from_bits(stats[7 + c]));
             out[p * 3 + c] = pil_paste_byte(original[p * 3 + c], r, mask[p]);
         }
+}
+
+int32_t hm_byte_piece_hits(int32_t left, int32_t top, int32_t box_w, int32_t box_h, int32_t W, int32_t r) {
+    return byte_piece_hits(left, top, box_w, box_h, W, r) ? 1 : 0;
+}
+
+int32_t hm_span_fits(int64_t offset, int64_t need, int64_t size) { return span_fits(offset, need, size) ? 1 : 0; }
+
+// launch_chunks over n records with a callable that records (first, count) and returns `code` on its call number `fail_call` (from 1; 0 = never)
+int32_t hm_launch_chunks(int64_t n, int32_t fail_call, int32_t code, int64_t* chunks, int32_t capacity, int32_t* calls) {
+    *calls = 0;
+    return launch_chunks(n, [&](int64_t first, int64_t count) {
+        if (*calls < capacity) {
+            chunks[2 * *calls] = first;
+            chunks[2 * *calls + 1] = count;
+        }
+        return ++*calls == fail_call ? code : (int)VRG_OK;
+    });
 }
 
 }  // extern "C"

@@ -1,7 +1,9 @@
 """The byte movers without a GPU (k_pil_paste of csrc/vrg_farface.hip, k_ff_composite of csrc/vrg_facefix.hip): the geometry sweep of
 far_face_support.MOVER_CASES really reaches every class of 16-byte piece the kernels distinguish (a model of the geometry, no kernel is
 called), and the expected bytes of the sweep are right at these sizes: every box through the headers compiled for the host, the numpy
-restatements and, where Pillow is importable, Image.paste itself.  tests/test_gpu_byte_movers.py runs the sweep on the GPU."""
+restatements and, where Pillow is importable, Image.paste itself.  The host side of what the two kernels share (csrc/vrg_byte_mover.hpp,
+csrc/vrg_common.hpp) is called here through tests/host_math/farface_check.cpp: the hit test against far_face_support.piece_hits, span_fits
+at its edges and the chunked launcher.  tests/test_gpu_byte_movers.py runs the sweep on the GPU."""
 import numpy as np
 import pytest
 
@@ -151,3 +153,62 @@ def test_builder_boxes_on_the_host_equal_the_restatement(hm_ff, name):
             target = np.ascontiguousarray(originals[f, top:bottom, left:right])
             got, _ = FS.host_composite(hm_ff, target, resized, mask, cm, strengths[f])
             assert np.array_equal(got, want[f, top:bottom, left:right]), (name, f, feather, cm)
+
+
+def test_the_header_hit_test_equals_the_restatement(hm_far, pieces):
+    """byte_piece_hits of csrc/vrg_byte_mover.hpp == far_face_support.piece_hits: every r that classify_pieces visits in a frame with a box,
+    and every r in 0 .. frame_bytes - 16 of the cases of at most 37 pixels of width"""
+    asked = narrow = 0
+    for p in pieces:
+        if p["asked"] is None:
+            continue
+        F, H, W, boxes = S.MOVER_CASES[p["case"]]
+        left, top, right, bottom = boxes[p["frame"]]
+        r = p["b0"] - p["frame"] * H * W * 3
+        assert bool(hm_far.hm_byte_piece_hits(left, top, right - left, bottom - top, W, r)) == p["asked"] == \
+            S.piece_hits(boxes[p["frame"]], W, r), (p["case"], p["frame"], r)
+        asked += 1
+    for name, (F, H, W, boxes) in S.MOVER_CASES.items():
+        if W > 37:
+            continue
+        for box in boxes:
+            if box is None:
+                continue
+            left, top, right, bottom = box
+            for r in range(H * W * 3 - 15):
+                assert bool(hm_far.hm_byte_piece_hits(left, top, right - left, bottom - top, W, r)) == S.piece_hits(box, W, r), (name, box, r)
+                narrow += 1
+    assert asked and narrow
+    assert sorted(n for n, c in S.MOVER_CASES.items() if c[2] <= 37) == ["a_1x1", "b_7x5", "c_corners", "c_lines", "d_left0", "d_left12", "d_left4", "d_left8"]
+
+
+@pytest.mark.parametrize("n", [0, 1, 32767, 32768, 32769, 32771])
+def test_the_launch_chunks_tile_the_records_in_order(hm_far, n):
+    chunks, calls = np.full((4, 2), -1, np.int64), np.zeros(1, np.int32)
+    assert hm_far.hm_launch_chunks(n, 0, 0, chunks, 4, calls) == 0
+    k = int(calls[0])
+    assert k == (n + 32767) // 32768
+    first, count = chunks[:k, 0], chunks[:k, 1]
+    assert (count >= 1).all() and (count <= 32768).all() and int(count.sum()) == n
+    assert list(first) == [int(count[:i].sum()) for i in range(k)]             # each chunk starts where the one before it ended, from 0
+
+
+def test_a_failing_launch_stops_the_chunks_and_returns_its_code(hm_far):
+    chunks, calls = np.full((4, 2), -1, np.int64), np.zeros(1, np.int32)
+    assert hm_far.hm_launch_chunks(3 * 32768 + 5, 2, 3, chunks, 4, calls) == 3
+    assert int(calls[0]) == 2 and chunks.tolist() == [[0, 32768], [32768, 32768], [-1, -1], [-1, -1]]
+    assert hm_far.hm_launch_chunks(32771, 1, 2, chunks, 4, calls) == 2 and int(calls[0]) == 1
+
+
+def test_span_fits_at_its_edges(hm_far):
+    fits = lambda offset, need, size: bool(hm_far.hm_span_fits(offset, need, size))
+    size = 100
+    assert fits(size, 0, size)                                                  # an empty span may start at the end
+    assert not fits(size, 1, size)
+    for offset in (0, 1, 37, size - 1):
+        assert fits(offset, size - offset, size) and not fits(offset, size - offset + 1, size)
+    assert not fits(-1, 0, size) and not fits(-1, 1, size)
+    assert not fits(size + 1, 0, size) and not fits(size + 1, -1, size)         # past the end, whatever the need
+    assert fits(0, 0, 0) and not fits(0, 1, 0)
+    big = 2 ** 63 - 1
+    assert fits(0, big, big) and not fits(1, big, big) and not fits(-big, 1, big)
