@@ -220,8 +220,8 @@ static int launch_adjust(const void* in, void* out, float* tmp, int64_t frames, 
     const elem* src = reinterpret_cast<const elem*>(in);
     elem* dst = reinterpret_cast<elem*>(out);
     const int tx = (width + AT_W - 1) / AT_W, ty = (height + AT_H - 1) / AT_H;
-    for (int64_t f0 = 0; f0 < frames; f0 += 32768) {
-        const uint32_t nf = (uint32_t)(frames - f0 < 32768 ? frames - f0 : 32768);
+    return launch_chunks(frames, [&](int64_t f0, int64_t count) {
+        const uint32_t nf = (uint32_t)count;
         const elem* s = src + f0 * ppf;
         elem* o = dst + f0 * ppf;
         px3* mid = both ? reinterpret_cast<px3*>(tmp) + f0 * ppf : nullptr;     // fp32 ring between the two boxes
@@ -241,9 +241,9 @@ static int launch_adjust(const void* in, void* out, float* tmp, int64_t frames, 
             if (both) hipLaunchKernelGGL((k_adjust_box<3, false, true, IoF32, IO>), tg, dim3(256), 0, st, (const px3*)mid, o, height, width, tx, A);
             else hipLaunchKernelGGL((k_adjust_box<3, true, true, IO, IO>), tg, dim3(256), 0, st, s, o, height, width, tx, A);
         }
-        if (hipGetLastError() != hipSuccess) return VRG_ERR_LAUNCH;
-    }
-    return VRG_OK;
+        VRG_CHECK_LAUNCH();
+        return VRG_OK;
+    });
 }
 
 // stand-alone conversions (the enhancer's sharpen -> per-frame-seeded grain order runs on fp32 tensors)

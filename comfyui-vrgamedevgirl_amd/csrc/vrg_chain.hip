@@ -303,8 +303,7 @@ static int launch_stats(const float* in, int64_t frames, int32_t H, int32_t W, c
     const int64_t ppf = (int64_t)H * W;
     const int bpf = stats_blocks_per_frame(ppf);
     double* partials = reinterpret_cast<double*>(scratch);
-    for (int64_t f0 = 0; f0 < frames; f0 += 32768) {
-        const int64_t nf = frames - f0 < 32768 ? frames - f0 : 32768;
+    return launch_chunks(frames, [&](int64_t f0, int64_t nf) {
         ChainK d = D;
         if (STAGES & VRG_STAGE_GRAIN) {
             if (f0 % D.noise.chunk_frames) return VRG_ERR_UNSUPPORTED;
@@ -314,16 +313,15 @@ static int launch_stats(const float* in, int64_t frames, int32_t H, int32_t W, c
         if (!stats) {                   // Lab image only
             hipLaunchKernelGGL((k_lab_partials<STAGES, false>), dim3((uint32_t)bpf, (uint32_t)nf), dim3(256), 0, st, src, (int32_t)ppf, bpf, d,
                                (double*)nullptr, reinterpret_cast<px3*>(lab_out) + f0 * ppf);
-            if (hipGetLastError() != hipSuccess) return VRG_ERR_LAUNCH;
-            continue;
+        } else {
+            hipLaunchKernelGGL((k_lab_partials<STAGES>), dim3((uint32_t)bpf, (uint32_t)nf), dim3(256), 0, st, src, (int32_t)ppf, bpf, d,
+                               partials + f0 * bpf * 6, lab_out ? reinterpret_cast<px3*>(lab_out) + f0 * ppf : nullptr);
+            hipLaunchKernelGGL(k_lab_merge<STAGES>, dim3((uint32_t)nf), dim3(64), 0, st, src, (int32_t)ppf, bpf, d,
+                               partials + f0 * bpf * 6, stats + f0 * 9);
         }
-        hipLaunchKernelGGL((k_lab_partials<STAGES>), dim3((uint32_t)bpf, (uint32_t)nf), dim3(256), 0, st, src, (int32_t)ppf, bpf, d,
-                           partials + f0 * bpf * 6, lab_out ? reinterpret_cast<px3*>(lab_out) + f0 * ppf : nullptr);
-        hipLaunchKernelGGL(k_lab_merge<STAGES>, dim3((uint32_t)nf), dim3(64), 0, st, src, (int32_t)ppf, bpf, d,
-                           partials + f0 * bpf * 6, stats + f0 * 9);
-        if (hipGetLastError() != hipSuccess) return VRG_ERR_LAUNCH;
-    }
-    return VRG_OK;
+        VRG_CHECK_LAUNCH();
+        return VRG_OK;
+    });
 }
 
 // (a function template of its own so that k_chain_pointwise4 is only instantiated for fp32 frames and colour-match chains)

@@ -43,6 +43,18 @@ inline int launch_chunks(int64_t n, Launch launch) {
     return VRG_OK;
 }
 
+// Device copy of vrg_noise_desc plus the per-call geometry the noise mapping needs.
+struct NoiseK {
+    uint64_t seed0, seed_stride, off0, off_stride;
+    int64_t chunk0;
+    int64_t frame_elems;   // H*W*3
+    int32_t chunk_frames;
+    uint32_t G;
+};
+
+VRG_HD uint64_t chunk_seed(const NoiseK& n, int64_t chunk_rel) { return n.seed0 + (uint64_t)(n.chunk0 + chunk_rel) * n.seed_stride; }
+VRG_HD uint64_t chunk_offset(const NoiseK& n, int64_t chunk_rel) { return n.off0 + (uint64_t)(n.chunk0 + chunk_rel) * n.off_stride; }
+
 }  // namespace vrg
 
 #if defined(__HIPCC__) || defined(__HIP__)
@@ -114,18 +126,6 @@ __device__ __forceinline__ void lut_nodes_to_lds(const LutParams& P, f32x4* node
         nodes[i] = v;
     }
 }
-
-// Device copy of vrg_noise_desc plus the per-call geometry the noise mapping needs.
-struct NoiseK {
-    uint64_t seed0, seed_stride, off0, off_stride;
-    int64_t chunk0;
-    int64_t frame_elems;   // H*W*3
-    int32_t chunk_frames;
-    uint32_t G;
-};
-
-VRG_HD uint64_t chunk_seed(const NoiseK& n, int64_t chunk_rel) { return n.seed0 + (uint64_t)(n.chunk0 + chunk_rel) * n.seed_stride; }
-VRG_HD uint64_t chunk_offset(const NoiseK& n, int64_t chunk_rel) { return n.off0 + (uint64_t)(n.chunk0 + chunk_rel) * n.off_stride; }
 
 struct CmK {
     const float* img_ms;   // [frames][3][2]

@@ -2,6 +2,8 @@
 // apply.  gfx950 only.  Every kernel is HBM-streaming: consecutive lanes touch consecutive addresses
 // (12 B/lane pixel records or 16 B/lane element quads), nothing is re-read from HBM.
 #include "vrg_common.hpp"
+#include "vrg_grain_block.hpp"
+#include <type_traits>
 
 namespace vrg {
 
@@ -41,11 +43,9 @@ __global__ __launch_bounds__(256) void k_noise(float* __restrict__ out, NoiseK n
 // {idx + G*(4k+ii)}.  Each element also needs the raw normal of its pixel's green element, which is
 // the element itself or its left/right neighbour: the normals are exchanged through LDS, and the two
 // neighbours outside the block's range (per sibling range) are produced by the general per-element
-// routine on 8 lanes.
+// routine on 8 lanes.  Block decode and noise stage: vrg_grain_block.hpp.
 // ----------------------------------------------------------------------------------------------
 #define VRG_GRAIN_NT 0
-constexpr int GRAIN_IPT = 4;                    // subsequences per thread
-constexpr int GRAIN_N = 256 * GRAIN_IPT;        // subsequences per block
 
 // U8: decoded video frames, uint8 B,G,R per pixel (element li = 3 p + c of the reference's fp32 R,G,B tensor lives in byte
 // 3 p + 2 - c); the / 255 and the * 255-clip-truncate of the frame converters happen at the load and the store.
@@ -56,26 +56,19 @@ __global__ __launch_bounds__(256) void k_grain(const void* __restrict__ in_, voi
     float* out = reinterpret_cast<float*>(out_);
     __shared__ float sn[4][GRAIN_N + 8];
     const uint32_t G = nk.G;
-    const uint32_t blocks_per_group = (G + GRAIN_N - 1) / GRAIN_N;
-    const uint32_t bpc = blocks_per_group * groups_per_chunk;
-    const int64_t chunk = blockIdx.x / bpc;
-    const uint32_t rem = blockIdx.x - (uint32_t)chunk * bpc;
-    const uint32_t k = rem / blocks_per_group;
-    const uint32_t idx_base = (rem - k * blocks_per_group) * GRAIN_N;
-    const uint32_t valid_n = (G - idx_base) < (uint32_t)GRAIN_N ? (G - idx_base) : (uint32_t)GRAIN_N;
+    const GrainBlock gb = grain_block(blockIdx.x, nk, groups_per_chunk);
+    const int64_t chunk = gb.unit;
+    const uint32_t valid_n = gb.valid_n;      // a multiple of 4 whenever G is (G = grid*256)
     const uint32_t t4 = threadIdx.x * GRAIN_IPT;
-    const uint64_t seed = chunk_seed(nk, chunk);
-    const uint64_t off = chunk_offset(nk, chunk);
-    const uint64_t ctr = (off >> 2) + k;
+    const int64_t group_base = (int64_t)4 * G * gb.k + gb.idx_base;   // chunk-local element of (ii=0, first idx)
 
     // the frame data of this thread's four element quads is requested BEFORE the Philox rounds: the ~700 instructions of noise
     // synthesis then run under the HBM latency instead of in front of it (VEC form; the ragged forms load below)
-    const int64_t group_base0 = (int64_t)4 * G * k + idx_base;
     float4 pre[4];
     bool pre_ok[4];
 #pragma unroll
     for (int ii = 0; ii < 4; ++ii) {
-        const int64_t li0 = group_base0 + (int64_t)G * ii + t4;
+        const int64_t li0 = group_base + (int64_t)G * ii + t4;
         pre_ok[ii] = VEC && !U8 && t4 < valid_n && li0 + 3 < chunk_numel;
         if (VEC && !U8) {       // branch-free: lanes with nothing to load re-read the chunk's first quad (the result is not used)
             typedef float v4 __attribute__((ext_vector_type(4)));
@@ -92,31 +85,7 @@ __global__ __launch_bounds__(256) void k_grain(const void* __restrict__ in_, voi
     }
 
     float nz[GRAIN_IPT][4];
-#pragma unroll
-    for (int j = 0; j < GRAIN_IPT; ++j) {
-        const u32x4 r = philox_for(seed, idx_base + t4 + j, ctr);
-        const f32x2 a = box_muller(r.x, r.y);
-        const f32x2 b = box_muller(r.z, r.w);
-        nz[j][0] = a.x; nz[j][1] = a.y; nz[j][2] = b.x; nz[j][3] = b.y;
-    }
-    if (t4 < valid_n) {   // valid_n is a multiple of 4 whenever G is (G = grid*256)
-#pragma unroll
-        for (int ii = 0; ii < 4; ++ii) {
-            float4 v = make_float4(nz[0][ii], nz[1][ii], nz[2][ii], nz[3][ii]);
-            *reinterpret_cast<float4*>(&sn[ii][4 + t4]) = v;
-        }
-    }
-    const int64_t group_base = (int64_t)4 * G * k + idx_base;   // chunk-local element of (ii=0, first idx)
-    if (threadIdx.x < 8) {
-        const int ii = threadIdx.x >> 1;
-        const int right = threadIdx.x & 1;
-        const int64_t li = group_base + (int64_t)G * ii + (right ? (int64_t)valid_n : -1);
-        float v = 0.0f;
-        if (li >= 0 && li < chunk_numel) v = torch_randn_element(seed, off, G, (uint64_t)li);
-        sn[ii][right ? 4 + valid_n : 3] = v;
-    }
-    __syncthreads();
-    if (t4 >= valid_n) return;
+    if (!grain_stage_normals<1>(sn, gb, G, chunk_numel, nz)) return;
 
     const float* cin = in + chunk * chunk_numel;
     float* cout = out + chunk * chunk_numel;
@@ -186,13 +155,31 @@ __global__ __launch_bounds__(256) void k_grain(const void* __restrict__ in_, voi
 // VRG_ERR_UNSUPPORTED and the caller runs the two kernels.  Same arithmetic as both (stencil_value, grain_element): bit-identical.
 // ----------------------------------------------------------------------------------------------
 typedef float sg4 __attribute__((ext_vector_type(4)));
-struct SgRaw { sg4 own[3], halo[3]; };
 
-__device__ __forceinline__ float sg_shr(float old, float v) {    // value of lane-1; lane 0 keeps `old`
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(v), 0x138 /* wave_shr:1 */, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float sg_shl(float old, float v) {    // value of lane+1; lane 63 keeps `old`
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(v), 0x130 /* wave_shl:1 */, 0xf, 0xf, false));
+// the three rows around this thread's vector vb + tid of a frame of H rows of n4 vectors (vb block-uniform), requested in one go
+// (branch-free: lanes that need no halo vector re-read their own, lanes past the frame end read its last row)
+template <class V>
+__device__ __forceinline__ void sg_request(const V* fin, uint32_t vb, int32_t H, int32_t n4, SgRaw<V>& q, uint32_t& v_out, int32_t& y_out,
+                                           int32_t& col_out) {
+    const uint32_t tid = threadIdx.x;
+    const int lane = (int)(tid & 63u);
+    const uint32_t yb = vb / (uint32_t)n4;
+    int32_t col = (int32_t)(vb - yb * (uint32_t)n4 + tid);
+    int32_t y = (int32_t)yb;
+    if (col >= n4) { col -= n4; y += 1; }                              // n4 >= 256: at most one row end inside a block
+    v_out = vb + tid;
+    y = y < H ? y : H - 1;
+    const int32_t yu = y > 0 ? y - 1 : 0, yd = y < H - 1 ? y + 1 : H - 1;
+    const int32_t hc = (lane == 0 && col > 0) ? col - 1 : ((lane == 63 && col + 1 < n4) ? col + 1 : col);
+    const int32_t ys[3] = {yu, y, yd};
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const V* row = fin + (int64_t)ys[r] * n4;
+        q.own[r] = row[col];
+        q.halo[r] = row[hc];
+    }
+    y_out = y;
+    col_out = col;
 }
 
 template <bool ZERO>
@@ -200,91 +187,27 @@ __global__ __launch_bounds__(256) void k_sharpen_grain(const float* __restrict__
                                                         uint32_t groups_per_frame, uint32_t total_blocks, float strength, float I, float S,
                                                         float T) {
     __shared__ float sn[4][GRAIN_N + 8];
-    // workgroup b runs on XCD b % 8: every XCD gets one contiguous run of (frame, call, segment) blocks
-    const uint32_t per_xcd = (total_blocks + 7u) >> 3;
-    const uint32_t b = (blockIdx.x & 7u) * per_xcd + (blockIdx.x >> 3);
-    if ((blockIdx.x >> 3) >= per_xcd || b >= total_blocks) return;
+    uint32_t b;
+    if (!xcd_block(blockIdx.x, total_blocks, b)) return;
     const uint32_t G = nk.G;
-    const uint32_t segs = (G + GRAIN_N - 1) / GRAIN_N;
-    const uint32_t bpf = segs * groups_per_frame;
-    const uint32_t frame = b / bpf;
-    const uint32_t rem = b - frame * bpf;
-    const uint32_t k = rem / segs;
-    const uint32_t idx_base = (rem - k * segs) * GRAIN_N;
-    const uint32_t valid_n = (G - idx_base) < (uint32_t)GRAIN_N ? (G - idx_base) : (uint32_t)GRAIN_N;      // a multiple of 256: whole waves
-    const uint32_t tid = threadIdx.x, t4 = tid * GRAIN_IPT;
-    const int lane = (int)(tid & 63u);
-    const uint64_t seed = chunk_seed(nk, frame);
-    const uint64_t off = chunk_offset(nk, frame);
-    const uint64_t ctr = (off >> 2) + k;
+    const GrainBlock gb = grain_block(b, nk, groups_per_frame);
+    const uint32_t t4 = threadIdx.x * GRAIN_IPT;
     const uint32_t nvec = (uint32_t)H * (uint32_t)n4;                 // float4 vectors per frame (< 2^29)
-    const sg4* fin = reinterpret_cast<const sg4*>(in) + (int64_t)frame * nvec;
-    sg4* fout = reinterpret_cast<sg4*>(out) + (int64_t)frame * nvec;
-    const uint32_t vec0 = (4u * G * k + idx_base) >> 2;               // first vector of sibling run 0 (4 G k < frame elements < 2^31)
+    const sg4* fin = reinterpret_cast<const sg4*>(in) + (int64_t)gb.unit * nvec;
+    sg4* fout = reinterpret_cast<sg4*>(out) + (int64_t)gb.unit * nvec;
+    const uint32_t vec0 = (4u * G * gb.k + gb.idx_base) >> 2;         // first vector of sibling run 0 (4 G k < frame elements < 2^31)
 
-    // the three rows around this thread's vector of sibling run ii, requested in one go (branch-free: lanes that need no halo vector
-    // re-read their own, lanes past the frame end read its last row)
-    auto request = [&](int ii, SgRaw& q, uint32_t& v_out, int32_t& y_out, int32_t& col_out) {
-        const uint32_t vb = vec0 + (G >> 2) * (uint32_t)ii;           // block-uniform
-        const uint32_t yb = vb / (uint32_t)n4;
-        int32_t col = (int32_t)(vb - yb * (uint32_t)n4 + tid);
-        int32_t y = (int32_t)yb;
-        if (col >= n4) { col -= n4; y += 1; }                          // n4 >= 256: at most one row end inside a block
-        v_out = vb + tid;
-        y = y < H ? y : H - 1;
-        const int32_t yu = y > 0 ? y - 1 : 0, yd = y < H - 1 ? y + 1 : H - 1;
-        const int32_t hc = (lane == 0 && col > 0) ? col - 1 : ((lane == 63 && col + 1 < n4) ? col + 1 : col);
-        const int32_t ys[3] = {yu, y, yd};
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            const sg4* row = fin + (int64_t)ys[r] * n4;
-            q.own[r] = row[col];
-            q.halo[r] = row[hc];
-        }
-        y_out = y;
-        col_out = col;
-    };
-
-#define VRG_SG_PIPE 0         /* 1: request run ii + 1's rows before run ii is computed (81 instead of 58 VGPRs); measured equal (6.71 / 6.82 against 6.75 / 6.80 ms per 128 4K frames, profiles/r03_sharpen_grain_fused_issue.log): the kernel does not wait on its loads */
-    SgRaw qq[2];
-    uint32_t vv[2];
-    int32_t yy[2], cc[2];
-    request(0, qq[0], vv[0], yy[0], cc[0]);                           // in flight under the Philox rounds
-
+    SgRaw<sg4> q;
+    uint32_t v;
+    int32_t y, col;
+    sg_request(fin, vec0, H, n4, q, v, y, col);                       // in flight under the Philox rounds
     float nz[GRAIN_IPT][4];
-#pragma unroll
-    for (int j = 0; j < GRAIN_IPT; ++j) {
-        const u32x4 r = philox_for(seed, idx_base + t4 + j, ctr);
-        const f32x2 a = box_muller(r.x, r.y);
-        const f32x2 bb = box_muller(r.z, r.w);
-        nz[j][0] = a.x; nz[j][1] = a.y; nz[j][2] = bb.x; nz[j][3] = bb.y;
-    }
-    if (t4 < valid_n) {
-#pragma unroll
-        for (int ii = 0; ii < 4; ++ii) *reinterpret_cast<float4*>(&sn[ii][4 + t4]) = make_float4(nz[0][ii], nz[1][ii], nz[2][ii], nz[3][ii]);
-    }
-    const int64_t fe = (int64_t)nvec * 4;
-    const int64_t group_base = (int64_t)4 * G * k + idx_base;
-    if (tid < 8) {                                                    // the green normals just outside the block's four runs
-        const int ii = (int)(tid >> 1);
-        const int right = (int)(tid & 1);
-        const int64_t li = group_base + (int64_t)G * ii + (right ? (int64_t)valid_n : -1);
-        float nv = 0.0f;
-        if (li >= 0 && li < fe) nv = torch_randn_element(seed, off, G, (uint64_t)li);
-        sn[ii][right ? 4 + valid_n : 3] = nv;
-    }
-    __syncthreads();
-    if (t4 >= valid_n) return;                                        // whole waves
+    if (!grain_stage_normals<1>(sn, gb, G, (int64_t)nvec * 4, nz)) return;
 
 #pragma unroll
     for (int ii = 0; ii < 4; ++ii) {
-        const int cur = VRG_SG_PIPE ? (ii & 1) : 0;
-        if (!VRG_SG_PIPE && ii > 0) request(ii, qq[0], vv[0], yy[0], cc[0]);
-        if (VRG_SG_PIPE && ii < 3) request(ii + 1, qq[(ii + 1) & 1], vv[(ii + 1) & 1], yy[(ii + 1) & 1], cc[(ii + 1) & 1]);   // clamped: in bounds even past the frame
+        if (ii > 0) sg_request(fin, vec0 + (G >> 2) * (uint32_t)ii, H, n4, q, v, y, col);      // clamped: in bounds even past the frame
         if (vec0 + (G >> 2) * (uint32_t)ii >= nvec) continue;         // block-uniform: this run starts past the frame
-        const SgRaw& q = qq[cur];
-        const uint32_t v = vv[cur];
-        const int32_t y = yy[cur], col = cc[cur];
         const bool first = col == 0, last = col == n4 - 1;
         // wave-uniform: does any lane of this wave sit at a row end / (zero border) on the frame's first or last row?  2 waves in 45 at 4K
         const bool row_end_here = __builtin_amdgcn_ballot_w64(first || last) != 0;
@@ -303,8 +226,8 @@ __global__ __launch_bounds__(256) void k_sharpen_grain(const float* __restrict__
             for (int i = 0; i < 4; ++i) o[r][i] = ow[i];
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
-                pl[r][i] = sg_shr(hw[1 + i], ow[1 + i]);              // floats -3 + i of this vector = the previous vector's tail
-                nr[r][i] = sg_shl(hw[i], ow[i]);                      // floats 4 + i = the next vector's head
+                pl[r][i] = lane_prev_or(hw[1 + i], ow[1 + i]);        // floats -3 + i of this vector = the previous vector's tail
+                nr[r][i] = lane_next_or(hw[i], ow[i]);                // floats 4 + i = the next vector's head
             }
             if (row_end_here) {                                       // row ends: replicate the end pixel, or zero
 #pragma unroll
@@ -318,12 +241,7 @@ __global__ __launch_bounds__(256) void k_sharpen_grain(const float* __restrict__
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
             float p[3][3];
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                p[r][0] = kk >= 3 ? o[r][kk >= 3 ? kk - 3 : 0] : pl[r][kk < 3 ? kk : 0];
-                p[r][1] = o[r][kk];
-                p[r][2] = kk < 1 ? o[r][kk < 1 ? kk + 3 : 0] : nr[r][kk >= 1 ? kk - 1 : 0];
-            }
+            window3(o, pl, nr, kk, p);
             x[kk] = stencil_value(0, p, strength, ZERO ? 1 : 0);
         }
         int c = (int)((4u * v) % 3u);                                 // channel of the vector's first float (frame-local element 4 v)
@@ -352,94 +270,31 @@ __global__ __launch_bounds__(256) void k_sharpen_grain(const float* __restrict__
 // elements per side and run instead of one).  Arithmetic: unit_from_u8, stencil_value, grain_element, u8_from_unit -- the functions
 // the three-kernel route evaluates, in its order: byte-identical to it.
 // ----------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t sg_shr_u(uint32_t old, uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)old, (int)v, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
-}
-__device__ __forceinline__ uint32_t sg_shl_u(uint32_t old, uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)old, (int)v, 0x130 /* wave_shl:1 */, 0xf, 0xf, false);
-}
-struct SgRawU8 { uint32_t own[3], halo[3]; };
-
 template <bool ZERO>
 __global__ __launch_bounds__(256) void k_sharpen_grain_u8(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, NoiseK nk, int32_t H,
                                                            int32_t n4, uint32_t groups_per_frame, uint32_t total_blocks, float strength,
                                                            float I, float S, float T) {
     __shared__ float sn[4][GRAIN_N + 8];                              // [run][4 + element of the run]; halo elements at 2, 3 and 4 + valid_n, 5 + valid_n
-    const uint32_t per_xcd = (total_blocks + 7u) >> 3;
-    const uint32_t b = (blockIdx.x & 7u) * per_xcd + (blockIdx.x >> 3);
-    if ((blockIdx.x >> 3) >= per_xcd || b >= total_blocks) return;
+    uint32_t b;
+    if (!xcd_block(blockIdx.x, total_blocks, b)) return;
     const uint32_t G = nk.G;
-    const uint32_t segs = (G + GRAIN_N - 1) / GRAIN_N;
-    const uint32_t bpf = segs * groups_per_frame;
-    const uint32_t frame = b / bpf;
-    const uint32_t rem = b - frame * bpf;
-    const uint32_t k = rem / segs;
-    const uint32_t idx_base = (rem - k * segs) * GRAIN_N;
-    const uint32_t valid_n = (G - idx_base) < (uint32_t)GRAIN_N ? (G - idx_base) : (uint32_t)GRAIN_N;      // a multiple of 256: whole waves
-    const uint32_t tid = threadIdx.x, t4 = tid * GRAIN_IPT;
-    const int lane = (int)(tid & 63u);
-    const uint64_t seed = chunk_seed(nk, frame);
-    const uint64_t off = chunk_offset(nk, frame);
-    const uint64_t ctr = (off >> 2) + k;
+    const GrainBlock gb = grain_block(b, nk, groups_per_frame);
+    const uint32_t t4 = threadIdx.x * GRAIN_IPT;
     const uint32_t nvec = (uint32_t)H * (uint32_t)n4;                 // dwords per frame
-    const uint32_t* fin = in + (int64_t)frame * nvec;
-    uint32_t* fout = out + (int64_t)frame * nvec;
-    const uint32_t vec0 = (4u * G * k + idx_base) >> 2;
+    const uint32_t* fin = in + (int64_t)gb.unit * nvec;
+    uint32_t* fout = out + (int64_t)gb.unit * nvec;
+    const uint32_t vec0 = (4u * G * gb.k + gb.idx_base) >> 2;
 
-    auto request = [&](int ii, SgRawU8& q, uint32_t& v_out, int32_t& y_out, int32_t& col_out) {
-        const uint32_t vb = vec0 + (G >> 2) * (uint32_t)ii;           // block-uniform
-        const uint32_t yb = vb / (uint32_t)n4;
-        int32_t col = (int32_t)(vb - yb * (uint32_t)n4 + tid);
-        int32_t y = (int32_t)yb;
-        if (col >= n4) { col -= n4; y += 1; }                          // n4 >= 256: at most one row end inside a block
-        v_out = vb + tid;
-        y = y < H ? y : H - 1;
-        const int32_t yu = y > 0 ? y - 1 : 0, yd = y < H - 1 ? y + 1 : H - 1;
-        const int32_t hc = (lane == 0 && col > 0) ? col - 1 : ((lane == 63 && col + 1 < n4) ? col + 1 : col);
-        const int32_t ys[3] = {yu, y, yd};
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            const uint32_t* row = fin + (int64_t)ys[r] * n4;
-            q.own[r] = row[col];
-            q.halo[r] = row[hc];
-        }
-        y_out = y;
-        col_out = col;
-    };
-
-    SgRawU8 q;
+    SgRaw<uint32_t> q;
     uint32_t v;
     int32_t y, col;
-    request(0, q, v, y, col);                                         // in flight under the Philox rounds
-
+    sg_request(fin, vec0, H, n4, q, v, y, col);                       // in flight under the Philox rounds
     float nz[GRAIN_IPT][4];
-#pragma unroll
-    for (int j = 0; j < GRAIN_IPT; ++j) {
-        const u32x4 r = philox_for(seed, idx_base + t4 + j, ctr);
-        const f32x2 a = box_muller(r.x, r.y);
-        const f32x2 bb = box_muller(r.z, r.w);
-        nz[j][0] = a.x; nz[j][1] = a.y; nz[j][2] = bb.x; nz[j][3] = bb.y;
-    }
-    if (t4 < valid_n) {
-#pragma unroll
-        for (int ii = 0; ii < 4; ++ii) *reinterpret_cast<float4*>(&sn[ii][4 + t4]) = make_float4(nz[0][ii], nz[1][ii], nz[2][ii], nz[3][ii]);
-    }
-    const int64_t fe = (int64_t)nvec * 4;
-    const int64_t group_base = (int64_t)4 * G * k + idx_base;
-    if (tid < 16) {                                                   // the two normals on either side of the block's four runs
-        const int ii = (int)(tid >> 2);
-        const int right = (int)((tid >> 1) & 1), d = (int)(tid & 1);
-        const int64_t li = group_base + (int64_t)G * ii + (right ? (int64_t)valid_n + d : -1 - d);
-        float nv = 0.0f;
-        if (li >= 0 && li < fe) nv = torch_randn_element(seed, off, G, (uint64_t)li);
-        sn[ii][right ? 4 + valid_n + d : 3 - d] = nv;
-    }
-    __syncthreads();
-    if (t4 >= valid_n) return;                                        // whole waves
+    if (!grain_stage_normals<2>(sn, gb, G, (int64_t)nvec * 4, nz)) return;
 
 #pragma unroll
     for (int ii = 0; ii < 4; ++ii) {
-        if (ii > 0) request(ii, q, v, y, col);
+        if (ii > 0) sg_request(fin, vec0 + (G >> 2) * (uint32_t)ii, H, n4, q, v, y, col);
         if (vec0 + (G >> 2) * (uint32_t)ii >= nvec) continue;         // block-uniform: this run starts past the frame
         const bool first = col == 0, last = col == n4 - 1;
         const bool row_end_here = __builtin_amdgcn_ballot_w64(first || last) != 0;
@@ -453,14 +308,7 @@ __global__ __launch_bounds__(256) void k_sharpen_grain_u8(const uint32_t* __rest
                 ow = outside ? 0u : ow;
                 hw = outside ? 0u : hw;
             }
-            const uint32_t prev = sg_shr_u(hw, ow), next = sg_shl_u(hw, ow);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) o[r][i] = unit_from_u8((uint8_t)(ow >> (8 * i)));
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                pl[r][i] = unit_from_u8((uint8_t)(prev >> (8 * (1 + i))));   // bytes -3 + i of this dword = the previous dword's tail
-                nr[r][i] = unit_from_u8((uint8_t)(next >> (8 * i)));         // bytes 4 + i = the next dword's head
-            }
+            sg_unpack_row(ow, hw, o[r], pl[r], nr[r]);
             if (row_end_here) {                                       // row ends: replicate the end pixel, or zero
 #pragma unroll
                 for (int i = 0; i < 3; ++i) {
@@ -474,16 +322,8 @@ __global__ __launch_bounds__(256) void k_sharpen_grain_u8(const uint32_t* __rest
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
             float p[3][3];
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                p[r][0] = kk >= 3 ? o[r][kk >= 3 ? kk - 3 : 0] : pl[r][kk < 3 ? kk : 0];
-                p[r][1] = o[r][kk];
-                p[r][2] = kk < 1 ? o[r][kk < 1 ? kk + 3 : 0] : nr[r][kk >= 1 ? kk - 1 : 0];
-            }
-            const float n_own = sn[ii][4 + t4 + kk + 2 - 2 * jj];     // element 3 p + 2 - jj of byte 3 p + jj
-            const float n_green = sn[ii][4 + t4 + kk + 1 - jj];       // element 3 p + 1
-            packed |= (uint32_t)sharpen_grain_byte<true, true>(p, strength, ZERO ? 1 : 0, n_own, n_green, 2 - jj, I, S, T) << (8 * kk);
-            jj = (jj == 2) ? 0 : jj + 1;
+            window3(o, pl, nr, kk, p);
+            packed |= sg_pack_byte(p, sn[ii], 4 + t4, kk, jj, strength, ZERO, I, S, T);
         }
         if (v < nvec) fout[v] = packed;
     }
@@ -512,24 +352,14 @@ __global__ __launch_bounds__(256) void k_sharpen_grain_u8_any(const uint8_t* __r
                                                                int32_t E, uint32_t fe, int64_t total_bytes, uint32_t groups_per_frame,
                                                                uint32_t total_blocks, float strength, float I, float S, float T) {
     __shared__ float sn[4][GRAIN_N + 8];
-    const uint32_t per_xcd = (total_blocks + 7u) >> 3;
-    const uint32_t b = (blockIdx.x & 7u) * per_xcd + (blockIdx.x >> 3);
-    if ((blockIdx.x >> 3) >= per_xcd || b >= total_blocks) return;
+    uint32_t b;
+    if (!xcd_block(blockIdx.x, total_blocks, b)) return;
     const uint32_t G = nk.G;
-    const uint32_t segs = (G + GRAIN_N - 1) / GRAIN_N;
-    const uint32_t bpf = segs * groups_per_frame;
-    const uint32_t frame = b / bpf;
-    const uint32_t rem = b - frame * bpf;
-    const uint32_t k = rem / segs;
-    const uint32_t idx_base = (rem - k * segs) * GRAIN_N;
-    const uint32_t valid_n = (G - idx_base) < (uint32_t)GRAIN_N ? (G - idx_base) : (uint32_t)GRAIN_N;
+    const GrainBlock gb = grain_block(b, nk, groups_per_frame);
     const uint32_t tid = threadIdx.x, t4 = tid * GRAIN_IPT;
     const int lane = (int)(tid & 63u);
-    const uint64_t seed = chunk_seed(nk, frame);
-    const uint64_t off = chunk_offset(nk, frame);
-    const uint64_t ctr = (off >> 2) + k;
-    const int64_t fbase = (int64_t)frame * (int64_t)fe;               // the frame's first byte in the batch
-    const uint32_t a_first = 4u * G * k + idx_base;                    // frame-relative byte (= element) of run 0's first element in this block
+    const int64_t fbase = (int64_t)gb.unit * (int64_t)fe;             // the frame's first byte in the batch
+    const uint32_t a_first = 4u * G * gb.k + gb.idx_base;              // frame-relative byte (= element) of run 0's first element in this block
 
     // bytes [g, g + 4) of the batch; positions outside it read as unspecified values
     auto load4 = [&](int64_t g) -> uint32_t {
@@ -560,37 +390,14 @@ __global__ __launch_bounds__(256) void k_sharpen_grain_u8_any(const uint8_t* __r
 
     Raw q;
     request(0, q);                                                    // in flight under the Philox rounds
-
     float nz[GRAIN_IPT][4];
-#pragma unroll
-    for (int j = 0; j < GRAIN_IPT; ++j) {
-        const u32x4 r = philox_for(seed, idx_base + t4 + j, ctr);
-        const f32x2 a = box_muller(r.x, r.y);
-        const f32x2 bb = box_muller(r.z, r.w);
-        nz[j][0] = a.x; nz[j][1] = a.y; nz[j][2] = bb.x; nz[j][3] = bb.y;
-    }
-    if (t4 < valid_n) {
-#pragma unroll
-        for (int ii = 0; ii < 4; ++ii) *reinterpret_cast<float4*>(&sn[ii][4 + t4]) = make_float4(nz[0][ii], nz[1][ii], nz[2][ii], nz[3][ii]);
-    }
-    const int64_t group_base = (int64_t)4 * G * k + idx_base;
-    if (tid < 16) {                                                   // the two normals on either side of the block's four runs
-        const int ii = (int)(tid >> 2);
-        const int right = (int)((tid >> 1) & 1), d = (int)(tid & 1);
-        const int64_t li = group_base + (int64_t)G * ii + (right ? (int64_t)valid_n + d : -1 - d);
-        float nv = 0.0f;
-        if (li >= 0 && li < (int64_t)fe) nv = torch_randn_element(seed, off, G, (uint64_t)li);
-        sn[ii][right ? 4 + valid_n + d : 3 - d] = nv;
-    }
-    __syncthreads();
-    if (t4 >= valid_n) return;                                        // whole waves
+    if (!grain_stage_normals<2>(sn, gb, G, (int64_t)fe, nz)) return;
 
 #pragma unroll
     for (int ii = 0; ii < 4; ++ii) {
         if (ii > 0) request(ii, q);
         if (a_first + G * (uint32_t)ii >= fe) continue;               // block-uniform: this run starts past the frame
-        // per byte: column (in bytes) and row, and which border rules apply
-        int32_t colk[4], yk[4];
+        // per byte: which border rules apply (from its column in bytes and its row)
         bool lft[4], rgt[4], top[4], bot[4];
         bool any_lr = false, any_tb = false;
 #pragma unroll
@@ -598,7 +405,6 @@ __global__ __launch_bounds__(256) void k_sharpen_grain_u8_any(const uint8_t* __r
             int32_t c = q.c0 + kk, y = q.y0;
             if (c >= E) { c -= E; y += 1; }                            // E >= 3: at most one row end inside c0 + 3
             if (c >= E) { c -= E; y += 1; }                            // (E == 3: two)
-            colk[kk] = c; yk[kk] = y;
             lft[kk] = c < 3; rgt[kk] = c >= E - 3; top[kk] = y == 0; bot[kk] = y >= H - 1;
             any_lr = any_lr || lft[kk] || rgt[kk];
             any_tb = any_tb || top[kk] || bot[kk];
@@ -607,28 +413,13 @@ __global__ __launch_bounds__(256) void k_sharpen_grain_u8_any(const uint8_t* __r
         const bool frame_edge_here = __builtin_amdgcn_ballot_w64(any_tb) != 0;
         float o[3][4], pl[3][3], nr[3][3];
 #pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            const uint32_t ow = q.own[r], hw = q.halo[r];
-            const uint32_t prev = sg_shr_u(hw, ow), next = sg_shl_u(hw, ow);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) o[r][i] = unit_from_u8((uint8_t)(ow >> (8 * i)));
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                pl[r][i] = unit_from_u8((uint8_t)(prev >> (8 * (1 + i))));
-                nr[r][i] = unit_from_u8((uint8_t)(next >> (8 * i)));
-            }
-        }
+        for (int r = 0; r < 3; ++r) sg_unpack_row(q.own[r], q.halo[r], o[r], pl[r], nr[r]);
         int jj = (int)(q.a0 % 3u);                                     // position of the first byte in its pixel: 0 = B, 1 = G, 2 = R
         uint32_t packed = 0;
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
             float p[3][3];
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                p[r][0] = kk >= 3 ? o[r][kk >= 3 ? kk - 3 : 0] : pl[r][kk < 3 ? kk : 0];
-                p[r][1] = o[r][kk];
-                p[r][2] = kk < 1 ? o[r][kk < 1 ? kk + 3 : 0] : nr[r][kk >= 1 ? kk - 1 : 0];
-            }
+            window3(o, pl, nr, kk, p);
             if (row_end_here) {                                       // left / right first ...
 #pragma unroll
                 for (int r = 0; r < 3; ++r) {
@@ -643,10 +434,7 @@ __global__ __launch_bounds__(256) void k_sharpen_grain_u8_any(const uint8_t* __r
                     p[2][j] = bot[kk] ? (ZERO ? 0.0f : p[1][j]) : p[2][j];
                 }
             }
-            const float n_own = sn[ii][4 + t4 + kk + 2 - 2 * jj];     // element 3 p + 2 - jj of byte 3 p + jj
-            const float n_green = sn[ii][4 + t4 + kk + 1 - jj];       // element 3 p + 1
-            packed |= (uint32_t)sharpen_grain_byte<true, true>(p, strength, ZERO ? 1 : 0, n_own, n_green, 2 - jj, I, S, T) << (8 * kk);
-            jj = (jj == 2) ? 0 : jj + 1;
+            packed |= sg_pack_byte(p, sn[ii], 4 + t4, kk, jj, strength, ZERO, I, S, T);
         }
         uint8_t* dst = out + fbase + (int64_t)q.a0;
         if (q.a0 + 4u <= fe) {
@@ -656,7 +444,6 @@ __global__ __launch_bounds__(256) void k_sharpen_grain_u8_any(const uint8_t* __r
             for (int kk = 0; kk < 4; ++kk)
                 if (q.a0 + (uint32_t)kk < fe) dst[kk] = (uint8_t)(packed >> (8 * kk));
         }
-        (void)colk; (void)yk;
     }
 }
 
@@ -820,51 +607,75 @@ __global__ __launch_bounds__(256) void k_colormatch_apply4(const px3* __restrict
 
 using namespace vrg;
 
+// The checks of a noise descriptor and the launch geometry that follows from it.  A unit is one noise chunk (chunk_frames frames of
+// frame_elems elements): `groups` Philox calls cover it, each of them split into blocks of block_n subsequences.  False: not a descriptor.
+struct GrainGeom {
+    NoiseK nk;
+    int64_t numel;                  // elements of a unit
+    uint64_t groups, per_unit;      // calls per unit = ceil(numel / (4 G)), blocks per unit
+};
+static bool grain_geom(const vrg_noise_desc* nd, int64_t frame_elems, uint32_t block_n, GrainGeom& g) {
+    if (!nd || nd->chunk_frames < 1 || nd->grid_threads == 0 || (nd->grid_threads % 256u) != 0) return false;
+    g.nk = make_noise(nd, frame_elems);
+    g.numel = (int64_t)nd->chunk_frames * frame_elems;
+    g.groups = (uint64_t)((g.numel + 4 * (int64_t)g.nk.G - 1) / (4 * (int64_t)g.nk.G));
+    g.per_unit = g.groups * ((g.nk.G + block_n - 1) / block_n);
+    return true;
+}
+
+// The launches of a fused sharpen -> grain entry point (one frame per noise chunk): as many frames per launch as a 32-bit block count takes,
+// launch(first frame, frames, the NoiseK of that frame on, blocks of work, grid blocks = the next multiple of 8 for xcd_block).
+template <class Launch>
+static int sharpen_grain_launch(int64_t frames, const GrainGeom& g, Launch launch) {
+    const int64_t step = (int64_t)(0x7fffffffull / g.per_unit) - 1;   // frames per launch
+    if (step < 1) return VRG_ERR_UNSUPPORTED;
+    for (int64_t f0 = 0; f0 < frames; f0 += step) {
+        const int64_t nf = frames - f0 < step ? frames - f0 : step;
+        NoiseK nk = g.nk;
+        nk.chunk0 += f0;
+        const uint32_t total = (uint32_t)(g.per_unit * (uint64_t)nf);
+        launch(f0, nf, nk, total, ((total + 7u) / 8u) * 8u);
+        VRG_CHECK_LAUNCH();
+    }
+    return VRG_OK;
+}
+
+// f(std::true_type) for the zero border, f(std::false_type) for the replicate border: one dispatch per entry point
+template <class F>
+static int with_border(int32_t border, F f) { return border == VRG_BORDER_ZERO ? f(std::true_type{}) : f(std::false_type{}); }
+
 extern "C" {
 
 int vrg_noise_f32(float* out, int64_t frames, int64_t frame_elems, const vrg_noise_desc* nd, void* stream) {
-    if (!out || !nd || frames < 0 || frame_elems <= 0 || nd->chunk_frames < 1 || nd->grid_threads == 0 ||
-        (nd->grid_threads % 256u) != 0)
-        return VRG_ERR_BAD_ARG;
+    GrainGeom g;
+    if (!out || frames < 0 || frame_elems <= 0 || !grain_geom(nd, frame_elems, 256, g)) return VRG_ERR_BAD_ARG;
     if (frames == 0) return VRG_OK;
     if (frames % nd->chunk_frames != 0) return VRG_ERR_BAD_ARG;
-    const int64_t chunks = frames / nd->chunk_frames;
-    const int64_t numel = (int64_t)nd->chunk_frames * frame_elems;
-    const NoiseK nk = make_noise(nd, frame_elems);
-    const uint64_t groups = (uint64_t)((numel + 4 * (int64_t)nk.G - 1) / (4 * (int64_t)nk.G));
-    const uint64_t blocks = (uint64_t)chunks * groups * ((nk.G + 255u) / 256u);
+    const uint64_t blocks = (uint64_t)(frames / nd->chunk_frames) * g.per_unit;
     if (blocks > 0x7fffffffull) return VRG_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(k_noise, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, out, nk, numel, (uint32_t)groups);
+    hipLaunchKernelGGL(k_noise, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, out, g.nk, g.numel, (uint32_t)g.groups);
     VRG_CHECK_LAUNCH();
     return VRG_OK;
 }
 
 static int launch_grain_any(const void* in, void* out, int64_t frames, int32_t height, int32_t width, float intensity, float sat,
                             float one_minus_sat, const vrg_noise_desc* nd, bool u8, void* stream) {
-    if (!in || !out || !nd || frames < 0 || height <= 0 || width <= 0 || nd->chunk_frames < 1 || nd->grid_threads == 0 ||
-        (nd->grid_threads % 256u) != 0)
-        return VRG_ERR_BAD_ARG;
+    GrainGeom g;
+    if (!in || !out || frames < 0 || height <= 0 || width <= 0 || !grain_geom(nd, (int64_t)height * width * 3, GRAIN_N, g)) return VRG_ERR_BAD_ARG;
     if (frames == 0) return VRG_OK;
     if (frames % nd->chunk_frames != 0) return VRG_ERR_BAD_ARG;
-    const int64_t frame_elems = (int64_t)height * width * 3;
-    const int64_t chunks = frames / nd->chunk_frames;
-    const int64_t numel = (int64_t)nd->chunk_frames * frame_elems;
-    if (numel > 0x7fffffffll) return VRG_ERR_UNSUPPORTED;   // torch itself splits randn above INT32 indexing
-    const NoiseK nk = make_noise(nd, frame_elems);
-    const uint64_t groups = (uint64_t)((numel + 4 * (int64_t)nk.G - 1) / (4 * (int64_t)nk.G));
-    const uint64_t blocks = (uint64_t)chunks * groups * ((nk.G + GRAIN_N - 1) / GRAIN_N);
+    if (g.numel > 0x7fffffffll) return VRG_ERR_UNSUPPORTED;   // torch itself splits randn above INT32 indexing
+    const uint64_t blocks = (uint64_t)(frames / nd->chunk_frames) * g.per_unit;
     if (blocks > 0x7fffffffull) return VRG_ERR_UNSUPPORTED;
     // float4 path needs every chunk base and G*ii offsets 16-byte aligned
-    const bool vec = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) % 16 == 0) && (numel % 4 == 0);
-    if (u8)
-        hipLaunchKernelGGL((k_grain<false, true>), dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, in, out, nk, numel,
-                           (uint32_t)groups, intensity, sat, one_minus_sat);
-    else if (vec)
-        hipLaunchKernelGGL((k_grain<true, false>), dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, in, out, nk, numel,
-                           (uint32_t)groups, intensity, sat, one_minus_sat);
-    else
-        hipLaunchKernelGGL((k_grain<false, false>), dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, in, out, nk, numel,
-                           (uint32_t)groups, intensity, sat, one_minus_sat);
+    const bool vec = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) % 16 == 0) && (g.numel % 4 == 0);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, in, out, g.nk, g.numel, (uint32_t)g.groups, intensity,
+                           sat, one_minus_sat);
+    };
+    if (u8) launch(k_grain<false, true>);
+    else if (vec) launch(k_grain<true, false>);
+    else launch(k_grain<false, false>);
     VRG_CHECK_LAUNCH();
     return VRG_OK;
 }
@@ -876,89 +687,52 @@ int vrg_grain_f32(const float* in, float* out, int64_t frames, int32_t height, i
 
 int vrg_sharpen_grain_f32(const float* in, float* out, int64_t frames, int32_t height, int32_t width, float strength, int32_t border,
                           float intensity, float sat, float one_minus_sat, const vrg_noise_desc* nd, void* stream) {
-    if (!in || !out || in == out || !nd || frames < 0 || height <= 0 || width <= 0 || border < 0 || border > 1 || nd->chunk_frames < 1 ||
-        nd->grid_threads == 0 || (nd->grid_threads % 256u) != 0)
+    const int64_t frame_elems = (int64_t)height * width * 3;
+    GrainGeom g;
+    if (!in || !out || in == out || frames < 0 || height <= 0 || width <= 0 || border < 0 || border > 1 || !grain_geom(nd, frame_elems, GRAIN_N, g))
         return VRG_ERR_BAD_ARG;
     if (frames == 0) return VRG_OK;
-    const int64_t frame_elems = (int64_t)height * width * 3;
     const bool aligned = (reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) % 16 == 0;
     if (nd->chunk_frames != 1 || width % 4 != 0 || (int64_t)width * 3 / 4 < 256 || frame_elems > 0x7fffffffll || !aligned)
         return VRG_ERR_UNSUPPORTED;                                   // the caller runs vrg_stencil3x3_f32 + vrg_grain_f32
-    const NoiseK nk = make_noise(nd, frame_elems);
-    const uint64_t groups = (uint64_t)((frame_elems + 4 * (int64_t)nk.G - 1) / (4 * (int64_t)nk.G));
-    const uint64_t per_frame = groups * ((nk.G + GRAIN_N - 1) / GRAIN_N);
-    const int64_t step = (int64_t)(0x7fffffffull / per_frame) - 1;   // frames per launch
-    if (step < 1) return VRG_ERR_UNSUPPORTED;
-    for (int64_t f0 = 0; f0 < frames; f0 += step) {
-        const int64_t nf = frames - f0 < step ? frames - f0 : step;
-        NoiseK nkk = nk;
-        nkk.chunk0 += f0;
-        const uint32_t total = (uint32_t)(per_frame * (uint64_t)nf);
-        const uint32_t blocks = ((total + 7u) / 8u) * 8u;
-        const float* src = in + f0 * frame_elems;
-        float* dst = out + f0 * frame_elems;
-        if (border == VRG_BORDER_ZERO)
-            hipLaunchKernelGGL((k_sharpen_grain<true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, src, dst, nkk, height, width * 3 / 4,
-                               (uint32_t)groups, total, strength, intensity, sat, one_minus_sat);
-        else
-            hipLaunchKernelGGL((k_sharpen_grain<false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, src, dst, nkk, height, width * 3 / 4,
-                               (uint32_t)groups, total, strength, intensity, sat, one_minus_sat);
-        VRG_CHECK_LAUNCH();
-    }
-    return VRG_OK;
+    return with_border(border, [&](auto zero) {
+        return sharpen_grain_launch(frames, g, [&](int64_t f0, int64_t, const NoiseK& nk, uint32_t total, uint32_t blocks) {
+            hipLaunchKernelGGL((k_sharpen_grain<decltype(zero)::value>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, in + f0 * frame_elems,
+                               out + f0 * frame_elems, nk, height, width * 3 / 4, (uint32_t)g.groups, total, strength, intensity, sat, one_minus_sat);
+        });
+    });
 }
 
 int vrg_sharpen_grain_u8(const uint8_t* in, uint8_t* out, int64_t frames, int32_t height, int32_t width, float strength, int32_t border,
                          float intensity, float sat, float one_minus_sat, const vrg_noise_desc* nd, void* stream) {
-    if (!in || !out || in == out || !nd || frames < 0 || height <= 0 || width <= 0 || border < 0 || border > 1 || nd->chunk_frames < 1 ||
-        nd->grid_threads == 0 || (nd->grid_threads % 256u) != 0)
+    const int64_t frame_elems = (int64_t)height * width * 3;
+    GrainGeom g;
+    if (!in || !out || in == out || frames < 0 || height <= 0 || width <= 0 || border < 0 || border > 1 || !grain_geom(nd, frame_elems, GRAIN_N, g))
         return VRG_ERR_BAD_ARG;
     if (frames == 0) return VRG_OK;
-    const int64_t frame_elems = (int64_t)height * width * 3;
     const bool aligned = (reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) % 4 == 0;
     // several frames per noise chunk: the enhancer seeds every frame on its own (reference :233-276), nothing calls that; a batch of less than
     // four bytes (one 1 x 1 frame) has no dword to load: the caller converts and runs the fp32 entry points
     if (nd->chunk_frames != 1 || frame_elems > 0x7fffffffll || frames * frame_elems < 4) return VRG_ERR_UNSUPPORTED;
     const bool fast = width % 4 == 0 && (int64_t)width * 3 / 4 >= 256 && aligned;      // rows on the frame's dword grid, at most one row end per block
-    const NoiseK nk = make_noise(nd, frame_elems);
-    const uint64_t groups = (uint64_t)((frame_elems + 4 * (int64_t)nk.G - 1) / (4 * (int64_t)nk.G));
-    const uint64_t per_frame = groups * ((nk.G + GRAIN_N - 1) / GRAIN_N);
-    const int64_t step = (int64_t)(0x7fffffffull / per_frame) - 1;   // frames per launch
-    if (step < 1) return VRG_ERR_UNSUPPORTED;
-    for (int64_t f0 = 0; f0 < frames; f0 += step) {
-        const int64_t nf = frames - f0 < step ? frames - f0 : step;
-        NoiseK nkk = nk;
-        nkk.chunk0 += f0;
-        const uint32_t total = (uint32_t)(per_frame * (uint64_t)nf);
-        const uint32_t blocks = ((total + 7u) / 8u) * 8u;
-        if (!fast) {
-            // any width, any alignment: flat byte space of the batch (k_sharpen_grain_u8_any); the windows may reach into the neighbouring
-            // frames of the WHOLE batch, so the kernel gets the batch's base and the launch's first frame through the chunk index
-            NoiseK nka = nk;
-            nka.chunk0 += f0;
-            const uint8_t* base = in + f0 * frame_elems;
-            uint8_t* obase = out + f0 * frame_elems;
-            const int64_t reach = (frames - f0) * frame_elems;       // bytes addressable from `base` upwards (windows below it are clamped)
-            if (border == VRG_BORDER_ZERO)
-                hipLaunchKernelGGL((k_sharpen_grain_u8_any<true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, base, obase, nka, height, width * 3,
-                                   (uint32_t)frame_elems, reach, (uint32_t)groups, total, strength, intensity, sat, one_minus_sat);
-            else
-                hipLaunchKernelGGL((k_sharpen_grain_u8_any<false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, base, obase, nka, height, width * 3,
-                                   (uint32_t)frame_elems, reach, (uint32_t)groups, total, strength, intensity, sat, one_minus_sat);
-            VRG_CHECK_LAUNCH();
-            continue;
-        }
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(in + f0 * frame_elems);
-        uint32_t* dst = reinterpret_cast<uint32_t*>(out + f0 * frame_elems);
-        if (border == VRG_BORDER_ZERO)
-            hipLaunchKernelGGL((k_sharpen_grain_u8<true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, src, dst, nkk, height, width * 3 / 4,
-                               (uint32_t)groups, total, strength, intensity, sat, one_minus_sat);
-        else
-            hipLaunchKernelGGL((k_sharpen_grain_u8<false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, src, dst, nkk, height, width * 3 / 4,
-                               (uint32_t)groups, total, strength, intensity, sat, one_minus_sat);
-        VRG_CHECK_LAUNCH();
-    }
-    return VRG_OK;
+    return with_border(border, [&](auto zero) {
+        constexpr bool ZERO = decltype(zero)::value;
+        return sharpen_grain_launch(frames, g, [&](int64_t f0, int64_t, const NoiseK& nk, uint32_t total, uint32_t blocks) {
+            const uint8_t* src = in + f0 * frame_elems;
+            uint8_t* dst = out + f0 * frame_elems;
+            if (fast) {
+                hipLaunchKernelGGL((k_sharpen_grain_u8<ZERO>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(src),
+                                   reinterpret_cast<uint32_t*>(dst), nk, height, width * 3 / 4, (uint32_t)g.groups, total, strength, intensity, sat,
+                                   one_minus_sat);
+            } else {
+                // any width, any alignment: flat byte space of the batch (k_sharpen_grain_u8_any); the windows may reach into the neighbouring
+                // frames of the WHOLE batch, so the kernel gets the launch's first frame as its base and through the chunk index
+                const int64_t reach = (frames - f0) * frame_elems;    // bytes addressable from `src` upwards (windows below it are clamped)
+                hipLaunchKernelGGL((k_sharpen_grain_u8_any<ZERO>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, src, dst, nk, height, width * 3,
+                                   (uint32_t)frame_elems, reach, (uint32_t)g.groups, total, strength, intensity, sat, one_minus_sat);
+            }
+        });
+    });
 }
 
 // uint8 B,G,R frames, grain only: the shared-Philox kernel (one Philox call per four elements instead of the point-wise
@@ -1030,8 +804,7 @@ int vrg_colormatch_apply_f32(const float* in, float* out, int64_t frames, int32_
     if (ppf > 0x7fffffff) return VRG_ERR_UNSUPPORTED;
     CmK cm{img_ms, ref_ms, ref_frames, k, one_minus_k};
     const uint32_t bx = (uint32_t)((ppf + 255) / 256);
-    for (int64_t f0 = 0; f0 < frames; f0 += 32768) {
-        const int64_t nf = frames - f0 < 32768 ? frames - f0 : 32768;
+    return launch_chunks(frames, [&](int64_t f0, int64_t nf) {
         CmK c = cm;
         c.img_ms = img_ms + f0 * 6;
         // ref frame index uses f % ref_frames relative to the call start; 32768 is a multiple of any
@@ -1052,8 +825,8 @@ int vrg_colormatch_apply_f32(const float* in, float* out, int64_t frames, int32_
             hipLaunchKernelGGL(k_colormatch_apply<false>, dim3(bx, (uint32_t)nf), dim3(256), 0, (hipStream_t)stream,
                                reinterpret_cast<const px3*>(in) + f0 * ppf, reinterpret_cast<px3*>(out) + f0 * ppf, (int32_t)ppf, c, host_dev_math());
         VRG_CHECK_LAUNCH();
-    }
-    return VRG_OK;
+        return VRG_OK;
+    });
 }
 
 }  // extern "C"

@@ -3,6 +3,7 @@
 // of a frame row, so all nine tap loads of a wave are contiguous 256-byte segments; the eight
 // neighbour loads hit the vector L1 / L2 (each input byte leaves HBM once).
 #include "vrg_common.hpp"
+#include "vrg_lanes.hpp"
 
 namespace vrg {
 
@@ -53,13 +54,6 @@ template <int C>
 struct FlatRow { float o[4], p[C], n[C]; };            // own vector, the C floats left of it, the C floats right of it
 struct FlatRaw { fv4 own, halo; };                      // as loaded: halo = neighbour vector for lane 0 (left) / lane 63 (right)
 
-__device__ __forceinline__ float flat_shr(float old, float v) {   // value of lane-1; lane 0 keeps `old`
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(v), 0x138 /* wave_shr:1 */, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float flat_shl(float old, float v) {   // value of lane+1; lane 63 keeps `old`
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(v), 0x130 /* wave_shl:1 */, 0xf, 0xf, false));
-}
-
 // One strip segment: rows [y0, y0 + rows) of the 64 vectors starting at column col - lane.
 // GENERAL = false (every launch on frames of at least 64 vectors x FLAT_ROWS rows): all 64 lanes hold a vector and the segment has
 // exactly FLAT_ROWS rows -- the last strip of a row and the last segment of a frame START EARLIER instead of ending short (they
@@ -100,8 +94,8 @@ __device__ __forceinline__ void flat_march(const fv4* __restrict__ fin, fv4* __r
         for (int i = 0; i < 4; ++i) r.o[i] = o[i];
 #pragma unroll
         for (int i = 0; i < C; ++i) {
-            r.p[i] = flat_shr(h[4 - C + i], o[4 - C + i]);           // floats -C+i .. of this vector = the previous vector's tail
-            r.n[i] = flat_shl(h[i], o[i]);                           // floats 4+i = the next vector's head
+            r.p[i] = lane_prev_or(h[4 - C + i], o[4 - C + i]);           // floats -C+i .. of this vector = the previous vector's tail
+            r.n[i] = lane_next_or(h[i], o[i]);                           // floats 4+i = the next vector's head
         }
         if (edge_strip) {                                            // the two ends of a frame row: replicate the end pixel, or zero
 #pragma unroll
@@ -232,11 +226,10 @@ extern "C" int vrg_stencil3x3_f32(const float* in, float* out, int64_t frames, i
     const int64_t fe = (int64_t)height * width * channels;
     if (fe > 0x7fffffff) return VRG_ERR_UNSUPPORTED;
     const uint32_t bx = (uint32_t)((fe + 255) / 256);
-    for (int64_t f0 = 0; f0 < frames; f0 += 32768) {
-        const int64_t nf = frames - f0 < 32768 ? frames - f0 : 32768;
+    return launch_chunks(frames, [&](int64_t f0, int64_t nf) {
         hipLaunchKernelGGL(k_stencil3x3, dim3(bx, (uint32_t)nf), dim3(256), 0, (hipStream_t)stream, in + f0 * fe, out + f0 * fe,
                            height, width, channels, op, border, strength);
         VRG_CHECK_LAUNCH();
-    }
-    return VRG_OK;
+        return VRG_OK;
+    });
 }

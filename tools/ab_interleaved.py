@@ -7,7 +7,8 @@ that.
            --cases chain3,chain3_video,chain4 --frames 64 --rounds 7 [--json gpurun_out/ab.json]
 
 Cases: chain3 / chain3_video (grain -> LUT 33^3 -> unsharp on uniform / video-like 4K frames), grain_lut, chain4 (per-pass times of the
-headline chain: pass1 / stats / pass2 / wall), kernels (grain, lut33, unsharp, sharpen>grain fused).
+headline chain: pass1 / stats / pass2 / wall), kernels (grain, lut33, unsharp, sharpen>grain fused), kernels_u8 (sharpen>grain fused on
+uint8 frames: 2160 x 3840 = the dword-grid kernel, 768 x 1366 = the any-size kernel).
 All builds must export the same ABI; outputs of the builds are compared bit for bit on the first round (a variant that changes bits
 is reported, not timed as a candidate)."""
 import argparse, ctypes as C, json, os, statistics, sys
@@ -47,6 +48,22 @@ out = torch.empty_like(x)
 ws = torch.empty_like(x) if "chain4" in a.cases else None
 lut = ops.upload_lut(cube.parse_cube_file(os.path.join(iv.LUTS_DIR, a.lut)), dev)
 gen = torch.Generator(device=dev)
+u8_frames = {}
+check = None                             # round 0: a list that takes the checksums of the results a case does not leave in `out`
+
+
+def checksum(t):
+    d = t.contiguous().view(torch.int32)
+    return (int(d.sum(dtype=torch.int64)), int((d.to(torch.int64) * 31 % 1000003).sum()))
+
+
+def timed_kept(fn):
+    """timed(), and in round 0 the checksum of what fn returned"""
+    kept = []
+    ms = timed(lambda: kept.append(fn()))
+    if check is not None:
+        check.append(checksum(kept[0]))
+    return ms
 
 
 def timed(fn):
@@ -113,10 +130,17 @@ def run_case(case):
     if case == "kernels":
         r = {}
         gen.manual_seed(5)
-        r["grain"] = timed(lambda: ops.film_grain(x, 0.04, 0.5, chunk_frames=4, generator=gen))
-        r["lut33"] = timed(lambda: ops.lut3d(x, lut, 10.0))
-        r["unsharp"] = timed(lambda: ops.stencil3x3(x, "unsharp", 0.5, False))
-        r["sharpen>grain"] = timed(lambda: ops.sharpen_then_seeded_grain(x, 0.5, False, 0.04, 0.5, 42, 0))
+        r["grain"] = timed_kept(lambda: ops.film_grain(x, 0.04, 0.5, chunk_frames=4, generator=gen))
+        r["lut33"] = timed_kept(lambda: ops.lut3d(x, lut, 10.0))
+        r["unsharp"] = timed_kept(lambda: ops.stencil3x3(x, "unsharp", 0.5, False))
+        r["sharpen>grain"] = timed_kept(lambda: ops.sharpen_then_seeded_grain(x, 0.5, False, 0.04, 0.5, 42, 0))
+        return r
+    if case == "kernels_u8":
+        r = {}
+        for h, w in ((2160, 3840), (768, 1366)):
+            if (h, w) not in u8_frames:
+                u8_frames[(h, w)] = torch.randint(0, 256, (F, h, w, 3), generator=torch.Generator(device=dev).manual_seed(7), device=dev, dtype=torch.uint8)
+            r[f"sharpen>grain u8 {h}x{w}"] = timed_kept(lambda: ops.sharpen_then_seeded_grain(u8_frames[(h, w)], 0.5, False, 0.04, 0.5, 42, 0))
         return r
     raise SystemExit(f"unknown case {case}")
 
@@ -134,12 +158,11 @@ for rnd in range(a.rounds + 1):          # round 0 = warm-up + the bit compariso
         torch.cuda.synchronize()
         for name, lib in order:
             _hip._lib = lib
+            check = [] if rnd == 0 else None
             res = run_case(case)
             torch.cuda.synchronize()
             if rnd == 0:
-                if case != "kernels":
-                    d = out.view(torch.int32)
-                    bits.setdefault(case, {})[name] = (int(d.sum(dtype=torch.int64)), int((d.to(torch.int64) * 31 % 1000003).sum()))
+                bits.setdefault(case, {})[name] = check or checksum(out)
                 continue
             for k, v in res.items():
                 times.setdefault(k, {}).setdefault(name, []).append(v)
