@@ -134,6 +134,16 @@ class PilBoxDesc(C.Structure):
                 ("reserved", C.c_int32), ("mask_offset", C.c_int64), ("rep_offset", C.c_int64)]
 
 
+class GridDesc(C.Structure):
+    """vrg_grid_desc"""
+    _fields_ = [("src", C.c_void_p), ("xtab", C.c_void_p), ("ytab", C.c_void_p), ("overlay", C.c_void_p),
+                ("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32), ("mode", C.c_int32),
+                ("frame", C.c_int32), ("dst_x", C.c_int32), ("dst_y", C.c_int32),
+                ("new_w", C.c_int32), ("new_h", C.c_int32), ("x_off", C.c_int32), ("y_off", C.c_int32),
+                ("band", C.c_int32), ("cps", C.c_int32), ("inv", C.c_float)]
+
+
+GRID_COPY, GRID_FAST, GRID_FAST_2X2, GRID_GENERAL, GRID_LINEAR = 0, 1, 2, 3, 4
 PIL_STATS_WORDS = 12            # uint32 per frame (csrc/vrg_pil_math.hpp: PIL_STATS_WORDS)
 PIL_MAX_LINE = 8192             # the longest mask row / column (csrc/vrg_pil_math.hpp: PIL_MAX_LINE)
 FACEFIX_STATS_WORDS = 12        # uint64 per frame (csrc/vrg_facefix_math.hpp: FF_STATS_WORDS)
@@ -223,6 +233,11 @@ _SIGNATURES = {
     "vrg_detect_check": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64]),
     "vrg_detect_blobs_f32": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     "vrg_detect_blobs_u8": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P, _P]),
+    "vrg_grid_plan": (C.c_int, [C.c_int32] * 5 + [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
+    "vrg_grid_taps": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P]),
+    "vrg_grid_check": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int64] + [C.c_int32] * 4),
+    "vrg_grid_tiles_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int64] + [C.c_int32] * 4 + [_P]),
+    "vrg_grid_tiles_u8": (C.c_int, [_P, C.c_int64, _P, C.c_int64] + [C.c_int32] * 4 + [_P]),
     "vrg_warp_linear_u8": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P, _P]),
 }
 

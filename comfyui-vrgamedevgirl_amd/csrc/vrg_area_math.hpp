@@ -58,9 +58,8 @@ inline int area_mode(int32_t in_h, int32_t in_w) {
     return (in_h == 2 * AREA_OUT && in_w == 2 * AREA_OUT) ? AREA_FAST_2X2 : AREA_FAST;
 }
 
-// HOST: the cell of output index d of an axis with n_in >= 64 samples
-inline AreaCell area_cell(int32_t d, int32_t n_in) {
-    const double scale = (double)n_in / (double)AREA_OUT;
+// HOST: the cell of output index d of an axis with n_in samples reduced by `scale` >= 1 (computeResizeAreaTab; the caller forms the scale)
+inline AreaCell area_cell_scaled(int32_t d, int32_t n_in, double scale) {
     const double fs1 = (double)d * scale, fs2 = fs1 + scale;
     const double rest = (double)n_in - fs1, cell = scale < rest ? scale : rest;
     int32_t s1 = (int32_t)ceil(fs1), s2 = (int32_t)floor(fs2);
@@ -79,6 +78,9 @@ inline AreaCell area_cell(int32_t d, int32_t n_in) {
     c.w_last = tail ? w_tail : (s2 > s1 ? c.w_mid : w_head);
     return c;
 }
+
+// HOST: the cell of output index d of an axis with n_in >= 64 samples
+inline AreaCell area_cell(int32_t d, int32_t n_in) { return area_cell_scaled(d, n_in, (double)n_in / (double)AREA_OUT); }
 
 // 64 column cells, then 64 row cells
 inline void area_fill_cells(int32_t in_h, int32_t in_w, AreaCell* cells) {

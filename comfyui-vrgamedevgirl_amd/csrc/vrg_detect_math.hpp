@@ -115,6 +115,10 @@ VRG_HD DtTap dt_tap(int32_t d, int32_t n_in, double scale, bool horizontal) {
 
 VRG_HD uint8_t dt_byte(int32_t v) { return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
 
+// the two passes of the byte resize: the horizontal one of a row (int32), the vertical one of two such rows
+VRG_HD int32_t dt_hpass(int32_t p0, int32_t p1, int32_t c0, int32_t c1) { return p0 * c0 + p1 * c1; }
+VRG_HD uint8_t dt_vpass(int32_t r0, int32_t r1, int32_t b0, int32_t b1) { return dt_byte((((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2); }
+
 // One pixel (dx, dy) of the n_out x n_out resize of an rw x rh region: pixel(y, x, b) gives the three bytes of the region.
 template <typename PIXEL>
 VRG_HD void dt_resize_pixel(int32_t dx, int32_t dy, int32_t rw, int32_t rh, int32_t n_out, PIXEL pixel, uint8_t o[3]) {
@@ -136,8 +140,8 @@ VRG_HD void dt_resize_pixel(int32_t dx, int32_t dy, int32_t rw, int32_t rh, int3
     pixel(ty.s1, tx.s1, p11);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        const int32_t r0 = (int32_t)p00[c] * tx.c0 + (int32_t)p01[c] * tx.c1, r1 = (int32_t)p10[c] * tx.c0 + (int32_t)p11[c] * tx.c1;
-        o[c] = dt_byte((((ty.c0 * (r0 >> 4)) >> 16) + ((ty.c1 * (r1 >> 4)) >> 16) + 2) >> 2);
+        const int32_t r0 = dt_hpass(p00[c], p01[c], tx.c0, tx.c1), r1 = dt_hpass(p10[c], p11[c], tx.c0, tx.c1);
+        o[c] = dt_vpass(r0, r1, ty.c0, ty.c1);
     }
 }
 

@@ -1,0 +1,326 @@
+// vrg_grid.hip -- the Video Folder Grid Plot (VRGDG_VideoFolderGridPlot, LTXLoraTrain.py:7926-8314 of the reference): every tile of every
+// output frame quantised, resized as cv2.resize(..., INTER_AREA) does on bytes and written as fp32 / 255 straight into its place in the grid
+// frame, with the letterbox bars, the label band and the empty cells, in one launch.  gfx950 only.  Arithmetic: csrc/vrg_grid_math.hpp.
+//
+// k_grid_tiles: one workgroup (four waves) = 64 tile columns of one tile row of one descriptor (one tile of one output frame), so a row of
+// any width is a row of workgroups.  A row of the band takes the overlay's bytes, a row of the picture is computed, everything else is 0;
+// the workgroup leaves its <= 192 bytes in LDS and stores (float)byte / 255 for all of them: every float of the grid is written once.
+//   The picture rows follow k_cut_thumbs (csrc/vrg_cut.hip), whose comment says why the order of the fp32 sums allows this much and no
+//   more: the source rows of the output row go round the four waves; a wave reads the samples its 64 columns need once with 16-byte loads,
+//   quantises them and keeps the BYTES in a row buffer of its own in LDS; lane d walks the taps of column d for the three channels; after
+//   every four rows the workgroup meets and 192 threads fold the rows' values in row order.  Samples that do not fit the row buffer go
+//   through in segments of whole columns (desc.cps columns each).  One walk serves every rule, the words it leaves differ:
+//     general   fp32 sums in cv2's order                         folded with the row weights, rounded
+//     fast/copy integer sums (copy: cells of one sample)         added, scaled by 1 / (sx * sy), rounded (2 x 2: (sum + 2) >> 2)
+//     linear    dt_hpass of the column's one or two samples      the one or two rows through dt_vpass
+//   The store goes in 16-byte pieces from the first 16-byte boundary of the destination on, the floats in front of and behind them one by
+//   one: a tile may start anywhere on the 4-byte grid.
+// There is no row buffer for the output.  The row buffer of a wave holds GRID_ROW_VALUES source values: when the 64 columns of a workgroup
+// need more, they go through it desc.cps columns at a time; the taps of ONE column must fit it (vrg_grid_plan refuses the rest), the
+// width of a source as such is not bounded: a row wider than the buffer is split across workgroups and, inside one, into these
+// segments.  The source is read once (rows that two output rows share are read by both); 12 B per source pixel with C = 3.
+#include "vrg_common.hpp"
+#include "vrg_grid_math.hpp"
+
+namespace vrg {
+
+constexpr int GRID_WAVES = 4, GRID_THREADS = GRID_WAVES * 64;
+constexpr int GRID_VALUES = GRID_LANES * 3;                                    // the values of one workgroup
+constexpr int GRID_PART_BYTES = 2 * GRID_WAVES * GRID_VALUES * 4;              // two sets of four rows' words
+constexpr int GRID_CELL_BYTES = GRID_LANES * (int)sizeof(AreaCell);
+constexpr int GRID_UNIT_BYTES = 256 * 4;                                       // k / 255
+constexpr int GRID_OUT_BYTES = 256;                                            // the bytes of the workgroup (192 used)
+constexpr int GRID_HEAD_BYTES = GRID_PART_BYTES + GRID_CELL_BYTES + GRID_UNIT_BYTES + GRID_OUT_BYTES;
+constexpr int GRID_ROWBUF = GRID_ROW_VALUES + 16;                              // a staged value lies at the byte phase of its source
+constexpr int GRID_LDS_BYTES = GRID_HEAD_BYTES + GRID_WAVES * GRID_ROWBUF;
+static_assert(GRID_HEAD_BYTES % 16 == 0 && GRID_ROWBUF % 16 == 0, "the row buffers start on a 16-byte boundary");
+
+struct GridGeom {
+    int64_t frames;
+    int32_t cell_w, cell_h, grid_w, grid_h, segments;
+};
+
+typedef float grid_f4 __attribute__((ext_vector_type(4)));
+typedef uint32_t grid_u4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ void grid_wave_sync() {                             // cut_wave_sync of vrg_cut.hip
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ uint32_t grid_quant4(const grid_f4 v) {
+    return (uint32_t)grid_quant(v.x) | ((uint32_t)grid_quant(v.y) << 8) | ((uint32_t)grid_quant(v.z) << 16) | ((uint32_t)grid_quant(v.w) << 24);
+}
+
+// n values from src as bytes into rb: value i lands at rb[ph + i], ph the returned phase (fp32: the float's index mod 4; bytes: the
+// address mod 16), so that the 16-byte loads and the LDS words they fill are both aligned.  n <= GRID_ROW_VALUES.
+__device__ __forceinline__ int grid_stage(const float* src, int n, uint8_t* rb, int lane) {
+    const int ph = (int)((reinterpret_cast<uintptr_t>(src) >> 2) & 3u);
+    int head = (4 - ph) & 3;
+    head = head < n ? head : n;
+    const int nq = (n - head) >> 2;
+    if (lane < head) rb[ph + lane] = grid_quant(src[lane]);
+    const grid_f4* body = reinterpret_cast<const grid_f4*>(src + head);
+    uint32_t* dst = reinterpret_cast<uint32_t*>(rb + ph + head);
+    int q = lane;
+    for (; q + 192 < nq; q += 256) {                                           // four loads in flight per lane
+        const grid_f4 v0 = __builtin_nontemporal_load(body + q), v1 = __builtin_nontemporal_load(body + q + 64);
+        const grid_f4 v2 = __builtin_nontemporal_load(body + q + 128), v3 = __builtin_nontemporal_load(body + q + 192);
+        dst[q] = grid_quant4(v0);
+        dst[q + 64] = grid_quant4(v1);
+        dst[q + 128] = grid_quant4(v2);
+        dst[q + 192] = grid_quant4(v3);
+    }
+    for (; q < nq; q += 64) dst[q] = grid_quant4(__builtin_nontemporal_load(body + q));
+    const int t = head + 4 * nq + lane;
+    if (t < n) rb[ph + t] = grid_quant(src[t]);
+    return ph;
+}
+
+__device__ __forceinline__ int grid_stage(const uint8_t* src, int n, uint8_t* rb, int lane) {
+    const int ph = (int)(reinterpret_cast<uintptr_t>(src) & 15u);
+    int head = (16 - ph) & 15;
+    head = head < n ? head : n;
+    const int nq = (n - head) >> 4;
+    if (lane < head) rb[ph + lane] = src[lane];
+    const grid_u4* body = reinterpret_cast<const grid_u4*>(src + head);
+    grid_u4* dst = reinterpret_cast<grid_u4*>(rb + ph + head);
+    for (int q = lane; q < nq; q += 64) dst[q] = __builtin_nontemporal_load(body + q);
+    const int t = head + 16 * nq + lane;                                       // at most 15 bytes behind the last 16-byte piece
+    if (t < n) rb[ph + t] = src[t];
+    return ph;
+}
+
+__device__ __forceinline__ AreaCell grid_clamped(AreaCell c, int32_t n_in) {   // a table made for another geometry reads nothing outside
+    c.first = c.first < 0 ? 0 : (c.first > n_in - 1 ? n_in - 1 : c.first);
+    c.count = c.count < 0 ? 0 : (c.count > n_in - c.first ? n_in - c.first : c.count);
+    return c;
+}
+
+template <typename T>
+__global__ __launch_bounds__(GRID_THREADS) void k_grid_tiles(const vrg_grid_desc* __restrict__ descs, float* __restrict__ out, GridGeom g) {
+    constexpr bool SWAP = sizeof(T) == 1;                                      // decoded frames are B,G,R
+    __shared__ __attribute__((aligned(16))) uint8_t lds[GRID_LDS_BYTES];
+    uint32_t* part = reinterpret_cast<uint32_t*>(lds);                        // [2][GRID_WAVES][GRID_VALUES]
+    AreaCell* xc = reinterpret_cast<AreaCell*>(lds + GRID_PART_BYTES);        // [64]
+    float* unit = reinterpret_cast<float*>(lds + GRID_PART_BYTES + GRID_CELL_BYTES);
+    uint8_t* ob = lds + GRID_PART_BYTES + GRID_CELL_BYTES + GRID_UNIT_BYTES;
+    const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    uint8_t* rb = lds + GRID_HEAD_BYTES + wave * GRID_ROWBUF;
+
+    const vrg_grid_desc d = descs[blockIdx.y];
+    const int seg = (int)(blockIdx.x % (uint32_t)g.segments), ty = (int)(blockIdx.x / (uint32_t)g.segments);
+    const int tx0 = seg * GRID_LANES;
+    const int ncol = g.cell_w - tx0 < GRID_LANES ? g.cell_w - tx0 : GRID_LANES;
+    // a tile outside the grid writes nothing (vrg_grid_check refuses it on the host)
+    if (d.frame < 0 || (int64_t)d.frame >= g.frames || d.dst_x < 0 || d.dst_y < 0 || d.dst_x > g.grid_w - g.cell_w || d.dst_y > g.grid_h - g.cell_h) return;
+
+    unit[tid] = grid_unit(tid);
+    const int C = d.channels, mode = d.mode;
+    // picture: the geometry must lie inside the tile, else the tile has none
+    const bool geometry = d.src && d.new_w >= 1 && d.new_h >= 1 && d.x_off >= 0 && d.y_off >= 0 && d.x_off <= g.cell_w - d.new_w &&
+                          d.y_off <= g.cell_h - d.new_h && d.xtab && d.ytab && d.height >= 1 && d.width >= 1 && (C == 3 || (C == 4 && !SWAP)) &&
+                          mode >= GRID_COPY && mode <= GRID_LINEAR;
+    int d_lo = tx0 - d.x_off, d_hi = tx0 + ncol - d.x_off;                     // the picture columns [d_lo, d_hi) of this workgroup
+    d_lo = d_lo < 0 ? 0 : d_lo;
+    d_hi = d_hi > d.new_w ? d.new_w : d_hi;
+    const bool picture = geometry && ty >= d.y_off && ty < d.y_off + d.new_h && d_lo < d_hi;       // workgroup-uniform
+    const int lane0 = d_lo + d.x_off - tx0;                                    // the lane of picture column d_lo
+
+    uint32_t total = 0, row0 = 0, row1 = 0;
+    AreaCell yc{0, 0, 0.0f, 0.0f, 0.0f};
+    if (picture) {
+        const AreaCell* xt = reinterpret_cast<const AreaCell*>(d.xtab);
+        const int nc = d_hi - d_lo;
+        if (tid < nc) xc[tid] = grid_clamped(xt[d_lo + tid], d.width);
+        yc = grid_clamped(reinterpret_cast<const AreaCell*>(d.ytab)[ty - d.y_off], d.height);
+        __syncthreads();
+        const int cl = lane - lane0;                                           // this lane's column of xc, if 0 <= cl < nc
+        const bool mine = cl >= 0 && cl < nc;
+        const AreaCell m = mine ? xc[cl] : AreaCell{0, 0, 0.0f, 0.0f, 0.0f};
+        int cps = d.cps < 1 ? 1 : (d.cps > GRID_LANES ? GRID_LANES : d.cps);
+        const T* fin = reinterpret_cast<const T*>(d.src);
+        const int batches = (yc.count + GRID_WAVES - 1) / GRID_WAVES;
+        for (int b = 0; b < batches; ++b) {
+            const int r = b * GRID_WAVES + wave;
+            if (r < yc.count) {                                                // wave-uniform
+                const T* row = fin + (int64_t)(yc.first + r) * d.width * C;
+                uint32_t a0 = 0, a1 = 0, a2 = 0;
+                for (int c0 = 0; c0 < nc; c0 += cps) {
+                    const int cl_last = (c0 + cps < nc ? c0 + cps : nc) - 1;
+                    const int x0 = xc[c0].first;
+                    int n = (xc[cl_last].first + xc[cl_last].count - x0) * C;  // values of this segment
+                    n = n < 0 ? 0 : (n > GRID_ROW_VALUES ? GRID_ROW_VALUES : n);           // (never taken with the cps of vrg_grid_plan)
+                    const int ph = grid_stage(row + (int64_t)x0 * C, n, rb, lane);
+                    grid_wave_sync();
+                    if (mine && cl >= c0 && cl <= cl_last) {
+                        const int at = (m.first - x0) * C;
+                        int count = m.count;
+                        if (at < 0 || at + count * C > n) count = 0;           // (never taken)
+                        const uint8_t* p = rb + ph + at;
+                        const int s0 = SWAP ? 2 : 0, s2 = SWAP ? 0 : 2;
+                        if (mode == GRID_GENERAL) {
+                            float f0 = 0.0f, f1 = 0.0f, f2 = 0.0f;
+                            for (int k = 0; k < count; ++k, p += C) {
+                                const float w = k == 0 ? m.w_first : (k == m.count - 1 ? m.w_last : m.w_mid);       // area_weight
+                                f0 = grid_term_general(f0, p[s0], w);
+                                f1 = grid_term_general(f1, p[1], w);
+                                f2 = grid_term_general(f2, p[s2], w);
+                            }
+                            a0 = __float_as_uint(f0); a1 = __float_as_uint(f1); a2 = __float_as_uint(f2);
+                        } else if (mode == GRID_LINEAR) {
+                            if (count > 0) {
+                                const uint8_t* q = p + (count - 1) * C;
+                                a0 = (uint32_t)grid_row_linear(p[s0], q[s0], m);
+                                a1 = (uint32_t)grid_row_linear(p[1], q[1], m);
+                                a2 = (uint32_t)grid_row_linear(p[s2], q[s2], m);
+                            }
+                        } else {
+                            int32_t i0 = 0, i1 = 0, i2 = 0;
+                            for (int k = 0; k < count; ++k, p += C) {
+                                i0 = grid_term_fast(i0, p[s0]);
+                                i1 = grid_term_fast(i1, p[1]);
+                                i2 = grid_term_fast(i2, p[s2]);
+                            }
+                            a0 = (uint32_t)i0; a1 = (uint32_t)i1; a2 = (uint32_t)i2;
+                        }
+                    }
+                    grid_wave_sync();                                          // the next segment overwrites the buffer
+                }
+                uint32_t* mine_out = part + ((b & 1) * GRID_WAVES + wave) * GRID_VALUES + lane * 3;
+                mine_out[0] = a0; mine_out[1] = a1; mine_out[2] = a2;
+            }
+            __syncthreads();
+            if (tid < GRID_VALUES) {
+#pragma unroll
+                for (int w = 0; w < GRID_WAVES; ++w) {
+                    const int rr = b * GRID_WAVES + w;
+                    if (rr < yc.count) {
+                        const uint32_t v = part[((b & 1) * GRID_WAVES + w) * GRID_VALUES + tid];
+                        if (mode == GRID_GENERAL)
+                            total = __float_as_uint(area_fold(__uint_as_float(total), __uint_as_float(v),
+                                                              rr == 0 ? yc.w_first : (rr == yc.count - 1 ? yc.w_last : yc.w_mid), rr == 0));
+                        else if (mode == GRID_LINEAR) {
+                            if (rr == 0) row0 = row1 = v;
+                            else if (rr == 1) row1 = v;
+                        } else
+                            total += v;
+                    }
+                }
+            }
+        }
+    }
+
+    // the bytes of this workgroup's values: picture, overlay or nothing
+    if (tid < GRID_VALUES) {
+        const int col = tid / 3;                                               // tile column tx0 + col, channel tid - 3 * col
+        uint8_t o = 0;
+        if (col < ncol) {
+            const int dcol = tx0 + col - d.x_off;
+            if (picture && dcol >= 0 && dcol < d.new_w) {
+                if (mode == GRID_GENERAL) o = area_cast(__uint_as_float(total));
+                else if (mode == GRID_LINEAR) o = grid_byte_linear((int32_t)row0, (int32_t)row1, yc);
+                else o = area_fast_cast((int32_t)total, d.inv, mode == GRID_FAST_2X2);
+            } else if (d.overlay && ty < d.band) {
+                o = d.overlay[((int64_t)ty * g.cell_w + tx0) * 3 + tid];
+            }
+        }
+        ob[tid] = o;
+    }
+    __syncthreads();
+
+    // (float)byte / 255 for the ncol * 3 values, 16-byte stores from the first 16-byte boundary on
+    const int n = ncol * 3;
+    float* dst = out + (((int64_t)d.frame * g.grid_h + d.dst_y + ty) * g.grid_w + d.dst_x + tx0) * 3;
+    const int ph = (int)((reinterpret_cast<uintptr_t>(dst) >> 2) & 3u);
+    int head = (4 - ph) & 3;
+    head = head < n ? head : n;
+    const int nq = (n - head) >> 2;
+    if (wave == 0) {
+        if (lane < head) dst[lane] = unit[ob[lane]];
+        const int t = head + 4 * nq + lane;
+        if (lane < 3 && t < n) dst[t] = unit[ob[t]];
+    } else if (tid - 64 < nq) {
+        const int i = head + 4 * (tid - 64);
+        grid_f4 v;
+        v.x = unit[ob[i]]; v.y = unit[ob[i + 1]]; v.z = unit[ob[i + 2]]; v.w = unit[ob[i + 3]];
+        *reinterpret_cast<grid_f4*>(dst + i) = v;
+    }
+}
+
+// is this descriptor one the kernel follows as the caller means it (host)
+static bool grid_desc_ok(const vrg_grid_desc& d, bool bytes, int64_t frames, int32_t cell_w, int32_t cell_h, int32_t grid_w, int32_t grid_h) {
+    if (d.frame < 0 || (int64_t)d.frame >= frames || d.dst_x < 0 || d.dst_y < 0 || d.dst_x > grid_w - cell_w || d.dst_y > grid_h - cell_h) return false;
+    if (d.band < 0 || d.band > cell_h) return false;
+    if (!d.src) return true;
+    if (!d.xtab || !d.ytab || d.height < 1 || d.width < 1 || !(d.channels == 3 || (d.channels == 4 && !bytes))) return false;
+    if ((reinterpret_cast<uintptr_t>(d.xtab) & 3u) || (reinterpret_cast<uintptr_t>(d.ytab) & 3u) || (!bytes && (reinterpret_cast<uintptr_t>(d.src) & 3u))) return false;
+    if ((int64_t)d.height * d.width * d.channels > 0x7fffffffll) return false;
+    if (d.new_w < 1 || d.new_h < 1 || d.x_off < 0 || d.y_off < d.band || d.x_off > cell_w - d.new_w || d.y_off > cell_h - d.new_h) return false;
+    if (d.mode != grid_mode(d.height, d.width, d.new_h, d.new_w) || d.cps < 1 || d.cps > GRID_LANES) return false;
+    return true;
+}
+
+template <typename T>
+static int grid_launch(const vrg_grid_desc* desc, int64_t n_desc, float* out, int64_t frames, int32_t cell_w, int32_t cell_h, int32_t grid_w,
+                       int32_t grid_h, void* stream) {
+    if (n_desc < 0 || frames < 0 || cell_w < 1 || cell_h < 1 || grid_w < cell_w || grid_h < cell_h) return VRG_ERR_BAD_ARG;
+    if (n_desc == 0 || frames == 0) return VRG_OK;
+    if (!desc || !out || (reinterpret_cast<uintptr_t>(desc) & 7u) != 0 || (reinterpret_cast<uintptr_t>(out) & 3u) != 0) return VRG_ERR_BAD_ARG;
+    GridGeom g{frames, cell_w, cell_h, grid_w, grid_h, (cell_w + GRID_LANES - 1) / GRID_LANES};
+    if ((int64_t)g.segments * cell_h > 0x7fffffffll) return VRG_ERR_UNSUPPORTED;
+    return launch_chunks(n_desc, [&](int64_t first, int64_t count) -> int {
+        hipLaunchKernelGGL((k_grid_tiles<T>), dim3((uint32_t)(g.segments * cell_h), (uint32_t)count), dim3(GRID_THREADS), 0, (hipStream_t)stream,
+                           desc + first, out, g);
+        VRG_CHECK_LAUNCH();
+        return VRG_OK;
+    });
+}
+
+}  // namespace vrg
+
+using namespace vrg;
+
+extern "C" {
+
+int vrg_grid_plan(int32_t in_h, int32_t in_w, int32_t channels, int32_t out_h, int32_t out_w, int32_t* mode, int32_t* cps, float* inv) {
+    if (!mode || !cps || !inv || in_h < 1 || in_w < 1 || out_h < 1 || out_w < 1 || channels < 3 || channels > 4) return VRG_ERR_BAD_ARG;
+    *mode = grid_mode(in_h, in_w, out_h, out_w);
+    *inv = *mode == GRID_FAST || *mode == GRID_FAST_2X2 ? grid_fast_inv(in_h, in_w, out_h, out_w) : 1.0f;
+    AreaCell* cells = new AreaCell[out_w];
+    grid_fill_taps(in_w, out_w, *mode, cells);
+    *cps = grid_cells_per_segment(cells, out_w, channels);
+    delete[] cells;
+    return *cps ? VRG_OK : VRG_ERR_UNSUPPORTED;
+}
+
+int vrg_grid_taps(int32_t n_in, int32_t n_out, int32_t mode, void* taps_host) {
+    if (!taps_host || n_in < 1 || n_out < 1 || mode < GRID_COPY || mode > GRID_LINEAR) return VRG_ERR_BAD_ARG;
+    if (mode == GRID_COPY && n_in != n_out) return VRG_ERR_BAD_ARG;
+    int32_t step;
+    if ((mode == GRID_FAST || mode == GRID_FAST_2X2) && (n_out > n_in || !grid_integer_scale(grid_scale(n_in, n_out), step))) return VRG_ERR_BAD_ARG;
+    if (mode == GRID_GENERAL && n_out > n_in) return VRG_ERR_BAD_ARG;
+    grid_fill_taps(n_in, n_out, mode, reinterpret_cast<AreaCell*>(taps_host));
+    return VRG_OK;
+}
+
+int vrg_grid_check(const vrg_grid_desc* desc_host, int64_t n_desc, int32_t bytes, int64_t frames, int32_t cell_w, int32_t cell_h, int32_t grid_w,
+                   int32_t grid_h) {
+    if (n_desc < 0 || frames < 0 || cell_w < 1 || cell_h < 1 || grid_w < cell_w || grid_h < cell_h || (n_desc > 0 && !desc_host)) return VRG_ERR_BAD_ARG;
+    for (int64_t i = 0; i < n_desc; ++i)
+        if (!grid_desc_ok(desc_host[i], bytes != 0, frames, cell_w, cell_h, grid_w, grid_h)) return VRG_ERR_BAD_ARG;
+    return VRG_OK;
+}
+
+int vrg_grid_tiles_f32(const vrg_grid_desc* desc, int64_t n_desc, float* out, int64_t frames, int32_t cell_w, int32_t cell_h, int32_t grid_w,
+                       int32_t grid_h, void* stream) {
+    return grid_launch<float>(desc, n_desc, out, frames, cell_w, cell_h, grid_w, grid_h, stream);
+}
+
+int vrg_grid_tiles_u8(const vrg_grid_desc* desc, int64_t n_desc, float* out, int64_t frames, int32_t cell_w, int32_t cell_h, int32_t grid_w,
+                      int32_t grid_h, void* stream) {
+    return grid_launch<uint8_t>(desc, n_desc, out, frames, cell_w, cell_h, grid_w, grid_h, stream);
+}
+
+}  // extern "C"

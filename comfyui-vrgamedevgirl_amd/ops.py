@@ -1509,6 +1509,273 @@ def cut_pair_sums(thumbs: torch.Tensor, hist: Optional[torch.Tensor] = None) -> 
 
 
 # ------------------------------------------------------------------------------------------------
+# The Video Folder Grid Plot (reference LTXLoraTrain.py:7926-8314): every tile of every output frame quantised, resized as
+# cv2.resize(..., INTER_AREA) does on bytes and written as fp32 / 255 straight into the grid frame (csrc/vrg_grid.hip, arithmetic
+# csrc/vrg_grid_math.hpp)
+# ------------------------------------------------------------------------------------------------
+GRID_MODES = ("copy", "fast", "fast 2x2", "general", "linear")          # include/vrgdg_hip.h, enum vrg_grid_mode
+GRID_ROW_VALUES = 4096          # source values one wave stages at a time (csrc/vrg_grid_math.hpp): the most one column's taps may cover
+GRID_DESC = np.dtype([("src", "<u8"), ("xtab", "<u8"), ("ytab", "<u8"), ("overlay", "<u8"), ("height", "<i4"), ("width", "<i4"),
+                      ("channels", "<i4"), ("mode", "<i4"), ("frame", "<i4"), ("dst_x", "<i4"), ("dst_y", "<i4"), ("new_w", "<i4"),
+                      ("new_h", "<i4"), ("x_off", "<i4"), ("y_off", "<i4"), ("band", "<i4"), ("cps", "<i4"), ("inv", "<f4")])      # vrg_grid_desc
+_grid_tables: dict = {}         # (n_in, n_out, mode, device) -> the uploaded table of one axis; at most 256, the oldest leaves first
+_grid_lock = threading.Lock()
+
+
+@dataclass(frozen=True)
+class GridTile:
+    """One tile: the source size and what `_fit_frame_to_tile` makes of it."""
+    height: int
+    width: int
+    channels: int
+    new_w: int
+    new_h: int
+    x_off: int
+    y_off: int
+    mode: int
+    cps: int
+    inv: float
+    xtab: np.ndarray
+    ytab: np.ndarray
+
+
+@dataclass(frozen=True)
+class GridPlan:
+    cell_w: int
+    cell_h: int
+    columns: int
+    rows: int
+    band: int
+    tiles: tuple
+
+    @property
+    def grid_w(self) -> int:
+        return self.columns * self.cell_w
+
+    @property
+    def grid_h(self) -> int:
+        return self.rows * self.cell_h
+
+
+def grid_taps(n_in: int, n_out: int, mode: int) -> np.ndarray:
+    """The table of one axis of one resize in one mode, made on the host (AREA_CELL records, n_out of them)."""
+    table = np.zeros(int(n_out), dtype=AREA_CELL)
+    _hip.check(_host_lib().vrg_grid_taps(int(n_in), int(n_out), int(mode), C.c_void_p(table.ctypes.data)), "vrg_grid_taps")
+    return table
+
+
+def grid_tile(height: int, width: int, channels: int, cell_w: int, cell_h: int, band: int) -> GridTile:
+    """The geometry of `_fit_frame_to_tile` (LTXLoraTrain.py:8063-8074) in Python doubles, the rule cv2 takes for it and its tables."""
+    height, width, channels, cell_w, cell_h, band = (int(v) for v in (height, width, channels, cell_w, cell_h, band))
+    if channels not in (3, 4):
+        raise ValueError(f"video grid: frames must have 3 or 4 channels, got {channels}")
+    if height < 1 or width < 1:
+        raise ValueError("video grid: empty frames")
+    content_h = max(16, cell_h - band)
+    scale = min(float(cell_w) / max(1, width), float(content_h) / max(1, height))
+    new_w, new_h = max(1, int(round(width * scale))), max(1, int(round(height * scale)))
+    x_off, y_off = max(0, (cell_w - new_w) // 2), band + max(0, (content_h - new_h) // 2)
+    if y_off + new_h > cell_h or x_off + new_w > cell_w:
+        raise ValueError(f"video grid: the {new_w} x {new_h} picture at ({x_off}, {y_off}) does not fit the {cell_w} x {cell_h} tile "
+                         "(the reference's slice assignment fails here too)")
+    mode, cps, inv = C.c_int32(), C.c_int32(), C.c_float()
+    status = _host_lib().vrg_grid_plan(height, width, channels, new_h, new_w, C.byref(mode), C.byref(cps), C.byref(inv))
+    if status == _hip.VRG_ERR_UNSUPPORTED:
+        raise ValueError(f"video grid: one column of the {new_w} x {new_h} picture covers more than {GRID_ROW_VALUES} source values of a "
+                         f"{width}-wide row with {channels} channels (more than {GRID_ROW_VALUES // channels} pixels); the kernel does not take that")
+    _hip.check(status, "vrg_grid_plan")
+    return GridTile(height, width, channels, new_w, new_h, x_off, y_off, mode.value, cps.value, inv.value,
+                    grid_taps(width, new_w, mode.value), grid_taps(height, new_h, mode.value))
+
+
+def grid_plan(sizes, cell_w: int, cell_h: int, columns: int, band: int = 0) -> GridPlan:
+    """Sizes ``[(height, width, channels), ...]`` of the tiles' sources -> geometry, modes and tables; no GPU is needed."""
+    cell_w, cell_h, columns, band = int(cell_w), int(cell_h), int(columns), int(band)
+    sizes = [tuple(int(v) for v in s) for s in sizes]
+    if not sizes:
+        raise ValueError("video grid: no tiles")
+    if cell_w < 1 or cell_h < 1 or columns < 1 or band < 0:
+        raise ValueError("video grid: cell_w, cell_h, columns must be positive and band non-negative")
+    tiles = tuple(grid_tile(h, w, c, cell_w, cell_h, band) for h, w, c in sizes)
+    return GridPlan(cell_w, cell_h, columns, -(-len(sizes) // columns), band, tiles)
+
+
+def _grid_table(n_in, n_out, mode, table, device) -> torch.Tensor:
+    key = (n_in, n_out, mode, str(device))
+    t = _grid_tables.get(key)
+    if t is None:
+        t = torch.from_numpy(table.view(np.uint8).copy()).to(device)
+        with _grid_lock:
+            while len(_grid_tables) >= 256:
+                _grid_tables.pop(next(iter(_grid_tables)))
+            _grid_tables[key] = t
+    return t
+
+
+def _grid_overlays(plan: GridPlan, overlays, device):
+    """[tiles, band, cell_w, 3] uint8 on the device (or None) and which tiles have one"""
+    n = len(plan.tiles)
+    if overlays is None or plan.band == 0 or all(o is None for o in overlays):
+        return None, [False] * n
+    if len(overlays) != n:
+        raise ValueError(f"{len(overlays)} overlays for {n} tiles")
+    host = np.zeros((n, plan.band, plan.cell_w, 3), dtype=np.uint8)
+    has = []
+    for i, o in enumerate(overlays):
+        has.append(o is not None)
+        if o is not None:
+            o = np.asarray(o)
+            if o.dtype != np.uint8 or o.shape != (plan.band, plan.cell_w, 3):
+                raise ValueError(f"overlay {i} must be uint8 [{plan.band}, {plan.cell_w}, 3]")
+            host[i] = o
+    return torch.from_numpy(host).to(device), has
+
+
+def _grid_descriptors(plan: GridPlan, device, jobs, dev_overlays, has_overlay):
+    """The vrg_grid_desc records of jobs [(tile index or None for an empty cell, cell index, device frames [n, H, W, C] or None, first
+    output frame, source index per output frame (int array; -1: no picture))] and the tensors they point into."""
+    parts, keep = [], []
+    for tile_index, cell, source, first, index in jobs:
+        index = np.asarray(index, dtype=np.int64)
+        d = np.zeros(len(index), dtype=GRID_DESC)
+        d["frame"] = first + np.arange(len(index))
+        d["dst_x"], d["dst_y"] = (cell % plan.columns) * plan.cell_w, (cell // plan.columns) * plan.cell_h
+        d["band"] = plan.band
+        if tile_index is not None:
+            t = plan.tiles[tile_index]
+            if dev_overlays is not None and has_overlay[tile_index]:
+                d["overlay"] = dev_overlays[tile_index].data_ptr()
+            if source is not None:
+                if tuple(source.shape[1:]) != (t.height, t.width, t.channels) or not source.is_contiguous() or source.device != device:
+                    raise ValueError("video grid: a source does not match its plan")
+                if index.size and (int(index.max()) >= int(source.shape[0]) or int(index.min()) < -1):
+                    raise ValueError("video grid: a source frame index lies outside its batch")
+                xtab = _grid_table(t.width, t.new_w, t.mode, t.xtab, device)
+                ytab = _grid_table(t.height, t.new_h, t.mode, t.ytab, device)
+                keep += [source, xtab, ytab]
+                frame_bytes = t.height * t.width * t.channels * source.element_size()
+                d["src"] = np.where(index >= 0, source.data_ptr() + index * frame_bytes, 0).astype(np.uint64)
+                d["xtab"], d["ytab"] = xtab.data_ptr(), ytab.data_ptr()
+                for name in ("height", "width", "channels", "mode", "new_w", "new_h", "x_off", "y_off", "cps", "inv"):
+                    d[name] = getattr(t, name)
+        parts.append(d)
+    return (np.concatenate(parts) if parts else np.zeros(0, dtype=GRID_DESC)), keep
+
+
+def _grid_launch(plan: GridPlan, out: torch.Tensor, jobs, dev_overlays, has_overlay, byte_sources: bool):
+    """One launch (vrg_grid_tiles_f32 / _u8) of the jobs of _grid_descriptors into `out`, checked on the host first."""
+    frames = int(out.shape[0])
+    desc, _keep = _grid_descriptors(plan, out.device, jobs, dev_overlays, has_overlay)
+    if not len(desc):
+        return
+    lib = _hip.lib()
+    geometry = (frames, plan.cell_w, plan.cell_h, plan.grid_w, plan.grid_h)
+    _hip.check(lib.vrg_grid_check(C.c_void_p(desc.ctypes.data), len(desc), int(byte_sources), *geometry), "vrg_grid_check")
+    dev_desc = torch.from_numpy(desc.view(np.uint8)).to(out.device)
+    entry = lib.vrg_grid_tiles_u8 if byte_sources else lib.vrg_grid_tiles_f32
+    _hip.check(entry(_hip.ptr(dev_desc), len(desc), _hip.ptr(out), *geometry, _hip.current_stream()),
+               "vrg_grid_tiles_u8" if byte_sources else "vrg_grid_tiles_f32")
+
+
+def _grid_batches(batches, dtype):
+    out = []
+    for i, b in enumerate(batches):
+        if not isinstance(b, torch.Tensor) or b.ndim not in (3, 4):
+            raise ValueError(f"video grid: batch {i} must be a [frames, height, width, channels] or [height, width, channels] tensor")
+        if b.ndim == 3:
+            b = b.unsqueeze(0)
+        if int(b.shape[0]) < 1:
+            raise ValueError(f"video grid: batch {i} is empty")
+        if int(b.shape[3]) not in (3, 4):
+            raise ValueError(f"video grid: frames must have 3 or 4 channels, got {int(b.shape[3])}")
+        if b.dtype != dtype:
+            b = b.to(dtype)
+        out.append(b.detach())
+    if not out:
+        raise ValueError("video grid: no batches")
+    return out
+
+
+def _grid_out(plan: GridPlan, frames: int, device, out):
+    shape = (frames, plan.grid_h, plan.grid_w, 3)
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    if tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != device:
+        raise ValueError(f"out must be a contiguous float32 tensor shaped {shape} on {device}")
+    return out
+
+
+def _grid_run(batches, index, plan, overlays, out, byte_sources):
+    """Device-resident batches and the empty cells in one launch; every CPU batch through the page-locked ring in pieces along its frames,
+    one launch per piece for its tile alone.  index[i][f]: the frame of batch i that output frame f shows (-1: none)."""
+    from . import _devices
+    frames = len(index[0])
+    dev = next((b.device for b in batches if b is not None and b.is_cuda), None)
+    if any(b is not None and not b.is_cuda for b in batches):
+        if dev is not None and dev != _devices.compute_device():             # the page-locked ring uploads to the compute device
+            raise RuntimeError(f"video grid: CPU batches go to {_devices.compute_device()}, the CUDA batches live on {dev}; move them there")
+        dev = _devices.compute_device()
+    elif dev is None:
+        dev = _devices.compute_device()
+    with torch.cuda.device(dev):
+        out = _grid_out(plan, frames, dev, out)
+        dev_overlays, has = _grid_overlays(plan, overlays, dev)
+        jobs = [(None, cell, None, 0, np.full(frames, -1)) for cell in range(len(batches), plan.rows * plan.columns)]
+        for i, b in enumerate(batches):
+            if b is None:
+                jobs.append((i, i, None, 0, index[i]))
+            elif b.is_cuda:
+                if b.device != dev:
+                    raise RuntimeError(f"video grid: batch {i} lives on {b.device}, the grid on {dev}")
+                jobs.append((i, i, b.contiguous(), 0, index[i]))
+        _grid_launch(plan, out, jobs, dev_overlays, has, byte_sources)
+        for i, b in enumerate(batches):
+            if b is None or b.is_cuda:
+                continue
+            idx = np.asarray(index[i], dtype=np.int64)
+
+            def piece(gpu, first, i=i, idx=idx):
+                n = int(gpu.shape[0])
+                shown = np.nonzero((idx >= first) & (idx < first + n))[0]         # the output frames that show a frame of this piece
+                if first == 0:
+                    shown = np.union1d(shown, np.nonzero(idx < 0)[0])
+                for run in np.split(shown, np.nonzero(np.diff(shown) != 1)[0] + 1):
+                    if len(run):
+                        local = np.where(idx[run] >= 0, idx[run] - first, -1)
+                        _grid_launch(plan, out, [(i, i, gpu, int(run[0]), local)], dev_overlays, has, byte_sources)
+
+            _devices.upload_frames(b, piece)
+    return out
+
+
+def video_grid(batches, cell_w: int, cell_h: int, columns: int, band: int = 0, overlays=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The grid frames of VRGDG_VideoFolderGridPlot for IMAGE batches (``[F, H, W, C]`` or ``[H, W, C]`` fp32, C 3 or 4, on the GPU or on
+    the CPU, never written): fp32 ``[max F, rows * cell_h, columns * cell_w, 3]`` on the GPU.  A batch that has ended holds its last
+    frame.  ``overlays[i]``: uint8 ``[band, cell_w, 3]`` R,G,B or None, shown / 255 in the first ``band`` rows of tile i."""
+    batches = _grid_batches(batches, torch.float32)
+    plan = grid_plan([tuple(b.shape[1:]) for b in batches], cell_w, cell_h, columns, band)
+    frames = max(int(b.shape[0]) for b in batches)
+    index = [np.minimum(np.arange(frames), int(b.shape[0]) - 1) for b in batches]
+    return _grid_run(batches, index, plan, overlays, out, False)
+
+
+def video_grid_bytes(batches, index, cell_w: int, cell_h: int, columns: int, band: int = 0, overlays=None,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """video_grid for decoded B,G,R byte frames: uint8 ``[n, H, W, 3]`` per tile, or None for a tile that never had a picture (the
+    reference fits a black frame there).  ``index[i][f]`` names the frame of batch i that output frame f shows, -1 for none."""
+    prepared = [None if b is None else _grid_batches([b], torch.uint8)[0] for b in batches]
+    if any(b is not None and int(b.shape[3]) != 3 for b in prepared):
+        raise ValueError("video grid: decoded frames must have 3 channels")
+    shapes = [tuple(b.shape[1:]) if b is not None else (max(16, int(cell_h) - int(band)), int(cell_w), 3) for b in prepared]
+    plan = grid_plan(shapes, cell_w, cell_h, columns, band)
+    index = [np.asarray(ix, dtype=np.int64) for ix in index]
+    if len(index) != len(prepared) or len({len(ix) for ix in index}) != 1 or not len(index[0]):
+        raise ValueError("video grid: one index row per tile, all of one positive length")
+    index = [np.full(len(ix), -1) if b is None else ix for b, ix in zip(prepared, index)]
+    return _grid_run(prepared, index, plan, overlays, out, True)
+
+
+# ------------------------------------------------------------------------------------------------
 # The input of the Face Fix face detector (reference VRGDG_StandaloneFaceFixNodes.py:95-185, VRGDG_FaceFix.py:67-157): rotated scans and
 # 300 x 300 blobs in one launch (csrc/vrg_detect.hip, arithmetic csrc/vrg_detect_math.hpp)
 # ------------------------------------------------------------------------------------------------

@@ -747,6 +747,52 @@ int vrg_pil_paste_u8(const uint8_t* originals, const uint8_t* repaired, int64_t 
  * download of a pageable batch overlap like those of a page-locked one.  Blocks until the bytes are there.  No device work. */
 int vrg_host_copy(void* dst, const void* src, int64_t bytes, int32_t threads);
 
+/* ---------------------------------------------------------------------------------------------
+ * The Video Folder Grid Plot (VRGDG_VideoFolderGridPlot, LTXLoraTrain.py:7926-8314 of the reference), restated in csrc/vrg_grid_math.hpp:
+ * every tile of every output frame is quantised (np.clip(x * 255.0, 0, 255).astype(uint8): truncation; NaN gives 0), resized to
+ * new_w x new_h as cv2.resize(..., INTER_AREA) does on bytes -- unchanged, its integer fast paths, its general fp32 area sums, or its
+ * fixed-point bilinear rule with area-mode coefficients when an axis enlarges -- and written as (float)byte / 255.0f into the grid frame
+ * [frames][grid_h][grid_w][3] at (dst_y + y_off, dst_x + x_off); the first `band` rows of the tile take the overlay's bytes / 255, every
+ * other float of the cell_w x cell_h tile is 0.  One descriptor per (output frame, tile), empty cells included (src null): the launch writes
+ * every float of every tile it is given exactly once and reads no float of the grid.  Sources are never written.
+ *
+ * vrg_grid_plan gives, ON THE HOST, the rule (enum vrg_grid_mode) a resize of in_w x in_h to out_w x out_h takes, 1.0f / (sx * sy) of the
+ * fast rules and `cps`, the columns a wave stages at a time; VRG_ERR_UNSUPPORTED when the taps of one column pass the staging buffer.
+ * vrg_grid_taps fills, ON THE HOST, the n_out records of 20 bytes of one axis in one mode (int32 first sample, int32 count, three fp32:
+ * the weights of the first, the middle and the last tap; for VRG_GRID_LINEAR count is 1 or 2 and the first and the last hold the two
+ * integer coefficients 0 .. 2048).  A mode the pair (n_in, n_out) cannot take is VRG_ERR_BAD_ARG.
+ * vrg_grid_check refuses ON THE HOST (VRG_ERR_BAD_ARG) descriptors that name a frame or a tile outside the grid, a picture outside the
+ * tile or above the band, a mode other than vrg_grid_plan's, or a source of more than 2^31 - 1 values; the kernel writes nothing for a
+ * tile outside the grid and no picture for one outside its tile.
+ * vrg_grid_tiles_f32: sources are [height][width][channels] fp32 R,G,B frames, channels 3 or 4 (the fourth ignored), 4-byte aligned.
+ * vrg_grid_tiles_u8: sources are [height][width][3] decoded B,G,R byte frames (their own quantisation); the grid is R,G,B.
+ * `desc`, the tables and the overlays ([band][cell_w][3] bytes R,G,B) are device memory; n_desc == 0 succeeds without a launch.
+ * ------------------------------------------------------------------------------------------- */
+enum vrg_grid_mode { VRG_GRID_COPY = 0, VRG_GRID_FAST = 1, VRG_GRID_FAST_2X2 = 2, VRG_GRID_GENERAL = 3, VRG_GRID_LINEAR = 4 };
+
+typedef struct vrg_grid_desc {         /* one tile of one output frame */
+    const void* src;                   /* the source frame, or null: no picture */
+    const void* xtab;                  /* new_w records of vrg_grid_taps(width, new_w, mode) */
+    const void* ytab;                  /* new_h records of vrg_grid_taps(height, new_h, mode) */
+    const uint8_t* overlay;            /* the label band, or null */
+    int32_t height, width, channels, mode;
+    int32_t frame;                     /* the output frame */
+    int32_t dst_x, dst_y;              /* the tile's origin in the grid frame */
+    int32_t new_w, new_h, x_off, y_off;
+    int32_t band;                      /* rows of the overlay */
+    int32_t cps;                       /* vrg_grid_plan */
+    float inv;                         /* vrg_grid_plan */
+} vrg_grid_desc;
+
+int vrg_grid_plan(int32_t in_h, int32_t in_w, int32_t channels, int32_t out_h, int32_t out_w, int32_t* mode, int32_t* cps, float* inv);
+int vrg_grid_taps(int32_t n_in, int32_t n_out, int32_t mode, void* taps_host);
+int vrg_grid_check(const vrg_grid_desc* desc_host, int64_t n_desc, int32_t bytes, int64_t frames, int32_t cell_w, int32_t cell_h,
+                   int32_t grid_w, int32_t grid_h);
+int vrg_grid_tiles_f32(const vrg_grid_desc* desc, int64_t n_desc, float* out, int64_t frames, int32_t cell_w, int32_t cell_h,
+                       int32_t grid_w, int32_t grid_h, void* stream);
+int vrg_grid_tiles_u8(const vrg_grid_desc* desc, int64_t n_desc, float* out, int64_t frames, int32_t cell_w, int32_t cell_h,
+                      int32_t grid_w, int32_t grid_h, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
