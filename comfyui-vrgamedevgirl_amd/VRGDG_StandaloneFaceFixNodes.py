@@ -9,7 +9,12 @@ launch, downloaded once); a host loop over the frames in order that asks the nod
 and keeps the reference's smoothing / reset bookkeeping in float32 numpy (aligned_transforms); one composite pass in which the frames with
 a transform blend cv2's byte Lanczos-4 affine warp of those bytes (csrc/vrg_warp_math.hpp) and the others the bicubic face.  Detection
 is a seam: `estimator` is a class attribute, None by default -- the reference's behaviour when its detector cannot be created: every frame
-takes the fallback path and the result is the opaque composite's.  INTEGRATION.md binds the reference's detector to it.  The module's
+takes the fallback path and the result is the opaque composite's.  INTEGRATION.md binds the reference's detector to it.  A finer seam
+moves the estimator's first act -- cv2.resize(face, (320, 320), INTER_AREA) and the R,G,B -> B,G,R flip -- to the GPU as well: with
+`landmark_detector(bgr_320) -> faces | None` and `transform_fit(generated_points, source_points) -> 2 x 3 | None` set (and no
+`estimator`), phase 1 makes the 320 x 320 thumbnails of both faces in one more launch (ops.face_thumbs, csrc/vrg_thumbs.hip) and downloads
+those alone, 614,400 bytes per frame whatever the box; `landmark_points` scales the detector's rows back to the box on the host and
+`cv2_landmark_seams()` builds both callables on cv2's FaceDetectorYN where cv2 and the model file exist.  The module's
 NODE_CLASS_MAPPINGS keeps its two keys (an existing test pins that set); the new node is listed in LANDMARK_NODE_CLASS_MAPPINGS /
 LANDMARK_NODE_DISPLAY_NAME_MAPPINGS beside them.
 
@@ -46,6 +51,7 @@ than 3 channels.
 from __future__ import annotations
 
 import math
+import os
 import sys
 
 import numpy as np
@@ -581,8 +587,73 @@ def _quantise_host(values: torch.Tensor) -> np.ndarray:
     return np.where(np.isnan(r), np.float32(0), r).astype(np.uint8)
 
 
-def _aligned_composite(plan, feather, transform_smoothing, estimator):
-    """(frames, masks, aligned) wherever the originals live."""
+LANDMARK_INPUT = ops.THUMB_SIDE                        # YuNet's input is fixed at 320 x 320
+
+
+def landmark_points(faces, width, height):
+    """The five landmarks of the best face among the detector's `[n, 15]` rows (box, right eye, left eye, nose, right and left mouth
+    corner, score), scaled from the 320 x 320 thumbnail back to the width x height box: float32 `[5, 2]`, or None without a face
+    (`_landmarks`, :971-979).  The row with the largest score wins, the first one on ties; each axis is multiplied by the quotient
+    side / 320 formed in double and rounded to float32 once, as NumPy does when a Python float meets a float32 array."""
+    if faces is None or len(faces) == 0:
+        return None
+    best = 0
+    for i in range(1, len(faces)):
+        if float(faces[i][-1]) > float(faces[best][-1]):
+            best = i
+    points = np.array(np.asarray(faces[best])[4:14], dtype=np.float32).reshape(5, 2)
+    scale = np.array([np.float32(float(width) / float(LANDMARK_INPUT)), np.float32(float(height) / float(LANDMARK_INPUT))], dtype=np.float32)
+    return points * scale[None, :]
+
+
+def cv2_landmark_seams():
+    """(landmark_detector, transform_fit) on cv2's FaceDetectorYN with the reference's arguments ("", (320, 320), 0.1, 0.3, 5000) and
+    cv2.estimateAffinePartial2D(..., RANSAC, 3.0), or None when cv2 cannot be imported, has no FaceDetectorYN, the model file
+    assets/face_detection_yunet_2023mar.onnx is not in the package (it is not shipped) or the detector cannot be created -- the
+    reference's own `_detector` guard, after which every frame takes the fallback."""
+    try:
+        import cv2
+    except Exception:
+        return None
+    model = os.path.join(os.path.dirname(os.path.abspath(__file__)), "assets", "face_detection_yunet_2023mar.onnx")
+    create = getattr(cv2, "FaceDetectorYN_create", None)
+    if create is None:
+        create = getattr(getattr(cv2, "FaceDetectorYN", None), "create", None)
+    if not callable(create) or not os.path.isfile(model):
+        return None
+    try:
+        detector = create(model, "", (LANDMARK_INPUT, LANDMARK_INPUT), 0.1, 0.3, 5000)
+    except Exception:
+        return None
+
+    def landmark_detector(bgr_320):
+        detector.setInputSize((LANDMARK_INPUT, LANDMARK_INPUT))
+        try:
+            result = detector.detect(np.ascontiguousarray(bgr_320))
+        except cv2.error:
+            return None
+        return result[1] if isinstance(result, tuple) and len(result) > 1 else result
+
+    def transform_fit(generated_points, source_points):
+        return cv2.estimateAffinePartial2D(generated_points, source_points, method=cv2.RANSAC, ransacReprojThreshold=3.0)[0]
+
+    return landmark_detector, transform_fit
+
+
+def _packed_source_bytes(faces, originals, entries, usable):
+    """Host-fed originals: every box quantised on the CPU (_quantise_host) and packed at faces.offsets, as face_bytes packs the device's"""
+    packed = np.zeros(int(faces.generated.numel()), dtype=np.uint8)
+    for index in range(min(int(usable), len(faces.offsets))):
+        if faces.offsets[index] < 0 or min(faces.sizes[index]) < 2:
+            continue
+        left, top, right, bottom = (int(v) for v in entries[index]["box"])
+        box = _quantise_host(originals[index, top:bottom, left:right, :3].cpu())
+        packed[faces.offsets[index]:faces.offsets[index] + box.size] = box.reshape(-1)
+    return packed
+
+
+def _aligned_composite(plan, feather, transform_smoothing, estimator, seams=None):
+    """(frames, masks, aligned) wherever the originals live.  `seams` = (landmark_detector, transform_fit): the thumbnail route."""
     work, originals, entries, offset = plan.work, plan.originals, plan.entries, plan.offset
     n_work, n_orig = plan.work_frames, int(originals.shape[0])
     rule = ops.CompositeRule("opaque", feather=feather)
@@ -597,16 +668,36 @@ def _aligned_composite(plan, feather, transform_smoothing, estimator):
         originals_dev = None if host_fed or not originals.is_cuda else originals.to(torch.float32)
         # phase 1: the faces as bytes, made on the GPU and downloaded once; the source bytes too when the originals are there
         faces = ops.face_bytes(work_dev, rows, height, width, originals=originals_dev)
-        generated_host = faces.generated.cpu().numpy()
-        source_host = faces.source.cpu().numpy() if faces.source is not None else None
+        if seams is None:
+            generated_host = faces.generated.cpu().numpy()
+            source_host = faces.source.cpu().numpy() if faces.source is not None else None
+        else:
+            # the 320 x 320 B,G,R thumbnails of both faces, made on the GPU; nothing else is downloaded
+            packed = None if faces.source is not None else torch.from_numpy(_packed_source_bytes(faces, originals, entries, plan.usable)).to(dev)
+            thumbs, thumb_row = ops.face_thumbs(faces, ("source", "generated"), source=packed)
+            thumbs_host = thumbs.cpu().numpy()
 
-    def estimate(index):
+    def estimate_from_faces(index):
         left, top, right, bottom = (int(v) for v in entries[index]["box"])
         if source_host is not None:
             source = faces.image(source_host, index)
         else:
             source = _quantise_host(originals[index, top:bottom, left:right, :3].cpu())
         return estimator(source, faces.image(generated_host, index))
+
+    def estimate_from_thumbs(index):
+        row = thumb_row[index]
+        if row < 0:                                         # a side below 2: `_landmarks` gives no points and resizes nothing
+            return None
+        detect, fit = seams
+        box_w, box_h = faces.sizes[index]
+        found_source, found_generated = detect(thumbs_host[row, 0]), detect(thumbs_host[row, 1])          # both, always, in this order
+        source_points, generated_points = landmark_points(found_source, box_w, box_h), landmark_points(found_generated, box_w, box_h)
+        if source_points is None or generated_points is None:
+            return None
+        return fit(generated_points, source_points)
+
+    estimate = estimate_from_faces if seams is None else estimate_from_thumbs
 
     # phase 2: the estimator and the smoothing / reset rules, frame by frame on the host
     transforms, aligned = aligned_transforms(entries, plan.usable, transform_smoothing, estimate)
@@ -638,6 +729,12 @@ class VRGDGFaceFixCompositeLandmarkAligned:
     #: `estimator(source_u8, generated_u8) -> 2 x 3 | None`: the transform that carries the generated face's landmarks onto the source's
     #: ([h, w, 3] uint8 RGB each), or None when either face gives no landmarks.  None = no detector: every frame takes the fallback.
     estimator = None
+    #: The finer seam, used when `estimator` is None and both are set: the estimator's resize runs on the GPU and only 320 x 320 B,G,R
+    #: thumbnails are downloaded.  `landmark_detector(bgr_320) -> faces | None`: the `[n, 15]` YuNet rows of one [320, 320, 3] uint8 image
+    #: (None or empty: no face); `transform_fit(generated_points, source_points) -> 2 x 3 | None` on float32 [5, 2] points in box
+    #: coordinates.  cv2_landmark_seams() builds both on cv2.  Assign functions with staticmethod(...), like `estimator`.
+    landmark_detector = None
+    transform_fit = None
 
     @classmethod
     def INPUT_TYPES(cls):
@@ -661,11 +758,14 @@ class VRGDGFaceFixCompositeLandmarkAligned:
         feather = int(feather_pixels) if int(feather_pixels) > 0 else 0
         repaired = plan.repaired(_has_area)
         estimator = self.estimator
-        if estimator is None or repaired == 0:
+        seams = None
+        if estimator is None and self.landmark_detector is not None and self.transform_fit is not None:
+            seams = (self.landmark_detector, self.transform_fit)
+        if (estimator is None and seams is None) or repaired == 0:
             output, masks = _composite(plan, ops.CompositeRule("opaque", feather=feather), 0.0)
             aligned = 0
         else:
-            output, masks, aligned = _aligned_composite(plan, feather, smoothing, estimator)
+            output, masks, aligned = _aligned_composite(plan, feather, smoothing, estimator, seams)
         _log(f"Landmark composite finished: repaired={repaired}, aligned={aligned}, fallback={repaired - aligned}, feather={feather_pixels}, "
              f"smoothing={smoothing:.2f}.")
         return output, masks, repaired

@@ -143,7 +143,15 @@ class GridDesc(C.Structure):
                 ("band", C.c_int32), ("cps", C.c_int32), ("inv", C.c_float)]
 
 
+class ThumbDesc(C.Structure):
+    """vrg_thumb_desc"""
+    _fields_ = [("xtab", C.c_void_p), ("ytab", C.c_void_p), ("offset", C.c_int64), ("which", C.c_int32),
+                ("box_w", C.c_int32), ("box_h", C.c_int32), ("mode", C.c_int32), ("cps", C.c_int32), ("inv", C.c_float)]
+
+
 GRID_COPY, GRID_FAST, GRID_FAST_2X2, GRID_GENERAL, GRID_LINEAR = 0, 1, 2, 3, 4
+THUMB_SIDE = 320                # include/vrgdg_hip.h: VRG_THUMB_SIDE
+THUMB_MAX_SIDE = 32767          # include/vrgdg_hip.h: VRG_THUMB_MAX_SIDE
 PIL_STATS_WORDS = 12            # uint32 per frame (csrc/vrg_pil_math.hpp: PIL_STATS_WORDS)
 PIL_MAX_LINE = 8192             # the longest mask row / column (csrc/vrg_pil_math.hpp: PIL_MAX_LINE)
 FACEFIX_STATS_WORDS = 12        # uint64 per frame (csrc/vrg_facefix_math.hpp: FF_STATS_WORDS)
@@ -239,6 +247,8 @@ _SIGNATURES = {
     "vrg_grid_tiles_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int64] + [C.c_int32] * 4 + [_P]),
     "vrg_grid_tiles_u8": (C.c_int, [_P, C.c_int64, _P, C.c_int64] + [C.c_int32] * 4 + [_P]),
     "vrg_warp_linear_u8": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P, _P]),
+    "vrg_face_thumbs_check": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int]),
+    "vrg_face_thumbs_u8": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
 }
 
 # include/vrgdg_hip_debug.h: self-tests and probes -- for the test suite and the measurement tools, not part of the drop-in boundary

@@ -1129,6 +1129,85 @@ def face_bytes(crops: torch.Tensor, entries, height: int, width: int, originals:
     return FaceBytes(generated, source, offsets, sizes)
 
 
+THUMB_SIDE = _hip.THUMB_SIDE    # the landmark network's input is 320 x 320
+THUMB_DESC = np.dtype([("xtab", "<u8"), ("ytab", "<u8"), ("offset", "<i8"), ("which", "<i4"), ("box_w", "<i4"), ("box_h", "<i4"),
+                       ("mode", "<i4"), ("cps", "<i4"), ("inv", "<f4")])                         # vrg_thumb_desc
+assert THUMB_DESC.itemsize == C.sizeof(_hip.ThumbDesc) == 48
+_THUMB_WHICH = {"generated": 0, "source": 1}
+
+
+def thumb_plan(box_h: int, box_w: int):
+    """(mode, cps, inv) of the resize of a box_w x box_h byte image to 320 x 320: vrg_grid_plan on the host (no GPU needed)"""
+    mode, cps, inv = C.c_int32(), C.c_int32(), C.c_float()
+    _hip.check(_host_lib().vrg_grid_plan(int(box_h), int(box_w), 3, THUMB_SIDE, THUMB_SIDE, C.byref(mode), C.byref(cps), C.byref(inv)),
+               "vrg_grid_plan")
+    return mode.value, cps.value, inv.value
+
+
+def thumb_descriptors(jobs):
+    """The vrg_thumb_desc records of jobs [(which 0 | 1, byte offset, box_w, box_h)] with the table pointers still relative, and the
+    tables they name: (records, table bytes, [(record index, field, byte position in the tables)]).  One table per distinct
+    (n_in, mode), made by grid_taps on the host (no GPU needed)."""
+    desc = np.zeros(len(jobs), dtype=THUMB_DESC)
+    tables, where, fix, plans = [], {}, [], {}
+    for i, (which, offset, w, h) in enumerate(jobs):
+        if (w, h) not in plans:
+            plans[(w, h)] = thumb_plan(h, w)
+        mode, cps, inv = plans[(w, h)]
+        desc[i] = (0, 0, offset, which, w, h, mode, cps, inv)
+        for field, n_in in (("xtab", w), ("ytab", h)):
+            if (n_in, mode) not in where:
+                where[(n_in, mode)] = len(tables) * THUMB_SIDE * AREA_CELL.itemsize
+                tables.append(grid_taps(n_in, THUMB_SIDE, mode))
+            fix.append((i, field, where[(n_in, mode)]))
+    return desc, (np.concatenate(tables).view(np.uint8) if tables else np.zeros(0, dtype=np.uint8)), fix
+
+
+def face_thumbs(faces: FaceBytes, which=("source", "generated"), source: Optional[torch.Tensor] = None):
+    """The landmark estimator's input for every entry of `faces` that has an image of at least 2 x 2 pixels (the reference's `_landmarks`
+    returns no landmarks below that and resizes nothing): ``cv2.cvtColor(cv2.resize(image, (320, 320), interpolation=cv2.INTER_AREA),
+    cv2.COLOR_RGB2BGR)`` of the packed byte images, one launch (vrg_face_thumbs_u8).  Returns (uint8 ``[n, k, 320, 320, 3]`` B,G,R on the
+    device, k = len(which) in that order; index[f] = the entry's row, -1 = none).  `source`: the packed source bytes at `faces.offsets`
+    when face_bytes made none (host-fed originals: the node quantises the boxes on the CPU and uploads this one buffer)."""
+    names = tuple(which)
+    if not names or any(n not in _THUMB_WHICH for n in names):
+        raise ValueError(f"which must name 'source' and / or 'generated', got {which!r}")
+    with torch.cuda.device(faces.generated.device):             # the stream and the pointers belong to the bytes' GPU (_on_device)
+        return _face_thumbs(faces, names, source)
+
+
+def _face_thumbs(faces, names, source):
+    g = faces.generated
+    src = faces.source if faces.source is not None else source
+    if "source" in names and src is None:
+        raise ValueError("face_thumbs: there are no source bytes (face_bytes ran without device originals and no `source` was given)")
+    if src is not None and (src.dtype != torch.uint8 or src.device != g.device or not src.is_contiguous() or src.numel() < g.numel()):
+        raise ValueError("face_thumbs: source must be a contiguous uint8 buffer of the size of faces.generated on its device")
+    k = len(names)
+    index, jobs = [], []
+    for offset, size in zip(faces.offsets, faces.sizes):
+        if offset < 0 or size is None or size[0] < 2 or size[1] < 2:
+            index.append(-1)
+            continue
+        index.append(len(jobs) // k)
+        jobs += [(_THUMB_WHICH[n], offset, size[0], size[1]) for n in names]
+    out = torch.empty((len(jobs) // k, k, THUMB_SIDE, THUMB_SIDE, 3), dtype=torch.uint8, device=g.device)
+    if not jobs:
+        return out, index
+    desc, tables, fix = thumb_descriptors(jobs)
+    records = torch.empty(desc.nbytes + tables.nbytes, dtype=torch.uint8, device=g.device)
+    base = records.data_ptr() + desc.nbytes
+    for i, field, at in fix:
+        desc[field][i] = base + at
+    n_bytes = int(g.numel())
+    lib = _hip.lib()
+    _hip.check(lib.vrg_face_thumbs_check(C.c_void_p(desc.ctypes.data), len(desc), n_bytes, int(src is not None)), "vrg_face_thumbs_check")
+    records.copy_(torch.from_numpy(np.concatenate([desc.view(np.uint8), tables])))
+    _hip.check(lib.vrg_face_thumbs_u8(_hip.ptr(g), _hip.ptr(src) if src is not None else None, n_bytes, _hip.ptr(records), len(desc),
+                                      _hip.ptr(out), _hip.current_stream()), "vrg_face_thumbs_u8")
+    return out, index
+
+
 @_on_device
 def warp_affine_u8(frames_u8: torch.Tensor, transforms, out_w: int, out_h: int) -> torch.Tensor:
     """``cv2.warpAffine(frame, transform, (out_w, out_h), flags=cv2.INTER_LANCZOS4, borderMode=cv2.BORDER_REFLECT101)`` on every frame of

@@ -793,6 +793,38 @@ int vrg_grid_tiles_f32(const vrg_grid_desc* desc, int64_t n_desc, float* out, in
 int vrg_grid_tiles_u8(const vrg_grid_desc* desc, int64_t n_desc, float* out, int64_t frames, int32_t cell_w, int32_t cell_h,
                       int32_t grid_w, int32_t grid_h, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The input of the landmark estimator (VRGDGFaceFixCompositeLandmarkAligned._landmarks, VRGDG_StandaloneFaceFixNodes.py:955-979 of the
+ * reference): cv2.cvtColor(cv2.resize(rgb, (320, 320), interpolation=cv2.INTER_AREA), COLOR_RGB2BGR) of the packed byte images
+ * vrg_face_bytes_u8 writes, for a list of descriptors in one launch.  out = [n_desc][320][320][3] bytes B,G,R, 16-byte aligned: channel c
+ * is channel 2 - c of the resize, which takes the rule, the tables and the arithmetic of the grid plot above
+ * (vrg_grid_plan(box_h, box_w, 3, 320, 320, ...), vrg_grid_taps(box_w | box_h, 320, mode)).  Every byte of every thumbnail is written
+ * exactly once, nothing else is, and the images are never written.
+ *
+ * vrg_face_thumbs_check refuses ON THE HOST (VRG_ERR_BAD_ARG) a side below 1 or above 32767, a `which` outside {0, 1}, which == 1 without
+ * a source buffer (has_source == 0), an image that does not end inside n_bytes, a mode, cps or inv other than vrg_grid_plan's and a null
+ * table.  vrg_face_thumbs_u8: `desc` and the tables are device memory; n_desc == 0 succeeds without a launch; a null or misaligned out
+ * and an out that is one of the inputs are argument errors; the kernel writes nothing for a descriptor whose image does not lie inside
+ * n_bytes (or that names a buffer that is not there).
+ * ------------------------------------------------------------------------------------------- */
+#define VRG_THUMB_SIDE 320
+#define VRG_THUMB_MAX_SIDE 32767
+
+typedef struct vrg_thumb_desc {        /* one thumbnail */
+    const void* xtab;                  /* 320 records of vrg_grid_taps(box_w, 320, mode) */
+    const void* ytab;                  /* 320 records of vrg_grid_taps(box_h, 320, mode) */
+    int64_t offset;                    /* bytes from `generated` / `source` to the [box_h][box_w][3] R,G,B image, any alignment */
+    int32_t which;                     /* 0: generated, 1: source */
+    int32_t box_w, box_h;
+    int32_t mode;                      /* enum vrg_grid_mode, vrg_grid_plan */
+    int32_t cps;                       /* vrg_grid_plan */
+    float inv;                         /* vrg_grid_plan */
+} vrg_thumb_desc;
+
+int vrg_face_thumbs_check(const vrg_thumb_desc* desc_host, int64_t n_desc, int64_t n_bytes, int has_source);
+int vrg_face_thumbs_u8(const uint8_t* generated, const uint8_t* source, int64_t n_bytes, const vrg_thumb_desc* desc, int64_t n_desc,
+                       uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
