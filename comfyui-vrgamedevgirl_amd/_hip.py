@@ -149,11 +149,23 @@ class ThumbDesc(C.Structure):
                 ("box_w", C.c_int32), ("box_h", C.c_int32), ("mode", C.c_int32), ("cps", C.c_int32), ("inv", C.c_float)]
 
 
+class SheetPanel(C.Structure):
+    """vrg_sheet_panel"""
+    _fields_ = [("src", C.c_void_p), ("h_table", C.c_int64), ("v_table", C.c_int64), ("span_offset", C.c_int64), ("tmp_offset", C.c_int64),
+                ("src_h", C.c_int32), ("src_w", C.c_int32), ("channels", C.c_int32), ("new_w", C.c_int32), ("new_h", C.c_int32),
+                ("h_ksize", C.c_int32), ("v_ksize", C.c_int32), ("win_x", C.c_int32), ("win_y", C.c_int32), ("pic_w", C.c_int32),
+                ("pic_h", C.c_int32), ("row0", C.c_int32), ("rows", C.c_int32), ("left", C.c_int32), ("top", C.c_int32), ("w", C.c_int32),
+                ("h", C.c_int32), ("pic_x", C.c_int32), ("pic_y", C.c_int32), ("cps", C.c_int32), ("cell", C.c_uint8 * 4),
+                ("reserved", C.c_int32)]
+
+
 GRID_COPY, GRID_FAST, GRID_FAST_2X2, GRID_GENERAL, GRID_LINEAR = 0, 1, 2, 3, 4
 THUMB_SIDE = 320                # include/vrgdg_hip.h: VRG_THUMB_SIDE
 THUMB_MAX_SIDE = 32767          # include/vrgdg_hip.h: VRG_THUMB_MAX_SIDE
 PIL_STATS_WORDS = 12            # uint32 per frame (csrc/vrg_pil_math.hpp: PIL_STATS_WORDS)
 PIL_MAX_LINE = 8192             # the longest mask row / column (csrc/vrg_pil_math.hpp: PIL_MAX_LINE)
+SHEET_MAX_SIDE = 32767          # include/vrgdg_hip.h: VRG_SHEET_MAX_SIDE
+SHEET_STAGE_VALUES = 16384      # include/vrgdg_hip.h: VRG_SHEET_STAGE_VALUES
 FACEFIX_STATS_WORDS = 12        # uint64 per frame (csrc/vrg_facefix_math.hpp: FF_STATS_WORDS)
 
 _F3 = C.c_float * 3
@@ -249,6 +261,15 @@ _SIGNATURES = {
     "vrg_warp_linear_u8": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     "vrg_face_thumbs_check": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int]),
     "vrg_face_thumbs_u8": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
+    "vrg_sheet_fit": (C.c_int, [C.c_int32] * 5 + [_P]),
+    "vrg_sheet_plan": (C.c_int, [_P, C.c_int64, _P, C.c_int64]),
+    "vrg_sheet_check": (C.c_int, [_P, C.c_int64, C.c_int32, _P, C.c_int64, C.c_int64, C.c_int64]),
+    "vrg_sheet_rows_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
+    "vrg_sheet_rows_u8": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
+    "vrg_sheet_compose_f32": (C.c_int, [_P, C.c_int64, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, C.c_int32, C.c_int32,
+                                        C.c_uint32, _P]),
+    "vrg_sheet_compose_u8": (C.c_int, [_P, C.c_int64, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, C.c_int32, C.c_int32,
+                                       C.c_uint32, _P]),
 }
 
 # include/vrgdg_hip_debug.h: self-tests and probes -- for the test suite and the measurement tools, not part of the drop-in boundary

@@ -2799,3 +2799,257 @@ class HipEvent:
                     _hip.lib().vrg_event_destroy(self._ev)
         except Exception:
             pass
+
+
+# ------------------------------------------------------------------------------------------------
+# Reference sheets (reference VRGDG_LTXICIngredientsGrid.py and VRGDG_MusicVideoBuilderNodes.py:7169-7238): pictures quantised, resized
+# with Pillow's LANCZOS and pasted as panels onto a coloured canvas, in two launches (csrc/vrg_sheet.hip, arithmetic
+# csrc/vrg_sheet_math.hpp)
+# ------------------------------------------------------------------------------------------------
+SHEET_PANEL = np.dtype([("src", "<u8"), ("h_table", "<i8"), ("v_table", "<i8"), ("span_offset", "<i8"), ("tmp_offset", "<i8"), ("src_h", "<i4"),
+                        ("src_w", "<i4"), ("channels", "<i4"), ("new_w", "<i4"), ("new_h", "<i4"), ("h_ksize", "<i4"), ("v_ksize", "<i4"),
+                        ("win_x", "<i4"), ("win_y", "<i4"), ("pic_w", "<i4"), ("pic_h", "<i4"), ("row0", "<i4"), ("rows", "<i4"), ("left", "<i4"),
+                        ("top", "<i4"), ("w", "<i4"), ("h", "<i4"), ("pic_x", "<i4"), ("pic_y", "<i4"), ("cps", "<i4"), ("cell", "u1", (4,)),
+                        ("reserved", "<i4")])                                   # vrg_sheet_panel
+assert SHEET_PANEL.itemsize == C.sizeof(_hip.SheetPanel) == 128
+SHEET_FITS = ("contain_pad", "cover_crop", "resize")
+
+
+@dataclass(frozen=True)
+class SheetPanel:
+    """One pasted picture: ``source`` indexes the sources, ``rect`` = (left, top, width, height) on the canvas, ``fit`` is "contain_pad" or
+    "cover_crop" (or "resize": the picture resized to the rectangle itself, as the Builder sheets paste it), ``cell`` the (R, G, B) bytes
+    around a contained picture, ``radius`` the corner radius (0: a plain paste; above 0 the
+    paste goes under ``ImageDraw.rounded_rectangle``'s mask with radius min(radius, width // 2, height // 2))."""
+    source: int
+    rect: tuple
+    fit: str = "contain_pad"
+    cell: tuple = (0, 0, 0)
+    radius: int = 0
+
+
+@functools.lru_cache(maxsize=512)
+def sheet_lanczos_table(n_in: int, n_out: int):
+    """(ksize, the table of one axis as the kernels read it: bounds [n_out, 2] then weights [n_out, ksize], int32) of
+    ``Image.resize(..., LANCZOS)``; host only, cached per (n_in, n_out)"""
+    lib = _host_lib()
+    ksize = int(lib.vrg_pil_lanczos_ksize(n_in, n_out))
+    if ksize < 1:
+        raise ValueError("sheet_lanczos_table: sizes must be at least 1")
+    table = np.zeros(n_out * (2 + ksize), dtype=np.int32)
+    rc = lib.vrg_pil_lanczos_table(n_in, n_out, C.c_void_p(table.ctypes.data), C.c_void_p(table[2 * n_out:].ctypes.data))
+    if rc != _hip.VRG_OK:
+        raise ValueError(f"vrg_pil_lanczos_table refused {n_in} -> {n_out}")
+    table.setflags(write=False)
+    return ksize, table
+
+
+@functools.lru_cache(maxsize=512)
+def rounded_spans(width: int, height: int, radius: int) -> np.ndarray:
+    """[height, 2] int32: the first and last column that ``ImageDraw.rounded_rectangle((0, 0, width - 1, height - 1), radius, fill=255)``
+    sets in every row of a ``width`` x ``height`` L mask (first > last: none) -- from Pillow itself, cached per (width, height, radius).
+    Every row of that mask is one run; a 1 x 1 mask is empty."""
+    from PIL import Image, ImageDraw
+    if width < 1 or height < 1 or radius < 0:
+        raise ValueError("rounded_spans: width and height must be at least 1, radius at least 0")
+    mask = Image.new("L", (width, height), 0)
+    ImageDraw.Draw(mask).rounded_rectangle((0, 0, width - 1, height - 1), radius=radius, fill=255)
+    plane = np.asarray(mask) != 0
+    any_set = plane.any(axis=1)
+    first = plane.argmax(axis=1)
+    last = width - 1 - plane[:, ::-1].argmax(axis=1)
+    if int(plane.sum()) != int((last - first + 1)[any_set].sum()):
+        raise RuntimeError("rounded_spans: a row of Pillow's rounded rectangle is not one run")
+    spans = np.where(any_set[:, None], np.stack([first, last], axis=1), np.array([[1, 0]])).astype(np.int32)
+    spans.setflags(write=False)
+    return spans
+
+
+def _sheet_rc(rc: int, what: str):
+    """_hip.check without the device its error strings need"""
+    if rc == _hip.VRG_ERR_BAD_ARG:
+        raise ValueError(f"{what}: invalid argument")
+    if rc != _hip.VRG_OK:
+        raise RuntimeError(f"{what}: " + ("not supported: a side above 32767, or the taps of one column do not fit the staging buffer"
+                                          if rc == _hip.VRG_ERR_UNSUPPORTED else f"error {rc}"))
+
+
+class SheetPlan:
+    """The host side of one reference sheet: the vrg_sheet_panel records (``records``, without source pointers), the axis tables back to
+    back (``tables``), the mask rows (``spans``), the size of the temp images and the grid of the first launch.  No device is needed.
+    ``shapes``: (height, width, channels) per source."""
+
+    def __init__(self, shapes, panels, canvas_size, background):
+        lib = _host_lib()
+        self.width, self.height = int(canvas_size[0]), int(canvas_size[1])
+        if self.width < 1 or self.height < 1 or self.width > _hip.SHEET_MAX_SIDE or self.height > _hip.SHEET_MAX_SIDE:
+            raise ValueError(f"reference sheet: the canvas must be 1 .. {_hip.SHEET_MAX_SIDE} pixels a side")
+        self.background = _sheet_colour(background, "background")
+        self.panels = [p if isinstance(p, SheetPanel) else SheetPanel(*p) for p in panels]
+        rec = np.zeros(len(self.panels), dtype=SHEET_PANEL)
+        tables, table_at, spans, span_at, n_ints, n_spans, tmp_bytes = [], {}, [], {}, 0, 0, 0
+        fit = np.zeros(8, dtype=np.int32)
+        for i, p in enumerate(self.panels):
+            if not 0 <= int(p.source) < len(shapes):
+                raise ValueError(f"reference sheet: panel {i} names source {p.source} of {len(shapes)}")
+            if p.fit not in SHEET_FITS:
+                raise ValueError(f"reference sheet: fit mode must be one of {SHEET_FITS}, got {p.fit!r}")
+            sh, sw, sc = (int(v) for v in shapes[int(p.source)])
+            left, top, w, h = (int(v) for v in p.rect)
+            if sc == 2 or sc < 1:
+                raise ValueError(f"reference sheet: a source has {sc} channels; 1, 3 or more are taken (Pillow refuses two as well)")
+            if w < 1 or h < 1 or sw < 1 or sh < 1:
+                raise ValueError("reference sheet: panels and sources must be at least 1 x 1")
+            if p.fit == "resize":
+                fit[:] = (w, h, 0, 0, w, h, 0, 0)
+            else:
+                _sheet_rc(lib.vrg_sheet_fit(sw, sh, w, h, int(p.fit == "cover_crop"), C.c_void_p(fit.ctypes.data)), "vrg_sheet_fit")
+            r = rec[i]
+            r["src_h"], r["src_w"], r["channels"] = sh, sw, sc
+            r["left"], r["top"], r["w"], r["h"] = left, top, w, h
+            for name, v in zip(("new_w", "new_h", "win_x", "win_y", "pic_w", "pic_h", "pic_x", "pic_y"), fit):
+                r[name] = int(v)
+            if max(int(fit[0]), int(fit[1])) > _hip.SHEET_MAX_SIDE:
+                raise RuntimeError(f"reference sheet: panel {i} resizes its source to more than {_hip.SHEET_MAX_SIDE} pixels a side")
+            for axis, (n_in, n_out) in enumerate(((sw, int(fit[0])), (sh, int(fit[1])))):
+                if n_in == n_out:
+                    continue
+                if (n_in, n_out) not in table_at:
+                    ksize, table = sheet_lanczos_table(n_in, n_out)
+                    table_at[(n_in, n_out)] = (n_ints, ksize)
+                    tables.append(table)
+                    n_ints += len(table)
+                r["v_table" if axis else "h_table"], r["v_ksize" if axis else "h_ksize"] = table_at[(n_in, n_out)]
+            r["cell"][:3] = _sheet_colour(p.cell, "cell colour")
+            r["span_offset"] = -1
+            if int(p.radius) > 0:
+                key = (w, h, min(int(p.radius), w // 2, h // 2))
+                if key not in span_at:
+                    span_at[key] = n_spans
+                    spans.append(rounded_spans(*key))
+                    n_spans += h
+                r["span_offset"] = span_at[key]
+        self.tables = np.concatenate(tables) if tables else np.zeros(1, np.int32)
+        self.table_ints = n_ints
+        self.spans = np.concatenate(spans) if spans else np.zeros((1, 2), np.int32)
+        self.n_spans = n_spans
+        if len(rec):
+            _sheet_rc(lib.vrg_sheet_plan(C.c_void_p(rec.ctypes.data), len(rec), C.c_void_p(self.tables.ctypes.data), n_ints), "vrg_sheet_plan")
+        for r in rec:
+            r["tmp_offset"] = tmp_bytes
+            tmp_bytes += int(r["rows"]) * int(r["pic_w"]) * 3
+        self.records, self.tmp_bytes = rec, tmp_bytes
+        self.max_rows = int(rec["rows"].max()) if len(rec) else 0
+        self.max_segments = int(((rec["pic_w"] + rec["cps"] - 1) // rec["cps"]).max()) if len(rec) else 0
+
+    def check(self, records, byte_sources: bool):
+        """vrg_sheet_check of `records` (this plan's, with their source pointers set) on the host"""
+        records = np.ascontiguousarray(records)
+        _sheet_rc(_host_lib().vrg_sheet_check(C.c_void_p(records.ctypes.data), len(records), int(byte_sources), C.c_void_p(self.tables.ctypes.data),
+                                              self.table_ints, self.n_spans, self.tmp_bytes), "vrg_sheet_check")
+
+
+def _sheet_colour(value, name):
+    c = tuple(int(v) for v in value)
+    if len(c) != 3 or any(v < 0 or v > 255 for v in c):
+        raise ValueError(f"reference sheet: {name} must be three bytes (R, G, B)")
+    return c
+
+
+def _sheet_sources(sources):
+    out = []
+    for i, s in enumerate(sources):
+        if isinstance(s, np.ndarray):
+            s = torch.from_numpy(np.ascontiguousarray(s) if s.flags.writeable else np.array(s))             # Pillow's arrays are read-only
+        if not isinstance(s, torch.Tensor):
+            raise ValueError(f"reference sheet: source {i} must be a tensor")
+        s = s.detach()
+        if s.ndim == 4 and int(s.shape[0]) == 1:
+            s = s[0]
+        if s.ndim == 2:
+            s = s.unsqueeze(-1)
+        if s.ndim != 3:
+            raise ValueError(f"reference sheet: source {i} must be one [height, width, channels] frame")
+        if s.dtype not in (torch.float32, torch.uint8):
+            s = s.to(torch.float32)
+        out.append(s)
+    if not out:
+        raise ValueError("reference sheet: no sources")
+    if len({s.dtype for s in out}) != 1:
+        raise ValueError("reference sheet: the sources must be all float32 or all uint8")
+    return out
+
+
+def reference_sheet(sources, panels, canvas_size, background=(0, 0, 0), *, out_bytes: bool = False, timings: Optional[dict] = None) -> torch.Tensor:
+    """A reference sheet as Pillow builds it: ``sources`` (frames ``[H, W, C]``, all fp32 R,G,B in 0 .. 1 or all uint8, C = 1, 3 or
+    more, on the GPU or on the CPU, of any sizes, never written) are quantised (``np.clip(x * 255.0, 0, 255).astype(uint8)``), resized
+    with ``Image.resize(..., LANCZOS)`` to fit (``contain_pad``) or fill (``cover_crop``) their panels and pasted in the order of
+    ``panels`` (SheetPanel records) onto a canvas of ``canvas_size`` = (width, height) filled with ``background``; a later panel wins
+    where two overlap, panels are clipped to the canvas.  Returns a device tensor ``[height, width, 3]``: fp32 byte / 255, or uint8 with
+    ``out_bytes``.  A view that is not contiguous is made contiguous (a copy; the view itself is not written).  CPU sources go up one
+    by one through the staging pipeline of _devices, each followed by the horizontal pass of its own panels."""
+    from . import _devices
+    srcs = _sheet_sources(sources)
+    byte_sources = srcs[0].dtype == torch.uint8
+    plan = SheetPlan([tuple(s.shape) for s in srcs], panels, canvas_size, background)
+    if not len(plan.records):
+        raise ValueError("reference sheet: no panels")
+    dev = next((s.device for s in srcs if s.is_cuda), None)
+    if dev is None or any(not s.is_cuda for s in srcs):
+        if dev is not None and dev != _devices.compute_device():
+            raise RuntimeError(f"reference sheet: CPU sources go to {_devices.compute_device()}, the CUDA sources live on {dev}; move them there")
+        dev = _devices.compute_device()
+    if any(s.is_cuda and s.device != dev for s in srcs):
+        raise RuntimeError("reference sheet: the sources live on more than one GPU")
+    lib = _hip.lib()
+    rows = lib.vrg_sheet_rows_u8 if byte_sources else lib.vrg_sheet_rows_f32
+    compose = lib.vrg_sheet_compose_u8 if out_bytes else lib.vrg_sheet_compose_f32
+    rec = plan.records.copy()
+    source_of = np.array([int(p.source) for p in plan.panels])
+    with torch.cuda.device(dev):
+        tables = torch.from_numpy(plan.tables).to(dev)
+        spans = torch.from_numpy(plan.spans).to(dev)
+        tmp = torch.empty(max(plan.tmp_bytes, 1), dtype=torch.uint8, device=dev)
+        out = torch.empty((plan.height, plan.width, 3), dtype=torch.uint8 if out_bytes else torch.float32, device=dev)
+        marks = [HipEvent() for _ in range(3)] if timings is not None else None
+
+        def run_rows(which):
+            part = np.ascontiguousarray(rec[which])
+            plan.check(part, byte_sources)
+            d = torch.from_numpy(part.view(np.uint8).reshape(-1)).to(dev)
+            _hip.check(rows(_hip.ptr(d), len(part), _hip.ptr(tables), plan.table_ints, _hip.ptr(tmp), plan.tmp_bytes, plan.max_segments,
+                            plan.max_rows, _hip.current_stream()), "vrg_sheet_rows")
+
+        resident = [i for i, s in enumerate(srcs) if s.is_cuda]
+        keep = {i: srcs[i].contiguous() for i in resident}
+        for i, s in keep.items():
+            rec["src"][source_of == i] = s.data_ptr()
+        if marks:
+            marks[0].record()
+        if resident:
+            which = np.nonzero(np.isin(source_of, resident))[0]
+            if len(which):
+                run_rows(which)
+        for i, s in enumerate(srcs):
+            which = np.nonzero(source_of == i)[0]
+            if s.is_cuda or not len(which):                                        # a source no panel shows is not uploaded
+                continue
+
+            def piece(gpu, first, which=which):
+                rec["src"][which] = gpu.data_ptr()
+                run_rows(which)
+
+            _devices.upload_frames(s.unsqueeze(0), piece)
+        if marks:
+            marks[1].record()
+        plan.check(rec, byte_sources)
+        d = torch.from_numpy(rec.view(np.uint8).reshape(-1)).to(dev)
+        r, g, b = plan.background
+        _hip.check(compose(_hip.ptr(d), len(rec), int(byte_sources), _hip.ptr(tables), plan.table_ints, _hip.ptr(spans), plan.n_spans, _hip.ptr(tmp),
+                           plan.tmp_bytes, _hip.ptr(out), plan.width, plan.height, r | (g << 8) | (b << 16), _hip.current_stream()),
+                   "vrg_sheet_compose")
+        if marks:
+            marks[2].record()
+            torch.cuda.current_stream().synchronize()
+            timings["rows_ms"], timings["compose_ms"] = marks[0].elapsed_ms(marks[1]), marks[1].elapsed_ms(marks[2])
+    return out

@@ -825,6 +825,71 @@ int vrg_face_thumbs_check(const vrg_thumb_desc* desc_host, int64_t n_desc, int64
 int vrg_face_thumbs_u8(const uint8_t* generated, const uint8_t* source, int64_t n_bytes, const vrg_thumb_desc* desc, int64_t n_desc,
                        uint8_t* out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The reference sheets (VRGDG_LTXICIngredientsGrid.build, VRGDG_LTXICIngredientsGrid.py of the reference, and the three sheet builders of
+ * VRGDG_MusicVideoBuilderNodes.py:7169-7238), restated in csrc/vrg_sheet_math.hpp: every panel's source quantised
+ * (np.clip(x * 255.0, 0, 255).astype(uint8): truncation; NaN gives 0), resized as Image.resize((new_w, new_h), LANCZOS) does on bytes
+ * (csrc/vrg_pil_math.hpp), cropped (cover_crop) or centred on the cell colour (contain_pad), and pasted in order onto a canvas of one
+ * colour, under the 0 / 255 mask of ImageDraw.rounded_rectangle where the panel has one.  Two launches:
+ *   vrg_sheet_rows_*     per panel, the horizontal pass over the source rows and the columns the kept window needs, into
+ *                        tmp + tmp_offset as [rows][pic_w][3] bytes (the quantised window itself where src_w == new_w).  `_f32`: sources
+ *                        are [src_h][src_w][channels] fp32 R,G,B, 4-byte aligned; `_u8`: the same as bytes.  channels == 1 is repeated,
+ *                        channels > 3 gives its first three.  Grid: max_segments x ceil(max_rows / 4) x n workgroups, max_segments >=
+ *                        ceil(pic_w / cps) and max_rows >= rows of every record.  Sources are never written.
+ *   vrg_sheet_compose_*  one pass over the canvas out[height][width][3]: every element is written exactly once and none is read.  For a
+ *                        pixel the LAST record whose rectangle (left, top, w, h) and mask span cover it decides: the vertical pass over
+ *                        tmp inside the window, the cell colour around it; no record: `background` (R | G << 8 | B << 16).  `_f32`
+ *                        writes (float)byte / 255.0f, `_u8` the byte.  Rectangles may leave the canvas.
+ * Tables: one axis table is vrg_pil_lanczos_table's bounds and weights back to back, n_out * (2 + ksize) int32, at h_table / v_table in
+ * `tables` (ignored for an axis whose size does not change).  Spans: [n_spans][2] int32, first and last covered column of a panel row
+ * (first > last: none); span_offset == -1: no mask.  All of `panels`, `tables`, `spans`, `tmp` and the sources are device memory.
+ *
+ * HOST helpers.  vrg_sheet_fit gives the eight integers new_w, new_h, win_x, win_y, pic_w, pic_h, pic_x, pic_y of _resize_to_panel for a
+ * source of src_w x src_h in a panel of w x h.  vrg_sheet_plan fills row0, rows and cps of records whose other fields are set, from a
+ * host copy of `tables`; VRG_ERR_UNSUPPORTED when the taps of ONE window column span more than VRG_SHEET_STAGE_VALUES source values
+ * (pixels x channels).  vrg_sheet_check refuses (VRG_ERR_BAD_ARG) a null source, channels outside {1, 3, 4, ...}, tables that are not
+ * vrg_pil_lanczos_table's for the stated sizes, a window outside the resized picture or the panel, row0 / rows / cps other than
+ * vrg_sheet_plan's, a mask or a temp image outside its buffer, and (VRG_ERR_UNSUPPORTED) a side above VRG_SHEET_MAX_SIDE.  The kernels
+ * follow no record that fails the checks which need no table; such a record pastes nothing.
+ * n == 0 succeeds without a launch.  A null or misaligned `out` (4 bytes for _f32) and an `out` that is `tmp`, `tables`, `spans` or
+ * `panels` are argument errors; so is a canvas side below 1 (above VRG_SHEET_MAX_SIDE: VRG_ERR_UNSUPPORTED).
+ * ------------------------------------------------------------------------------------------- */
+#define VRG_SHEET_MAX_SIDE 32767
+#define VRG_SHEET_STAGE_VALUES 16384
+
+typedef struct vrg_sheet_panel {       /* one pasted picture */
+    const void* src;                   /* the source frame */
+    int64_t h_table, v_table;          /* int32 offsets into `tables` */
+    int64_t span_offset;               /* rows into `spans` of the panel's h mask rows, or -1 */
+    int64_t tmp_offset;                /* bytes into `tmp` */
+    int32_t src_h, src_w, channels;
+    int32_t new_w, new_h;              /* the resized picture */
+    int32_t h_ksize, v_ksize;          /* vrg_pil_lanczos_ksize per axis */
+    int32_t win_x, win_y;              /* the kept window's origin in the resized picture */
+    int32_t pic_w, pic_h;              /* the window's size */
+    int32_t row0, rows;                /* the rows of tmp: source rows (window rows where src_h == new_h); vrg_sheet_plan */
+    int32_t left, top, w, h;           /* the panel on the canvas */
+    int32_t pic_x, pic_y;              /* the window's origin inside the panel */
+    int32_t cps;                       /* window columns per staged segment; vrg_sheet_plan */
+    uint8_t cell[4];                   /* the cell colour R, G, B, 0 */
+    int32_t reserved;
+} vrg_sheet_panel;
+
+int vrg_sheet_fit(int32_t src_w, int32_t src_h, int32_t w, int32_t h, int32_t cover, int32_t* fit_host);
+int vrg_sheet_plan(vrg_sheet_panel* panels_host, int64_t n, const int32_t* tables_host, int64_t table_ints);
+int vrg_sheet_check(const vrg_sheet_panel* panels_host, int64_t n, int32_t bytes, const int32_t* tables_host, int64_t table_ints,
+                    int64_t n_spans, int64_t tmp_bytes);
+int vrg_sheet_rows_f32(const vrg_sheet_panel* panels, int64_t n, const int32_t* tables, int64_t table_ints, uint8_t* tmp, int64_t tmp_bytes,
+                       int32_t max_segments, int32_t max_rows, void* stream);
+int vrg_sheet_rows_u8(const vrg_sheet_panel* panels, int64_t n, const int32_t* tables, int64_t table_ints, uint8_t* tmp, int64_t tmp_bytes,
+                      int32_t max_segments, int32_t max_rows, void* stream);
+int vrg_sheet_compose_f32(const vrg_sheet_panel* panels, int64_t n, int32_t bytes, const int32_t* tables, int64_t table_ints,
+                          const int32_t* spans, int64_t n_spans, const uint8_t* tmp, int64_t tmp_bytes, float* out, int32_t width,
+                          int32_t height, uint32_t background, void* stream);
+int vrg_sheet_compose_u8(const vrg_sheet_panel* panels, int64_t n, int32_t bytes, const int32_t* tables, int64_t table_ints,
+                         const int32_t* spans, int64_t n_spans, const uint8_t* tmp, int64_t tmp_bytes, uint8_t* out, int32_t width,
+                         int32_t height, uint32_t background, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
