@@ -5,14 +5,9 @@
 // k_grid_tiles: one workgroup (four waves) = 64 tile columns of one tile row of one descriptor (one tile of one output frame), so a row of
 // any width is a row of workgroups.  A row of the band takes the overlay's bytes, a row of the picture is computed, everything else is 0;
 // the workgroup leaves its <= 192 bytes in LDS and stores (float)byte / 255 for all of them: every float of the grid is written once.
-//   The picture rows follow k_cut_thumbs (csrc/vrg_cut.hip), whose comment says why the order of the fp32 sums allows this much and no
-//   more: the source rows of the output row go round the four waves; a wave reads the samples its 64 columns need once with 16-byte loads,
-//   quantises them and keeps the BYTES in a row buffer of its own in LDS; lane d walks the taps of column d for the three channels; after
-//   every four rows the workgroup meets and 192 threads fold the rows' values in row order.  Samples that do not fit the row buffer go
-//   through in segments of whole columns (desc.cps columns each).  One walk serves every rule, the words it leaves differ:
-//     general   fp32 sums in cv2's order                         folded with the row weights, rounded
-//     fast/copy integer sums (copy: cells of one sample)         added, scaled by 1 / (sx * sy), rounded (2 x 2: (sum + 2) >> 2)
-//     linear    dt_hpass of the column's one or two samples      the one or two rows through dt_vpass
+//   The picture rows go through the source walk of csrc/vrg_area_walk.hpp with the rule of the descriptor: fp32 sources are quantised by
+//   grid_quant (truncation) as they are staged, decoded byte frames are B,G,R and read swapped; the lanes of the picture columns [d_lo,
+//   d_hi) of this workgroup own a column each.
 //   The store goes in 16-byte pieces from the first 16-byte boundary of the destination on, the floats in front of and behind them one by
 //   one: a tile may start anywhere on the 4-byte grid.
 // There is no row buffer for the output.  The row buffer of a wave holds GRID_ROW_VALUES source values: when the 64 columns of a workgroup
@@ -20,19 +15,15 @@
 // width of a source as such is not bounded: a row wider than the buffer is split across workgroups and, inside one, into these
 // segments.  The source is read once (rows that two output rows share are read by both); 12 B per source pixel with C = 3.
 #include "vrg_common.hpp"
-#include "vrg_grid_math.hpp"
+#include "vrg_area_walk.hpp"
 
 namespace vrg {
 
-constexpr int GRID_WAVES = 4, GRID_THREADS = GRID_WAVES * 64;
-constexpr int GRID_VALUES = GRID_LANES * 3;                                    // the values of one workgroup
-constexpr int GRID_PART_BYTES = 2 * GRID_WAVES * GRID_VALUES * 4;              // two sets of four rows' words
-constexpr int GRID_CELL_BYTES = GRID_LANES * (int)sizeof(AreaCell);
 constexpr int GRID_UNIT_BYTES = 256 * 4;                                       // k / 255
 constexpr int GRID_OUT_BYTES = 256;                                            // the bytes of the workgroup (192 used)
-constexpr int GRID_HEAD_BYTES = GRID_PART_BYTES + GRID_CELL_BYTES + GRID_UNIT_BYTES + GRID_OUT_BYTES;
+constexpr int GRID_HEAD_BYTES = WALK_PART_BYTES + WALK_CELL_BYTES + GRID_UNIT_BYTES + GRID_OUT_BYTES;
 constexpr int GRID_ROWBUF = GRID_ROW_VALUES + 16;                              // a staged value lies at the byte phase of its source
-constexpr int GRID_LDS_BYTES = GRID_HEAD_BYTES + GRID_WAVES * GRID_ROWBUF;
+constexpr int GRID_LDS_BYTES = GRID_HEAD_BYTES + WALK_WAVES * GRID_ROWBUF;
 static_assert(GRID_HEAD_BYTES % 16 == 0 && GRID_ROWBUF % 16 == 0, "the row buffers start on a 16-byte boundary");
 
 struct GridGeom {
@@ -40,72 +31,14 @@ struct GridGeom {
     int32_t cell_w, cell_h, grid_w, grid_h, segments;
 };
 
-typedef float grid_f4 __attribute__((ext_vector_type(4)));
-typedef uint32_t grid_u4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void grid_wave_sync() {                             // cut_wave_sync of vrg_cut.hip
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ uint32_t grid_quant4(const grid_f4 v) {
-    return (uint32_t)grid_quant(v.x) | ((uint32_t)grid_quant(v.y) << 8) | ((uint32_t)grid_quant(v.z) << 16) | ((uint32_t)grid_quant(v.w) << 24);
-}
-
-// n values from src as bytes into rb: value i lands at rb[ph + i], ph the returned phase (fp32: the float's index mod 4; bytes: the
-// address mod 16), so that the 16-byte loads and the LDS words they fill are both aligned.  n <= GRID_ROW_VALUES.
-__device__ __forceinline__ int grid_stage(const float* src, int n, uint8_t* rb, int lane) {
-    const int ph = (int)((reinterpret_cast<uintptr_t>(src) >> 2) & 3u);
-    int head = (4 - ph) & 3;
-    head = head < n ? head : n;
-    const int nq = (n - head) >> 2;
-    if (lane < head) rb[ph + lane] = grid_quant(src[lane]);
-    const grid_f4* body = reinterpret_cast<const grid_f4*>(src + head);
-    uint32_t* dst = reinterpret_cast<uint32_t*>(rb + ph + head);
-    int q = lane;
-    for (; q + 192 < nq; q += 256) {                                           // four loads in flight per lane
-        const grid_f4 v0 = __builtin_nontemporal_load(body + q), v1 = __builtin_nontemporal_load(body + q + 64);
-        const grid_f4 v2 = __builtin_nontemporal_load(body + q + 128), v3 = __builtin_nontemporal_load(body + q + 192);
-        dst[q] = grid_quant4(v0);
-        dst[q + 64] = grid_quant4(v1);
-        dst[q + 128] = grid_quant4(v2);
-        dst[q + 192] = grid_quant4(v3);
-    }
-    for (; q < nq; q += 64) dst[q] = grid_quant4(__builtin_nontemporal_load(body + q));
-    const int t = head + 4 * nq + lane;
-    if (t < n) rb[ph + t] = grid_quant(src[t]);
-    return ph;
-}
-
-__device__ __forceinline__ int grid_stage(const uint8_t* src, int n, uint8_t* rb, int lane) {
-    const int ph = (int)(reinterpret_cast<uintptr_t>(src) & 15u);
-    int head = (16 - ph) & 15;
-    head = head < n ? head : n;
-    const int nq = (n - head) >> 4;
-    if (lane < head) rb[ph + lane] = src[lane];
-    const grid_u4* body = reinterpret_cast<const grid_u4*>(src + head);
-    grid_u4* dst = reinterpret_cast<grid_u4*>(rb + ph + head);
-    for (int q = lane; q < nq; q += 64) dst[q] = __builtin_nontemporal_load(body + q);
-    const int t = head + 16 * nq + lane;                                       // at most 15 bytes behind the last 16-byte piece
-    if (t < n) rb[ph + t] = src[t];
-    return ph;
-}
-
-__device__ __forceinline__ AreaCell grid_clamped(AreaCell c, int32_t n_in) {   // a table made for another geometry reads nothing outside
-    c.first = c.first < 0 ? 0 : (c.first > n_in - 1 ? n_in - 1 : c.first);
-    c.count = c.count < 0 ? 0 : (c.count > n_in - c.first ? n_in - c.first : c.count);
-    return c;
-}
-
 template <typename T>
-__global__ __launch_bounds__(GRID_THREADS) void k_grid_tiles(const vrg_grid_desc* __restrict__ descs, float* __restrict__ out, GridGeom g) {
+__global__ __launch_bounds__(WALK_THREADS) void k_grid_tiles(const vrg_grid_desc* __restrict__ descs, float* __restrict__ out, GridGeom g) {
     constexpr bool SWAP = sizeof(T) == 1;                                      // decoded frames are B,G,R
     __shared__ __attribute__((aligned(16))) uint8_t lds[GRID_LDS_BYTES];
-    uint32_t* part = reinterpret_cast<uint32_t*>(lds);                        // [2][GRID_WAVES][GRID_VALUES]
-    AreaCell* xc = reinterpret_cast<AreaCell*>(lds + GRID_PART_BYTES);        // [64]
-    float* unit = reinterpret_cast<float*>(lds + GRID_PART_BYTES + GRID_CELL_BYTES);
-    uint8_t* ob = lds + GRID_PART_BYTES + GRID_CELL_BYTES + GRID_UNIT_BYTES;
+    uint32_t* part = reinterpret_cast<uint32_t*>(lds);                        // [2][WALK_WAVES][WALK_VALUES]
+    AreaCell* xc = reinterpret_cast<AreaCell*>(lds + WALK_PART_BYTES);        // [64]
+    float* unit = reinterpret_cast<float*>(lds + WALK_PART_BYTES + WALK_CELL_BYTES);
+    uint8_t* ob = lds + WALK_PART_BYTES + WALK_CELL_BYTES + GRID_UNIT_BYTES;
     const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
     uint8_t* rb = lds + GRID_HEAD_BYTES + wave * GRID_ROWBUF;
 
@@ -128,100 +61,36 @@ __global__ __launch_bounds__(GRID_THREADS) void k_grid_tiles(const vrg_grid_desc
     const bool picture = geometry && ty >= d.y_off && ty < d.y_off + d.new_h && d_lo < d_hi;       // workgroup-uniform
     const int lane0 = d_lo + d.x_off - tx0;                                    // the lane of picture column d_lo
 
-    uint32_t total = 0, row0 = 0, row1 = 0;
+    WalkSums s{0, 0, 0};
     AreaCell yc{0, 0, 0.0f, 0.0f, 0.0f};
     if (picture) {
         const AreaCell* xt = reinterpret_cast<const AreaCell*>(d.xtab);
         const int nc = d_hi - d_lo;
-        if (tid < nc) xc[tid] = grid_clamped(xt[d_lo + tid], d.width);
-        yc = grid_clamped(reinterpret_cast<const AreaCell*>(d.ytab)[ty - d.y_off], d.height);
+        if (tid < nc) xc[tid] = walk_clamped(xt[d_lo + tid], d.width);
+        yc = walk_clamped(reinterpret_cast<const AreaCell*>(d.ytab)[ty - d.y_off], d.height);
         __syncthreads();
         const int cl = lane - lane0;                                           // this lane's column of xc, if 0 <= cl < nc
-        const bool mine = cl >= 0 && cl < nc;
-        const AreaCell m = mine ? xc[cl] : AreaCell{0, 0, 0.0f, 0.0f, 0.0f};
-        int cps = d.cps < 1 ? 1 : (d.cps > GRID_LANES ? GRID_LANES : d.cps);
+        const AreaCell m = cl >= 0 && cl < nc ? xc[cl] : AreaCell{0, 0, 0.0f, 0.0f, 0.0f};
+        const int cps = d.cps < 1 ? 1 : (d.cps > GRID_LANES ? GRID_LANES : d.cps);
         const T* fin = reinterpret_cast<const T*>(d.src);
-        const int batches = (yc.count + GRID_WAVES - 1) / GRID_WAVES;
+        const int batches = (yc.count + WALK_WAVES - 1) / WALK_WAVES;
         for (int b = 0; b < batches; ++b) {
-            const int r = b * GRID_WAVES + wave;
-            if (r < yc.count) {                                                // wave-uniform
-                const T* row = fin + (int64_t)(yc.first + r) * d.width * C;
-                uint32_t a0 = 0, a1 = 0, a2 = 0;
-                for (int c0 = 0; c0 < nc; c0 += cps) {
-                    const int cl_last = (c0 + cps < nc ? c0 + cps : nc) - 1;
-                    const int x0 = xc[c0].first;
-                    int n = (xc[cl_last].first + xc[cl_last].count - x0) * C;  // values of this segment
-                    n = n < 0 ? 0 : (n > GRID_ROW_VALUES ? GRID_ROW_VALUES : n);           // (never taken with the cps of vrg_grid_plan)
-                    const int ph = grid_stage(row + (int64_t)x0 * C, n, rb, lane);
-                    grid_wave_sync();
-                    if (mine && cl >= c0 && cl <= cl_last) {
-                        const int at = (m.first - x0) * C;
-                        int count = m.count;
-                        if (at < 0 || at + count * C > n) count = 0;           // (never taken)
-                        const uint8_t* p = rb + ph + at;
-                        const int s0 = SWAP ? 2 : 0, s2 = SWAP ? 0 : 2;
-                        if (mode == GRID_GENERAL) {
-                            float f0 = 0.0f, f1 = 0.0f, f2 = 0.0f;
-                            for (int k = 0; k < count; ++k, p += C) {
-                                const float w = k == 0 ? m.w_first : (k == m.count - 1 ? m.w_last : m.w_mid);       // area_weight
-                                f0 = grid_term_general(f0, p[s0], w);
-                                f1 = grid_term_general(f1, p[1], w);
-                                f2 = grid_term_general(f2, p[s2], w);
-                            }
-                            a0 = __float_as_uint(f0); a1 = __float_as_uint(f1); a2 = __float_as_uint(f2);
-                        } else if (mode == GRID_LINEAR) {
-                            if (count > 0) {
-                                const uint8_t* q = p + (count - 1) * C;
-                                a0 = (uint32_t)grid_row_linear(p[s0], q[s0], m);
-                                a1 = (uint32_t)grid_row_linear(p[1], q[1], m);
-                                a2 = (uint32_t)grid_row_linear(p[s2], q[s2], m);
-                            }
-                        } else {
-                            int32_t i0 = 0, i1 = 0, i2 = 0;
-                            for (int k = 0; k < count; ++k, p += C) {
-                                i0 = grid_term_fast(i0, p[s0]);
-                                i1 = grid_term_fast(i1, p[1]);
-                                i2 = grid_term_fast(i2, p[s2]);
-                            }
-                            a0 = (uint32_t)i0; a1 = (uint32_t)i1; a2 = (uint32_t)i2;
-                        }
-                    }
-                    grid_wave_sync();                                          // the next segment overwrites the buffer
-                }
-                uint32_t* mine_out = part + ((b & 1) * GRID_WAVES + wave) * GRID_VALUES + lane * 3;
-                mine_out[0] = a0; mine_out[1] = a1; mine_out[2] = a2;
-            }
-            __syncthreads();
-            if (tid < GRID_VALUES) {
-#pragma unroll
-                for (int w = 0; w < GRID_WAVES; ++w) {
-                    const int rr = b * GRID_WAVES + w;
-                    if (rr < yc.count) {
-                        const uint32_t v = part[((b & 1) * GRID_WAVES + w) * GRID_VALUES + tid];
-                        if (mode == GRID_GENERAL)
-                            total = __float_as_uint(area_fold(__uint_as_float(total), __uint_as_float(v),
-                                                              rr == 0 ? yc.w_first : (rr == yc.count - 1 ? yc.w_last : yc.w_mid), rr == 0));
-                        else if (mode == GRID_LINEAR) {
-                            if (rr == 0) row0 = row1 = v;
-                            else if (rr == 1) row1 = v;
-                        } else
-                            total += v;
-                    }
-                }
-            }
+            const int r = b * WALK_WAVES + wave;
+            if (r < yc.count)                                                  // wave-uniform
+                walk_row<grid_quant, SWAP>(fin + (int64_t)(yc.first + r) * d.width * C, C, mode, xc, nc, cl, m, cps, rb, GRID_ROW_VALUES, lane,
+                                           walk_words(part, b, wave, lane));
+            walk_fold(part, b, tid, mode, yc, s);
         }
     }
 
     // the bytes of this workgroup's values: picture, overlay or nothing
-    if (tid < GRID_VALUES) {
+    if (tid < WALK_VALUES) {
         const int col = tid / 3;                                               // tile column tx0 + col, channel tid - 3 * col
         uint8_t o = 0;
         if (col < ncol) {
             const int dcol = tx0 + col - d.x_off;
             if (picture && dcol >= 0 && dcol < d.new_w) {
-                if (mode == GRID_GENERAL) o = area_cast(__uint_as_float(total));
-                else if (mode == GRID_LINEAR) o = grid_byte_linear((int32_t)row0, (int32_t)row1, yc);
-                else o = area_fast_cast((int32_t)total, d.inv, mode == GRID_FAST_2X2);
+                o = walk_byte(s, mode, yc, d.inv);
             } else if (d.overlay && ty < d.band) {
                 o = d.overlay[((int64_t)ty * g.cell_w + tx0) * 3 + tid];
             }
@@ -243,9 +112,9 @@ __global__ __launch_bounds__(GRID_THREADS) void k_grid_tiles(const vrg_grid_desc
         if (lane < 3 && t < n) dst[t] = unit[ob[t]];
     } else if (tid - 64 < nq) {
         const int i = head + 4 * (tid - 64);
-        grid_f4 v;
+        walk_f4 v;
         v.x = unit[ob[i]]; v.y = unit[ob[i + 1]]; v.z = unit[ob[i + 2]]; v.w = unit[ob[i + 3]];
-        *reinterpret_cast<grid_f4*>(dst + i) = v;
+        *reinterpret_cast<walk_f4*>(dst + i) = v;
     }
 }
 
@@ -271,7 +140,7 @@ static int grid_launch(const vrg_grid_desc* desc, int64_t n_desc, float* out, in
     GridGeom g{frames, cell_w, cell_h, grid_w, grid_h, (cell_w + GRID_LANES - 1) / GRID_LANES};
     if ((int64_t)g.segments * cell_h > 0x7fffffffll) return VRG_ERR_UNSUPPORTED;
     return launch_chunks(n_desc, [&](int64_t first, int64_t count) -> int {
-        hipLaunchKernelGGL((k_grid_tiles<T>), dim3((uint32_t)(g.segments * cell_h), (uint32_t)count), dim3(GRID_THREADS), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL((k_grid_tiles<T>), dim3((uint32_t)(g.segments * cell_h), (uint32_t)count), dim3(WALK_THREADS), 0, (hipStream_t)stream,
                            desc + first, out, g);
         VRG_CHECK_LAUNCH();
         return VRG_OK;

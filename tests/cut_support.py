@@ -28,6 +28,9 @@ CELL = np.dtype([("first", "<i4"), ("count", "<i4"), ("w_first", "<f4"), ("w_mid
 # (height, width, channels): the sizes of the issue
 SIZES = ((2160, 3840, 3), (1080, 1920, 3), (720, 1280, 3), (480, 854, 3), (512, 512, 3), (128, 128, 3), (64, 64, 3), (65, 67, 3), (64, 4096, 3),
          (96, 130, 4), (1080, 1920, 4))
+# rows just past one wave's row buffer (W * C + 4 > CUT_ROW_MAX): k_cut_thumbs stages them 32 cells at a time
+SEGMENTED_SIZES = ((64, 4864, 3), (65, 4850, 3), (64, 3640, 4))
+CUT_ROW_MAX = ((65536 - 7424) // 4) & ~15          # bytes of one wave's row buffer at most (csrc/vrg_cut.hip)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -56,6 +59,18 @@ def axis_taps(n_in, n_out=64):
         if fs2 - s2 > 1e-3:
             out.append((d, s2, F32(min(min(fs2 - s2, 1.0), cell) / cell)))
     return out
+
+
+def cells_per_segment(width, channels):
+    """cut_segments of csrc/vrg_cut.hip restated from the tap table: the most cells (64, 32, .. 1) whose samples, for every aligned run of
+    that many cells, fit the row buffer with the 4 bytes of the phase; 0: not even one cell does"""
+    taps = axis_taps(width)
+    first = [min(s for d, s, _ in taps if d == i) for i in range(64)]
+    end = [max(s for d, s, _ in taps if d == i) + 1 for i in range(64)]
+    cps = 64
+    while cps and max((end[d0 + cps - 1] - first[d0]) * channels for d0 in range(0, 64, cps)) + 4 > CUT_ROW_MAX:
+        cps >>= 1
+    return cps
 
 
 def _padded(taps, n_out=64):

@@ -52,10 +52,11 @@ def report(name, got, want):
 
 
 @pytest.mark.parametrize("kind", ("uniform", "smooth", "special"))
-@pytest.mark.parametrize("size", CS.SIZES)
+@pytest.mark.parametrize("size", CS.SIZES + CS.SEGMENTED_SIZES)
 def test_device_frames_equal_the_restatement(ops, size, kind):
     h, w, c = size
-    n = 3 if h * w <= 1500 * 2500 else 2
+    assert (CS.cells_per_segment(w, c) < 64) == (size in CS.SEGMENTED_SIZES)           # the segmented sizes, and they alone, take that path
+    n = 1 if size in CS.SEGMENTED_SIZES else (3 if h * w <= 1500 * 2500 else 2)
     x = CS.FRAME_KINDS[kind]((n, h, w, c), 500 + h + w)
     xd = torch.from_numpy(x).to(dev())
     got = device_sums(ops, xd)
