@@ -159,6 +159,14 @@ class SheetPanel(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class ThumbEntry(C.Structure):
+    """vrg_thumb_entry"""
+    _fields_ = [("left_offset", C.c_int64), ("right_offset", C.c_int64), ("tmp_offset", C.c_int64), ("h_table", C.c_int64), ("v_table", C.c_int64),
+                ("left_w", C.c_int32), ("left_h", C.c_int32), ("right_w", C.c_int32), ("right_h", C.c_int32), ("fx", C.c_int32), ("fy", C.c_int32),
+                ("red_w", C.c_int32), ("red_h", C.c_int32), ("out_w", C.c_int32), ("out_h", C.c_int32), ("h_ksize", C.c_int32),
+                ("v_ksize", C.c_int32), ("dst_x", C.c_int32), ("dst_y", C.c_int32), ("cps", C.c_int32), ("reserved", C.c_int32)]
+
+
 GRID_COPY, GRID_FAST, GRID_FAST_2X2, GRID_GENERAL, GRID_LINEAR = 0, 1, 2, 3, 4
 THUMB_SIDE = 320                # include/vrgdg_hip.h: VRG_THUMB_SIDE
 THUMB_MAX_SIDE = 32767          # include/vrgdg_hip.h: VRG_THUMB_MAX_SIDE
@@ -166,6 +174,7 @@ PIL_STATS_WORDS = 12            # uint32 per frame (csrc/vrg_pil_math.hpp: PIL_S
 PIL_MAX_LINE = 8192             # the longest mask row / column (csrc/vrg_pil_math.hpp: PIL_MAX_LINE)
 SHEET_MAX_SIDE = 32767          # include/vrgdg_hip.h: VRG_SHEET_MAX_SIDE
 SHEET_STAGE_VALUES = 16384      # include/vrgdg_hip.h: VRG_SHEET_STAGE_VALUES
+PIL_FILTER_LANCZOS, PIL_FILTER_BICUBIC = 1, 3      # include/vrgdg_hip.h: VRG_PIL_FILTER_* (Pillow's own numbers)
 FACEFIX_STATS_WORDS = 12        # uint64 per frame (csrc/vrg_facefix_math.hpp: FF_STATS_WORDS)
 
 _F3 = C.c_float * 3
@@ -270,6 +279,14 @@ _SIGNATURES = {
                                         C.c_uint32, _P]),
     "vrg_sheet_compose_u8": (C.c_int, [_P, C.c_int64, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, C.c_int32, C.c_int32,
                                        C.c_uint32, _P]),
+    "vrg_pil_filter_ksize": (C.c_int32, [C.c_int32, C.c_float, C.c_float, C.c_int32]),
+    "vrg_pil_filter_table": (C.c_int, [C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32, _P, _P]),
+    "vrg_pil_reduce_host": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "vrg_thumb_plan": (C.c_int, [_P, C.c_int64, _P, C.c_int32, C.c_double, C.c_int32, _P]),
+    "vrg_thumb_plan_reduce": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "vrg_thumb_check": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64] + [C.c_int32] * 5),
+    "vrg_thumb_rows_u8": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
+    "vrg_thumb_compose_u8": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P] + [C.c_int32] * 5 + [C.c_uint32, _P]),
 }
 
 # include/vrgdg_hip_debug.h: self-tests and probes -- for the test suite and the measurement tools, not part of the drop-in boundary

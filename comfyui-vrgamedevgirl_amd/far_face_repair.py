@@ -10,11 +10,14 @@ under the reference's names.
                                              with Pillow's LANCZOS, the mask, the optional colour match and ``Image.paste`` into a copy of
                                              the frame -- a handful of launches for the batch, no host round trip in between.
 ``pil_lanczos_resize``                       ``Image.resize(size, Image.Resampling.LANCZOS)`` for a batch of RGB or L images of any sizes.
+``contact_sheet``                            :374-408 -- original and fixed frame side by side, ``Image.thumbnail`` (``Image.reduce`` and a
+                                             BICUBIC resize over the fractional box) and the paste into the cells of the sheet: two launches.
+``pil_thumbnail`` / ``pil_reduce``           ``Image.thumbnail`` and ``Image.reduce`` for a batch of RGB images of any sizes, on the same kernels.
 
 Every step equals Pillow / numpy byte for byte (csrc/vrg_pil_math.hpp).  The channel order is the caller's: the arithmetic treats the three
 channels alike.  Device-resident inputs stay on the device; CPU inputs are uploaded whole and the result comes back in the form the frames
-came in.  Detection, PNG / video I/O, manifests, ``contact_sheet`` and ``rebuild_video`` are out of scope.  The library is reached through
-``_hip`` only; Pillow is needed for the ellipse outline alone.
+came in.  Detection, PNG / video / JPEG I/O, manifests and ``rebuild_video`` are out of scope.  The library is reached through ``_hip`` only;
+Pillow is needed for the ellipse outline alone.
 """
 from __future__ import annotations
 
@@ -47,6 +50,12 @@ _BOX_DESC = np.dtype([("left", "<i4"), ("top", "<i4"), ("box_w", "<i4"), ("box_h
                       ("mask_offset", "<i8"), ("rep_offset", "<i8")])
 assert _RESIZE_DESC.itemsize == C.sizeof(_hip.PilResizeDesc) and _MASK_DESC.itemsize == C.sizeof(_hip.PilMaskDesc)
 assert _BOX_DESC.itemsize == C.sizeof(_hip.PilBoxDesc)
+_THUMB_ENTRY = np.dtype([(name, "<i8" if ctype is C.c_int64 else "<i4") for name, ctype in _hip.ThumbEntry._fields_])
+assert _THUMB_ENTRY.itemsize == C.sizeof(_hip.ThumbEntry)
+
+SHEET_CANVAS = (24, 24, 24)
+NO_FRAMES = "No frames were available for the contact sheet."
+_FILTERS = {"bicubic": _hip.PIL_FILTER_BICUBIC, "lanczos": _hip.PIL_FILTER_LANCZOS}
 
 
 # ------------------------------------------------------------------------------------------------
@@ -98,6 +107,40 @@ def lanczos_table(n_in: int, n_out: int):
     _hip.check(_host().vrg_pil_lanczos_table(n_in, n_out, C.c_void_p(bounds.ctypes.data), C.c_void_p(weights.ctypes.data)), "vrg_pil_lanczos_table")
     table.setflags(write=False)
     return ksize, table
+
+
+def _filter_number(resample):
+    key = resample.lower() if isinstance(resample, str) else {v: k for k, v in _FILTERS.items()}.get(int(resample))
+    if key not in _FILTERS:
+        raise ValueError(f"resample must be one of {sorted(_FILTERS)}, got {resample!r}")
+    return _FILTERS[key]
+
+
+def _host_check(status, what):
+    if status == _hip.VRG_OK:
+        return
+    msg = _host().vrg_error_string(status).decode()
+    raise (ValueError if status == 1 else RuntimeError)(f"{what}: {msg}")
+
+
+@functools.lru_cache(maxsize=512)
+def _filter_table(number, n_in, in0, in1, n_out):
+    ksize = int(_host().vrg_pil_filter_ksize(number, in0, in1, n_out))
+    if n_in < 1 or n_out < 1 or ksize < 1:
+        raise ValueError("filter_table: sizes must be at least 1 and 0 <= in0 <= in1 <= n_in")
+    table = np.zeros(n_out * (2 + ksize), dtype=np.int32)
+    bounds, weights = table[:2 * n_out], table[2 * n_out:]
+    _host_check(_host().vrg_pil_filter_table(number, n_in, in0, in1, n_out, C.c_void_p(bounds.ctypes.data), C.c_void_p(weights.ctypes.data)),
+                "vrg_pil_filter_table")
+    table.setflags(write=False)
+    return ksize, table
+
+
+def filter_table(resample, n_in: int, in0: float, in1: float, n_out: int):
+    """(ksize, one axis table as the kernels read it) of ``Image.resize(.., resample, box)``: ``n_out`` outputs from the source interval
+    [in0, in1) of an axis of ``n_in`` pixels; ``resample`` "bicubic" or "lanczos".  The interval is rounded to C float, as Pillow takes it.
+    Host only."""
+    return _filter_table(_filter_number(resample), int(n_in), float(np.float32(in0)), float(np.float32(in1)), int(n_out))
 
 
 @functools.lru_cache(maxsize=64)
@@ -436,3 +479,169 @@ def masked_means(original, repaired, mask) -> dict:
         rec = plan.stats.cpu().numpy().view(np.uint32)[:_hip.PIL_STATS_WORDS]
     return {"count": int(rec[0]), "original_mean": rec[1:4].view(np.float32).copy(), "repaired_mean": rec[4:7].view(np.float32).copy(),
             "shift": rec[7:10].view(np.float32).copy(), "matched": bool(rec[10])}
+
+
+# ------------------------------------------------------------------------------------------------
+# the contact sheet
+# ------------------------------------------------------------------------------------------------
+def _sources(items, device):
+    """the images as one source buffer -> (first byte, bytes, [offset per image], what keeps it alive): device images are read where they
+    lie (a dense view stays a view, at any byte address), anything else is packed and uploaded"""
+    if all(isinstance(i, torch.Tensor) and i.is_cuda and i.device == device for i in items):
+        kept = [i if i.is_contiguous() else i.contiguous() for i in items]
+        base = min(k.data_ptr() for k in kept)
+        return base, max(k.data_ptr() + k.numel() for k in kept) - base, [k.data_ptr() - base for k in kept], kept
+    buf, offsets = _pack(items, device)
+    return buf.data_ptr(), buf.numel(), offsets, buf
+
+
+class ThumbPlan:
+    """The entries, tables and buffers of one sheet of thumbnails on ``device`` and its two launches (``contact_sheet`` and
+    ``pil_thumbnail`` run them in order; tools/bench_contact_sheet.py times each).  ``lefts``: one RGB image per entry; ``rights``: None or
+    one image or None per entry (an image makes the entry a pair); ``requests``: the (width, height) asked of ``Image.thumbnail`` per entry,
+    or None with ``factors`` = (fx, fy): ``Image.reduce`` alone."""
+
+    def __init__(self, lefts, rights, requests, device, resample="bicubic", reducing_gap=2.0, columns=1, factors=None):
+        number = _filter_number(resample)
+        n = len(lefts)
+        rights = list(rights) if rights is not None else [None] * n
+        images = list(lefts) + [r for l, r in zip(lefts, rights) if r is not None and r is not l]
+        self.base, self.src_bytes, offsets, self._kept = _sources(images, device)
+        entries = np.zeros(n, dtype=_THUMB_ENTRY)
+        k = n
+        for i, (left, right) in enumerate(zip(lefts, rights)):
+            e = entries[i]
+            e["left_offset"], e["left_h"], e["left_w"], e["right_offset"] = offsets[i], left.shape[0], left.shape[1], -1
+            if right is not None:
+                e["right_offset"], e["right_h"], e["right_w"] = offsets[i if right is left else k], right.shape[0], right.shape[1]
+                k += right is not left
+        sheet = np.zeros(5, dtype=np.int64)
+        if factors is None:
+            if reducing_gap is not None and not float(reducing_gap) >= 1.0:
+                raise ValueError("reducing_gap must be 1.0 or greater")
+            req = np.ascontiguousarray(np.asarray(requests, dtype=np.float64).reshape(n, 2))
+            _host_check(_host().vrg_thumb_plan(C.c_void_p(entries.ctypes.data), n, C.c_void_p(req.ctypes.data), number,
+                                               0.0 if reducing_gap is None else float(reducing_gap), int(columns),
+                                               C.c_void_p(sheet.ctypes.data)), "vrg_thumb_plan")
+        else:
+            _host_check(_host().vrg_thumb_plan_reduce(C.c_void_p(entries.ctypes.data), n, int(factors[0]), int(factors[1]), int(columns),
+                                                      C.c_void_p(sheet.ctypes.data)), "vrg_thumb_plan_reduce")
+        self.columns, self.rows, self.cell_w, self.cell_h, self.tmp_bytes = (int(v) for v in sheet)
+        self.width, self.height = self.columns * self.cell_w, self.rows * self.cell_h
+        tables, table_at, n_ints = [], {}, 0
+        for e in entries:
+            pair = (int(e["left_w"]) * (2 if e["right_offset"] >= 0 else 1), int(e["left_h"]))
+            for axis, f, red, out, ks, at in ((0, "fx", "red_w", "out_w", "h_ksize", "h_table"), (1, "fy", "red_h", "out_h", "v_ksize", "v_table")):
+                if not e[ks]:
+                    continue
+                key = (int(e[red]), float(np.float32(pair[axis] / int(e[f]))), int(e[out]))
+                if key not in table_at:
+                    ksize, table = _filter_table(number, key[0], 0.0, key[1], key[2])
+                    assert ksize == e[ks]
+                    table_at[key] = n_ints
+                    tables.append(table)
+                    n_ints += len(table)
+                e[at] = table_at[key]
+        host_tables = np.concatenate(tables) if tables else np.zeros(1, np.int32)
+        self.n, self.n_ints, self.entries_host = n, n_ints, entries
+        _host_check(_host().vrg_thumb_check(C.c_void_p(entries.ctypes.data), n, C.c_void_p(host_tables.ctypes.data), n_ints, self.src_bytes,
+                                            self.tmp_bytes, self.width, self.height, self.columns, self.cell_w, self.cell_h), "vrg_thumb_check")
+        self.max_segments = max([-(-int(e["out_w"]) // int(e["cps"])) for e in entries] or [0])
+        self.max_rows = max([int(e["red_h"]) for e in entries] or [0])
+        self.tables = _upload(host_tables, device)
+        self.entries = _upload(entries, device) if n else None
+        self.tmp = torch.empty(max(self.tmp_bytes, 1), dtype=torch.uint8, device=device)
+        self.out = torch.empty((self.height, self.width, 3), dtype=torch.uint8, device=device)
+
+    def run_rows(self):
+        _hip.check(_hip.lib().vrg_thumb_rows_u8(C.c_void_p(self.base), self.src_bytes, _hip.ptr(self.entries), self.n, _hip.ptr(self.tables),
+                                                self.n_ints, _hip.ptr(self.tmp), self.tmp_bytes, self.max_segments, self.max_rows,
+                                                _hip.current_stream()), "vrg_thumb_rows_u8")
+
+    def run_compose(self):
+        r, g, b = SHEET_CANVAS
+        _hip.check(_hip.lib().vrg_thumb_compose_u8(_hip.ptr(self.entries), self.n, _hip.ptr(self.tables), self.n_ints, _hip.ptr(self.tmp),
+                                                   self.tmp_bytes, _hip.ptr(self.out), self.width, self.height, self.columns, self.cell_w,
+                                                   self.cell_h, r | g << 8 | b << 16, _hip.current_stream()), "vrg_thumb_compose_u8")
+        return self.out
+
+    def thumbnails(self):
+        """the thumbnails cut out of the sheet, each of its own size"""
+        return [self.out[int(e["dst_y"]):int(e["dst_y"]) + int(e["out_h"]), int(e["dst_x"]):int(e["dst_x"]) + int(e["out_w"])]
+                for e in self.entries_host]
+
+
+def _rgb_batch(images, name):
+    """-> (the RGB images of a batch, the device they are on or None, how a device tensor goes back in the caller's form)"""
+    items, _ = _image_list(images, name, 3)
+    if any(i is not None and i.ndim != 3 for i in items):
+        raise ValueError(f"{name} must be uint8 images of shape [h, w, 3]")
+    first = next((i for i in items if i is not None), None)
+    tensor = isinstance(images, torch.Tensor) or isinstance(first, torch.Tensor)
+    on_device = tensor and first is not None and first.is_cuda and all(i is None or (isinstance(i, torch.Tensor) and i.is_cuda) for i in items)
+    back = (lambda t: t) if on_device else (lambda t: t.cpu()) if tensor else (lambda t: t.cpu().numpy())
+    return items, (first.device if on_device else None), back
+
+
+def contact_sheet(originals, fixed=None, limit=24, columns=3, thumb_width=900):
+    """``contact_sheet`` of the reference (:382-406) on decoded frames: for each of the first ``limit`` originals the pair original | fixed
+    (the original again where ``fixed`` or its entry is None; a fixed frame of another size is pasted on black and clipped),
+    ``pair.thumbnail((thumb_width, int(thumb_width * pair.height / pair.width)))``, and the thumbnails pasted ``columns`` to a row onto
+    (24, 24, 24).  ``originals`` / ``fixed``: uint8 [n, H, W, 3] tensors or sequences of [H, W, 3] images of any sizes, on the device or
+    the CPU.  -> the sheet, uint8 [rows * cell_h, columns * cell_w, 3], in the form the frames came in.  Raises the reference's
+    RuntimeError when there is no frame.  The JPEG encode stays with the caller."""
+    lefts, device, back = _rgb_batch(originals, "originals")
+    if any(i is None for i in lefts):
+        raise ValueError("originals must not hold None")
+    rights = [None] * len(lefts)
+    if fixed is not None:
+        rights, fixed_device, _ = _rgb_batch(fixed, "fixed")
+        if len(rights) != len(lefts):
+            raise ValueError(f"fixed must hold one entry per original ({len(lefts)}), got {len(rights)}")
+        if any(r is not None for r in rights) and fixed_device != device:
+            device = None                                                    # mixed: everything is packed and uploaded
+    lefts, rights = lefts[:int(limit)], rights[:int(limit)]
+    if not lefts:
+        raise RuntimeError(NO_FRAMES)
+    thumb_width = int(thumb_width)
+    requests = [(thumb_width, int(thumb_width * int(i.shape[0]) / (2 * int(i.shape[1])))) for i in lefts]
+    if thumb_width < 1 or any(r[1] < 1 for r in requests):
+        raise ValueError("thumb_width gives a thumbnail below 1 x 1")
+    device = device if device is not None else compute_device()
+    with torch.cuda.device(device):
+        plan = ThumbPlan(lefts, [l if r is None else r for l, r in zip(lefts, rights)], requests, device, columns=columns)
+        plan.run_rows()
+        return back(plan.run_compose())
+
+
+def _thumb_batch(images, plan_of, name):
+    items, device, back = _rgb_batch(images, name)
+    if any(i is None for i in items):
+        raise ValueError(f"{name} must not hold None")
+    if not items:
+        return [] if not isinstance(images, (torch.Tensor, np.ndarray)) else images[:0]
+    device = device if device is not None else compute_device()
+    with torch.cuda.device(device):
+        plan = plan_of(items, device)
+        plan.run_rows()
+        plan.run_compose()
+        cut = plan.thumbnails()
+        if isinstance(images, (torch.Tensor, np.ndarray)):
+            return back(torch.stack(cut))
+        return [back(c.contiguous()) for c in cut]
+
+
+def pil_thumbnail(images, size, resample="bicubic", reducing_gap=2.0):
+    """``Image.thumbnail(size, resample, reducing_gap)`` (size = (width, height)) of every RGB image of a batch: a uint8 tensor
+    [n, h, w, 3] -> [n, h', w', 3], or a sequence of [h, w, 3] images of any sizes -> a list, each in the form it came in.  ``resample``:
+    "bicubic" or "lanczos"; ``reducing_gap=None`` skips the reduce.  An image already within ``size`` comes back as a copy."""
+    if not (size[0] >= 1 and size[1] >= 1):
+        raise ValueError("size must be at least 1 x 1")
+    return _thumb_batch(images, lambda items, device: ThumbPlan(items, None, [(size[0], size[1])] * len(items), device, resample, reducing_gap),
+                        "images")
+
+
+def pil_reduce(images, factor):
+    """``Image.reduce(factor)`` (an integer or (fx, fy)) of every RGB image of a batch, in the forms of ``pil_thumbnail``"""
+    fx, fy = (factor, factor) if not isinstance(factor, (tuple, list)) else factor
+    return _thumb_batch(images, lambda items, device: ThumbPlan(items, None, None, device, factors=(fx, fy)), "images")

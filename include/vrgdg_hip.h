@@ -890,6 +890,74 @@ int vrg_sheet_compose_u8(const vrg_sheet_panel* panels, int64_t n, int32_t bytes
                          const int32_t* spans, int64_t n_spans, const uint8_t* tmp, int64_t tmp_bytes, uint8_t* out, int32_t width,
                          int32_t height, uint32_t background, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The far-face repair contact sheet (contact_sheet of scripts/far_face_repair_backend.py:374-408 of the reference): per entry the
+ * original and the fixed frame side by side, shrunk by Image.thumbnail -- Image.reduce by integer factors, then a BICUBIC (or LANCZOS)
+ * resize over the fractional source box -- and pasted into the cells of a sheet.  Arithmetic: csrc/vrg_pil_math.hpp, pinned byte for byte
+ * to the installed Pillow.  Two launches (csrc/vrg_thumb.hip):
+ *   vrg_thumb_rows_u8     per entry, the pair (never stored), the reduce (never stored) and the horizontal pass into tmp + tmp_offset as
+ *                         [red_h][out_w][3] bytes.  The left half is src + left_offset as [left_h][left_w][3]; the right half is
+ *                         src + right_offset as [right_h][right_w][3] pasted at (left_w, 0) onto black and clipped to left_w x left_h;
+ *                         right_offset == -1: a single picture, no pair.  A workgroup reads fy source rows of a segment of `cps` output
+ *                         columns once.  Grid: max_segments x max_rows x n, max_segments >= ceil(out_w / cps), max_rows >= red_h.
+ *                         Sources are never written and may lie at any byte address.
+ *   vrg_thumb_compose_u8  one pass over out[height][width][3]: every byte is written once and none is read.  Entry i owns the cell
+ *                         (i % columns, i / columns) of cell_w x cell_h; inside its thumbnail at (dst_x, dst_y) the byte is the vertical
+ *                         pass over tmp, everywhere else `background` (R | G << 8 | B << 16).
+ * Tables: one axis table is vrg_pil_filter_table's bounds and weights back to back, n_out * (2 + ksize) int32, at h_table / v_table in
+ * `tables`; h_ksize / v_ksize == 0: the axis is copied (out == red and the box is the whole axis).
+ *
+ * HOST helpers.  vrg_pil_filter_ksize / vrg_pil_filter_table: one axis of Image.resize(size, filter, box) -- filter 3 = BICUBIC,
+ * 1 = LANCZOS, the source interval [in0, in1) given as the C floats Pillow receives, 0 <= in0 <= in1 <= n_in; with the box (0, n_in) and
+ * LANCZOS they equal vrg_pil_lanczos_*.  vrg_pil_reduce_host: Image.reduce((fx, fy)) of a whole host picture.
+ * vrg_thumb_plan fills, from left_w, left_h, right_offset (>= 0: a pair) of every entry and the size requested of Image.thumbnail
+ * (req_host[i] = {width, height} as given, >= 1), fx, fy, red_w, red_h, out_w, out_h, h_ksize, v_ksize, cps, tmp_offset, dst_x, dst_y --
+ * reducing_gap <= 0 stands for None, else it must be >= 1 -- and sheet_host = {columns, rows, cell_w, cell_h, bytes of tmp}.
+ * VRG_ERR_UNSUPPORTED -- before any launch, nothing is truncated -- for a factor above VRG_THUMB_MAX_FACTOR, a side above
+ * VRG_THUMB_MAX_SOURCE, taps of one output column that pass the staging buffer (VRG_THUMB_STAGE_BYTES source bytes of one row,
+ * VRG_THUMB_STAGE_VALUES reduced values), and a reduced picture more than 100 times as tall as wide (Pillow resizes it vertically first).
+ * vrg_thumb_plan_reduce plans Image.reduce((fx, fy)) alone in the same way: the reduced picture is the thumbnail, no table.
+ * vrg_thumb_check refuses (VRG_ERR_BAD_ARG) entries that are not vrg_thumb_plan's, tables that do not fit them, sources or temp images
+ * outside their buffers and a sheet that is not the plan's; (VRG_ERR_UNSUPPORTED) a segment whose taps pass the staging buffer.  The kernels
+ * follow no entry that fails the checks which need no table; such an entry pastes nothing.  n == 0 succeeds without a launch.
+ * ------------------------------------------------------------------------------------------- */
+#define VRG_THUMB_MAX_FACTOR 64
+#define VRG_THUMB_MAX_SOURCE 32767
+#define VRG_THUMB_STAGE_BYTES 8192
+#define VRG_THUMB_STAGE_VALUES 4096
+#define VRG_PIL_FILTER_LANCZOS 1
+#define VRG_PIL_FILTER_BICUBIC 3
+
+typedef struct vrg_thumb_entry {       /* one thumbnail of the sheet */
+    int64_t left_offset;               /* bytes into `src` */
+    int64_t right_offset;              /* bytes into `src`, or -1: no right half */
+    int64_t tmp_offset;                /* bytes into `tmp`; vrg_thumb_plan */
+    int64_t h_table, v_table;          /* int32 offsets into `tables` */
+    int32_t left_w, left_h;            /* the original; the pair is 2 left_w x left_h */
+    int32_t right_w, right_h;          /* the fixed frame */
+    int32_t fx, fy;                    /* the reduce factors */
+    int32_t red_w, red_h;              /* the reduced pair: ceil(pair / factor) */
+    int32_t out_w, out_h;              /* the thumbnail */
+    int32_t h_ksize, v_ksize;          /* vrg_pil_filter_ksize per axis, 0: the axis is copied */
+    int32_t dst_x, dst_y;              /* the thumbnail's origin on the sheet */
+    int32_t cps;                       /* output columns per staged segment */
+    int32_t reserved;
+} vrg_thumb_entry;
+
+int32_t vrg_pil_filter_ksize(int32_t filter, float in0, float in1, int32_t n_out);
+int vrg_pil_filter_table(int32_t filter, int32_t n_in, float in0, float in1, int32_t n_out, int32_t* bounds_host, int32_t* weights_host);
+int vrg_pil_reduce_host(const uint8_t* src_host, int32_t height, int32_t width, int32_t channels, int32_t fx, int32_t fy, uint8_t* dst_host);
+int vrg_thumb_plan(vrg_thumb_entry* entries_host, int64_t n, const double* req_host, int32_t filter, double reducing_gap, int32_t columns,
+                   int64_t* sheet_host);
+int vrg_thumb_plan_reduce(vrg_thumb_entry* entries_host, int64_t n, int32_t fx, int32_t fy, int32_t columns, int64_t* sheet_host);
+int vrg_thumb_check(const vrg_thumb_entry* entries_host, int64_t n, const int32_t* tables_host, int64_t table_ints, int64_t src_bytes,
+                    int64_t tmp_bytes, int32_t width, int32_t height, int32_t columns, int32_t cell_w, int32_t cell_h);
+int vrg_thumb_rows_u8(const uint8_t* src, int64_t src_bytes, const vrg_thumb_entry* entries, int64_t n, const int32_t* tables,
+                      int64_t table_ints, uint8_t* tmp, int64_t tmp_bytes, int32_t max_segments, int32_t max_rows, void* stream);
+int vrg_thumb_compose_u8(const vrg_thumb_entry* entries, int64_t n, const int32_t* tables, int64_t table_ints, const uint8_t* tmp,
+                         int64_t tmp_bytes, uint8_t* out, int32_t width, int32_t height, int32_t columns, int32_t cell_w, int32_t cell_h,
+                         uint32_t background, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
