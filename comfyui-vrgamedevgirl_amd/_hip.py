@@ -159,6 +159,12 @@ class SheetPanel(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class MsrDesc(C.Structure):
+    """vrg_msr_desc"""
+    _fields_ = [("src", C.c_void_p), ("in_h", C.c_int32), ("in_w", C.c_int32), ("taps", C.c_int32), ("first_frame", C.c_int32),
+                ("repeats", C.c_int32), ("fill", C.c_uint8 * 4)]
+
+
 class ThumbEntry(C.Structure):
     """vrg_thumb_entry"""
     _fields_ = [("left_offset", C.c_int64), ("right_offset", C.c_int64), ("tmp_offset", C.c_int64), ("h_table", C.c_int64), ("v_table", C.c_int64),
@@ -287,6 +293,8 @@ _SIGNATURES = {
     "vrg_thumb_check": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64] + [C.c_int32] * 5),
     "vrg_thumb_rows_u8": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
     "vrg_thumb_compose_u8": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P] + [C.c_int32] * 5 + [C.c_uint32, _P]),
+    "vrg_msr_check": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+    "vrg_msr_frames_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
 }
 
 # include/vrgdg_hip_debug.h: self-tests and probes -- for the test suite and the measurement tools, not part of the drop-in boundary

@@ -3053,3 +3053,141 @@ def reference_sheet(sources, panels, canvas_size, background=(0, 0, 0), *, out_b
             torch.cuda.current_stream().synchronize()
             timings["rows_ms"], timings["compose_ms"] = marks[0].elapsed_ms(marks[1]), marks[1].elapsed_ms(marks[2])
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# The LTX MSR reference frames (vrgdg_ltx_msr_reference_builder.py of the reference): a few byte stills, each stretched with cv2's byte
+# Lanczos-4 and repeated into a run of fp32 / 255 frames, in one launch (csrc/vrg_msr.hip)
+# ---------------------------------------------------------------------------------------------
+MSR_DESC = np.dtype([("src", "<u8"), ("in_h", "<i4"), ("in_w", "<i4"), ("taps", "<i4"), ("first_frame", "<i4"), ("repeats", "<i4"),
+                     ("fill", "u1", (4,))])           # vrg_msr_desc
+_msr_tables: dict = {}          # (distinct source sizes, out_h, out_w, device) -> the uploaded table
+
+
+def expand_counts(pictures: int, frame_count: int) -> list:
+    """The repeats of the reference's ``_expand_frames``: ``base + (1 if index < remainder else 0)``"""
+    base, remainder = divmod(int(frame_count), int(pictures))
+    return [base + (1 if index < remainder else 0) for index in range(int(pictures))]
+
+
+@dataclass
+class MsrPlan:
+    """The host side of one launch: ``desc`` (MSR_DESC records in picture order, ``src`` still 0; a constant colour comes last), the
+    sizes that are filtered with the index of each one's first record in the concatenated table, and the geometry."""
+    desc: np.ndarray
+    sizes: tuple
+    offsets: dict
+    n_taps: int
+    frames: int
+    height: int
+    width: int
+
+    def table(self) -> np.ndarray:
+        """the concatenated records of vrg_lanczos4_taps, one table per distinct (in_h, in_w), as bytes"""
+        parts = [lanczos4_taps(h, w, self.height, self.width).view(np.uint8).reshape(-1) for h, w in self.sizes]
+        return np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8)
+
+    def check(self, desc: Optional[np.ndarray] = None) -> None:
+        d = np.ascontiguousarray(self.desc if desc is None else desc)
+        _hip.check(_hip.load_library().vrg_msr_check(C.c_void_p(d.ctypes.data), len(d), self.n_taps, self.frames, self.height, self.width),
+                   "vrg_msr_check")
+
+
+def msr_plan(shapes, size, frame_count: int, fill=None) -> MsrPlan:
+    """Descriptors, repeats and frame ranges of ``len(shapes)`` pictures of ``shapes[i] = (height, width)`` -- and, with ``fill`` =
+    (R, G, B), a constant colour after them -- spread over ``frame_count`` frames of ``size`` = (width, height).  No GPU needed."""
+    width, height = int(size[0]), int(size[1])
+    frame_count = int(frame_count)
+    if width < 1 or height < 1:
+        raise ValueError("msr reference frames: width and height must be at least 1")
+    if frame_count < 0 or frame_count > 0x7fffffff:
+        raise ValueError("msr reference frames: frame_count must be 0 .. 2^31 - 1")
+    shapes = [(int(h), int(w)) for h, w in shapes]
+    if any(h < 1 or w < 1 for h, w in shapes):
+        raise ValueError("msr reference frames: pictures must be at least 1 x 1")
+    n = len(shapes) + (fill is not None)
+    if n == 0:
+        raise ValueError("msr reference frames: no pictures")
+    sizes = tuple(sorted({s for s in shapes if s != (height, width)}))
+    offsets, at = {}, 0
+    for s in sizes:
+        offsets[s] = at
+        at += width + height
+    if at > 0x7fffffff:
+        raise ValueError("msr reference frames: the tap tables pass 2^31 - 1 records")
+    desc = np.zeros(n, dtype=MSR_DESC)
+    desc["repeats"] = expand_counts(n, frame_count)
+    desc["first_frame"] = np.cumsum(desc["repeats"]) - desc["repeats"]
+    for i, (h, w) in enumerate(shapes):
+        desc["in_h"][i], desc["in_w"][i], desc["taps"][i] = h, w, offsets.get((h, w), -1)
+    if fill is not None:
+        desc["taps"][n - 1] = -1
+        desc["fill"][n - 1, :3] = _sheet_colour(fill, "the background colour")
+    return MsrPlan(desc, sizes, offsets, at, frame_count, height, width)
+
+
+def _msr_table(plan: MsrPlan, device) -> torch.Tensor:
+    key = (plan.sizes, plan.height, plan.width, str(device))
+    t = _msr_tables.get(key)
+    if t is None:
+        t = torch.from_numpy(plan.table()).to(device)
+        with _lanczos_lock:
+            if len(_msr_tables) >= 64:              # a handful of geometries per job; never grows without bound
+                _msr_tables.clear()
+            _msr_tables[key] = t
+    return t
+
+
+def _msr_picture(p, i):
+    if isinstance(p, np.ndarray):
+        p = torch.from_numpy(np.ascontiguousarray(p) if p.flags.writeable else np.array(p))                 # Pillow's arrays are read-only
+    if not isinstance(p, torch.Tensor) or p.dtype != torch.uint8 or p.ndim != 3 or int(p.shape[2]) != 3:
+        raise ValueError(f"msr reference frames: picture {i} must be a [height, width, 3] uint8 tensor or array")
+    return p.detach()
+
+
+def msr_reference_frames(pictures, size, frame_count: int, background=None) -> torch.Tensor:
+    """``np.stack(_expand_frames([cv2.resize(p, size, INTER_LANCZOS4) for p in pictures + [background]], frame_count)).astype(np.float32)
+    / 255.0`` of the reference's MSR builder as one launch: ``pictures`` are ``[h, w, 3]`` uint8 R,G,B tensors or arrays of any sizes, on
+    the GPU or on the CPU (uploaded as bytes), ``size`` = (width, height), ``background`` a further picture, an (R, G, B) tuple for a
+    constant colour, or None.  A picture that already has the size is taken unfiltered.  Returns the ``[frame_count, height, width, 3]``
+    fp32 device tensor; every distinct picture is filtered once, whatever its repeats.  Inputs are never written."""
+    from . import _devices
+    pics = [_msr_picture(p, i) for i, p in enumerate(pictures)]
+    fill = None
+    if isinstance(background, (tuple, list)):
+        fill = tuple(background)
+    elif background is not None:
+        pics.append(_msr_picture(background, "background"))
+    plan = msr_plan([tuple(p.shape[:2]) for p in pics], size, frame_count, fill)
+    dev = next((p.device for p in pics if p.is_cuda), None)
+    if dev is None or any(not p.is_cuda for p in pics):
+        if dev is not None and dev != _devices.compute_device():
+            raise RuntimeError(f"msr reference frames: CPU pictures go to {_devices.compute_device()}, the CUDA pictures live on {dev}; move them there")
+        dev = _devices.compute_device()
+    if any(p.is_cuda and p.device != dev for p in pics):
+        raise RuntimeError("msr reference frames: the pictures live on more than one GPU")
+    desc = plan.desc.copy()
+    with torch.cuda.device(dev):
+        out = torch.empty((plan.frames, plan.height, plan.width, 3), dtype=torch.float32, device=dev)
+        if plan.frames == 0:
+            return out
+        keep = [p.contiguous().to(dev) if desc["repeats"][i] > 0 else None for i, p in enumerate(pics)]      # a picture no frame shows is not uploaded
+        for i, p in enumerate(keep):
+            if p is None:
+                desc["in_h"][i], desc["in_w"][i], desc["taps"][i] = 1, 1, -1                                   # src stays null: follows nothing
+            else:
+                desc["src"][i] = p.data_ptr()
+        plan.check(desc)
+        table = _msr_table(plan, dev)
+        d = torch.from_numpy(desc.view(np.uint8).reshape(-1)).to(dev)
+        _hip.check(_hip.lib().vrg_msr_frames_f32(_hip.ptr(d), len(desc), _hip.ptr(table), plan.n_taps, _hip.ptr(out), plan.frames, plan.height,
+                                                 plan.width, _hip.current_stream()), "vrg_msr_frames_f32")
+    return out
+
+
+def bytes_to_image(picture) -> torch.Tensor:
+    """``np.asarray(picture, dtype=np.float32) / 255.0`` as ``[1, h, w, 3]`` fp32 on the device (the reference's _pil_to_image_tensor): the
+    launch of msr_reference_frames with one descriptor, no filter, one frame."""
+    p = _msr_picture(picture, 0)
+    return msr_reference_frames([p], (int(p.shape[1]), int(p.shape[0])), 1)

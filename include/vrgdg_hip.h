@@ -958,6 +958,33 @@ int vrg_thumb_compose_u8(const vrg_thumb_entry* entries, int64_t n, const int32_
                          int64_t tmp_bytes, uint8_t* out, int32_t width, int32_t height, int32_t columns, int32_t cell_w, int32_t cell_h,
                          uint32_t background, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The LTX MSR reference frames (VRGDG_LTXMSRReferenceBuilder and VRGDG_LTX25MSRReferenceLoader, vrgdg_ltx_msr_reference_builder.py of the
+ * reference), csrc/vrg_msr.hip and csrc/vrg_msr_math.hpp: a few distinct byte pictures, each stretched to out_w x out_h as
+ * cv2.resize(..., INTER_LANCZOS4) does on bytes (what vrg_lanczos4_u8 computes, from the records of vrg_lanczos4_taps) unless it already has
+ * that size, each repeated into a run of frames of out = [frames][out_h][out_w][3] fp32 (4-byte aligned) as (float)byte / 255.0f,
+ * correctly rounded.  One launch: a workgroup filters one tile of one descriptor once, converts it once and stores it to every frame of
+ * the run -- 16-byte non-temporal stores where the address allows them, 4-byte stores elsewhere.  Every float of every frame a
+ * descriptor names is written exactly once and none is read; sources are never written and may lie at any byte address.  Any sizes >= 1
+ * and any ratio.
+ * vrg_msr_check refuses ON THE HOST (VRG_ERR_BAD_ARG) descriptors whose frame ranges overlap or leave a frame of 0 .. frames - 1
+ * uncovered, a `taps` range outside the table of n_taps records, taps == -1 at a size other than the output's and sizes below 1.  The
+ * kernel follows no descriptor that names a frame outside the batch or records outside the table; it cannot see a gap.
+ * `desc` and `taps` of the launch are device memory (`taps` 4-byte aligned); zero frames or zero descriptors succeed without a launch.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct vrg_msr_desc {      /* one distinct picture of the batch */
+    const uint8_t* src;            /* [in_h][in_w][3] bytes R,G,B in device memory, any alignment; null = the constant colour `fill` */
+    int32_t in_h, in_w;
+    int32_t taps;                  /* index of this picture's first record in `taps` (out_w column records, then out_h row records,
+                                      as vrg_lanczos4_taps writes them); -1 = the picture already has the output size: its bytes, unfiltered */
+    int32_t first_frame, repeats;  /* it becomes output frames first_frame .. first_frame + repeats - 1; repeats may be 0 */
+    uint8_t fill[4];               /* R,G,B for src == null */
+} vrg_msr_desc;
+
+int vrg_msr_check(const vrg_msr_desc* desc_host, int64_t n_desc, int64_t n_taps, int64_t frames, int32_t out_h, int32_t out_w);
+int vrg_msr_frames_f32(const vrg_msr_desc* desc, int64_t n_desc, const void* taps, int64_t n_taps,
+                       float* out, int64_t frames, int32_t out_h, int32_t out_w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
