@@ -21,7 +21,6 @@ aiohttp routes are out of scope.  The arithmetic is csrc/vrg_facefix_math.hpp; t
 from __future__ import annotations
 
 import ctypes as C
-import threading
 
 import numpy as np
 import torch
@@ -43,18 +42,7 @@ _FF_DESC = np.dtype([("enhanced_index", "<i4"), ("left", "<i4"), ("top", "<i4"),
 assert _BOX_DESC.itemsize == C.sizeof(_hip.FaceFixBoxDesc) and _MASK_DESC.itemsize == C.sizeof(_hip.FaceFixMaskDesc)
 assert _FF_DESC.itemsize == C.sizeof(_hip.FaceFixDesc)
 
-_lock = threading.Lock()
-_host_lib = None
-
-
-def _host():
-    """the library for its HOST table functions (no GPU needed)"""
-    global _host_lib
-    if _host_lib is None:
-        with _lock:
-            if _host_lib is None:
-                _host_lib = _hip.load_library()
-    return _host_lib
+_host = _hip.host_library       # the library for its HOST table functions (no GPU needed); far_face_repair imports the name
 
 
 # ------------------------------------------------------------------------------------------------

@@ -314,6 +314,7 @@ EXPORTED_SYMBOLS = tuple(sorted(_SIGNATURES))
 DEBUG_SYMBOLS = tuple(sorted(_DEBUG_SIGNATURES))
 
 _lib = None
+_host_lib = None
 _lock = threading.Lock()
 
 
@@ -378,6 +379,16 @@ def lib() -> Library:
                                        "PyTorch-ROCm; there is no CPU fallback")
                 _lib = load_library()
     return _lib
+
+
+def host_library() -> Library:
+    """The loaded library, for its HOST functions (tables, plans, checks): no device needed.  One handle per process."""
+    global _host_lib
+    if _host_lib is None:
+        with _lock:
+            if _host_lib is None:
+                _host_lib = load_library()
+    return _host_lib
 
 
 def check(status: int, what: str):

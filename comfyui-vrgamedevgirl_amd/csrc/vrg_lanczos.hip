@@ -3,16 +3,11 @@
 // clip truncate, :311-324 and :278-294).  gfx950 only.  Arithmetic: csrc/vrg_lanczos_math.hpp (integer, exact) and the shared byte pipeline
 // of csrc/vrg_pixel_math.hpp (sharpen_grain_byte: what k_sharpen_grain_u8 evaluates).
 //
-// k_lanczos4_tile: one workgroup = one 64 x 32 tile of output pixels (HALO = 1: plus a one-pixel ring) of one frame.
-//   stage   the tile's column and row records (s, eight int16 as four dwords) from the table into LDS;
-//   pass 1  every source row the tile's output rows touch (s(first) - 3 .. s(last) + 4, clamped on use) is filtered horizontally for the
-//           tile's columns: one thread = one (row, column), the eight source pixels are 24 consecutive bytes = six unaligned dword loads
-//           (columns whose taps are clamped at a frame edge gather byte by byte), the byte pairs of taps 2k, 2k + 1 are lined up with
-//           v_perm_b32 and multiplied with the int16 weight pair by v_dot2_i32_i16: 4 + 4 instructions per channel instead of 8 extracts
-//           + 8 multiply-adds.  The sums (|h| < 2^20) go to LDS as int32, channel-planar: consecutive lanes hit consecutive banks;
-//   pass 2  one thread = one output pixel: eight LDS rows x three channels, v_mad_i32_i24 (|h| < 2^23, |w| < 2^12: exact, and full rate
-//           where v_mul_lo_i32 is not), then FixedPtCast.  HALO = 0 stores the bytes; HALO = 1 keeps them in LDS, the ring outside the
-//           frame being the replicated edge pixel (the clamped coordinate) or zero bytes;
+// k_lanczos4_tile: one workgroup = one 64 x 32 tile of output pixels (HALO = 1: plus a one-pixel ring) of one frame, on the tile filter of
+// csrc/vrg_lanczos_tile.hpp, whose comment describes the staging and the two filter passes.  What is this kernel's own:
+//   pass 1  the source rows are the consecutive rows s(first) - 3 .. s(last) + 4 that the tile's output rows touch, clamped on use;
+//   pass 2  HALO = 0 stores the bytes; HALO = 1 keeps them in LDS, the ring outside the frame being the replicated edge pixel (the clamped
+//           coordinate) or zero bytes;
 //   pass 3  (HALO = 1) one thread = one pixel: 3 x 3 window per channel from the LDS bytes, sharpen_grain_byte, three normals of
 //           torch.randn's stream per pixel by the general per-element form (torch_randn_element: one Philox call per element -- the
 //           sibling elements of a call lie G elements apart, outside any tile).
@@ -20,7 +15,7 @@
 // A tile whose rows span more than LZ_MAXROWS source rows (vertical ratios below about 0.9) is not tiled: vrg_lanczos4_u8 runs the plain
 // per-pixel kernel, vrg_upscale_sharpen_grain_u8 reports VRG_ERR_UNSUPPORTED and the caller runs the two entry points.
 #include "vrg_common.hpp"
-#include "vrg_lanczos_math.hpp"
+#include "vrg_lanczos_tile.hpp"
 
 namespace vrg {
 
@@ -39,31 +34,6 @@ struct LzShared {
     uint8_t ub[HALO ? CH : 1][HALO ? CW * 3 + 2 : 4];
 };
 
-__device__ __forceinline__ int32_t lz_dot2(uint32_t pair, uint32_t w, int32_t acc) {
-    typedef short lz_s2 __attribute__((ext_vector_type(2)));
-    lz_s2 a, b;
-    __builtin_memcpy(&a, &pair, 4);
-    __builtin_memcpy(&b, &w, 4);
-    return __builtin_amdgcn_sdot2(a, b, acc, false);
-}
-
-// bytes j0 and j1 of the 24-byte window d[6] as (byte j0) | (byte j1) << 16
-template <int J0, int J1>
-__device__ __forceinline__ uint32_t lz_pair(const uint32_t (&d)[6]) {
-    constexpr uint32_t sel = 0x0c000c00u | (uint32_t)(J0 & 3) | ((uint32_t)(4 + (J1 & 3)) << 16);
-    return __builtin_amdgcn_perm(d[J1 >> 2], d[J0 >> 2], sel);
-}
-
-template <int C>
-__device__ __forceinline__ int32_t lz_hsum_window(const uint32_t (&d)[6], const uint32_t (&w)[4]) {
-    int32_t acc = 0;
-    acc = lz_dot2(lz_pair<C, C + 3>(d), w[0], acc);
-    acc = lz_dot2(lz_pair<C + 6, C + 9>(d), w[1], acc);
-    acc = lz_dot2(lz_pair<C + 12, C + 15>(d), w[2], acc);
-    acc = lz_dot2(lz_pair<C + 18, C + 21>(d), w[3], acc);
-    return acc;
-}
-
 template <int HALO, bool ZERO, bool SHARP, bool GRAIN>
 __global__ __launch_bounds__(256) void k_lanczos4_tile(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, const uint32_t* __restrict__ taps,
                                                         LzGeom g, NoiseK nk, float strength, float I, float S, float T) {
@@ -80,21 +50,7 @@ __global__ __launch_bounds__(256) void k_lanczos4_tile(const uint8_t* __restrict
     const uint8_t* fin = in + (int64_t)frame * g.in_h * in_pitch;
     uint8_t* fout = out + (int64_t)frame * g.out_h * g.out_w * 3;
 
-    for (int i = (int)tid; i < CW + CH; i += 256) {
-        const bool col = i < CW;
-        const int l = col ? i : i - CW;
-        const int32_t gi = col ? lz_clampi(x0 + l - HALO, g.out_w - 1) : g.out_w + lz_clampi(y0 + l - HALO, g.out_h - 1);
-        const uint32_t* e = taps + (int64_t)gi * 5;
-        if (col) {
-            sh.cs[l] = (int32_t)e[0];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) sh.cw[l][k] = e[1 + k];
-        } else {
-            sh.rs[l] = (int32_t)e[0];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) sh.rw[l][k] = e[1 + k];
-        }
-    }
+    lz_stage_records(taps, x0 - HALO, y0 - HALO, g.out_w, g.out_h, (int)tid, sh.cs, sh.cw, sh.rs, sh.rw);
     __syncthreads();
     const int32_t r0 = sh.rs[0] - 3;
     int32_t nrows = sh.rs[CH - 1] + 4 - r0 + 1;
@@ -104,24 +60,12 @@ __global__ __launch_bounds__(256) void k_lanczos4_tile(const uint8_t* __restrict
     for (int it = (int)tid; it < nrows * CW; it += 256) {
         const int row = it / CW, col = it - row * CW;
         const uint8_t* src = fin + (int64_t)lz_clampi(r0 + row, g.in_h - 1) * in_pitch;
-        const int32_t s = sh.cs[col];
         uint32_t d[6];
-        if (s - 3 >= 0 && s + 4 <= g.in_w - 1) {
-            __builtin_memcpy(d, src + (s - 3) * 3, 24);
-        } else {
+        int32_t h[3];
+        lz_window(src, sh.cs[col], g.in_w, d);
+        lz_hsum3(d, sh.cw[col], h);
 #pragma unroll
-            for (int q = 0; q < 6; ++q) d[q] = 0u;
-#pragma unroll
-            for (int k = 0; k < LZ_TAPS; ++k) {
-                const uint8_t* px = src + lz_clampi(s - 3 + k, g.in_w - 1) * 3;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) d[(3 * k + c) >> 2] |= (uint32_t)px[c] << (8 * ((3 * k + c) & 3));
-            }
-        }
-        const uint32_t w[4] = {sh.cw[col][0], sh.cw[col][1], sh.cw[col][2], sh.cw[col][3]};
-        sh.h[row][0][col] = lz_hsum_window<0>(d, w);
-        sh.h[row][1][col] = lz_hsum_window<1>(d, w);
-        sh.h[row][2][col] = lz_hsum_window<2>(d, w);
+        for (int c = 0; c < 3; ++c) sh.h[row][c][col] = h[c];
     }
     __syncthreads();
 
@@ -134,20 +78,10 @@ __global__ __launch_bounds__(256) void k_lanczos4_tile(const uint8_t* __restrict
         int32_t base = sh.rs[ly] - 3 - r0;
         base = base < 0 ? 0 : (base > LZ_MAXROWS - LZ_TAPS ? LZ_MAXROWS - LZ_TAPS : base);     // never taken (see nrows)
         int32_t wk[LZ_TAPS];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const uint32_t pw = sh.rw[ly][k];
-            wk[2 * k] = (int32_t)(int16_t)(pw & 0xffffu);
-            wk[2 * k + 1] = (int32_t)pw >> 16;
-        }
+        lz_unpack_weights(sh.rw[ly], wk);
         uint8_t o[3];
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            uint32_t v = 0;
-#pragma unroll
-            for (int k = 0; k < LZ_TAPS; ++k) v += (uint32_t)__mul24(sh.h[base + k][c][lx], wk[k]);
-            o[c] = lz_cast((int32_t)v);
-        }
+        for (int c = 0; c < 3; ++c) o[c] = lz_vsum(wk, [&](int k) { return sh.h[base + k][c][lx]; });
         if (HALO == 0) {
             uint8_t* dst = fout + ((int64_t)gy * g.out_w + gx) * 3;
             dst[0] = o[0]; dst[1] = o[1]; dst[2] = o[2];

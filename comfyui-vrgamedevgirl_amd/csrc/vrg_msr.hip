@@ -4,14 +4,12 @@
 //
 // The output is `repeats` times what is computed, so the launch is bounded by its stores: k_msr_tile filters a tile once and writes it
 // to every frame of the descriptor's run.  One workgroup = one 64 x 32 tile of one descriptor (blockIdx.x = tile, blockIdx.y = descriptor).
-//   stage    the tile's column and row records (s, eight int16 as four dwords) from the table into LDS, as k_lanczos4_tile does;
+// The filter is the tile filter of csrc/vrg_lanczos_tile.hpp, whose comment describes the staging and the two filter passes.
 //   strips   thread 0 plans the next strip of output rows (msr_plan_strip: the distinct source rows of the strip, at most MSR_SLOTS, with
 //            no gap between rows that do not overlap);
-//   pass 1   every slot's source row is filtered horizontally for the tile's columns: one thread = one (slot, column), 24 consecutive
-//            bytes = six unaligned dword loads (clamped columns gather byte by byte), v_perm_b32 + v_dot2_i32_i16; int32 sums to LDS,
-//            channel-planar;
-//   pass 2   one thread = one output pixel of the strip: eight LDS rows x three channels, v_mad_i32_i24, FixedPtCast; the bytes stay in
-//            LDS.  A picture that already has the output size, or a constant colour, puts its bytes there directly;
+//   pass 1   every slot's source row is filtered horizontally for the tile's columns: one thread = one (slot, column);
+//   pass 2   one thread = one output pixel of the strip, its taps' rows found through the slots; the bytes stay in LDS.  A picture that
+//            already has the output size, or a constant colour, puts its bytes there directly;
 //   convert  one thread = six groups of four consecutive values of a tile row (a row is 192 values = 48 groups): four bytes are one LDS
 //            dword, each becomes (float)byte / 255.0f by the IEEE division, once;
 //   store    the same 24 registers go to every frame of the run.  A group whose address is a multiple of 16 is one non-temporal
@@ -20,6 +18,7 @@
 //            non-temporal stores.
 // LDS: 40 x 3 x 64 x 4 B = 30.0 KB of sums + 6.0 KB of bytes + 2.8 KB of records and plans: four workgroups per CU.
 #include "vrg_common.hpp"
+#include "vrg_lanczos_tile.hpp"
 #include "vrg_msr_math.hpp"
 
 namespace vrg {
@@ -34,31 +33,6 @@ struct MsrShared {
     int32_t slot0[MSR_TH], srcrow[MSR_SLOTS];
     int32_t strip_rows, strip_slots;
 };
-
-__device__ __forceinline__ int32_t msr_dot2(uint32_t pair, uint32_t w, int32_t acc) {
-    typedef short msr_s2 __attribute__((ext_vector_type(2)));
-    msr_s2 a, b;
-    __builtin_memcpy(&a, &pair, 4);
-    __builtin_memcpy(&b, &w, 4);
-    return __builtin_amdgcn_sdot2(a, b, acc, false);
-}
-
-// bytes j0 and j1 of the 24-byte window d[6] as (byte j0) | (byte j1) << 16
-template <int J0, int J1>
-__device__ __forceinline__ uint32_t msr_pair(const uint32_t (&d)[6]) {
-    constexpr uint32_t sel = 0x0c000c00u | (uint32_t)(J0 & 3) | ((uint32_t)(4 + (J1 & 3)) << 16);
-    return __builtin_amdgcn_perm(d[J1 >> 2], d[J0 >> 2], sel);
-}
-
-template <int C>
-__device__ __forceinline__ int32_t msr_hsum_window(const uint32_t (&d)[6], const uint32_t (&w)[4]) {
-    int32_t acc = 0;
-    acc = msr_dot2(msr_pair<C, C + 3>(d), w[0], acc);
-    acc = msr_dot2(msr_pair<C + 6, C + 9>(d), w[1], acc);
-    acc = msr_dot2(msr_pair<C + 12, C + 15>(d), w[2], acc);
-    acc = msr_dot2(msr_pair<C + 18, C + 21>(d), w[3], acc);
-    return acc;
-}
 
 __global__ __launch_bounds__(256) void k_msr_tile(const vrg_msr_desc* __restrict__ desc, const uint32_t* __restrict__ taps, int64_t n_taps,
                                                    float* __restrict__ out, int64_t frames, int32_t out_h, int32_t out_w, int32_t tiles_x) {
@@ -81,22 +55,7 @@ __global__ __launch_bounds__(256) void k_msr_tile(const vrg_msr_desc* __restrict
             ub[it] = d.src ? d.src[(int64_t)(y0 + ly) * pitch + (int64_t)x0 * 3 + i] : (uint8_t)(fill >> (8 * (i % 3)));
         }
     } else {
-        const uint32_t* ctab = taps + (int64_t)d.taps * 5;
-        for (int i = tid; i < MSR_TW + MSR_TH; i += 256) {
-            const bool col = i < MSR_TW;
-            const int l = col ? i : i - MSR_TW;
-            const int32_t gi = col ? lz_clampi(x0 + l, out_w - 1) : out_w + lz_clampi(y0 + l, out_h - 1);
-            const uint32_t* e = ctab + (int64_t)gi * 5;
-            if (col) {
-                sh.cs[l] = (int32_t)e[0];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) sh.cw[l][k] = e[1 + k];
-            } else {
-                sh.rs[l] = (int32_t)e[0];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) sh.rw[l][k] = e[1 + k];
-            }
-        }
+        lz_stage_records(taps + (int64_t)d.taps * 5, x0, y0, out_w, out_h, tid, sh.cs, sh.cw, sh.rs, sh.rw);
         const int64_t in_pitch = (int64_t)d.in_w * 3;
         for (int32_t ly0 = 0; ly0 < rows;) {
             __syncthreads();                       // the records are staged; the previous strip's sums have been read
@@ -113,24 +72,12 @@ __global__ __launch_bounds__(256) void k_msr_tile(const vrg_msr_desc* __restrict
                 const int slot = it / MSR_TW, col = it - slot * MSR_TW;
                 if (col >= cols) continue;
                 const uint8_t* src = d.src + (int64_t)sh.srcrow[slot] * in_pitch;
-                const int32_t s = sh.cs[col];
                 uint32_t w6[6];
-                if (s >= 3 && s <= d.in_w - 5) {
-                    __builtin_memcpy(w6, src + (int64_t)(s - 3) * 3, 24);
-                } else {
+                int32_t h[3];
+                lz_window(src, sh.cs[col], d.in_w, w6);
+                lz_hsum3(w6, sh.cw[col], h);
 #pragma unroll
-                    for (int q = 0; q < 6; ++q) w6[q] = 0u;
-#pragma unroll
-                    for (int k = 0; k < LZ_TAPS; ++k) {
-                        const uint8_t* px = src + (int64_t)lz_clampi(s - 3 + k, d.in_w - 1) * 3;
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) w6[(3 * k + c) >> 2] |= (uint32_t)px[c] << (8 * ((3 * k + c) & 3));
-                    }
-                }
-                const uint32_t w[4] = {sh.cw[col][0], sh.cw[col][1], sh.cw[col][2], sh.cw[col][3]};
-                sh.h[slot][0][col] = msr_hsum_window<0>(w6, w);
-                sh.h[slot][1][col] = msr_hsum_window<1>(w6, w);
-                sh.h[slot][2][col] = msr_hsum_window<2>(w6, w);
+                for (int c = 0; c < 3; ++c) sh.h[slot][c][col] = h[c];
             }
             __syncthreads();
 
@@ -140,24 +87,15 @@ __global__ __launch_bounds__(256) void k_msr_tile(const vrg_msr_desc* __restrict
                 if (lx >= cols) continue;
                 const int32_t s = sh.rs[ly], a = lz_clampi(s - 3, d.in_h - 1), first = sh.slot0[ly];
                 int32_t wk[LZ_TAPS], sk[LZ_TAPS];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const uint32_t pw = sh.rw[ly][k];
-                    wk[2 * k] = (int32_t)(int16_t)(pw & 0xffffu);
-                    wk[2 * k + 1] = (int32_t)pw >> 16;
-                }
+                lz_unpack_weights(sh.rw[ly], wk);
 #pragma unroll
                 for (int k = 0; k < LZ_TAPS; ++k) {
                     const int32_t slot = first + lz_clampi(s - 3 + k, d.in_h - 1) - a;
                     sk[k] = slot < 0 ? 0 : (slot > MSR_SLOTS - 1 ? MSR_SLOTS - 1 : slot);       // never taken (see msr_plan_strip)
                 }
 #pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    uint32_t v = 0;
-#pragma unroll
-                    for (int k = 0; k < LZ_TAPS; ++k) v += (uint32_t)__mul24(sh.h[sk[k]][c][lx], wk[k]);
-                    ub[ly * MSR_ROW_VALUES + lx * 3 + c] = lz_cast((int32_t)v);
-                }
+                for (int c = 0; c < 3; ++c)
+                    ub[ly * MSR_ROW_VALUES + lx * 3 + c] = lz_vsum(wk, [&](int k) { return sh.h[sk[k]][c][lx]; });
             }
             ly0 += n;
         }

@@ -389,39 +389,39 @@ def _sharpen_then_seeded_grain_u8(frames_bgr, sharpen_strength, zero_border, gra
 # VRGDG_StandaloneVideoEnhancerNodes.py:213-230) and the upscale fused into sharpen -> grain
 # ---------------------------------------------------------------------------------------------
 LANCZOS_TAP_BYTES = 20          # one record of the table: int32 s, eight int16 weights (csrc/vrg_lanczos_math.hpp: LzTap)
-_lanczos_lock = threading.Lock()
-_lanczos_host_lib = None
+_host_lib = _hip.host_library   # the library for its HOST table functions (no GPU needed)
+_upload_lock = threading.Lock()
 _lanczos_tables: dict = {}      # (in_h, in_w, out_h, out_w, device) -> the uploaded table
+
+
+def _uploaded(cache: dict, key, build, device) -> torch.Tensor:
+    """``cache[key]``: on a miss the byte table of ``build()`` (a numpy array), uploaded to ``device``.  A cache that holds 64 tables is
+    cleared first: a handful of geometries per job; never grows without bound."""
+    t = cache.get(key)
+    if t is None:
+        t = torch.from_numpy(build()).to(device)
+        with _upload_lock:
+            if len(cache) >= 64:
+                cache.clear()
+            cache[key] = t
+    return t
 
 
 def lanczos4_taps(in_h: int, in_w: int, out_h: int, out_w: int) -> np.ndarray:
     """The table of the two Lanczos kernels, made on the host (no GPU needed): ``out_w`` column records then ``out_h`` row records as a
     structured array with fields ``s`` (floor of the source coordinate; the taps are s - 3 .. s + 4, clamped) and ``w`` (eight int16)."""
-    global _lanczos_host_lib
     in_h, in_w, out_h, out_w = int(in_h), int(in_w), int(out_h), int(out_w)
     if min(in_h, in_w, out_h, out_w) < 1:
         raise ValueError("lanczos4_taps: sizes must be at least 1")
-    if _lanczos_host_lib is None:
-        with _lanczos_lock:
-            if _lanczos_host_lib is None:
-                _lanczos_host_lib = _hip.load_library()
     table = np.zeros(out_w + out_h, dtype=np.dtype([("s", "<i4"), ("w", "<i2", (8,))]))
     assert table.dtype.itemsize == LANCZOS_TAP_BYTES
-    _hip.check(_lanczos_host_lib.vrg_lanczos4_taps(in_h, in_w, out_h, out_w, C.c_void_p(table.ctypes.data)), "vrg_lanczos4_taps")
+    _hip.check(_host_lib().vrg_lanczos4_taps(in_h, in_w, out_h, out_w, C.c_void_p(table.ctypes.data)), "vrg_lanczos4_taps")
     return table
 
 
 def _lanczos_table(in_h, in_w, out_h, out_w, device) -> torch.Tensor:
-    key = (in_h, in_w, out_h, out_w, str(device))
-    t = _lanczos_tables.get(key)
-    if t is None:
-        host = torch.from_numpy(lanczos4_taps(in_h, in_w, out_h, out_w).view(np.uint8).copy())
-        t = host.to(device)
-        with _lanczos_lock:
-            if len(_lanczos_tables) >= 64:          # a handful of geometries per job; never grows without bound
-                _lanczos_tables.clear()
-            _lanczos_tables[key] = t
-    return t
+    return _uploaded(_lanczos_tables, (in_h, in_w, out_h, out_w, str(device)),
+                     lambda: lanczos4_taps(in_h, in_w, out_h, out_w).view(np.uint8).copy(), device)
 
 
 def _lanczos_sizes(x, out_w, out_h):
@@ -983,18 +983,8 @@ def composite_frames(originals: torch.Tensor, crops: torch.Tensor, entries, rule
 # (csrc/vrg_warp_math.hpp), the warp fused into the composite pass
 # ------------------------------------------------------------------------------------------------
 _warp_lock = threading.Lock()
-_warp_host_lib = None
 _warp_host_table = None
 _warp_tables: dict = {}          # device -> the uploaded phase table
-
-
-def _warp_lib():
-    global _warp_host_lib
-    if _warp_host_lib is None:
-        with _warp_lock:
-            if _warp_host_lib is None:
-                _warp_host_lib = _hip.load_library()
-    return _warp_host_lib
 
 
 def warp_phase_table() -> np.ndarray:
@@ -1003,7 +993,7 @@ def warp_phase_table() -> np.ndarray:
     global _warp_host_table
     if _warp_host_table is None:
         table = np.zeros((1024, 8, 8), dtype=np.int16)
-        _hip.check(_warp_lib().vrg_warp_phase_table(C.c_void_p(table.ctypes.data)), "vrg_warp_phase_table")
+        _hip.check(_host_lib().vrg_warp_phase_table(C.c_void_p(table.ctypes.data)), "vrg_warp_phase_table")
         table.setflags(write=False)
         _warp_host_table = table
     return _warp_host_table
@@ -1046,7 +1036,7 @@ def _warp_record_table(transforms, sizes, sources, offsets):
     """ctypes array of _hip.WarpDesc: result size sizes[f], source image sources[f] = (w, h) at offsets[f]; transforms[f] None = not set"""
     n = len(transforms)
     table = (_hip.WarpDesc * max(1, n))()
-    lib = _warp_lib()
+    lib = _host_lib()
     for f, t in enumerate(transforms):
         if t is None or sizes[f] is None or offsets[f] < 0:
             continue
@@ -1491,29 +1481,16 @@ def _check_cut_shape(shape):
 def area_taps(in_h: int, in_w: int) -> np.ndarray:
     """The table of the thumbnail kernel, made on the host (no GPU needed): 64 column cells then 64 row cells (AREA_CELL records: the
     taps of output index d are the source samples first .. first + count - 1, the first weighs w_first, the last w_last, the others w_mid)."""
-    global _lanczos_host_lib
     in_h, in_w = int(in_h), int(in_w)
     if min(in_h, in_w) < CUT_THUMB:
         raise ValueError(f"area_taps: sides must be at least {CUT_THUMB}")
-    if _lanczos_host_lib is None:
-        with _lanczos_lock:
-            if _lanczos_host_lib is None:
-                _lanczos_host_lib = _hip.load_library()
     table = np.zeros(2 * CUT_THUMB, dtype=AREA_CELL)
-    _hip.check(_lanczos_host_lib.vrg_area_taps(in_h, in_w, C.c_void_p(table.ctypes.data)), "vrg_area_taps")
+    _hip.check(_host_lib().vrg_area_taps(in_h, in_w, C.c_void_p(table.ctypes.data)), "vrg_area_taps")
     return table
 
 
 def _area_table(in_h, in_w, device) -> torch.Tensor:
-    key = (in_h, in_w, str(device))
-    t = _area_tables.get(key)
-    if t is None:
-        t = torch.from_numpy(area_taps(in_h, in_w).view(np.uint8).copy()).to(device)
-        with _lanczos_lock:
-            if len(_area_tables) >= 64:
-                _area_tables.clear()
-            _area_tables[key] = t
-    return t
+    return _uploaded(_area_tables, (in_h, in_w, str(device)), lambda: area_taps(in_h, in_w).view(np.uint8).copy(), device)
 
 
 @_on_device
@@ -1864,16 +1841,6 @@ DETECT_MAX_SIDE = 32767         # positions of the warp are int16
 DETECT_DESC = np.dtype([("frame", "<i4"), ("transform", "<i4"), ("left", "<i4"), ("top", "<i4"), ("right", "<i4"), ("bottom", "<i4")])
 DETECT_FRAME_DESC = np.dtype([("frame", "<i4"), ("transform", "<i4")])
 assert DETECT_DESC.itemsize == C.sizeof(_hip.DetectDesc) and DETECT_FRAME_DESC.itemsize == C.sizeof(_hip.DetectFrameDesc)
-
-
-def _host_lib():
-    """the library for its HOST table functions (no GPU needed)"""
-    global _lanczos_host_lib
-    if _lanczos_host_lib is None:
-        with _lanczos_lock:
-            if _lanczos_host_lib is None:
-                _lanczos_host_lib = _hip.load_library()
-    return _lanczos_host_lib
 
 
 def linear_taps(n_in: int, n_out: int = DETECT_BLOB) -> dict:
@@ -3089,7 +3056,7 @@ class MsrPlan:
 
     def check(self, desc: Optional[np.ndarray] = None) -> None:
         d = np.ascontiguousarray(self.desc if desc is None else desc)
-        _hip.check(_hip.load_library().vrg_msr_check(C.c_void_p(d.ctypes.data), len(d), self.n_taps, self.frames, self.height, self.width),
+        _hip.check(_host_lib().vrg_msr_check(C.c_void_p(d.ctypes.data), len(d), self.n_taps, self.frames, self.height, self.width),
                    "vrg_msr_check")
 
 
@@ -3127,15 +3094,7 @@ def msr_plan(shapes, size, frame_count: int, fill=None) -> MsrPlan:
 
 
 def _msr_table(plan: MsrPlan, device) -> torch.Tensor:
-    key = (plan.sizes, plan.height, plan.width, str(device))
-    t = _msr_tables.get(key)
-    if t is None:
-        t = torch.from_numpy(plan.table()).to(device)
-        with _lanczos_lock:
-            if len(_msr_tables) >= 64:              # a handful of geometries per job; never grows without bound
-                _msr_tables.clear()
-            _msr_tables[key] = t
-    return t
+    return _uploaded(_msr_tables, (plan.sizes, plan.height, plan.width, str(device)), plan.table, device)
 
 
 def _msr_picture(p, i):

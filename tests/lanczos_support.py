@@ -115,6 +115,14 @@ def smooth_frames(shape, seed):
     return out
 
 
+def has_both_column_kinds(column_s, in_w):
+    """Of the columns of a table (their ``s``): do some read their eight pixels as one 24-byte window (taps s - 3 .. s + 4 inside the row)
+    and some gather them clamped?  With in_w == 8 the only window is s == 3, the row's 24 bytes exactly."""
+    s = np.asarray(column_s)
+    window = (s >= 3) & (s <= in_w - 5)
+    return bool(window.any() and not window.all()) and (in_w != 8 or bool((s[window] == 3).all()))
+
+
 def build_host_lib(directory):
     out = os.path.join(str(directory), "liblanczos_check.so")
     src = os.path.join(ROOT, "tests", "host_math", "lanczos_check.cpp")

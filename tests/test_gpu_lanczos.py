@@ -41,11 +41,14 @@ def report(name, got, want):
 
 # frames, (h, w) -> (oh, ow)
 RESIZE_CASES = ((1, (1, 1), (1, 1)), (1, (1, 1), (5, 7)), (2, (480, 854), (768, 1366)), (2, (60, 80), (90, 120)), (3, (54, 96), (108, 192)),
-                (1, (72, 128), (216, 384)), (2, (64, 96), (32, 48)), (5, (37, 53), (89, 131)), (2, (3, 200), (41, 7)), (1, (130, 70), (131, 260)))
+                (1, (72, 128), (216, 384)), (2, (64, 96), (32, 48)), (5, (37, 53), (89, 131)), (2, (3, 200), (41, 7)), (1, (130, 70), (131, 260)),
+                (1, (2, 8), (3, 16)))          # 8 wide: the one column position (s == 3) whose 24-byte window is the whole row; the others gather
 
 
 @pytest.mark.parametrize("frames,src,dst", RESIZE_CASES)
 def test_lanczos4_equals_the_restatement(ops, frames, src, dst):
+    if src[1] == 8:
+        assert LS.has_both_column_kinds(ops.lanczos4_taps(src[0], src[1], dst[0], dst[1])["s"][:dst[1]], src[1])
     x = LS.random_frames((frames, src[0], src[1], 3), 3 + src[1])
     xd = torch.from_numpy(x).to(dev())
     got = ops.resize_frames_u8(xd, dst[1], dst[0])
@@ -85,8 +88,11 @@ SETTINGS = [(strength, zero, intensity) for zero in (False, True) for strength, 
 
 
 @pytest.mark.parametrize("strength,zero,intensity", SETTINGS)
-@pytest.mark.parametrize("src,dst", (((54, 96), (108, 192)), ((48, 85), (77, 137)), ((1, 1), (5, 7)), ((270, 480), (540, 960))))
+@pytest.mark.parametrize("src,dst", (((54, 96), (108, 192)), ((48, 85), (77, 137)), ((1, 1), (5, 7)), ((270, 480), (540, 960)),
+                                     ((2, 8), (3, 16))))
 def test_fused_equals_the_two_launches(ops, src, dst, strength, zero, intensity):
+    if src[1] == 8:
+        assert LS.has_both_column_kinds(ops.lanczos4_taps(src[0], src[1], dst[0], dst[1])["s"][:dst[1]], src[1])
     x = LS.random_frames((3, src[0], src[1], 3), 23)
     xd = torch.from_numpy(x).to(dev())
     args = (strength, zero, intensity, 0.35, 42, 5)                       # frame_start = 5

@@ -16,8 +16,10 @@ from conftest import PKG_NAME
 pytestmark = pytest.mark.gpu
 
 #: (in_w, in_h, out_w, out_h, repeats of the picture): one source pixel; frames off the 16-byte grid (33 * 5 * 3 values); an enlargement
-#: with a tile seam; a shrink above 3 (disjoint tap rows); a strong shrink along one axis; a picture that already has the size
-GEOMETRIES = ((1, 1, 32, 32, 2), (7, 5, 33, 5, 3), (37, 53, 96, 64, 2), (301, 203, 64, 96, 2), (1024, 16, 32, 64, 1), (96, 64, 96, 64, 2))
+#: with a tile seam; a shrink above 3 (disjoint tap rows); a strong shrink along one axis; a picture that already has the size;
+#: a source 8 wide: the one column position (s == 3) whose 24-byte window is the whole row, every other column gathers
+GEOMETRIES = ((1, 1, 32, 32, 2), (7, 5, 33, 5, 3), (37, 53, 96, 64, 2), (301, 203, 64, 96, 2), (1024, 16, 32, 64, 1), (96, 64, 96, 64, 2),
+              (8, 2, 16, 3, 1))
 GUARD = 64                      # floats before and after the output inside the larger allocation
 
 
@@ -65,6 +67,8 @@ def test_launch_equals_the_restatement(ops, in_w, in_h, out_w, out_h, repeats):
     the floats around it must stay NaN"""
     from comfyui_vrgamedevgirl_amd import _hip
     dev = torch.device("cuda", 0)
+    if in_w == 8:
+        assert LS.has_both_column_kinds(ops.lanczos4_taps(in_h, in_w, out_h, out_w)["s"][:out_w], in_w)
     first = LS.random_frames((1, in_h, in_w, 3), 7 * in_w + in_h)[0]
     second = LS.smooth_frames((1, in_h + 3, in_w + 2, 3), 5)[0]
     colour = (3, 127, 252)
