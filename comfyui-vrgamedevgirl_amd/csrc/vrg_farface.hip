@@ -1,6 +1,7 @@
 // vrg_farface.hip -- the pixels of the far-face repair composite (reference scripts/far_face_repair_backend.py: composite :339-371) on
 // decoded bytes: Pillow's LANCZOS resize, its GaussianBlur of the soft-ellipse mask, numpy's fp32 mean shift and Image.paste under an L
-// mask, each byte for byte.  gfx950 only.  Arithmetic: csrc/vrg_pil_math.hpp.
+// mask, each byte for byte.  gfx950 only.  Arithmetic: csrc/vrg_pil_math.hpp; the resize's tables, tap records and passes:
+// csrc/vrg_pil_resample.hpp, whose four HOST table functions (vrg_pil_lanczos_*, vrg_pil_filter_*) are exported below.
 //
 // Shape of the work.  A job is a batch of byte frames, at most one box per frame, and one repaired crop (of any size) per box.
 //   k_pil_resize_h / _v   Image.resize: blockIdx.y = the output image, so its record is wave-uniform; one thread = one pixel of the pass,
@@ -37,13 +38,6 @@ __device__ __forceinline__ bool pil_resize_ok(const vrg_pil_resize_desc& d, cons
     return true;
 }
 
-// the bounds of output index i of a table of n_out records, checked against the n_in sources
-__device__ __forceinline__ bool pil_bounds(const int32_t* __restrict__ table, int32_t i, int32_t ksize, int32_t n_in, int32_t& first, int32_t& n) {
-    first = table[2 * i];
-    n = table[2 * i + 1];
-    return first >= 0 && n >= 0 && n <= ksize && first <= n_in - n;
-}
-
 template <int C>
 __global__ __launch_bounds__(256) void k_pil_resize_h(const uint8_t* __restrict__ src, const vrg_pil_resize_desc* __restrict__ desc,
                                                        const int32_t* __restrict__ tables, uint8_t* __restrict__ tmp, uint8_t* __restrict__ dst,
@@ -53,13 +47,12 @@ __global__ __launch_bounds__(256) void k_pil_resize_h(const uint8_t* __restrict_
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= (int64_t)d.in_h * d.out_w) return;
     const int32_t y = (int32_t)(p / d.out_w), x = (int32_t)(p - (int64_t)y * d.out_w);
-    const int32_t* table = tables + d.h_table;
     uint8_t* out = (d.in_h != d.out_h ? tmp + d.tmp_offset : dst + d.dst_offset) + p * C;
     uint8_t o[C];
-    int32_t first, n;
-    if (pil_bounds(table, x, d.h_ksize, d.in_w, first, n)) {
-        const uint8_t* row = src + d.src_offset + ((int64_t)y * d.in_w + first) * C;
-        pil_taps<C>(table + 2 * (int64_t)d.out_w + (int64_t)x * d.h_ksize, n, [&](int32_t i, int c) { return row[i * C + c]; }, o);
+    const PilRecord t = pil_record(tables + d.h_table, d.out_w, x, d.h_ksize, 0, d.in_w);
+    if (t.ok) {
+        const uint8_t* row = src + d.src_offset + ((int64_t)y * d.in_w + t.first) * C;
+        pil_taps<C>(t.w, t.n, [&](int32_t i, int c) { return row[i * C + c]; }, o);
     } else {
         for (int c = 0; c < C; ++c) o[c] = 0;
     }
@@ -83,12 +76,9 @@ __global__ __launch_bounds__(256) void k_pil_resize_v(const uint8_t* __restrict_
         for (int c = 0; c < C; ++c) o[c] = from[p * C + c];
     } else {
         const int32_t y = (int32_t)(p / d.out_w), x = (int32_t)(p - (int64_t)y * d.out_w);
-        const int32_t* table = tables + d.v_table;
-        int32_t first, n;
-        if (pil_bounds(table, y, d.v_ksize, d.in_h, first, n)) {
-            const uint8_t* col = from + ((int64_t)first * d.out_w + x) * C;
-            const int64_t pitch = (int64_t)d.out_w * C;
-            pil_taps<C>(table + 2 * (int64_t)d.out_h + (int64_t)y * d.v_ksize, n, [&](int32_t i, int c) { return col[i * pitch + c]; }, o);
+        const PilRecord t = pil_record(tables + d.v_table, d.out_h, y, d.v_ksize, 0, d.in_h);
+        if (t.ok) {
+            pil_walk<C>(t.w, t.n, from + ((int64_t)t.first * d.out_w + x) * C, (int64_t)d.out_w * C, o);
         } else {
             for (int c = 0; c < C; ++c) o[c] = 0;
         }
@@ -321,11 +311,29 @@ using namespace vrg;
 
 extern "C" {
 
-int32_t vrg_pil_lanczos_ksize(int32_t n_in, int32_t n_out) { return (n_in < 1 || n_out < 1) ? 0 : pil_lanczos_ksize(n_in, n_out); }
+// the whole axis: the one builder over (0, n_in), which no float passes through
+int32_t vrg_pil_lanczos_ksize(int32_t n_in, int32_t n_out) {
+    return (n_in < 1 || n_out < 1) ? 0 : pil_lanczos_ksize(n_in, n_out);
+}
 
 int vrg_pil_lanczos_table(int32_t n_in, int32_t n_out, int32_t* bounds_host, int32_t* weights_host) {
     if (!bounds_host || !weights_host || n_in < 1 || n_out < 1) return VRG_ERR_BAD_ARG;
     pil_lanczos_table(n_in, n_out, bounds_host, weights_host);
+    return VRG_OK;
+}
+
+// a box, as Pillow's C takes it
+int32_t vrg_pil_filter_ksize(int32_t filter, float in0, float in1, int32_t n_out) {
+    if (!pil_filter_known(filter) || n_out < 1 || !(in0 >= 0.0f) || !(in1 >= in0) || !(in1 <= 2147483520.0f)) return 0;
+    const double k = ceil(pil_filter_support(filter) * fmax(pil_box_span(in0, in1) / n_out, 1.0)) * 2 + 1;
+    return k > 2147483647.0 ? 0 : (int32_t)k;
+}
+
+int vrg_pil_filter_table(int32_t filter, int32_t n_in, float in0, float in1, int32_t n_out, int32_t* bounds_host, int32_t* weights_host) {
+    if (!bounds_host || !weights_host || !pil_filter_known(filter) || n_in < 1 || n_out < 1 || !(in0 >= 0.0f) || !(in1 >= in0) ||
+        !(in1 <= (float)n_in) || vrg_pil_filter_ksize(filter, in0, in1, n_out) < 1)
+        return VRG_ERR_BAD_ARG;
+    pil_filter_table(filter, n_in, in0, pil_box_span(in0, in1), n_out, bounds_host, weights_host);
     return VRG_OK;
 }
 

@@ -1,6 +1,7 @@
 // vrg_sheet.hip -- the reference sheets (VRGDG_LTXICIngredientsGrid.build and the three sheet builders of the AI Video Builder of the
 // reference): fp32 or byte pictures quantised, shrunk with Pillow's LANCZOS and pasted as panels onto a coloured canvas, byte for byte.
-// gfx950 only.  Arithmetic: csrc/vrg_sheet_math.hpp (on top of vrg_pil_math.hpp and vrg_grid_math.hpp).
+// gfx950 only.  Arithmetic: csrc/vrg_sheet_math.hpp (on top of vrg_pil_resample.hpp, whose byte staging and flat piece writer the kernels
+// share with the contact sheet, and vrg_grid_math.hpp).
 //
 // k_sheet_rows     the horizontal pass.  One workgroup = SHEET_ROWS source rows of one column segment of one panel.  Per row the 256
 //                  threads read the source values the segment's taps touch ONCE with 16-byte non-temporal loads, quantise them and leave
@@ -11,9 +12,7 @@
 //                  of the window never touch and columns outside the window's taps are not read at all.
 // k_sheet_compose  one pass over the canvas as a flat run of elements, one 16-byte piece per thread (four floats or sixteen bytes): per
 //                  pixel the panels are walked from last to first (sheet_panel_at), the element is the vertical pass over tmp, the cell
-//                  colour or the background (sheet_canvas_byte), and the piece goes out in one non-temporal store.  The elements in front
-//                  of the first 16-byte boundary of `out` and behind the last whole piece are stored one by one by one extra thread.
-//                  Nothing of `out` is read.
+//                  colour or the background (sheet_canvas_byte); SheetCursor gives pil_flat_write the elements.
 #include "vrg_sheet_math.hpp"
 
 namespace vrg {
@@ -21,27 +20,24 @@ namespace vrg {
 constexpr int SHEET_THREADS = 256;
 constexpr int SHEET_STAGE_BYTES = SHEET_STAGE_VALUES + 32;                    // a staged value lies at the phase of its source address
 
-typedef float sheet_f4 __attribute__((ext_vector_type(4)));
-typedef uint32_t sheet_u4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ uint32_t sheet_quant4(const sheet_f4 v) {
+__device__ __forceinline__ uint32_t sheet_quant4(const pil_f4 v) {
     return (uint32_t)grid_quant(v.x) | ((uint32_t)grid_quant(v.y) << 8) | ((uint32_t)grid_quant(v.z) << 16) | ((uint32_t)grid_quant(v.w) << 24);
 }
 
-// n values from src as bytes into rb by the whole workgroup: value i lands at rb[ph + i], ph the returned phase (fp32: the float's index
-// mod 4; bytes: the address mod 16), so that the 16-byte loads and the LDS words they fill are both aligned.  n <= SHEET_STAGE_VALUES.
+// n floats from src quantised into rb by the whole workgroup: value i lands at rb[ph + i], ph the returned phase (the float's index mod 4),
+// so that the 16-byte loads and the LDS words they fill are both aligned; bytes go through pil_stage_bytes.  n <= SHEET_STAGE_VALUES.
 __device__ __forceinline__ int sheet_stage(const float* src, int n, uint8_t* rb, int tid) {
     const int ph = (int)((reinterpret_cast<uintptr_t>(src) >> 2) & 3u);
     int head = (4 - ph) & 3;
     head = head < n ? head : n;
     const int nq = (n - head) >> 2;
     if (tid < head) rb[ph + tid] = grid_quant(src[tid]);
-    const sheet_f4* body = reinterpret_cast<const sheet_f4*>(src + head);
+    const pil_f4* body = reinterpret_cast<const pil_f4*>(src + head);
     uint32_t* dst = reinterpret_cast<uint32_t*>(rb + ph + head);
     int q = tid;
     for (; q + 3 * SHEET_THREADS < nq; q += 4 * SHEET_THREADS) {                // four loads in flight per thread
-        const sheet_f4 v0 = __builtin_nontemporal_load(body + q), v1 = __builtin_nontemporal_load(body + q + SHEET_THREADS);
-        const sheet_f4 v2 = __builtin_nontemporal_load(body + q + 2 * SHEET_THREADS), v3 = __builtin_nontemporal_load(body + q + 3 * SHEET_THREADS);
+        const pil_f4 v0 = __builtin_nontemporal_load(body + q), v1 = __builtin_nontemporal_load(body + q + SHEET_THREADS);
+        const pil_f4 v2 = __builtin_nontemporal_load(body + q + 2 * SHEET_THREADS), v3 = __builtin_nontemporal_load(body + q + 3 * SHEET_THREADS);
         dst[q] = sheet_quant4(v0);
         dst[q + SHEET_THREADS] = sheet_quant4(v1);
         dst[q + 2 * SHEET_THREADS] = sheet_quant4(v2);
@@ -53,19 +49,7 @@ __device__ __forceinline__ int sheet_stage(const float* src, int n, uint8_t* rb,
     return ph;
 }
 
-__device__ __forceinline__ int sheet_stage(const uint8_t* src, int n, uint8_t* rb, int tid) {
-    const int ph = (int)(reinterpret_cast<uintptr_t>(src) & 15u);
-    int head = (16 - ph) & 15;
-    head = head < n ? head : n;
-    const int nq = (n - head) >> 4;
-    if (tid < head) rb[ph + tid] = src[tid];
-    const sheet_u4* body = reinterpret_cast<const sheet_u4*>(src + head);
-    sheet_u4* dst = reinterpret_cast<sheet_u4*>(rb + ph + head);
-    for (int q = tid; q < nq; q += SHEET_THREADS) dst[q] = __builtin_nontemporal_load(body + q);
-    const int t = head + 16 * nq + tid;                                        // at most 15 bytes behind the last 16-byte piece
-    if (t < n) rb[ph + t] = src[t];
-    return ph;
-}
+__device__ __forceinline__ int sheet_stage(const uint8_t* src, int n, uint8_t* rb, int tid) { return pil_stage_bytes(src, n, rb, tid, SHEET_THREADS); }
 
 template <typename T>
 __global__ __launch_bounds__(SHEET_THREADS) void k_sheet_rows(const vrg_sheet_panel* __restrict__ panels, const int32_t* __restrict__ tables,
@@ -108,53 +92,36 @@ struct SheetCanvas {
     uint32_t background;
 };
 
-// element e of the canvas; `px`, `at`: the pixel the caller resolved last and its panel
-__device__ __forceinline__ uint8_t sheet_element(const vrg_sheet_panel* __restrict__ panels, const int32_t* __restrict__ tables,
-                                                 const int32_t* __restrict__ spans, const uint8_t* __restrict__ tmp, const SheetCanvas& g, int64_t e,
-                                                 int64_t& px, int64_t& at) {
-    const int64_t pixel = e / 3;
-    const int32_t c = (int32_t)(e - pixel * 3);
-    const int32_t y = (int32_t)(pixel / g.width), x = (int32_t)(pixel - (int64_t)y * g.width);
-    if (pixel != px) {
-        px = pixel;
-        at = sheet_panel_at(panels, g.n, spans, g.n_spans, g.bytes != 0, g.table_ints, g.tmp_bytes, x, y);
+// the elements of the canvas for pil_flat_write; `px`, `at`: the pixel resolved last and its panel
+struct SheetCursor {
+    const vrg_sheet_panel* __restrict__ panels;
+    const int32_t* __restrict__ tables;
+    const int32_t* __restrict__ spans;
+    const uint8_t* __restrict__ tmp;
+    const SheetCanvas& g;
+    int64_t e, px, at;
+
+    __device__ __forceinline__ void seek(int64_t to) { e = to; }
+    __device__ __forceinline__ uint8_t next() {
+        const int64_t pixel = e / 3;
+        const int32_t c = (int32_t)(e - pixel * 3);
+        const int32_t y = (int32_t)(pixel / g.width), x = (int32_t)(pixel - (int64_t)y * g.width);
+        if (pixel != px) {
+            px = pixel;
+            at = sheet_panel_at(panels, g.n, spans, g.n_spans, g.bytes != 0, g.table_ints, g.tmp_bytes, x, y);
+        }
+        ++e;
+        return sheet_canvas_byte(panels, at, tables, tmp, g.background, x, y, c);
     }
-    return sheet_canvas_byte(panels, at, tables, tmp, g.background, x, y, c);
-}
+    static __device__ __forceinline__ float unit(uint8_t b) { return sheet_unit(b); }
+};
 
 template <typename O>
 __global__ __launch_bounds__(SHEET_THREADS) void k_sheet_compose(const vrg_sheet_panel* __restrict__ panels, const int32_t* __restrict__ tables,
                                                                   const int32_t* __restrict__ spans, const uint8_t* __restrict__ tmp,
                                                                   O* __restrict__ out, SheetCanvas g, int64_t lead, int64_t pieces) {
-    constexpr int V = 16 / (int)sizeof(O);                                     // elements of a piece
-    const int64_t t = (int64_t)blockIdx.x * SHEET_THREADS + threadIdx.x;
-    int64_t px = -1, at = -1;
-    if (t < pieces) {
-        const int64_t e0 = lead + t * V;
-        uint8_t b[V];
-#pragma unroll
-        for (int i = 0; i < V; ++i) b[i] = sheet_element(panels, tables, spans, tmp, g, e0 + i, px, at);
-        if constexpr (sizeof(O) == 4) {
-            sheet_f4 v;
-            v.x = sheet_unit(b[0]); v.y = sheet_unit(b[1]); v.z = sheet_unit(b[2]); v.w = sheet_unit(b[3]);
-            __builtin_nontemporal_store(v, reinterpret_cast<sheet_f4*>(out + e0));
-        } else {
-            sheet_u4 v;
-            v.x = (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24);
-            v.y = (uint32_t)b[4] | ((uint32_t)b[5] << 8) | ((uint32_t)b[6] << 16) | ((uint32_t)b[7] << 24);
-            v.z = (uint32_t)b[8] | ((uint32_t)b[9] << 8) | ((uint32_t)b[10] << 16) | ((uint32_t)b[11] << 24);
-            v.w = (uint32_t)b[12] | ((uint32_t)b[13] << 8) | ((uint32_t)b[14] << 16) | ((uint32_t)b[15] << 24);
-            __builtin_nontemporal_store(v, reinterpret_cast<sheet_u4*>(out + e0));
-        }
-    } else if (t == pieces) {                                                  // the elements off the 16-byte grid: fewer than 2 V
-        const int64_t behind = lead + pieces * V;
-        for (int64_t e = 0; e < lead + g.total - behind; ++e) {
-            const int64_t at_e = e < lead ? e : behind + (e - lead);
-            const uint8_t b = sheet_element(panels, tables, spans, tmp, g, at_e, px, at);
-            if constexpr (sizeof(O) == 4) out[at_e] = sheet_unit(b);
-            else out[at_e] = b;
-        }
-    }
+    pil_flat_write(out, g.total, lead, pieces, (int64_t)blockIdx.x * SHEET_THREADS + threadIdx.x,
+                   SheetCursor{panels, tables, spans, tmp, g, 0, -1, -1});
 }
 
 template <typename T>
@@ -188,14 +155,11 @@ static int sheet_compose_launch(const vrg_sheet_panel* panels, int64_t n, int32_
     const void* o = out;
     if (o == (const void*)tmp || o == (const void*)tables || o == (const void*)spans || o == (const void*)panels) return VRG_ERR_BAD_ARG;
     if (width > SHEET_MAX_SIDE || height > SHEET_MAX_SIDE) return VRG_ERR_UNSUPPORTED;
-    constexpr int V = 16 / (int)sizeof(O);
     SheetCanvas g{n, table_ints, n_spans, tmp_bytes, (int64_t)width * height * 3, width, bytes, background & 0xffffffu};
-    int64_t lead = (int64_t)(((16 - (reinterpret_cast<uintptr_t>(out) & 15u)) & 15u) / sizeof(O));
-    lead = lead < g.total ? lead : g.total;
-    const int64_t pieces = (g.total - lead) / V;
-    const int64_t blocks = (pieces + 1 + SHEET_THREADS - 1) / SHEET_THREADS;   // one thread more: the elements off the grid
-    hipLaunchKernelGGL((k_sheet_compose<O>), dim3((uint32_t)blocks), dim3(SHEET_THREADS), 0, (hipStream_t)stream, panels, tables, spans, tmp, out, g,
-                       lead, pieces);
+    PilFlat f;
+    if (!pil_flat_plan(out, sizeof(O), g.total, SHEET_THREADS, f)) return VRG_ERR_UNSUPPORTED;       // (never with SHEET_MAX_SIDE)
+    hipLaunchKernelGGL((k_sheet_compose<O>), dim3((uint32_t)f.blocks), dim3(SHEET_THREADS), 0, (hipStream_t)stream, panels, tables, spans, tmp, out, g,
+                       f.lead, f.pieces);
     VRG_CHECK_LAUNCH();
     return VRG_OK;
 }

@@ -2,8 +2,8 @@
 //
 // What is restated: VRGDG_LTXICIngredientsGrid.build of the reference (VRGDG_LTXICIngredientsGrid.py:37-95, :337-400) and the three sheet
 // builders of the AI Video Builder (VRGDG_MusicVideoBuilderNodes.py:7169-7238) -- numpy and Pillow, no cv2.  Nothing of
-// vrg_pil_math.hpp (Pillow's 22-bit LANCZOS tables and its two byte passes) or vrg_grid_math.hpp (the truncating quantiser, byte / 255)
-// is stated again; this header holds the glue between them.
+// vrg_pil_resample.hpp (Pillow's 22-bit LANCZOS tables, its tap records and its two byte passes) or vrg_grid_math.hpp (the truncating
+// quantiser, byte / 255) is stated again; this header holds the glue between them.
 //   source -> bytes   C == 1 is repeated to three channels, C == 3 is taken as is, C > 3 gives its first three; C == 2 is refused (so does
 //                     Image.fromarray).  byte = grid_quant(x) = trunc(clip(fl(x * 255.0f), 0, 255)).  NaN has no defined result in numpy;
 //                     here it gives 0, as in the grid plot.  A byte source is its own quantisation.
@@ -23,7 +23,7 @@
 #pragma once
 #include "vrg_common.hpp"
 #include "vrg_grid_math.hpp"
-#include "vrg_pil_math.hpp"
+#include "vrg_pil_resample.hpp"
 
 namespace vrg {
 
@@ -109,14 +109,12 @@ VRG_HD void sheet_row_pixel(const vrg_sheet_panel& p, const int32_t* tables, int
         out[2] = in ? load(xx, c2) : 0;
         return;
     }
-    const int32_t* hb = tables + p.h_table;
-    const int32_t first = hb[2 * xx], n = hb[2 * xx + 1];
-    if (first < lo || n < 0 || n > p.h_ksize || first > hi - n) {
+    const PilRecord t = pil_record(tables + p.h_table, p.new_w, xx, p.h_ksize, lo, hi);
+    if (!t.ok) {
         out[0] = out[1] = out[2] = 0;
         return;
     }
-    const int32_t* w = hb + 2 * (int64_t)p.new_w + (int64_t)xx * p.h_ksize;
-    pil_taps<3>(w, n, [&](int32_t i, int c) { return load(first + i, c == 0 ? 0 : (c == 1 ? c1 : c2)); }, out);
+    pil_taps<3>(t.w, t.n, [&](int32_t i, int c) { return load(t.first + i, c == 0 ? 0 : (c == 1 ? c1 : c2)); }, out);
 }
 
 // channel c of window pixel (cx, cy): the vertical pass over `tmp`
@@ -124,14 +122,9 @@ VRG_HD uint8_t sheet_picture_byte(const vrg_sheet_panel& p, const int32_t* table
     const uint8_t* t = tmp + p.tmp_offset;
     const int64_t pitch = (int64_t)p.pic_w * 3;
     if (p.src_h == p.new_h) return t[(int64_t)cy * pitch + cx * 3 + c];
-    const int32_t yy = p.win_y + cy;
-    const int32_t* vb = tables + p.v_table;
-    const int32_t first = vb[2 * yy], n = vb[2 * yy + 1];
-    if (first < p.row0 || n < 0 || n > p.v_ksize || first > p.row0 + p.rows - n) return 0;    // (never taken with sheet_plan's rows)
-    const uint8_t* col = t + (int64_t)(first - p.row0) * pitch + cx * 3 + c;
-    uint8_t o;
-    pil_taps<1>(vb + 2 * (int64_t)p.new_h + (int64_t)yy * p.v_ksize, n, [&](int32_t i, int) { return col[(int64_t)i * pitch]; }, &o);
-    return o;
+    const PilRecord v = pil_record(tables + p.v_table, p.new_h, p.win_y + cy, p.v_ksize, p.row0, p.row0 + p.rows);
+    if (!v.ok) return 0;                                                      // (never taken with sheet_plan's rows)
+    return pil_walk_byte(v.w, v.n, t + (int64_t)(v.first - p.row0) * pitch + cx * 3 + c, pitch);
 }
 
 // which panel decides canvas pixel (x, y): its index, or -1 for the background
@@ -192,7 +185,7 @@ inline bool sheet_plan(vrg_sheet_panel& p, const int32_t* tables) {
     }
 }
 
-// are the tables of the record vrg_pil_lanczos_table's for its sizes, and row0 / rows / cps sheet_plan's
+// are the tables of the record the whole-axis LANCZOS tables for its sizes (vrg_pil_lanczos_table), and row0 / rows / cps sheet_plan's
 inline bool sheet_tables_ok(const vrg_sheet_panel& p, const int32_t* tables) {
     for (int axis = 0; axis < 2; ++axis) {
         const int32_t n_in = axis ? p.src_h : p.src_w, n_out = axis ? p.new_h : p.new_w, ksize = axis ? p.v_ksize : p.h_ksize;

@@ -1,6 +1,9 @@
 // vrg_thumb.hip -- the contact sheet of the far-face repair backend (reference scripts/far_face_repair_backend.py: contact_sheet :374-408)
 // on decoded bytes: original and fixed frame side by side, Image.thumbnail (Image.reduce, then a BICUBIC resize over the fractional source
-// box) and the paste into the cells of the sheet, byte for byte.  gfx950 only.  Arithmetic: csrc/vrg_pil_math.hpp.
+// box) and the paste into the cells of the sheet, byte for byte.  gfx950 only.  Arithmetic, byte staging and the flat piece writer:
+// csrc/vrg_pil_resample.hpp.  The resize is over the box (0, 0, w / fx, h / fy) of the reduced picture; one more than PIL_TALL_RATIO times
+// as tall as wide resizes vertically first in Pillow: not restated, refused.  The sheet (:398-406): cols = max(1, columns),
+// rows = ceil(n / cols), the cell is the largest thumbnail, thumbnail i is pasted at ((i % cols) cell_w, (i / cols) cell_h) on (24, 24, 24).
 //
 // k_thumb_rows     the pair, the reduce and the horizontal pass.  One workgroup = ONE reduced row (fy source rows) of a segment of `cps`
 //                  output columns of one entry.  Per source row the 256 threads read the bytes the segment's taps touch ONCE with 16-byte
@@ -12,11 +15,9 @@
 //                  picture reaches memory.  Factors (1, 1): the staged bytes are the reduced row; no table: they are the output row.
 //                  LDS: 8.1 KB of source bytes, 16 KB of sums, 8 KB of reduced bytes -- 32 KB, four workgroups (16 waves) on a CU.
 // k_thumb_compose  one pass over the sheet as a flat run of bytes, one 16-byte piece per thread: a byte inside a thumbnail is the vertical
-//                  pass over tmp (one channel's taps), every other byte the canvas colour; the piece goes out in one non-temporal store.
-//                  The bytes in front of the first 16-byte boundary of `out` and behind the last whole piece are stored one by one by one
-//                  extra thread.  Nothing of `out` is read.
+//                  pass over tmp (one channel's taps), every other byte the canvas colour; ThumbCursor gives pil_flat_write the bytes.
 #include "vrg_common.hpp"
-#include "vrg_pil_math.hpp"
+#include "vrg_pil_resample.hpp"
 
 namespace vrg {
 
@@ -24,8 +25,6 @@ constexpr int PT_THREADS = 256;
 constexpr int PT_STAGE = VRG_THUMB_STAGE_BYTES;
 constexpr int PT_VALUES = VRG_THUMB_STAGE_VALUES;
 constexpr int PT_STAGE_LDS = PT_STAGE + 64;                                    // two runs, each at its phase behind a 16-byte boundary
-
-typedef uint32_t thumb_u4 __attribute__((ext_vector_type(4)));
 
 struct ThumbGeom {
     int64_t src_bytes, table_ints, tmp_bytes;
@@ -63,9 +62,10 @@ VRG_HD bool thumb_source_range(const vrg_thumb_entry& e, const int32_t* tables, 
     }
     const int32_t* table = tables + e.h_table;
     lo = table[2 * c0];
-    const int32_t n_lo = table[2 * c0 + 1], first = table[2 * (c1 - 1)], n = table[2 * (c1 - 1) + 1];
-    if (lo < 0 || n_lo < 0 || n < 0 || n > e.h_ksize || first < lo || first > e.red_w - n) return false;
-    hi = first + n;
+    if (lo < 0 || table[2 * c0 + 1] < 0) return false;
+    const PilRecord last = pil_record(table, e.out_w, c1 - 1, e.h_ksize, lo, e.red_w);
+    if (!last.ok) return false;
+    hi = last.first + last.n;
     return hi > lo;
 }
 
@@ -73,22 +73,6 @@ VRG_HD bool thumb_source_range(const vrg_thumb_entry& e, const int32_t* tables, 
 VRG_HD bool thumb_segment_fits(const vrg_thumb_entry& e, int32_t lo, int32_t hi) {
     const int64_t p1 = (int64_t)hi * e.fx < thumb_pair_w(e) ? (int64_t)hi * e.fx : thumb_pair_w(e);
     return (p1 - (int64_t)lo * e.fx) * 3 <= PT_STAGE && (int64_t)(hi - lo) * 3 <= thumb_value_cap(e);
-}
-
-// n bytes from src into rb by the whole workgroup: byte i lands at rb[ph + i], ph the returned phase (the address mod 16), so that the
-// 16-byte loads and the LDS words they fill are both aligned (as sheet_stage of csrc/vrg_sheet.hip).  rb is 16-byte aligned.
-__device__ __forceinline__ int thumb_stage(const uint8_t* src, int n, uint8_t* rb, int tid) {
-    const int ph = (int)(reinterpret_cast<uintptr_t>(src) & 15u);
-    int head = (16 - ph) & 15;
-    head = head < n ? head : n;
-    const int nq = (n - head) >> 4;
-    if (tid < head) rb[ph + tid] = src[tid];
-    const thumb_u4* body = reinterpret_cast<const thumb_u4*>(src + head);
-    thumb_u4* dst = reinterpret_cast<thumb_u4*>(rb + ph + head);
-    for (int q = tid; q < nq; q += PT_THREADS) dst[q] = __builtin_nontemporal_load(body + q);
-    const int t = head + 16 * nq + tid;                                        // at most 15 bytes behind the last 16-byte piece
-    if (t < n) rb[ph + t] = src[t];
-    return ph;
 }
 
 __global__ __launch_bounds__(PT_THREADS) void k_thumb_rows(const uint8_t* __restrict__ src, const vrg_thumb_entry* __restrict__ entries,
@@ -117,12 +101,12 @@ __global__ __launch_bounds__(PT_THREADS) void k_thumb_rows(const uint8_t* __rest
         for (int j = tid; j < nvals; j += PT_THREADS) acc[j] = 0u;
     for (int32_t y = y0; y < y1; ++y) {
         int phl = 0, offr = 0;
-        if (nl > 0) phl = thumb_stage(src + e.left_offset + ((int64_t)y * Wl + l0) * 3, nl, stage, tid);
+        if (nl > 0) phl = pil_stage_bytes(src + e.left_offset + ((int64_t)y * Wl + l0) * 3, nl, stage, tid, PT_THREADS);
         if (nr > 0) {
             int32_t have = (y < e.right_h ? (q1 < e.right_w ? q1 : e.right_w) : 0) - q0;   // columns the fixed frame has in this row
             have = have > 0 ? have : 0;
             int phr = 0;
-            if (have > 0) phr = thumb_stage(src + e.right_offset + ((int64_t)y * e.right_w + q0) * 3, have * 3, rb, tid);
+            if (have > 0) phr = pil_stage_bytes(src + e.right_offset + ((int64_t)y * e.right_w + q0) * 3, have * 3, rb, tid, PT_THREADS);
             for (int j = have * 3 + tid; j < nr; j += PT_THREADS) rb[phr + j] = 0;                 // Image.new(.., (0, 0, 0)) shows
             offr = (int)(rb - stage) + phr;
         }
@@ -153,16 +137,15 @@ __global__ __launch_bounds__(PT_THREADS) void k_thumb_rows(const uint8_t* __rest
         __syncthreads();
     }
     uint8_t* row = tmp + e.tmp_offset + (int64_t)r * e.out_w * 3;
-    const int32_t* table = tables + e.h_table;
     for (int32_t col = c0 + tid; col < c1; col += PT_THREADS) {
         uint8_t o[3] = {0, 0, 0};
         if (!e.h_ksize) {
             for (int c = 0; c < 3; ++c) o[c] = red[(col - lo) * 3 + c];
         } else {
-            const int32_t first = table[2 * col], n = table[2 * col + 1];
-            if (n >= 0 && n <= e.h_ksize && first >= lo && first <= hi - n) {
-                const uint8_t* at = red + (first - lo) * 3;
-                pil_taps<3>(table + 2 * (int64_t)e.out_w + (int64_t)col * e.h_ksize, n, [&](int32_t i, int c) { return at[i * 3 + c]; }, o);
+            const PilRecord t = pil_record(tables + e.h_table, e.out_w, col, e.h_ksize, lo, hi);
+            if (t.ok) {
+                const uint8_t* at = red + (t.first - lo) * 3;
+                pil_taps<3>(t.w, t.n, [&](int32_t i, int c) { return at[i * 3 + c]; }, o);
             }
         }
         row[col * 3 + 0] = o[0];
@@ -185,85 +168,63 @@ struct ThumbAt {
     vrg_thumb_entry e;
 };
 
-// where a byte of the sheet lies; the 64-bit divisions are made once per thread, the bytes that follow are stepped to
-struct ThumbPos {
+// the bytes of the sheet for pil_flat_write: channel c of pixel (x, y); the 64-bit divisions are made once per seek, the bytes that follow
+// are stepped to
+struct ThumbCursor {
+    const vrg_thumb_entry* __restrict__ entries;
+    const int32_t* __restrict__ tables;
+    const uint8_t* __restrict__ tmp;
+    const ThumbSheet& s;
+    ThumbAt at;
     int32_t x, y, c;
-};
 
-__device__ __forceinline__ ThumbPos thumb_pos(const ThumbSheet& s, int64_t b) {
-    const int64_t pixel = b / 3;
-    ThumbPos p;
-    p.c = (int32_t)(b - pixel * 3);
-    p.y = (int32_t)(pixel / s.width);
-    p.x = (int32_t)(pixel - (int64_t)p.y * s.width);
-    return p;
-}
-
-__device__ __forceinline__ void thumb_step(const ThumbSheet& s, ThumbPos& p) {
-    if (++p.c == 3) {
-        p.c = 0;
-        if (++p.x == s.width) {
-            p.x = 0;
-            ++p.y;
+    __device__ __forceinline__ void seek(int64_t b) {
+        const int64_t pixel = b / 3;
+        c = (int32_t)(b - pixel * 3);
+        y = (int32_t)(pixel / s.width);
+        x = (int32_t)(pixel - (int64_t)y * s.width);
+    }
+    __device__ __forceinline__ uint8_t next() {
+        const uint8_t v = element();
+        if (++c == 3) {
+            c = 0;
+            if (++x == s.width) {
+                x = 0;
+                ++y;
+            }
         }
+        return v;
     }
-}
-
-// the byte of the sheet at channel c of pixel (x, y)
-__device__ __forceinline__ uint8_t thumb_element(const vrg_thumb_entry* __restrict__ entries, const int32_t* __restrict__ tables,
-                                                 const uint8_t* __restrict__ tmp, const ThumbSheet& s, const ThumbPos& p, ThumbAt& at) {
-    const int32_t x = p.x, y = p.y, c = p.c;
-    const uint8_t ground = (uint8_t)(s.background >> (8 * c));
-    const int32_t cx = x / s.cell_w, cy = y / s.cell_h;
-    const int64_t i = (int64_t)cy * s.columns + cx;
-    if (cx >= s.columns || i >= s.n) return ground;
-    if (i != at.i) {
-        at.i = i;
-        at.e = entries[i];
-        at.ok = thumb_entry_ok(at.e, s.g);
+    __device__ __forceinline__ uint8_t element() {
+        const uint8_t ground = (uint8_t)(s.background >> (8 * c));
+        const int32_t cx = x / s.cell_w, cy = y / s.cell_h;
+        const int64_t i = (int64_t)cy * s.columns + cx;
+        if (cx >= s.columns || i >= s.n) return ground;
+        if (i != at.i) {
+            at.i = i;
+            at.e = entries[i];
+            at.ok = thumb_entry_ok(at.e, s.g);
+        }
+        if (!at.ok) return ground;
+        const vrg_thumb_entry& e = at.e;
+        const int64_t lx = (int64_t)x - e.dst_x, ly = (int64_t)y - e.dst_y;
+        if (lx < 0 || ly < 0 || lx >= e.out_w || ly >= e.out_h) return ground;
+        const int64_t pitch = (int64_t)e.out_w * 3;
+        const uint8_t* col = tmp + e.tmp_offset + lx * 3 + c;                  // [red_h][out_w][3]
+        if (!e.v_ksize) return col[ly * pitch];
+        const PilRecord v = pil_record(tables + e.v_table, e.out_h, (int32_t)ly, e.v_ksize, 0, e.red_h);
+        if (!v.ok) return ground;                                             // (never with vrg_thumb_check) pastes nothing
+        return pil_walk_byte(v.w, v.n, col + v.first * pitch, pitch);
     }
-    if (!at.ok) return ground;
-    const vrg_thumb_entry& e = at.e;
-    const int64_t lx = (int64_t)x - e.dst_x, ly = (int64_t)y - e.dst_y;
-    if (lx < 0 || ly < 0 || lx >= e.out_w || ly >= e.out_h) return ground;
-    const int64_t pitch = (int64_t)e.out_w * 3;
-    const uint8_t* col = tmp + e.tmp_offset + lx * 3 + c;                      // [red_h][out_w][3]
-    if (!e.v_ksize) return col[ly * pitch];
-    const int32_t* table = tables + e.v_table;
-    const int32_t first = table[2 * ly], n = table[2 * ly + 1];
-    if (first < 0 || n < 0 || n > e.v_ksize || first > e.red_h - n) return ground;  // (never with vrg_thumb_check) pastes nothing
-    const int32_t* w = table + 2 * (int64_t)e.out_h + ly * e.v_ksize;
-    int32_t ss = 1 << (PIL_PRECISION_BITS - 1);
-    for (int32_t k = 0; k < n; ++k) ss += (int32_t)col[(first + k) * pitch] * w[k];
-    return pil_clip8(ss);
-}
+};
 
 __global__ __launch_bounds__(PT_THREADS) void k_thumb_compose(const vrg_thumb_entry* __restrict__ entries, const int32_t* __restrict__ tables,
                                                                const uint8_t* __restrict__ tmp, uint8_t* __restrict__ out, ThumbSheet s,
                                                                int64_t lead, int64_t pieces) {
-    const int64_t t = (int64_t)blockIdx.x * PT_THREADS + threadIdx.x;
-    ThumbAt at;
-    at.i = -1;
-    at.ok = false;
-    if (t < pieces) {
-        const int64_t b0 = lead + t * 16;
-        uint32_t w[4] = {0u, 0u, 0u, 0u};
-        ThumbPos p = thumb_pos(s, b0);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            w[i >> 2] |= (uint32_t)thumb_element(entries, tables, tmp, s, p, at) << (8 * (i & 3));
-            thumb_step(s, p);
-        }
-        thumb_u4 v;
-        v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
-        __builtin_nontemporal_store(v, reinterpret_cast<thumb_u4*>(out + b0));
-    } else if (t == pieces) {                                                  // the bytes off the 16-byte grid: fewer than 32
-        const int64_t behind = lead + pieces * 16;
-        for (int64_t k = 0; k < lead + s.total - behind; ++k) {
-            const int64_t b = k < lead ? k : behind + (k - lead);
-            out[b] = thumb_element(entries, tables, tmp, s, thumb_pos(s, b), at);
-        }
-    }
+    ThumbCursor cur{entries, tables, tmp, s};
+    cur.at.i = -1;
+    cur.at.ok = false;
+    pil_flat_write(out, s.total, lead, pieces, (int64_t)blockIdx.x * PT_THREADS + threadIdx.x, cur);
 }
 
 // HOST.  cps of an entry whose sizes, factors and h_ksize are set: `k` output columns read at most (k - 1) scale + 2 support + 3 reduced
@@ -306,8 +267,8 @@ inline int thumb_plan_entry(vrg_thumb_entry& e, double req_w, double req_h, int3
     }
     e.red_w = pil_reduced_size(pw, e.fx);
     e.red_h = pil_reduced_size(ph, e.fy);
-    if (e.out_w != e.red_w || in1[0] != (float)e.red_w) e.h_ksize = pil_filter_ksize(filter, 0.0f, in1[0], e.out_w);
-    if (e.out_h != e.red_h || in1[1] != (float)e.red_h) e.v_ksize = pil_filter_ksize(filter, 0.0f, in1[1], e.out_h);
+    if (e.out_w != e.red_w || in1[0] != (float)e.red_w) e.h_ksize = pil_filter_ksize(filter, pil_box_span(0.0f, in1[0]), e.out_w);
+    if (e.out_h != e.red_h || in1[1] != (float)e.red_h) e.v_ksize = pil_filter_ksize(filter, pil_box_span(0.0f, in1[1]), e.out_h);
     if ((e.h_ksize || e.v_ksize) && e.red_h > (int64_t)e.red_w * PIL_TALL_RATIO && e.out_h < e.red_h) return VRG_ERR_UNSUPPORTED;
     return thumb_plan_cps(e, filter, in1[0]) ? VRG_OK : VRG_ERR_UNSUPPORTED;
 }
@@ -346,20 +307,6 @@ inline int thumb_plan_sheet(vrg_thumb_entry* entries_host, int64_t n, int32_t co
 using namespace vrg;
 
 extern "C" {
-
-int32_t vrg_pil_filter_ksize(int32_t filter, float in0, float in1, int32_t n_out) {
-    if (!pil_filter_known(filter) || n_out < 1 || !(in0 >= 0.0f) || !(in1 >= in0) || !(in1 <= 2147483520.0f)) return 0;
-    const double k = ceil(pil_filter_support(filter) * fmax((double)(in1 - in0) / n_out, 1.0)) * 2 + 1;
-    return k > 2147483647.0 ? 0 : (int32_t)k;
-}
-
-int vrg_pil_filter_table(int32_t filter, int32_t n_in, float in0, float in1, int32_t n_out, int32_t* bounds_host, int32_t* weights_host) {
-    if (!bounds_host || !weights_host || !pil_filter_known(filter) || n_in < 1 || n_out < 1 || !(in0 >= 0.0f) || !(in1 >= in0) ||
-        !(in1 <= (float)n_in) || vrg_pil_filter_ksize(filter, in0, in1, n_out) < 1)
-        return VRG_ERR_BAD_ARG;
-    pil_filter_table(filter, n_in, in0, in1, n_out, bounds_host, weights_host);
-    return VRG_OK;
-}
 
 int vrg_pil_reduce_host(const uint8_t* src_host, int32_t height, int32_t width, int32_t channels, int32_t fx, int32_t fy, uint8_t* dst_host) {
     if (!src_host || !dst_host || src_host == dst_host || height < 1 || width < 1 || channels < 1 || channels > 4 || fx < 1 || fy < 1)
@@ -407,23 +354,15 @@ int vrg_thumb_check(const vrg_thumb_entry* entries_host, int64_t n, const int32_
         if (e.fx > VRG_THUMB_MAX_FACTOR || e.fy > VRG_THUMB_MAX_FACTOR) return VRG_ERR_UNSUPPORTED;
         if (!thumb_entry_ok(e, g) || e.cps > e.out_w) return VRG_ERR_BAD_ARG;
         if (e.out_w > cell_w || e.out_h > cell_h || e.dst_x != (i % columns) * cell_w || e.dst_y != (i / columns) * cell_h) return VRG_ERR_BAD_ARG;
-        if (e.v_ksize) {
-            const int32_t* table = tables_host + e.v_table;
-            for (int32_t y = 0; y < e.out_h; ++y)
-                if (table[2 * y] < 0 || table[2 * y + 1] < 0 || table[2 * y + 1] > e.v_ksize || table[2 * y] > e.red_h - table[2 * y + 1])
-                    return VRG_ERR_BAD_ARG;
-        }
+        for (int32_t y = 0; e.v_ksize && y < e.out_h; ++y)
+            if (!pil_record(tables_host + e.v_table, e.out_h, y, e.v_ksize, 0, e.red_h).ok) return VRG_ERR_BAD_ARG;
         for (int64_t c0 = 0; c0 < e.out_w; c0 += e.cps) {
             const int32_t c1 = (int32_t)(c0 + e.cps < e.out_w ? c0 + e.cps : e.out_w);
             int32_t lo, hi;
             if (!thumb_source_range(e, tables_host, (int32_t)c0, c1, lo, hi)) return VRG_ERR_BAD_ARG;
             if (!thumb_segment_fits(e, lo, hi)) return VRG_ERR_UNSUPPORTED;
-            if (e.h_ksize) {
-                const int32_t* table = tables_host + e.h_table;
-                for (int32_t c = (int32_t)c0; c < c1; ++c)
-                    if (table[2 * c + 1] < 0 || table[2 * c + 1] > e.h_ksize || table[2 * c] < lo || table[2 * c] > hi - table[2 * c + 1])
-                        return VRG_ERR_BAD_ARG;
-            }
+            for (int32_t c = (int32_t)c0; e.h_ksize && c < c1; ++c)
+                if (!pil_record(tables_host + e.h_table, e.out_w, c, e.h_ksize, lo, hi).ok) return VRG_ERR_BAD_ARG;
         }
     }
     return VRG_OK;
@@ -459,12 +398,10 @@ int vrg_thumb_compose_u8(const vrg_thumb_entry* entries, int64_t n, const int32_
     if (o == (const void*)tmp || o == (const void*)tables || o == (const void*)entries) return VRG_ERR_BAD_ARG;
     const ThumbSheet s{n, (int64_t)width * height * 3, ThumbGeom{0x7fffffffffffffffll, table_ints, tmp_bytes}, width, columns, cell_w, cell_h,
                        background & 0xffffffu};
-    int64_t lead = (int64_t)((16 - (reinterpret_cast<uintptr_t>(out) & 15u)) & 15u);
-    lead = lead < s.total ? lead : s.total;
-    const int64_t pieces = (s.total - lead) / 16;
-    const int64_t blocks = (pieces + 1 + PT_THREADS - 1) / PT_THREADS;         // one thread more: the bytes off the grid
-    if (blocks > 0x7fffffffll) return VRG_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(k_thumb_compose, dim3((uint32_t)blocks), dim3(PT_THREADS), 0, (hipStream_t)stream, entries, tables, tmp, out, s, lead, pieces);
+    PilFlat f;
+    if (!pil_flat_plan(out, 1, s.total, PT_THREADS, f)) return VRG_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(k_thumb_compose, dim3((uint32_t)f.blocks), dim3(PT_THREADS), 0, (hipStream_t)stream, entries, tables, tmp, out, s, f.lead,
+                       f.pieces);
     VRG_CHECK_LAUNCH();
     return VRG_OK;
 }

@@ -29,7 +29,7 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from . import _hip
+from . import _hip, ops
 from ._devices import compute_device
 from .VRGDG_FaceFix import _boxes, _frames_in, _host, _peek, _upload
 
@@ -96,17 +96,9 @@ def expanded_square_crop(face, image_width, image_height, padding):
 # ------------------------------------------------------------------------------------------------
 # host tables
 # ------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=512)
 def lanczos_table(n_in: int, n_out: int):
     """(ksize, one axis table as the kernels read it: bounds [n_out, 2] then weights [n_out, ksize], int32); host only"""
-    if n_in < 1 or n_out < 1:
-        raise ValueError("lanczos_table: sizes must be at least 1")
-    ksize = int(_host().vrg_pil_lanczos_ksize(n_in, n_out))
-    table = np.zeros(n_out * (2 + ksize), dtype=np.int32)
-    bounds, weights = table[:2 * n_out], table[2 * n_out:]
-    _hip.check(_host().vrg_pil_lanczos_table(n_in, n_out, C.c_void_p(bounds.ctypes.data), C.c_void_p(weights.ctypes.data)), "vrg_pil_lanczos_table")
-    table.setflags(write=False)
-    return ksize, table
+    return ops.pil_axis_table(_hip.PIL_FILTER_LANCZOS, n_in, n_out)
 
 
 def _filter_number(resample):
@@ -123,24 +115,11 @@ def _host_check(status, what):
     raise (ValueError if status == 1 else RuntimeError)(f"{what}: {msg}")
 
 
-@functools.lru_cache(maxsize=512)
-def _filter_table(number, n_in, in0, in1, n_out):
-    ksize = int(_host().vrg_pil_filter_ksize(number, in0, in1, n_out))
-    if n_in < 1 or n_out < 1 or ksize < 1:
-        raise ValueError("filter_table: sizes must be at least 1 and 0 <= in0 <= in1 <= n_in")
-    table = np.zeros(n_out * (2 + ksize), dtype=np.int32)
-    bounds, weights = table[:2 * n_out], table[2 * n_out:]
-    _host_check(_host().vrg_pil_filter_table(number, n_in, in0, in1, n_out, C.c_void_p(bounds.ctypes.data), C.c_void_p(weights.ctypes.data)),
-                "vrg_pil_filter_table")
-    table.setflags(write=False)
-    return ksize, table
-
-
 def filter_table(resample, n_in: int, in0: float, in1: float, n_out: int):
     """(ksize, one axis table as the kernels read it) of ``Image.resize(.., resample, box)``: ``n_out`` outputs from the source interval
     [in0, in1) of an axis of ``n_in`` pixels; ``resample`` "bicubic" or "lanczos".  The interval is rounded to C float, as Pillow takes it.
     Host only."""
-    return _filter_table(_filter_number(resample), int(n_in), float(np.float32(in0)), float(np.float32(in1)), int(n_out))
+    return ops.pil_axis_table(_filter_number(resample), int(n_in), int(n_out), (float(np.float32(in0)), float(np.float32(in1))))
 
 
 @functools.lru_cache(maxsize=64)
@@ -536,7 +515,7 @@ class ThumbPlan:
                     continue
                 key = (int(e[red]), float(np.float32(pair[axis] / int(e[f]))), int(e[out]))
                 if key not in table_at:
-                    ksize, table = _filter_table(number, key[0], 0.0, key[1], key[2])
+                    ksize, table = ops.pil_axis_table(number, key[0], key[2], (0.0, key[1]))
                     assert ksize == e[ks]
                     table_at[key] = n_ints
                     tables.append(table)

@@ -390,6 +390,30 @@ def _sharpen_then_seeded_grain_u8(frames_bgr, sharpen_strength, zero_border, gra
 # ---------------------------------------------------------------------------------------------
 LANCZOS_TAP_BYTES = 20          # one record of the table: int32 s, eight int16 weights (csrc/vrg_lanczos_math.hpp: LzTap)
 _host_lib = _hip.host_library   # the library for its HOST table functions (no GPU needed)
+
+
+@functools.lru_cache(maxsize=512)
+def pil_axis_table(number: int, n_in: int, n_out: int, box=None):
+    """(ksize, one axis table as the kernels read it: bounds [n_out, 2] then weights [n_out, ksize], int32, read-only) of
+    ``Image.resize(.., filter, box)``: ``n_out`` outputs from the source interval ``box`` = (in0, in1), as C floats, of an axis of ``n_in``
+    pixels; ``number`` is Pillow's (1 LANCZOS, 3 BICUBIC).  Without a box: the whole axis under LANCZOS.  Host only, cached."""
+    lib = _host_lib()
+    if box is None:
+        ksize = int(lib.vrg_pil_lanczos_ksize(n_in, n_out))
+    else:
+        ksize = int(lib.vrg_pil_filter_ksize(number, box[0], box[1], n_out))
+    if n_in < 1 or n_out < 1 or ksize < 1:
+        raise ValueError("pil_axis_table: sizes must be at least 1 and 0 <= in0 <= in1 <= n_in")
+    table = np.zeros(n_out * (2 + ksize), dtype=np.int32)
+    bounds, weights = C.c_void_p(table.ctypes.data), C.c_void_p(table[2 * n_out:].ctypes.data)
+    if box is None:
+        status = lib.vrg_pil_lanczos_table(n_in, n_out, bounds, weights)
+    else:
+        status = lib.vrg_pil_filter_table(number, n_in, box[0], box[1], n_out, bounds, weights)
+    if status != _hip.VRG_OK:
+        raise (ValueError if status == 1 else RuntimeError)(f"pil_axis_table: {lib.vrg_error_string(status).decode()}")
+    table.setflags(write=False)
+    return ksize, table
 _upload_lock = threading.Lock()
 _lanczos_tables: dict = {}      # (in_h, in_w, out_h, out_w, device) -> the uploaded table
 
@@ -2795,20 +2819,10 @@ class SheetPanel:
     radius: int = 0
 
 
-@functools.lru_cache(maxsize=512)
 def sheet_lanczos_table(n_in: int, n_out: int):
     """(ksize, the table of one axis as the kernels read it: bounds [n_out, 2] then weights [n_out, ksize], int32) of
     ``Image.resize(..., LANCZOS)``; host only, cached per (n_in, n_out)"""
-    lib = _host_lib()
-    ksize = int(lib.vrg_pil_lanczos_ksize(n_in, n_out))
-    if ksize < 1:
-        raise ValueError("sheet_lanczos_table: sizes must be at least 1")
-    table = np.zeros(n_out * (2 + ksize), dtype=np.int32)
-    rc = lib.vrg_pil_lanczos_table(n_in, n_out, C.c_void_p(table.ctypes.data), C.c_void_p(table[2 * n_out:].ctypes.data))
-    if rc != _hip.VRG_OK:
-        raise ValueError(f"vrg_pil_lanczos_table refused {n_in} -> {n_out}")
-    table.setflags(write=False)
-    return ksize, table
+    return pil_axis_table(_hip.PIL_FILTER_LANCZOS, n_in, n_out)
 
 
 @functools.lru_cache(maxsize=512)

@@ -676,7 +676,8 @@ int vrg_selfcheck_pow_f32(const float* in, float* out, int64_t n, int32_t site, 
  *
  * HOST tables.  vrg_pil_lanczos_ksize gives the taps per output index of one axis `n_in` -> `n_out` (0: a size below 1);
  * vrg_pil_lanczos_table fills bounds[n_out][2] (first source index, tap count) and weights[n_out][ksize] (22-bit fixed point, zero beyond
- * the count).  On the device one axis table is these two arrays back to back: n_out * (2 + ksize) int32.  vrg_pil_box_parameters fills
+ * the count); it is vrg_pil_filter_table with filter 1 over the whole axis, with no float in between: exact for every n_in.  On the
+ * device one axis table is these two arrays back to back: n_out * (2 + ksize) int32.  vrg_pil_box_parameters fills
  * out[3] = radius, ww, fw (the last two uint32) of one box pass of GaussianBlur(radius = sigma), 0 < sigma <= 4096.
  *
  * Every table and record below is device memory; a record that names anything outside the stated sizes, or a box that does not lie inside

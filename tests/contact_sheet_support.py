@@ -1,6 +1,6 @@
 """Test scaffolding for the far-face repair contact sheet (comfyui-vrgamedevgirl_amd/far_face_repair.py: contact_sheet, pil_thumbnail,
 pil_reduce; csrc/vrg_thumb.hip): the seeded inputs of tests/golden/contact_sheet.npz, the ctypes face of the library's HOST entry points
-(csrc/vrg_pil_math.hpp compiled for the host: no GPU needed) and a numpy walk that applies their tables, so that the arithmetic can be
+(csrc/vrg_pil_resample.hpp compiled for the host: no GPU needed) and a numpy walk that applies their tables, so that the arithmetic can be
 held against the installed Pillow without a device.  The cases are shared by the fixture tool, the CPU tests and the GPU tests."""
 import ctypes as C
 import os

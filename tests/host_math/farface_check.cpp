@@ -23,9 +23,9 @@ static void resize_c(const uint8_t* in, int32_t in_h, int32_t in_w, uint8_t* out
     std::vector<uint8_t> tmp;
     const uint8_t* src = in;
     if (in_w != out_w) {
-        const int32_t k = pil_lanczos_ksize(in_w, out_w);
+        const int32_t k = pil_filter_ksize(PIL_FILTER_LANCZOS, in_w, out_w);
         std::vector<int32_t> b((size_t)out_w * 2), w((size_t)out_w * k);
-        pil_lanczos_table(in_w, out_w, b.data(), w.data());
+        pil_filter_table(PIL_FILTER_LANCZOS, in_w, 0.0, in_w, out_w, b.data(), w.data());
         tmp.resize((size_t)in_h * out_w * C);
         for (int32_t y = 0; y < in_h; ++y)
             for (int32_t x = 0; x < out_w; ++x) {
@@ -39,9 +39,9 @@ static void resize_c(const uint8_t* in, int32_t in_h, int32_t in_w, uint8_t* out
         memcpy(out, src, (size_t)out_h * out_w * C);
         return;
     }
-    const int32_t k = pil_lanczos_ksize(in_h, out_h);
+    const int32_t k = pil_filter_ksize(PIL_FILTER_LANCZOS, in_h, out_h);
     std::vector<int32_t> b((size_t)out_h * 2), w((size_t)out_h * k);
-    pil_lanczos_table(in_h, out_h, b.data(), w.data());
+    pil_filter_table(PIL_FILTER_LANCZOS, in_h, 0.0, in_h, out_h, b.data(), w.data());
     for (int32_t y = 0; y < out_h; ++y)
         for (int32_t x = 0; x < out_w; ++x) {
             const uint8_t* col = src + ((size_t)b[2 * y] * out_w + x) * C;
@@ -84,9 +84,9 @@ static uint64_t sum_parallel(const std::vector<uint8_t>& v) {
 
 extern "C" {
 
-int32_t hm_pil_ksize(int32_t n_in, int32_t n_out) { return pil_lanczos_ksize(n_in, n_out); }
+int32_t hm_pil_ksize(int32_t n_in, int32_t n_out) { return pil_filter_ksize(PIL_FILTER_LANCZOS, n_in, n_out); }
 
-void hm_pil_table(int32_t n_in, int32_t n_out, int32_t* bounds, int32_t* weights) { pil_lanczos_table(n_in, n_out, bounds, weights); }
+void hm_pil_table(int32_t n_in, int32_t n_out, int32_t* bounds, int32_t* weights) { pil_filter_table(PIL_FILTER_LANCZOS, n_in, 0.0, n_in, n_out, bounds, weights); }
 
 void hm_pil_resize(const uint8_t* in, int32_t in_h, int32_t in_w, int32_t channels, uint8_t* out, int32_t out_h, int32_t out_w) {
     if (channels == 3) resize_c<3>(in, in_h, in_w, out, out_h, out_w);

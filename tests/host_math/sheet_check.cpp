@@ -1,5 +1,5 @@
 // Test scaffolding: the reference-sheet arithmetic of csrc/vrg_sheet_math.hpp on the host -- the header compiled with g++
-// (-ffp-contract=off): sheet_fit places the picture, pil_lanczos_table makes the tables, sheet_plan picks rows and segments, sheet_check
+// (-ffp-contract=off): sheet_fit places the picture, pil_filter_table makes the tables, sheet_plan picks rows and segments, sheet_check
 // judges the records, sheet_rows_host / sheet_compose_host evaluate a whole sheet straight from the definition.  Checked byte for byte
 // against installed Pillow and the reference's recorded canvases (tests/test_sheet_host.py).  Never loaded by the package.
 // With -DSHEET_CHECK_MAIN it is a stand-alone program (the sanitizer build): it reads a list of sheets from the file named on its command
@@ -55,10 +55,10 @@ static int sheet_run(const void* const* srcs, const int32_t* shapes, int32_t byt
         for (int axis = 0; axis < 2; ++axis) {
             const int32_t n_in = axis ? p.src_h : p.src_w, n_out = axis ? p.new_h : p.new_w;
             if (n_in == n_out) continue;
-            const int32_t k = pil_lanczos_ksize(n_in, n_out);
+            const int32_t k = pil_filter_ksize(PIL_FILTER_LANCZOS, n_in, n_out);
             const size_t at = tables.size();
             tables.resize(at + (size_t)n_out * (2 + (size_t)k));
-            pil_lanczos_table(n_in, n_out, tables.data() + at, tables.data() + at + 2 * (size_t)n_out);
+            pil_filter_table(PIL_FILTER_LANCZOS, n_in, 0.0, n_in, n_out, tables.data() + at, tables.data() + at + 2 * (size_t)n_out);
             (axis ? p.v_table : p.h_table) = (int64_t)at;
             (axis ? p.v_ksize : p.h_ksize) = k;
         }

@@ -1,4 +1,4 @@
-"""The far-face repair contact sheet without a GPU: csrc/vrg_pil_math.hpp compiled for the host (the library's host entry points) equals the
+"""The far-face repair contact sheet without a GPU: csrc/vrg_pil_resample.hpp compiled for the host (the library's host entry points) equals the
 INSTALLED PILLOW byte for byte -- Image.reduce on every route, Image.resize with a BICUBIC / LANCZOS filter over a source box,
 Image.thumbnail as plan + reduce + tables, and the whole sheet -- and what the reference's own contact_sheet recorded in
 tests/golden/contact_sheet.npz (and gives live, where the reference checkout is readable); the C ABI of the new entry points."""
@@ -121,6 +121,43 @@ def test_filter_table_with_the_whole_axis_is_the_lanczos_table(ffr):
         ffr.filter_table("nearest", 10, 0.0, 10.0, 5)
     with pytest.raises(ValueError):
         ffr.filter_table("bicubic", 10, 0.0, 10.5, 5)
+
+
+AXIS_SIZES = (1, 2, 3, 5, 7, 13, 16, 31, 64, 127, 256, 1009, 4096, 32767)        # 1, 2, 3, primes, powers of two, the largest side
+
+
+def test_the_lanczos_exports_are_the_filter_exports_over_the_whole_axis(lib):
+    """vrg_pil_lanczos_ksize / _table == vrg_pil_filter_ksize / _table with filter 1 and the box (0, n_in), up- and down-scaling, every
+    pair of AXIS_SIZES but 32767 -> 32767 (229 K rows of the same rule as 4096 -> 4096)"""
+    import ctypes as C
+    for n_in in AXIS_SIZES:
+        for n_out in AXIS_SIZES:
+            if n_in == n_out == 32767:
+                continue
+            ksize = lib.vrg_pil_lanczos_ksize(n_in, n_out)
+            assert ksize == lib.vrg_pil_filter_ksize(S.LANCZOS, 0.0, float(n_in), n_out) and ksize >= 7, (n_in, n_out)
+            bounds, weights = np.zeros((n_out, 2), np.int32), np.zeros((n_out, ksize), np.int32)
+            assert lib.vrg_pil_lanczos_table(n_in, n_out, C.c_void_p(bounds.ctypes.data), C.c_void_p(weights.ctypes.data)) == 0
+            b1, w1 = S.host_table(lib, S.LANCZOS, n_in, 0.0, float(n_in), n_out)
+            assert np.array_equal(bounds, b1) and np.array_equal(weights, w1), (n_in, n_out)
+
+
+def test_the_whole_axis_table_does_not_round_its_length_to_float(lib):
+    """n_in = 2^24 + 1 is no C float: rounded to one it gives ksize 98305, exact 98307.  The table (n_out (2 + ksize) int32, 403 MB -- six
+    ints per source pixel whatever n_out, so the fixture holds its SHA-256, its bounds and every 4099th weight, recorded from the library
+    before vrg_pil_lanczos_table became a call of the one builder: tools/make_golden_pil_axis.py)"""
+    import ctypes as C
+    import hashlib
+    rec = np.load(os.path.join(ROOT, "tests", "golden", "pil_lanczos_axis.npz"))
+    n_in, n_out, ksize = (int(v) for v in rec["sizes"])
+    assert n_in == (1 << 24) + 1 and float(np.float32(n_in)) != n_in
+    assert lib.vrg_pil_lanczos_ksize(n_in, n_out) == ksize == 98307
+    assert lib.vrg_pil_filter_ksize(S.LANCZOS, 0.0, float(np.float32(n_in)), n_out) == 98305          # what a float box gives
+    table = np.zeros(n_out * (2 + ksize), np.int32)
+    assert lib.vrg_pil_lanczos_table(n_in, n_out, C.c_void_p(table.ctypes.data), C.c_void_p(table[2 * n_out:].ctypes.data)) == 0
+    assert np.array_equal(table[:2 * n_out].reshape(-1, 2), rec["bounds"])
+    assert np.array_equal(table[2 * n_out::int(rec["stride"])], rec["weights"])
+    assert hashlib.sha256(table).hexdigest() == str(rec["sha256"])
 
 
 @pytest.mark.parametrize("index", range(len(S.THUMB_CASES)))

@@ -139,3 +139,85 @@ def test_a_refused_geometry_is_unsupported_without_a_launch(ffr):
                                            _hip.current_stream()) == 0
     torch.cuda.synchronize()
     assert bool((out == 24).all())
+
+
+# ------------------------------------------------------------------------------------------------
+# the flat piece writer and the byte staging at their edges.  Before these, every sheet was torch's own allocation (16-byte aligned: no
+# lead) and the smallest one 24 x 6; sources off the 16-byte grid (5, 16, 3 above) were 40 pixels wide or more: never n < head, and no
+# pair had a left run of one pixel.
+# ------------------------------------------------------------------------------------------------
+def at_phase(array, phase):
+    """a dense device copy of a uint8 array whose first byte lies at an address = phase (mod 16)"""
+    buf = torch.zeros(array.size + 32, dtype=torch.uint8, device="cuda")
+    view = buf[phase:phase + array.size].view(array.shape)
+    view.copy_(torch.from_numpy(array))
+    assert view.data_ptr() % 16 == phase and view.is_contiguous()
+    return view
+
+
+def sheet_at(ffr, lefts, rights, lead, requests=None, factors=None):
+    """the two launches of a ThumbPlan with the sheet starting `lead` bytes into a larger buffer; the bytes around it must stay"""
+    plan = ffr.ThumbPlan(lefts, rights, requests, torch.device("cuda", torch.cuda.current_device()), factors=factors)
+    total = plan.height * plan.width * 3
+    big = torch.full((total + 64,), 0xA5, dtype=torch.uint8, device="cuda")
+    plan.out = big[lead:lead + total].view(plan.height, plan.width, 3)
+    assert plan.out.data_ptr() % 16 == lead % 16
+    plan.run_rows()
+    plan.run_compose()
+    torch.cuda.synchronize()
+    host = big.cpu().numpy()
+    assert (host[:lead] == 0xA5).all() and (host[lead + total:] == 0xA5).all(), "bytes around the sheet were written"
+    return host[lead:lead + total].reshape(plan.height, plan.width, 3)
+
+
+def noise(seed, h, w):
+    return np.random.default_rng(seed).integers(0, 256, (h, w, 3), dtype=np.uint8)
+
+
+def pillow_thumbnail(img, request):
+    from PIL import Image
+    im = Image.fromarray(img, "RGB")
+    im.thumbnail(request, Image.Resampling.BICUBIC, reducing_gap=2.0)
+    return np.asarray(im)
+
+
+# (picture h x w, the size asked for, leads).  1 x 1 and 2 x 2 sheets (3 and 12 bytes) end before the first 16-byte boundary or one piece: pieces == 0,
+# lead clamped to total -- as a copy and (4 x 4 -> 2 x 2) through both passes.  3 x 3 = 27 bytes: 5 in -> lead 11, 16 left: no tail; 6 in
+# -> lead 10, 17 left: a tail of one.
+FLAT_CASES = [((1, 1), (1, 1), (0, 1, 15)), ((2, 2), (2, 2), (0, 1, 15)), ((4, 4), (2, 2), (0, 1, 15)), ((3, 3), (3, 3), (5, 6)),
+              ((6, 6), (3, 3), (5, 6))]
+
+
+@pytest.mark.parametrize("size,ask,leads", FLAT_CASES)
+def test_sheets_around_one_piece_at_every_lead(ffr, size, ask, leads):
+    img = noise(500 + size[0], *size)
+    want, _ = S.host_thumbnail(ffr._host(), img, ask)
+    assert want.shape == (ask[1], ask[0], 3)
+    try:
+        assert np.array_equal(pillow_thumbnail(img, ask), want)
+    except ImportError:
+        pass
+    for lead in leads:
+        assert np.array_equal(sheet_at(ffr, [torch.from_numpy(img).cuda()], None, lead, requests=[ask]), want), lead
+
+
+# pairs two pixels wide: the left run is ONE pixel and the right run is staged behind it.  16 rows of 3 bytes from an address = 13 (mod 16)
+# lie at every phase: at 13 the run ends on a 16-byte boundary (head == n), at 14 and 15 n = 3 > head, from 0 to 12 n < head or head == 0.
+@pytest.mark.parametrize("phases", [(13, 13), (13, 2), (0, 13)])
+def test_pairs_with_a_left_run_of_one_pixel(ffr, phases):
+    lib = ffr._host()
+    left, right = noise(610, 16, 1), noise(611, 16, 1)
+    pair = S.make_pair(left, right)
+    on = lambda: ([at_phase(left, phases[0])], [at_phase(right, phases[1])])
+    for request in ((2, 16), (1, 8)):                                        # the pair itself (a copy); BICUBIC 2 -> 1 and 16 -> 8
+        want, factors = S.host_thumbnail(lib, pair, request)
+        assert factors == (1, 1) and want.shape == (request[1], request[0], 3)
+        try:
+            assert np.array_equal(pillow_thumbnail(pair, request), want)
+        except ImportError:
+            pass
+        assert np.array_equal(sheet_at(ffr, *on(), 0, requests=[request]), want), request
+    for fx, fy in ((2, 2), (2, 1), (1, 3)):                                  # cells that straddle the seam; rows folded with the seam whole
+        assert np.array_equal(sheet_at(ffr, *on(), 0, factors=(fx, fy)), S.host_reduce(lib, pair, fx, fy)), (fx, fy)
+    short = noise(612, 9, 1)                                        # the fixed frame ends at row 9: black below
+    assert np.array_equal(sheet_at(ffr, [at_phase(left, phases[0])], [at_phase(short, phases[1])], 0, factors=(1, 1)), S.make_pair(left, short))

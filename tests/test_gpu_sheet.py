@@ -139,3 +139,96 @@ def test_builder_sheets_equal_the_reference(mods, golden, key):
     assert np.array_equal(got[::7, ::5], golden[1][f"builder.{key}"])
     assert hashlib.sha256(np.ascontiguousarray(got).tobytes()).hexdigest() == rec["sha256"]
     assert all(np.array_equal(a, b) for a, b in zip(arrays, keep))
+
+
+# ------------------------------------------------------------------------------------------------
+# the flat piece writer and the byte staging at their edges.  Before these, every `out` was torch's own allocation (16-byte aligned: no
+# lead) and the smallest canvas 16 x 9; byte sources came in whole tensors (phase 0) or, in fp32 only, one float off the grid.
+# ------------------------------------------------------------------------------------------------
+def compose_at(ops, sources, case, out_bytes, lead):
+    """the two launches through the C ABI with `out` starting `lead` ELEMENTS into a larger buffer -> (canvas, the buffer, its fill)"""
+    from comfyui_vrgamedevgirl_amd import _hip
+    lib = _hip.lib()
+    panels = panels_of(ops, case)
+    width, height = case["canvas"]
+    plan = ops.SheetPlan([tuple(s.shape) for s in sources], panels, case["canvas"], case["background"])
+    byte_sources = sources[0].dtype == torch.uint8
+    rec = plan.records.copy()
+    for i, p in enumerate(panels):
+        rec["src"][i] = sources[p.source].data_ptr()
+    plan.check(rec, byte_sources)
+    d = torch.from_numpy(rec.view(np.uint8).reshape(-1)).cuda()
+    tables, spans = torch.from_numpy(plan.tables).cuda(), torch.from_numpy(plan.spans).cuda()
+    tmp = torch.empty(max(plan.tmp_bytes, 1), dtype=torch.uint8, device="cuda")
+    total = height * width * 3
+    fill = 0xA5 if out_bytes else -7.0
+    big = torch.full((total + 64,), fill, dtype=torch.uint8 if out_bytes else torch.float32, device="cuda")
+    out = big[lead:lead + total]
+    assert out.data_ptr() % 16 == (lead * big.element_size()) % 16
+    rows = lib.vrg_sheet_rows_u8 if byte_sources else lib.vrg_sheet_rows_f32
+    compose = lib.vrg_sheet_compose_u8 if out_bytes else lib.vrg_sheet_compose_f32
+    assert rows(_hip.ptr(d), len(rec), _hip.ptr(tables), plan.table_ints, _hip.ptr(tmp), plan.tmp_bytes, plan.max_segments, plan.max_rows,
+                _hip.current_stream()) == 0
+    r, g, b = plan.background
+    assert compose(_hip.ptr(d), len(rec), int(byte_sources), _hip.ptr(tables), plan.table_ints, _hip.ptr(spans), plan.n_spans, _hip.ptr(tmp),
+                   plan.tmp_bytes, _hip.ptr(out), width, height, r | (g << 8) | (b << 16), _hip.current_stream()) == 0
+    torch.cuda.synchronize()
+    host = big.cpu().numpy()
+    around = np.concatenate([host[:lead], host[lead + total:]])
+    assert len(around) == 64 and (around == host.dtype.type(fill)).all(), "bytes around the canvas were written"
+    return host[lead:lead + total].reshape(height, width, 3)
+
+
+def one_panel(canvas, fit="contain_pad"):
+    return {"sources": ["53x37"], "canvas": canvas, "background": (9, 200, 31),
+            "panels": [S.P(0, (0, 0, canvas[0], canvas[1]), fit, (1, 2, 3), 0)]}
+
+
+# (canvas, elements in front of `out`, as bytes / as floats): 3 and 12 elements end before the first 16-byte boundary or one piece
+# (pieces == 0, lead clamped to total); 3 x 3 = 27 elements: bytes 5 in -> lead 11, 16 left: no tail; 6 in -> lead 10, 17 left: a tail of
+# one; floats 1 in -> lead 3, 24 left: no tail; 2 in -> lead 2, 25 left: a tail of one.  A float canvas starts on a float: 0, 1, 3 floats
+# in are bytes 0, 4, 12.
+FLAT_CASES = [((1, 1), (0, 1, 15), (0, 1, 3)), ((2, 2), (0, 1, 15), (0, 1, 3)), ((3, 3), (5, 6), (1, 2))]
+
+
+@pytest.mark.parametrize("canvas,byte_leads,float_leads", FLAT_CASES)
+def test_canvases_around_one_piece_at_every_lead(mods, hm, canvas, byte_leads, float_leads):
+    ops = mods[0]
+    case = one_panel(canvas)
+    host = [S.source(n) for n in case["sources"]]
+    rc, want, want_f, _ = S.host_sheet(hm, host, case["panels"], case["canvas"], case["background"])
+    assert rc == 0 and np.array_equal(want, S.pillow_sheet([S.quantise(a) for a in host], case["panels"], case["canvas"], case["background"]))
+    dev = [torch.from_numpy(a).cuda() for a in host]
+    for lead in byte_leads:
+        assert np.array_equal(compose_at(ops, dev, case, True, lead), want), lead
+    for lead in float_leads:
+        assert np.array_equal(compose_at(ops, dev, case, False, lead).view(np.uint32), want_f.view(np.uint32)), lead
+
+
+def at_phase(array, phase):
+    """a dense device copy of a uint8 array whose first byte lies at an address = phase (mod 16)"""
+    buf = torch.zeros(array.size + 32, dtype=torch.uint8, device="cuda")
+    view = buf[phase:phase + array.size].view(array.shape)
+    view.copy_(torch.from_numpy(array))
+    assert view.data_ptr() % 16 == phase and view.is_contiguous()
+    return view
+
+
+# (height, width, channels, phase of the first byte).  One channel, two pixels at 13: n = 2 < head = 3.  Three channels, two pixels, eight
+# rows from 13: the rows lie at 13, 3, 9, 15, 5, 11, 1, 7 -- at 9 n = 6 < head = 7.  Two pixels at 10 and six pixels at 14 end on a
+# 16-byte boundary (head == n, and head 2 + one whole piece, no tail).
+STAGED = [(8, 2, 1, 13), (8, 2, 3, 13), (1, 2, 3, 10), (1, 6, 3, 14)]
+
+
+@pytest.mark.parametrize("shape", STAGED)
+def test_byte_sources_staged_from_short_and_boundary_segments(mods, hm, shape):
+    ops = mods[0]
+    h, w, c, phase = shape
+    src = np.random.default_rng(sum(shape)).integers(0, 256, (h, w, c), dtype=np.uint8)
+    rgb = np.repeat(src, 3, axis=2) if c == 1 else src
+    for canvas, fit in (((5, h), "resize"), ((w, 2 * h), "resize"), ((7, 11), "cover_crop")):         # taps over the row; the row itself; a window
+        case = {"sources": [None], "canvas": canvas, "background": (0, 0, 0), "panels": [S.P(0, (0, 0, canvas[0], canvas[1]), fit, (4, 5, 6), 0)]}
+        rc, want, _f, _d = S.host_sheet(hm, [src], case["panels"], canvas, case["background"])
+        assert rc == 0 and np.array_equal(want, S.pillow_sheet([rgb], case["panels"], canvas, case["background"]))
+        got = ops.reference_sheet([at_phase(src, phase)], panels_of(ops, case), canvas, case["background"], out_bytes=True)
+        assert np.array_equal(got.cpu().numpy(), want), (canvas, fit)
