@@ -6,7 +6,7 @@ resize + blend + clamp of the node is ONE pass over the originals (ops.restore_f
 kernels and temporaries.  CPU tensors (what ComfyUI hands a node) go through the host-fed pipeline of _devices (staging ring, pieces
 along the frame axis, upload / kernel / download overlapped); device tensors are processed where they are.
 
-What is NOT here: the Prepare node (PNG dumps, ffmpeg, job folders -- its pixels are `_resize_batch`), the anchor
+What is NOT here: the Prepare node (it has a module of its own, VRGDG_VideoEnhancePrepare.py), the anchor
 and collect nodes, and the registration in the package's NODE_CLASS_MAPPINGS: INTEGRATION.md shows the two lines that merge this
 module's mapping.  The node is eager: it is not part of the deferred graph fusion of nodes.py.
 """

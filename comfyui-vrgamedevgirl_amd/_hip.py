@@ -233,6 +233,7 @@ _SIGNATURES = {
     "vrg_selfcheck_pow_f32": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P]),
     "vrg_resize_f32": (C.c_int, [_P, _P, C.c_int64] + [C.c_int32] * 13 + [C.c_int32, _P]),
     "vrg_restore_f32": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64] + [C.c_int32] * 13 + [C.c_int32, C.c_int32, C.c_float, C.c_float, _P]),
+    "vrg_prepare_frames_f32": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64] + [C.c_int32] * 10 + [C.c_int32, _P, _P, _P]),
     "vrg_composite_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "vrg_composite_stats_f32": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int64] + [C.c_int64] * 4 + [C.c_int32] * 10 + [_P, _P, _P]),
     "vrg_composite_apply_f32": (C.c_int, [_P, _P, _P, _P, _P, _P, _P] + [C.c_int64] * 4 + [C.c_int32] * 10 + [_P]),

@@ -209,7 +209,7 @@ struct PilFlat {
     int64_t lead, pieces, blocks;
 };
 
-inline bool pil_flat_plan(const void* out, int64_t elem, int64_t total, int64_t threads, PilFlat& f) {
+VRG_HD bool pil_flat_plan(const void* out, int64_t elem, int64_t total, int64_t threads, PilFlat& f) {
     f.lead = (int64_t)((16 - (reinterpret_cast<uintptr_t>(out) & 15u)) & 15u) / elem;
     f.lead = f.lead < total ? f.lead : total;
     f.pieces = (total - f.lead) / (16 / elem);

@@ -153,19 +153,10 @@ __global__ __launch_bounds__(256) void k_clamp_copy(const float* __restrict__ in
         __builtin_nontemporal_store(clamp01(__builtin_nontemporal_load(in + i)), out + i);
 }
 
-static bool geom_ok(const ResizeGeom& g) {
-    if (g.in_h <= 0 || g.in_w <= 0 || g.in_c < 3 || g.out_h <= 0 || g.out_w <= 0) return false;
-    if (g.sx0 < 0 || g.sy0 < 0 || g.sw <= 0 || g.sh <= 0 || (int64_t)g.sx0 + g.sw > g.in_w || (int64_t)g.sy0 + g.sh > g.in_h) return false;
-    // the destination rectangle may hang over the output frame (crop to fill) but must meet it
-    if (g.dw <= 0 || g.dh <= 0 || g.dx0 >= g.out_w || g.dy0 >= g.out_h || (int64_t)g.dx0 + g.dw <= 0 || (int64_t)g.dy0 + g.dh <= 0) return false;
-    return true;
-}
-
 template <bool RESTORE>
 static int launch_resize(const float* in, float* out, int64_t frames, const ResizeGeom& g, int32_t method, RestoreK r, hipStream_t st) {
     const int32_t oc = RESTORE ? r.channels : 3;
-    // in-frame offsets of the source are 32-bit; frames are addressed with 64 bits
-    if ((int64_t)g.in_w * g.in_c > 0x7fffffff || (int64_t)g.out_h * g.out_w > 0x7fffffff / 4) return VRG_ERR_UNSUPPORTED;
+    if (!rs_sizes_ok(g)) return VRG_ERR_UNSUPPORTED;
     const uint32_t bx = (uint32_t)((g.out_w + 255) / 256), by = (uint32_t)((g.out_h + RS_ROWS - 1) / RS_ROWS);
     if (by > 65535u) return VRG_ERR_UNSUPPORTED;
     const int64_t in_fe = (int64_t)g.in_h * g.in_w * g.in_c, out_fe = (int64_t)g.out_h * g.out_w * oc;
@@ -190,7 +181,7 @@ extern "C" int vrg_resize_f32(const float* in, float* out, int64_t frames, int32
                               int32_t src_x0, int32_t src_y0, int32_t src_w, int32_t src_h, int32_t out_h, int32_t out_w,
                               int32_t dst_x0, int32_t dst_y0, int32_t dst_w, int32_t dst_h, int32_t method, void* stream) {
     const ResizeGeom g{in_h, in_w, in_channels, src_x0, src_y0, src_w, src_h, out_h, out_w, dst_x0, dst_y0, dst_w, dst_h};
-    if (!in || !out || in == out || frames < 0 || method < 0 || method > 3 || !geom_ok(g)) return VRG_ERR_BAD_ARG;
+    if (!in || !out || in == out || frames < 0 || method < 0 || method > 3 || !rs_geom_ok(g)) return VRG_ERR_BAD_ARG;
     if (frames == 0) return VRG_OK;
     return launch_resize<false>(in, out, frames, g, method, RestoreK{nullptr, 3, 0.0f, 0.0f}, (hipStream_t)stream);
 }
@@ -201,7 +192,7 @@ extern "C" int vrg_restore_f32(const float* work, const float* originals, float*
                                int32_t channels, int32_t method, float strength, float one_minus_strength, void* stream) {
     const ResizeGeom g{in_h, in_w, in_channels, src_x0, src_y0, src_w, src_h, out_h, out_w, dst_x0, dst_y0, dst_w, dst_h};
     if (!work || !originals || !out || out == originals || out == work || work_frames < 0 || frames < 0 || channels < 3 || method < 0 ||
-        method > 3 || !geom_ok(g))
+        method > 3 || !rs_geom_ok(g))
         return VRG_ERR_BAD_ARG;
     if (frames == 0) return VRG_OK;
     const int64_t usable = work_frames < frames ? work_frames : frames;

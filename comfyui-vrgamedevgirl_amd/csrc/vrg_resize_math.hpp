@@ -101,6 +101,19 @@ struct ResizeGeom {
     int32_t dx0, dy0, dw, dh;
 };
 
+// The argument rules of a geometry, shared by every entry point that takes one (vrg_resize_f32, vrg_restore_f32, vrg_prepare_frames_f32)
+inline bool rs_geom_ok(const ResizeGeom& g) {
+    if (g.in_h <= 0 || g.in_w <= 0 || g.in_c < 3 || g.out_h <= 0 || g.out_w <= 0) return false;
+    if (g.sx0 < 0 || g.sy0 < 0 || g.sw <= 0 || g.sh <= 0 || (int64_t)g.sx0 + g.sw > g.in_w || (int64_t)g.sy0 + g.sh > g.in_h) return false;
+    // the destination rectangle may hang over the output frame (crop to fill) but must meet it
+    if (g.dw <= 0 || g.dh <= 0 || g.dx0 >= g.out_w || g.dy0 >= g.out_h || (int64_t)g.dx0 + g.dw <= 0 || (int64_t)g.dy0 + g.dh <= 0) return false;
+    return true;
+}
+// in-frame offsets of the source are 32-bit; frames are addressed with 64 bits
+inline bool rs_sizes_ok(const ResizeGeom& g) {
+    return (int64_t)g.in_w * g.in_c <= 0x7fffffff && (int64_t)g.out_h * g.out_w <= 0x7fffffff / 4;
+}
+
 // One RGB output pixel (ox, oy) of one frame, straight from the definitions above (no reuse between pixels): the form the host check
 // runs, and the nearest / area kernels.  `frame`: the [in_h][in_w][in_c] input frame.  Result clamped to [0, 1].
 template <typename LOAD>

@@ -744,6 +744,43 @@ def resize_frames(images: torch.Tensor, target_width, target_height, fit_mode, r
     return resize_geometry_frames(x, resize_geometry(x.shape[1], x.shape[2], target_width, target_height, fit_mode), resize_method, out)
 
 
+def _check_frame_indices(indices, frames: int) -> list:
+    try:
+        listed = [int(i) for i in indices]
+    except TypeError:
+        raise ValueError(f"indices must be a sequence of frame numbers or None, got {type(indices).__name__}") from None
+    for i in listed:
+        if not 0 <= i < frames:
+            raise ValueError(f"frame index {i} is outside the batch of {frames} frame(s)")
+    return listed
+
+
+@_on_device
+def prepare_frames(images: torch.Tensor, geometry: ResizeGeometry, resize_method, indices=None, want_f32: bool = True, want_u8: bool = True):
+    """The pixels of VRGDGVideoEnhancePrepare.prepare (:224-228) in one launch: frame i of the result is `images[indices[i]]` (every frame in
+    order for None; repeats and any order are fine) resampled as resize_geometry_frames does, bit for bit -- as float32
+    [N, out_h, out_w, 3] and/or as the uint8 R,G,B bytes ``(x * 255).round().astype("uint8")`` of _save_image_batch (:117).  Returns
+    (f32 | None, u8 | None).  The index list is checked here, before anything is launched."""
+    x = _check_resize_source(images, "images")
+    if not (want_f32 or want_u8):
+        raise ValueError("prepare_frames: at least one of want_f32 and want_u8 must be set")
+    frames = int(x.shape[0])
+    args = _geometry_args(x, geometry)
+    listed = None if indices is None else _check_frame_indices(indices, frames)
+    n_out = frames if listed is None else len(listed)
+    shape = (n_out, geometry.out_h, geometry.out_w, 3)
+    f32 = torch.empty(shape, dtype=torch.float32, device=x.device) if want_f32 else None
+    u8 = torch.empty(shape, dtype=torch.uint8, device=x.device) if want_u8 else None
+    if n_out == 0:
+        return f32, u8
+    index = None if listed is None else torch.tensor(listed, dtype=torch.int32).to(x.device)
+    null = C.c_void_p(0)
+    _hip.check(_hip.lib().vrg_prepare_frames_f32(_hip.ptr(x), frames, *args[:3], null if index is None else _hip.ptr(index), n_out, *args[3:],
+                                                RESIZE_METHODS[interpolation_mode(resize_method)], null if f32 is None else _hip.ptr(f32),
+                                                null if u8 is None else _hip.ptr(u8), _hip.current_stream()), "vrg_prepare_frames_f32")
+    return f32, u8
+
+
 @_on_device
 def restore_frames(work: torch.Tensor, originals: torch.Tensor, source_width, source_height, fit_mode, resize_method, strength: float,
                    frame_count: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -343,6 +343,20 @@ int vrg_restore_f32(const float* work, const float* originals, float* out, int64
                     int32_t out_h, int32_t out_w, int32_t dst_x0, int32_t dst_y0, int32_t dst_w, int32_t dst_h,
                     int32_t channels, int32_t method, float strength, float one_minus_strength, void* stream);
 
+/* The pixels of VRGDGVideoEnhancePrepare.prepare (:224-228) in one launch: output frame i is the resize of source frame frame_index[i]
+ * of `in` = [frames][in_h][in_w][in_channels >= 3], by the geometry and method rules of vrg_resize_f32 and bit-identical to it.
+ * `frame_index`: n_out entries in DEVICE memory, in any order and with repeats, or null for source frames 0 .. n_out - 1; the caller checks
+ * the list (an entry outside 0 .. frames - 1 is VRG_ERR_BAD_ARG there); the kernel leaves the output frame of such an entry unwritten
+ * and reads nothing for it.  Both outputs are [n_out][out_h][out_w][3] and come from the same computed value v in [0, 1]: out_f32 gets
+ * v, out_u8 gets rintf(v * 255.0f) as R,G,B bytes -- the fp32 product rounded half to even, numpy's (x * 255).round().astype("uint8")
+ * of _save_image_batch (:117).  Letterbox padding is 0.0f and 0.  Either output may be null, not both; no two of `in`, `frame_index`,
+ * `out_f32` and `out_u8` may overlap anywhere in the bytes the call covers (checked: VRG_ERR_BAD_ARG).  n_out == 0 succeeds without a launch; frames == 0 with n_out > 0 is VRG_ERR_BAD_ARG.  Bicubic brings every
+ * source row a band of output rows needs through LDS once (csrc/vrg_prepare.hip); the other methods run the direct form. */
+int vrg_prepare_frames_f32(const float* in, int64_t frames, int32_t in_h, int32_t in_w, int32_t in_channels,
+                           const int32_t* frame_index, int64_t n_out, int32_t src_x0, int32_t src_y0, int32_t src_w, int32_t src_h,
+                           int32_t out_h, int32_t out_w, int32_t dst_x0, int32_t dst_y0, int32_t dst_w, int32_t dst_h, int32_t method,
+                           float* out_f32, uint8_t* out_u8, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Feathered crop composite.  Replaces the per-frame loops of VRGDG_ImagePasteBack.paste_back (VRGDG_ImagePasteBack.py:224-260),
  * VRGDGFaceFixComposite.composite and VRGDGFaceFixCompositeOpaque.composite (VRGDG_StandaloneFaceFixNodes.py:827-849, 891-916):
