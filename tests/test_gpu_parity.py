@@ -891,6 +891,74 @@ def test_colour_match_node_is_the_device_oracle_for_every_batch_size(pkg, dev, F
     assert_bit_equal(out, R.color_match(x.to(dev), ref.to(dev), k, bs), f"batch_size {bs}")
 
 
+# The reference runs its colour match inside `torch.no_grad(), torch.cuda.amp.autocast()` (nodes.py:97,104); the device oracle above is
+# evaluated outside any autocast.  (frames, batch_size, strength): batch sizes 1, 2 and a ragged 3 (5 frames: 3 + 2), strengths 1.0 and
+# 0.35, and the widget values of the shipped graph Workflows/Z-ImageUpscale/AnyImageZImageUpscaleWithCN.json, node 195: [1, 4].
+CM_CONTEXT_CASES = [((4, 135, 240, 3), 1, 1.0), ((4, 135, 240, 3), 2, 0.35), ((5, 45, 51, 3), 3, 1.0), ((5, 45, 51, 3), 3, 0.35),
+                    ((3, 45, 51, 3), 1, 0.35), ((4, 45, 51, 3), 2, 1.0), ((6, 135, 240, 3), 4, 1)]
+CM_CONTEXT_IDS = [f"{s[0]}x{s[1]}x{s[2]}-bs{bs}-k{k}" for s, bs, k in CM_CONTEXT_CASES[:-1]] + ["graph-node-195-widgets-1-4"]
+
+
+def _context_frames(shape, dev):
+    return _cm_image(shape, 171).to(dev), (_rand((1, 37, 53, 3), 172) * 0.8 + 0.1).to(dev)
+
+
+@pytest.mark.parametrize("shape,bs,k", CM_CONTEXT_CASES, ids=CM_CONTEXT_IDS)
+def test_device_oracle_is_the_same_inside_the_reference_s_autocast(dev, shape, bs, k):
+    """(a) oracle.restated.color_match on device tensors inside torch.no_grad(), torch.autocast("cuda") == the same call outside, bit for
+    bit and in fp32 -- and so are its three stages on their own, so that a difference would name its stage."""
+    x, ref = _context_frames(shape, dev)
+    nchw = x.permute(0, 3, 1, 2)
+    g = torch.Generator(device=dev).manual_seed(173)
+    lab = R.kornia_rgb_to_lab(nchw)
+    wild = lab * (1.0 + 0.3 * torch.randn(lab.shape, generator=g, device=dev))          # out of gamut: the clamps and the negative fz
+    chunks = [lab[i:i + bs] for i in range(0, lab.shape[0], bs)]
+    outside = {"rgb_to_lab": lab, "lab_to_rgb": R.kornia_lab_to_rgb(wild), "color_match": R.color_match(x, ref, k, bs)}
+    outside.update({f"lab_stats.{j}.{n}": t for j, c in enumerate(chunks) for n, t in zip(("mean", "std"), R.lab_stats(c))})
+    with torch.no_grad(), torch.autocast("cuda"):
+        assert torch.is_autocast_enabled()
+        inside = {"rgb_to_lab": R.kornia_rgb_to_lab(nchw), "lab_to_rgb": R.kornia_lab_to_rgb(wild), "color_match": R.color_match(x, ref, k, bs)}
+        inside.update({f"lab_stats.{j}.{n}": t for j, c in enumerate(chunks) for n, t in zip(("mean", "std"), R.lab_stats(c))})
+    for name, want in outside.items():
+        assert inside[name].dtype == want.dtype == torch.float32, (name, inside[name].dtype)
+        assert_bit_equal(inside[name], want, f"{name} inside torch.no_grad(), torch.autocast('cuda') vs outside")
+
+
+@pytest.mark.parametrize("shape,bs,k", CM_CONTEXT_CASES, ids=CM_CONTEXT_IDS)
+def test_colour_match_node_inside_a_caller_s_autocast_and_inference_mode(pkg, dev, shape, bs, k):
+    """(b) ColorMatchToReference().match_color called from inside a caller's torch.autocast("cuda") and torch.inference_mode() == the
+    device oracle evaluated in the reference's own context, bit for bit; the node returns fp32."""
+    x, ref = _context_frames(shape, dev)
+    with torch.no_grad(), torch.autocast("cuda"):
+        want = R.color_match(x, ref, k, bs)
+    node = pkg.NODE_CLASS_MAPPINGS["ColorMatchToReference"]()
+    for where in ("cpu", "device"):
+        xi, ri = (x.cpu(), ref.cpu()) if where == "cpu" else (x.clone(), ref.clone())
+        with torch.inference_mode(), torch.autocast("cuda"):
+            (out,) = node.match_color(xi, ri, k, bs)
+            assert out.dtype == torch.float32 and tuple(out.shape) == tuple(x.shape)
+            got = out.clone()
+        assert_bit_equal(got, want, f"node inside autocast + inference_mode, {where} frames")
+
+
+def test_film_grain_node_with_the_shipped_graph_s_widgets_inside_autocast(pkg, dev):
+    """(c) the grain widgets of the shipped graph Wan2.22ziamge.json, node 135: [0.01, 0.5, 4] -- 6 frames, so a ragged last chunk of 2 --
+    plainly and inside a caller's autocast + inference_mode: the oracle on the identical seed, in fp32"""
+    node = pkg.NODE_CLASS_MAPPINGS["FastFilmGrain"]()
+    x = _rand((6, 45, 51, 3), 174, -0.1, 1.1)
+    torch.manual_seed(175)
+    want = R.fast_film_grain(x, 0.01, 0.5, 4, noise_fn=lambda i, shp: torch.randn(shp, device=dev).cpu())
+    torch.manual_seed(175)
+    (plain,) = node.apply_grain(x, 0.01, 0.5, 4)
+    assert_bit_equal(plain, want, "FastFilmGrain [0.01, 0.5, 4]")
+    torch.manual_seed(175)
+    with torch.inference_mode(), torch.autocast("cuda"):
+        (out,) = node.apply_grain(x.clone(), 0.01, 0.5, 4)
+        assert out.dtype == torch.float32
+        got = out.clone()
+    assert_bit_equal(got, want, "FastFilmGrain [0.01, 0.5, 4] inside autocast + inference_mode")
+
+
 @pytest.mark.parametrize("shape,ref_shape,k,bs", [((4, 135, 240, 3), (1, 64, 80, 3), 1.0, 1), ((3, 270, 480, 3), (1, 300, 400, 3), 0.35, 1),
                                                   ((4, 96, 128, 3), (4, 50, 60, 3), 0.8, 4)])
 def test_colour_match_end_to_end_ulp_budget_vs_device_oracle(pkg, ops, dev, shape, ref_shape, k, bs):
