@@ -181,6 +181,7 @@ PIL_MAX_LINE = 8192             # the longest mask row / column (csrc/vrg_pil_ma
 SHEET_MAX_SIDE = 32767          # include/vrgdg_hip.h: VRG_SHEET_MAX_SIDE
 SHEET_STAGE_VALUES = 16384      # include/vrgdg_hip.h: VRG_SHEET_STAGE_VALUES
 PIL_FILTER_LANCZOS, PIL_FILTER_BICUBIC = 1, 3      # include/vrgdg_hip.h: VRG_PIL_FILTER_* (Pillow's own numbers)
+FLF_CHUNK = 32                  # frames one workgroup writes (csrc/vrg_flf_math.hpp: FLF_CHUNK)
 FACEFIX_STATS_WORDS = 12        # uint64 per frame (csrc/vrg_facefix_math.hpp: FF_STATS_WORDS)
 
 _F3 = C.c_float * 3
@@ -296,6 +297,8 @@ _SIGNATURES = {
     "vrg_thumb_compose_u8": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P] + [C.c_int32] * 5 + [C.c_uint32, _P]),
     "vrg_msr_check": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
     "vrg_msr_frames_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
+    "vrg_flf_check": (C.c_int, [C.c_int64] + [C.c_int32] * 9),
+    "vrg_flf_guide_f32": (C.c_int, [_P, _P, _P, _P, C.c_int64] + [C.c_int32] * 9 + [_P]),
 }
 
 # include/vrgdg_hip_debug.h: self-tests and probes -- for the test suite and the measurement tools, not part of the drop-in boundary

@@ -89,6 +89,13 @@ VRG_HD float rs_dot(const float (&w)[N], const float (&v)[N]) {
     return acc;
 }
 
+// One bilinear value from its four taps.  torch picks its channels-last kernel (four products of weight pairs: `paired`) or its generic
+// separable kernel (rows first, as bicubic); which one runs is the caller's to say (rs_pixel, csrc/vrg_flf_math.hpp).  Not clamped.
+VRG_HD float rs_bilinear_value(bool paired, const float (&wx)[2], const float (&wy)[2], float i00, float i01, float i10, float i11) {
+    return paired ? (wy[0] * wx[0]) * i00 + (wy[0] * wx[1]) * i01 + (wy[1] * wx[0]) * i10 + (wy[1] * wx[1]) * i11
+                  : (i00 * wx[0] + i01 * wx[1]) * wy[0] + (i10 * wx[0] + i11 * wx[1]) * wy[1];
+}
+
 // The blend of VRGDGVideoEnhanceRestoreOriginal.restore on one value: clamp(o * (1 - s) + clamp01(resampled) * s, 0, 1)
 VRG_HD float rs_blend(float original, float restored, float s, float oms) { return clamp01(original * oms + restored * s); }
 
@@ -155,15 +162,12 @@ VRG_HD void rs_pixel(const ResizeGeom& g, int32_t method, int32_t ox, int32_t oy
         rs_linear_taps(dx, sx, g.sw, ix, wx);
         rs_linear_taps(dy, sy, g.sh, iy, wy);
         const bool small = g.dh + g.dw <= 128;
-        const float w00 = wy[0] * wx[0], w01 = wy[0] * wx[1], w10 = wy[1] * wx[0], w11 = wy[1] * wx[1];
         for (int c = 0; c < 3; ++c) {
             const float i00 = load(g.sy0 + iy[0], g.sx0 + ix[0], c), i01 = load(g.sy0 + iy[0], g.sx0 + ix[1], c);
             const float i10 = load(g.sy0 + iy[1], g.sx0 + ix[0], c), i11 = load(g.sy0 + iy[1], g.sx0 + ix[1], c);
             // torch picks its channels-last kernel (four products of weight pairs) for RGB frames whose resampled height + width is at
             // most 128 and its generic separable kernel (rows first, as bicubic) for everything larger
-            const float v = small ? w00 * i00 + w01 * i01 + w10 * i10 + w11 * i11
-                                  : (i00 * wx[0] + i01 * wx[1]) * wy[0] + (i10 * wx[0] + i11 * wx[1]) * wy[1];
-            o[c] = clamp01(v);
+            o[c] = clamp01(rs_bilinear_value(small, wx, wy, i00, i01, i10, i11));
         }
     }
 }

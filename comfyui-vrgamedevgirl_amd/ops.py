@@ -3201,3 +3201,112 @@ def bytes_to_image(picture) -> torch.Tensor:
     launch of msr_reference_frames with one descriptor, no filter, one frame."""
     p = _msr_picture(picture, 0)
     return msr_reference_frames([p], (int(p.shape[1]), int(p.shape[0])), 1)
+
+
+# ---------------------------------------------------------------------------------------------
+# The LTX First / Last temporal guide (VRGDG_LTXFirstLastGuide.py:52-69 of the reference): `last` centre-cropped and bilinearly resampled to
+# the size of `first`, the two cross-faded into a batch of frames, in one launch (csrc/vrg_flf.hip)
+# ---------------------------------------------------------------------------------------------
+FLF_CURVES = ("smoothstep", "linear", "ease_in", "ease_out")
+FLF_CHUNK = _hip.FLF_CHUNK
+
+
+def flf_curve(value, name):
+    """The reference's ``_curve``: any name but "linear", "ease_in" and "ease_out" is the smoothstep."""
+    if name == "linear":
+        return value
+    if name == "ease_in":
+        return value * value
+    if name == "ease_out":
+        return 1.0 - (1.0 - value) * (1.0 - value)
+    return value * value * (3.0 - 2.0 * value)
+
+
+def flf_weights(frame_count: int, transition_start=0.05, transition_end=0.90, curve="smoothstep") -> np.ndarray:
+    """``[frame_count, 2]`` float32: ``(1.0 - amount, amount)`` of every frame, formed in Python doubles as the reference's loop forms them
+    (:61-67) and rounded to fp32 once, which is what torch does with a Python scalar that meets an fp32 tensor."""
+    frame_count = int(frame_count)
+    if frame_count < 1:
+        raise ValueError("first/last guide: frame_count must be at least 1")
+    start = max(0.0, min(0.95, float(transition_start)))
+    end = max(start + 0.01, min(1.0, float(transition_end)))
+    weights = np.empty((frame_count, 2), dtype=np.float64)
+    for index in range(frame_count):
+        position = index / max(1, frame_count - 1)
+        amount = flf_curve(max(0.0, min(1.0, (position - start) / (end - start))), str(curve))
+        weights[index] = (1.0 - amount, amount)
+    return weights.astype(np.float32)
+
+
+def center_crop_rect(old_w: int, old_h: int, new_w: int, new_h: int) -> tuple:
+    """(x0, y0, width, height) of the view ``comfy.utils.common_upscale(..., crop="center")`` narrows an ``old_w`` x ``old_h`` picture to
+    before it resamples it to ``new_w`` x ``new_h``: the wider or taller side loses ``round()`` (Python's, half to even) of half its
+    surplus at both ends.  A restatement of the published function; comfy is not vendored."""
+    old_w, old_h, new_w, new_h = int(old_w), int(old_h), int(new_w), int(new_h)
+    old_aspect, new_aspect = old_w / old_h, new_w / new_h
+    x = y = 0
+    if old_aspect > new_aspect:
+        x = round((old_w - old_w * (new_aspect / old_aspect)) / 2)
+    elif old_aspect < new_aspect:
+        y = round((old_h - old_h * (old_aspect / new_aspect)) / 2)
+    return x, y, old_w - 2 * x, old_h - 2 * y
+
+
+def _flf_picture(t, name):
+    if not isinstance(t, torch.Tensor) or t.ndim != 4:
+        raise ValueError(f"first/last guide: {name} must be a [batch, height, width, channels] IMAGE tensor")
+    if int(t.shape[0]) < 1:
+        raise ValueError(f"first/last guide: {name} is an empty batch")
+    if t.dtype != torch.float32:
+        raise ValueError(f"first/last guide: {name} must be fp32")
+    return t.detach()[:1]
+
+
+def flf_plan(first_shape, last_shape, frame_count: int, transition_start=0.05, transition_end=0.90, curve="smoothstep"):
+    """The host side of one launch, no GPU needed: ``(rectangle, weights)`` for pictures of ``first_shape`` / ``last_shape`` =
+    (height, width, channels), checked by vrg_flf_check."""
+    (h, w, c), (last_h, last_w, last_c) = (tuple(int(v) for v in s) for s in (first_shape, last_shape))
+    if c != last_c:
+        raise ValueError(f"first/last guide: first has {c} channels, last has {last_c}")
+    if c not in (3, 4):
+        raise ValueError(f"first/last guide: {c} channels (3 or 4 are taken)")
+    if min(h, w, last_h, last_w) < 1:
+        raise ValueError("first/last guide: pictures must be at least 1 x 1")
+    weights = flf_weights(frame_count, transition_start, transition_end, curve)
+    rect = (0, 0, last_w, last_h) if (last_h, last_w) == (h, w) else center_crop_rect(last_w, last_h, w, h)
+    rc = _host_lib().vrg_flf_check(len(weights), h, w, c, last_h, last_w, *rect)
+    if rc == _hip.VRG_ERR_BAD_ARG:
+        raise ValueError(f"first/last guide: vrg_flf_check refuses {last_w} x {last_h} -> {w} x {h}, rectangle {rect}")
+    if rc != _hip.VRG_OK:
+        raise RuntimeError(f"first/last guide: {len(weights)} frames of {w} x {h} x {c} are more than one launch takes")
+    return rect, weights
+
+
+def flf_guide_frames(first, last, frame_count: int, transition_start=0.05, transition_end=0.90, curve="smoothstep", out=None) -> torch.Tensor:
+    """``torch.cat([first * (1.0 - amount) + last' * amount for every frame])`` of the reference's First / Last guide as one launch:
+    ``first[:1]`` and ``last[:1]`` are fp32 IMAGE tensors on the GPU (used in place) or on the CPU (the two pictures are uploaded),
+    ``last'`` is ``last`` centre-cropped and bilinearly resampled to the size of ``first`` (not clamped) unless it already has it.
+    Returns the ``[frame_count, H, W, C]`` fp32 device tensor, ``out`` where one is given.  Inputs are never written."""
+    from . import _devices
+    a, b = _flf_picture(first, "first"), _flf_picture(last, "last")
+    rect, weights = flf_plan(tuple(a.shape[1:]), tuple(b.shape[1:]), frame_count, transition_start, transition_end, curve)
+    dev = next((t.device for t in (a, b) if t.is_cuda), None)
+    if dev is None or not (a.is_cuda and b.is_cuda):
+        if dev is not None and dev != _devices.compute_device():
+            raise RuntimeError(f"first/last guide: a CPU picture goes to {_devices.compute_device()}, the CUDA picture lives on {dev}; move it there")
+        dev = _devices.compute_device()
+    if any(t.is_cuda and t.device != dev for t in (a, b)):
+        raise RuntimeError("first/last guide: the pictures live on two GPUs")
+    frames, (h, w, c) = len(weights), (int(v) for v in a.shape[1:])
+    if out is not None:
+        if (not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.float32 or tuple(out.shape) != (frames, h, w, c)
+                or not out.is_contiguous()):
+            raise ValueError(f"first/last guide: out must be a contiguous fp32 [{frames}, {h}, {w}, {c}] tensor on {dev}")
+    with torch.cuda.device(dev):
+        a, b = (t.contiguous() if t.is_cuda else _devices.on_device(t, dev).contiguous() for t in (a, b))
+        if out is None:
+            out = torch.empty((frames, h, w, c), dtype=torch.float32, device=dev)
+        wd = torch.from_numpy(weights).to(dev)
+        _hip.check(_hip.lib().vrg_flf_guide_f32(_hip.ptr(a), _hip.ptr(b), _hip.ptr(wd), _hip.ptr(out), frames, h, w, c, int(b.shape[1]),
+                                                int(b.shape[2]), *rect, _hip.current_stream()), "vrg_flf_guide_f32")
+    return out

@@ -1000,6 +1000,25 @@ int vrg_msr_check(const vrg_msr_desc* desc_host, int64_t n_desc, int64_t n_taps,
 int vrg_msr_frames_f32(const vrg_msr_desc* desc, int64_t n_desc, const void* taps, int64_t n_taps,
                        float* out, int64_t frames, int32_t out_h, int32_t out_w, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The LTX First / Last temporal guide (VRGDG_LTXFirstLastGuide.add_first_last_guide, VRGDG_LTXFirstLastGuide.py:52-69 of the reference),
+ * csrc/vrg_flf.hip and csrc/vrg_flf_math.hpp: out[f] = first * w0[f] + last' * w1[f] for every frame f, each product and the sum rounded
+ * once, where last' is the rectangle (src_x0, src_y0, src_w, src_h) of `last` resampled to w x h as F.interpolate(mode="bilinear",
+ * align_corners=False) resamples the narrowed channels-last view (taps clamped to the rectangle, the result not clamped) -- or `last`
+ * itself, no filter evaluated, when it has h x w and the rectangle is all of it.  first = [h][w][channels], last =
+ * [last_h][last_w][channels], weights = [frames][2] (w0, w1: (float)(1.0 - amount), (float)amount, formed in double by the caller),
+ * out = [frames][h][w][channels]; all fp32 in device memory, 4-byte aligned, `out` at any such address (frames that start off the 16-byte
+ * grid are written with 4-byte stores).  Every float of `out` is written exactly once and none is read; `out` aliases neither input.
+ * channels is 3 or 4.  vrg_flf_check refuses ON THE HOST what the launch refuses: VRG_ERR_BAD_ARG for negative frames, sizes below 1,
+ * other channel counts and a rectangle that does not lie inside `last`; VRG_ERR_UNSUPPORTED for pictures of more than 2^31 - 1 floats or
+ * more than 65535 * 32 frames.  Zero frames succeed without a launch.
+ * ------------------------------------------------------------------------------------------- */
+int vrg_flf_check(int64_t frames, int32_t h, int32_t w, int32_t channels, int32_t last_h, int32_t last_w,
+                  int32_t src_x0, int32_t src_y0, int32_t src_w, int32_t src_h);
+int vrg_flf_guide_f32(const float* first, const float* last, const float* weights, float* out, int64_t frames, int32_t h, int32_t w,
+                      int32_t channels, int32_t last_h, int32_t last_w, int32_t src_x0, int32_t src_y0, int32_t src_w, int32_t src_h,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
