@@ -173,6 +173,14 @@ class ThumbEntry(C.Structure):
                 ("v_ksize", C.c_int32), ("dst_x", C.c_int32), ("dst_y", C.c_int32), ("cps", C.c_int32), ("reserved", C.c_int32)]
 
 
+class RefbatchDesc(C.Structure):
+    """vrg_refbatch_desc"""
+    _fields_ = [("src_offset", C.c_int64), ("dst_offset", C.c_int64), ("src_h", C.c_int32), ("src_w", C.c_int32), ("src_c", C.c_int32),
+                ("src_x0", C.c_int32), ("src_y0", C.c_int32), ("src_rw", C.c_int32), ("src_rh", C.c_int32), ("dst_h", C.c_int32),
+                ("dst_w", C.c_int32), ("dst_c", C.c_int32), ("method", C.c_int32), ("frames", C.c_int32), ("first_tile", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 GRID_COPY, GRID_FAST, GRID_FAST_2X2, GRID_GENERAL, GRID_LINEAR = 0, 1, 2, 3, 4
 THUMB_SIDE = 320                # include/vrgdg_hip.h: VRG_THUMB_SIDE
 THUMB_MAX_SIDE = 32767          # include/vrgdg_hip.h: VRG_THUMB_MAX_SIDE
@@ -182,6 +190,8 @@ SHEET_MAX_SIDE = 32767          # include/vrgdg_hip.h: VRG_SHEET_MAX_SIDE
 SHEET_STAGE_VALUES = 16384      # include/vrgdg_hip.h: VRG_SHEET_STAGE_VALUES
 PIL_FILTER_LANCZOS, PIL_FILTER_BICUBIC = 1, 3      # include/vrgdg_hip.h: VRG_PIL_FILTER_* (Pillow's own numbers)
 FLF_CHUNK = 32                  # frames one workgroup writes (csrc/vrg_flf_math.hpp: FLF_CHUNK)
+REFBATCH_TILE = 1024            # include/vrgdg_hip.h: VRG_REFBATCH_TILE
+REFBATCH_BICUBIC, REFBATCH_BILINEAR, REFBATCH_AREA, REFBATCH_NEAREST_EXACT, REFBATCH_COPY, REFBATCH_BYTES = 0, 1, 2, 3, 4, 5
 FACEFIX_STATS_WORDS = 12        # uint64 per frame (csrc/vrg_facefix_math.hpp: FF_STATS_WORDS)
 
 _F3 = C.c_float * 3
@@ -299,6 +309,9 @@ _SIGNATURES = {
     "vrg_msr_frames_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
     "vrg_flf_check": (C.c_int, [C.c_int64] + [C.c_int32] * 9),
     "vrg_flf_guide_f32": (C.c_int, [_P, _P, _P, _P, C.c_int64] + [C.c_int32] * 9 + [_P]),
+    "vrg_refbatch_check": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
+    "vrg_refbatch_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int64, _P, C.c_int64, _P]),
+    "vrg_refbatch_quantise_u8": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int64, _P, C.c_int64, _P]),
 }
 
 # include/vrgdg_hip_debug.h: self-tests and probes -- for the test suite and the measurement tools, not part of the drop-in boundary

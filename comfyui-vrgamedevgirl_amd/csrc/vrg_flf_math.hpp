@@ -35,8 +35,7 @@ VRG_HD bool flf_plain(const FlfGeom& g) {
 
 // torch's kernel choice for the narrowed view (see above)
 VRG_HD bool flf_paired(const FlfGeom& g) {
-    const bool contiguous = g.sh == 1 || g.sw == g.last_w;
-    return (contiguous && g.c > 3) || g.h + g.w <= 128;
+    return rs_bilinear_paired(rs_view_contiguous(1, g.last_h, g.last_w, g.sw, g.sh), g.c, g.h, g.w);
 }
 
 inline int flf_check(int64_t frames, int32_t h, int32_t w, int32_t channels, int32_t last_h, int32_t last_w, int32_t sx0, int32_t sy0,

@@ -96,6 +96,18 @@ VRG_HD float rs_bilinear_value(bool paired, const float (&wx)[2], const float (&
                   : (i00 * wx[0] + i01 * wx[1]) * wy[0] + (i10 * wx[0] + i11 * wx[1]) * wy[1];
 }
 
+// Which of the two torch runs (ATen/native/cpu/UpSampleKernel.cpp: _use_vectorized_kernel_cond_2d, torch with at least two threads): the
+// channels-last kernel when the resampled view is channels-last contiguous and has more than 3 channels, or when the output height +
+// width is at most 128; the generic kernel otherwise.
+VRG_HD bool rs_bilinear_paired(bool contiguous, int32_t channels, int32_t out_h, int32_t out_w) {
+    return (contiguous && channels > 3) || out_h + out_w <= 128;
+}
+// Is the rectangle sw x sh narrowed out of `frames` channels-last pictures [h][w][c] still channels-last contiguous?  Dimensions of
+// size 1 do not count: rows narrowed only in y stay contiguous within a picture, several pictures only when nothing is narrowed.
+VRG_HD bool rs_view_contiguous(int64_t frames, int32_t h, int32_t w, int32_t sw, int32_t sh) {
+    return (sh == 1 || sw == w) && (frames == 1 || (int64_t)sh * sw == (int64_t)h * w);
+}
+
 // The blend of VRGDGVideoEnhanceRestoreOriginal.restore on one value: clamp(o * (1 - s) + clamp01(resampled) * s, 0, 1)
 VRG_HD float rs_blend(float original, float restored, float s, float oms) { return clamp01(original * oms + restored * s); }
 

@@ -3310,3 +3310,287 @@ def flf_guide_frames(first, last, frame_count: int, transition_start=0.05, trans
         _hip.check(_hip.lib().vrg_flf_guide_f32(_hip.ptr(a), _hip.ptr(b), _hip.ptr(wd), _hip.ptr(out), frames, h, w, c, int(b.shape[1]),
                                                 int(b.shape[2]), *rect, _hip.current_stream()), "vrg_flf_guide_f32")
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# Multi-reference image batches (VRGDG_MultiReferenceConditioning, ...FromPaths and VRGDG_ImageBatchMultiFromPaths,
+# VRGDG_GeneralNodes2.py:3801-4145 of the reference): up to 50 pictures of unrelated sizes and channel counts, each brought to a megapixel
+# budget, or all to the first one's shape, by comfy.utils.common_upscale's rule -- one launch of csrc/vrg_refbatch.hip for all of them
+# ---------------------------------------------------------------------------------------------
+REFBATCH_METHODS = ("nearest-exact", "bilinear", "area", "bicubic", "lanczos")          # the reference's upscale_methods, in its order
+_REFBATCH_FILTERS = {"bicubic": _hip.REFBATCH_BICUBIC, "bilinear": _hip.REFBATCH_BILINEAR, "area": _hip.REFBATCH_AREA,
+                     "nearest-exact": _hip.REFBATCH_NEAREST_EXACT}
+REFBATCH_DESC = np.dtype([("src_offset", "<i8"), ("dst_offset", "<i8"), ("src_h", "<i4"), ("src_w", "<i4"), ("src_c", "<i4"), ("src_x0", "<i4"),
+                          ("src_y0", "<i4"), ("src_rw", "<i4"), ("src_rh", "<i4"), ("dst_h", "<i4"), ("dst_w", "<i4"), ("dst_c", "<i4"),
+                          ("method", "<i4"), ("frames", "<i4"), ("first_tile", "<i4"), ("reserved", "<i4")])           # vrg_refbatch_desc
+assert REFBATCH_DESC.itemsize == C.sizeof(_hip.RefbatchDesc)
+
+
+def total_pixels_size(height: int, width: int, megapixels, resolution_steps=1) -> tuple:
+    """(height, width) a picture of ``height`` x ``width`` is scaled to for a budget of ``megapixels`` * 1024 * 1024 pixels, each side
+    rounded (Python's ``round``, half to even) to a multiple of ``resolution_steps`` and at least 1: the size rule of the reference's
+    ``_scale_to_total_pixels`` (:3861-3865)."""
+    height, width = int(height), int(width)
+    if height < 1 or width < 1:
+        raise ValueError("total_pixels_size: the picture must be at least 1 x 1")
+    total = float(megapixels) * 1024 * 1024
+    scale_by = math.sqrt(total / (width * height))
+    steps = max(1, int(resolution_steps))
+    new_w = max(1, round(width * scale_by / steps) * steps)
+    new_h = max(1, round(height * scale_by / steps) * steps)
+    return int(new_h), int(new_w)
+
+
+@dataclass
+class _RefJob:
+    """one record of a launch: `frames` pictures [h][w][c] at element `src_offset` of `src`, their rectangle resampled to `dst`"""
+    src: torch.Tensor
+    src_offset: int
+    src_shape: tuple             # (h, w, c)
+    rect: tuple                  # (x0, y0, w, h)
+    dst_offset: int
+    dst_shape: tuple             # (h, w, c)
+    method: int
+    frames: int
+
+
+def _refbatch_method(name, what):
+    if name not in REFBATCH_METHODS:
+        raise ValueError(f"{what}: unknown upscale_method {name!r} (one of {', '.join(REFBATCH_METHODS)})")
+    return str(name)
+
+
+def refbatch_table(jobs, out_elems: int):
+    """The host side of one launch, no GPU needed: ``(records, tiles, (f32 base, floats), (u8 base, bytes))``.  The sources of a call
+    are addressed from the lowest address among them, so device-resident pictures are read where they lie; the records are checked by
+    vrg_refbatch_check."""
+    spans = {}
+    for dtype in (torch.float32, torch.uint8):
+        ts = [j.src for j in jobs if j.src.dtype == dtype]
+        lo = min((t.data_ptr() for t in ts), default=0)
+        hi = max((t.data_ptr() + t.numel() * t.element_size() for t in ts), default=0)
+        spans[dtype] = (lo, (hi - lo) // (4 if dtype == torch.float32 else 1))
+    desc = np.zeros(len(jobs), dtype=REFBATCH_DESC)
+    tiles = 0
+    for i, j in enumerate(jobs):
+        lo = spans[j.src.dtype][0]
+        offset = (j.src.data_ptr() - lo) // j.src.element_size() + int(j.src_offset)
+        if tiles > 0x7fffffff:
+            raise RuntimeError("reference batch: more tiles than one launch takes")
+        desc[i] = (offset, int(j.dst_offset), *j.src_shape, *j.rect, *j.dst_shape, int(j.method), int(j.frames), tiles, 0)
+        tiles += int(j.frames) * -(-int(np.prod(j.dst_shape, dtype=np.int64)) // _hip.REFBATCH_TILE)
+    rc = _host_lib().vrg_refbatch_check(C.c_void_p(desc.ctypes.data), len(jobs), spans[torch.float32][1], spans[torch.uint8][1], int(out_elems))
+    if rc == _hip.VRG_ERR_BAD_ARG:
+        raise ValueError("reference batch: vrg_refbatch_check refuses the records (sizes, channel counts, rectangles or overlapping outputs)")
+    if rc != _hip.VRG_OK:
+        raise RuntimeError("reference batch: a picture is larger than one launch takes (2^31 - 1 elements a picture, 65536 source pixels "
+                           "under one area pixel)")
+    return desc, tiles, spans[torch.float32], spans[torch.uint8]
+
+
+def _refbatch_launch(dev, jobs, out: torch.Tensor):
+    """every record of `jobs` into the flat fp32 (or, for quantise records, uint8) buffer `out`: one launch on the current stream"""
+    if not jobs:
+        return
+    desc, tiles, (f_base, f_floats), (b_base, b_bytes) = refbatch_table(jobs, out.numel())
+    table = _upload_records(desc, dev)
+    if out.dtype == torch.uint8:
+        _hip.check(_hip.lib().vrg_refbatch_quantise_u8(C.c_void_p(f_base), f_floats, _hip.ptr(table), len(jobs), tiles, _hip.ptr(out), out.numel(),
+                                                       _hip.current_stream()), "vrg_refbatch_quantise_u8")
+    else:
+        _hip.check(_hip.lib().vrg_refbatch_f32(C.c_void_p(f_base), f_floats, C.c_void_p(b_base), b_bytes, _hip.ptr(table), len(jobs), tiles,
+                                               _hip.ptr(out), out.numel(), _hip.current_stream()), "vrg_refbatch_f32")
+
+
+def _refbatch_pictures(images, what):
+    """the checked pictures of a call on one device: ``(device, [contiguous fp32 [B, H, W, C] tensors])``"""
+    if isinstance(images, torch.Tensor):
+        raise ValueError(f"{what}: images must be a list of IMAGE tensors")
+    images = list(images)
+    for i, t in enumerate(images):
+        if not isinstance(t, torch.Tensor) or t.ndim != 4:
+            raise ValueError(f"{what}: image {i} must be a [batch, height, width, channels] IMAGE tensor")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{what}: image {i} must be fp32")
+        if min(int(v) for v in t.shape[:3]) < 1:
+            raise ValueError(f"{what}: image {i} is empty")
+        if int(t.shape[3]) not in (3, 4):
+            raise ValueError(f"{what}: image {i} has {int(t.shape[3])} channels (3 or 4 are taken)")
+    return _refbatch_place(images, what)
+
+
+def _refbatch_place(images, what):
+    """device tensors as they are, all CPU pictures in ONE upload"""
+    from . import _devices
+    on = [t.device for t in images if t.is_cuda]
+    dev = on[0] if on else _devices.compute_device()
+    if any(d != dev for d in on):
+        raise RuntimeError(f"{what}: the pictures live on two GPUs")
+    pics = [t.detach() for t in images]
+    host = [i for i, t in enumerate(pics) if not t.is_cuda]
+    with torch.cuda.device(dev):
+        if host:
+            packed = torch.cat([pics[i].contiguous().reshape(-1) for i in host]).to(dev)
+            at = 0
+            for i in host:
+                shape, n = pics[i].shape, pics[i].numel()
+                pics[i] = packed[at:at + n].view(shape)
+                at += n
+        pics = [t.contiguous() for t in pics]
+    return dev, pics
+
+
+def _refbatch_out(out, total: int, dev, what):
+    if out is None:
+        return torch.empty(max(total, 1), dtype=torch.float32, device=dev)
+    if (not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.float32 or out.ndim != 1 or not out.is_contiguous()
+            or out.numel() < total):
+        raise ValueError(f"{what}: out must be a contiguous flat fp32 tensor of at least {total} elements on {dev}")
+    return out
+
+
+def _refbatch_lanczos_jobs(dev, items):
+    """comfy's ``lanczos`` for ``items`` = [(fp32 [B, h, w, 3] device picture, rectangle, (out_w, out_h))]: the rectangles quantised to
+    bytes in one launch, ``Image.resize(..., LANCZOS)`` of every frame by vrg_pil_resize_u8 (one call, all sizes), and the
+    VRG_REFBATCH_BYTES jobs (dst_offset left at 0) that turn the result into fp32"""
+    from . import far_face_repair
+    quantise, offsets, sizes, at = [], [], [], 0
+    for t, (x0, y0, rw, rh), (ow, oh) in items:
+        frames, h, w, c = (int(v) for v in t.shape)
+        quantise.append(_RefJob(t, 0, (h, w, c), (x0, y0, rw, rh), at, (rh, rw, c), _hip.REFBATCH_COPY, frames))
+        for f in range(frames):
+            offsets.append(at + f * rh * rw * c)
+            sizes.append((rw, rh, ow, oh))
+        at += frames * rh * rw * c
+    qbuf = torch.empty(max(at, 1), dtype=torch.uint8, device=dev)
+    _refbatch_launch(dev, quantise, qbuf)
+    plan = far_face_repair.ResizePlan(qbuf, offsets, sizes, 3, dev)
+    resized = plan.run()
+    jobs, k = [], 0
+    for t, _, (ow, oh) in items:
+        frames = int(t.shape[0])
+        jobs.append(_RefJob(resized, plan.offsets[k], (oh, ow, 3), (0, 0, ow, oh), 0, (oh, ow, 3), _hip.REFBATCH_BYTES, frames))
+        k += frames
+    return jobs
+
+
+def _lanczos_rgb_only(channels, what):
+    if any(c != 3 for c in channels):
+        raise NotImplementedError(f"{what}: lanczos takes 3-channel pictures only (Pillow's byte Lanczos is restated for RGB); "
+                                  f"got {sorted(set(channels))} channels")
+
+
+def scale_reference_images(images, upscale_method="nearest-exact", megapixels=1.0, resolution_steps=1, out=None) -> list:
+    """``_scale_to_total_pixels`` of the reference for a list of fp32 ``[B, H, W, C]`` pictures (C = 3 or 4; on the GPU, used where they
+    lie, or on the CPU, uploaded together): each is resampled to ``total_pixels_size`` of its own size by
+    ``comfy.utils.common_upscale(..., upscale_method, "disabled")`` -- all channels, not clamped, the filter evaluated even at an equal size
+    -- and all of them by ONE launch.  "lanczos" goes through bytes and Pillow's filter as comfy does and takes 3 channels only.
+    Returns the device tensors, views of one buffer: ``out`` (flat fp32), which they fill back to back from its start, or a new one in
+    which every picture starts on the 16-byte grid.  Inputs are never written."""
+    what = "scale_reference_images"
+    method = _refbatch_method(upscale_method, what)
+    dev, pics = _refbatch_pictures(images, what)
+    if method == "lanczos":
+        _lanczos_rgb_only([int(t.shape[3]) for t in pics], what)
+    sizes = [total_pixels_size(int(t.shape[1]), int(t.shape[2]), megapixels, resolution_steps) for t in pics]
+    offsets, total = [], 0
+    for t, (oh, ow) in zip(pics, sizes):
+        if out is None:
+            total = (total + 3) & ~3
+        offsets.append(total)
+        total += int(t.shape[0]) * oh * ow * int(t.shape[3])
+    with torch.cuda.device(dev):
+        buf = _refbatch_out(out, total, dev, what)
+        if method == "lanczos":
+            jobs = _refbatch_lanczos_jobs(dev, [(t, (0, 0, int(t.shape[2]), int(t.shape[1])), (ow, oh)) for t, (oh, ow) in zip(pics, sizes)])
+            for j, at in zip(jobs, offsets):
+                j.dst_offset = at
+        else:
+            jobs = [_RefJob(t, 0, tuple(int(v) for v in t.shape[1:]), (0, 0, int(t.shape[2]), int(t.shape[1])), at, (oh, ow, int(t.shape[3])),
+                            _REFBATCH_FILTERS[method], int(t.shape[0])) for t, (oh, ow), at in zip(pics, sizes, offsets)]
+        _refbatch_launch(dev, jobs, buf)
+    return [buf[at:at + int(t.shape[0]) * oh * ow * int(t.shape[3])].view(int(t.shape[0]), oh, ow, int(t.shape[3]))
+            for t, (oh, ow), at in zip(pics, sizes, offsets)]
+
+
+def batch_channels(channels) -> int:
+    """The channel count of the reference's batch for pictures of ``channels`` (in order): the base is re-padded with 1.0 whenever a wider
+    picture arrives and narrower ones are padded to it.  A picture that was appended before the base grew keeps its count in the
+    reference, whose ``torch.cat`` then fails; that order is refused here as well."""
+    channels = [int(c) for c in channels]
+    base, appended = channels[0], []
+    for c in channels[1:]:
+        base = max(base, c)
+        appended.append(base)
+    if any(c != base for c in appended):
+        raise ValueError(f"reference batch: pictures of {channels} channels cannot be joined in this order (the reference's torch.cat fails: a "
+                         f"{base}-channel picture follows narrower ones that were already appended)")
+    return base
+
+
+def batch_reference_images(images, upscale_method="bilinear", out=None) -> torch.Tensor:
+    """``_batch_for_image_output`` / ``load_batch`` of the reference: every picture brought to the first one's height, width and (padded)
+    channel count and joined along the batch axis.  Missing channels are 1.0, padded BEFORE the resize; a picture of another size is
+    centre-cropped (``center_crop_rect``) and resampled by ``upscale_method``; one that already fits, the base included, is copied bit for
+    bit.  ONE launch writes the whole ``torch.cat`` result (``out``: an optional contiguous fp32 tensor of its shape).  A single picture
+    is returned as it is.  Inputs are never written."""
+    what = "batch_reference_images"
+    method = _refbatch_method(upscale_method, what)
+    if not isinstance(images, torch.Tensor) and len(images) == 1 and isinstance(images[0], torch.Tensor):
+        return images[0]
+    dev, pics = _refbatch_pictures(images, what)
+    if not pics:
+        raise ValueError(f"{what}: no pictures")
+    height, width = int(pics[0].shape[1]), int(pics[0].shape[2])
+    channels = batch_channels([int(t.shape[3]) for t in pics])
+    fits = [(int(t.shape[1]), int(t.shape[2])) == (height, width) for t in pics]
+    if method == "lanczos" and not all(fits):
+        _lanczos_rgb_only([channels], what)
+    frame = height * width * channels
+    offsets = np.concatenate([[0], np.cumsum([int(t.shape[0]) * frame for t in pics])])
+    shape = (int(sum(int(t.shape[0]) for t in pics)), height, width, channels)
+    if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or not out.is_contiguous()):
+        raise ValueError(f"{what}: out must be a contiguous fp32 {list(shape)} tensor")
+    with torch.cuda.device(dev):
+        buf = _refbatch_out(None if out is None else out.view(-1), int(offsets[-1]), dev, what)
+        jobs, lanczos = [], []
+        for t, fit, at in zip(pics, fits, offsets[:-1]):
+            frames, h, w, c = (int(v) for v in t.shape)
+            rect = (0, 0, w, h) if fit else center_crop_rect(w, h, width, height)
+            if fit:
+                jobs.append(_RefJob(t, 0, (h, w, c), rect, int(at), (height, width, channels), _hip.REFBATCH_COPY, frames))
+            elif method == "lanczos":
+                lanczos.append((t, rect, (width, height), int(at)))
+            else:
+                jobs.append(_RefJob(t, 0, (h, w, c), rect, int(at), (height, width, channels), _REFBATCH_FILTERS[method], frames))
+        if lanczos:
+            for j, item in zip(_refbatch_lanczos_jobs(dev, [i[:3] for i in lanczos]), lanczos):
+                j.dst_offset = item[3]
+                jobs.append(j)
+        _refbatch_launch(dev, jobs, buf)
+    return buf[:int(offsets[-1])].view(shape)
+
+
+def reference_bytes_to_images(pictures) -> list:
+    """``torch.from_numpy(np.asarray(picture).astype(np.float32) / 255.0).unsqueeze(0)`` (the reference's ``_load_image_tensor`` after its
+    decode) for a list of uint8 ``[H, W, 3]`` pictures, arrays or tensors: one upload of the bytes, one launch (VRG_REFBATCH_BYTES), a list
+    of ``[1, H, W, 3]`` fp32 device tensors, each on the 16-byte grid."""
+    what = "reference_bytes_to_images"
+    items = [p if isinstance(p, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(p)) for p in pictures]
+    for i, t in enumerate(items):
+        if t.dtype != torch.uint8 or t.ndim != 3 or int(t.shape[2]) != 3 or min(int(v) for v in t.shape[:2]) < 1:
+            raise ValueError(f"{what}: picture {i} must be uint8 [height, width, 3]")
+    if not items:
+        return []
+    dev, srcs = _refbatch_place(items, what)
+    offsets, total = [], 0
+    for t in items:
+        total = (total + 3) & ~3
+        offsets.append(total)
+        total += t.numel()
+    with torch.cuda.device(dev):
+        buf = torch.empty(total, dtype=torch.float32, device=dev)
+        jobs = [_RefJob(s, 0, tuple(int(v) for v in t.shape), (0, 0, int(t.shape[1]), int(t.shape[0])), at, tuple(int(v) for v in t.shape),
+                        _hip.REFBATCH_BYTES, 1) for s, t, at in zip(srcs, items, offsets)]
+        _refbatch_launch(dev, jobs, buf)
+    return [buf[at:at + t.numel()].view(1, *t.shape) for t, at in zip(items, offsets)]

@@ -1019,6 +1019,55 @@ int vrg_flf_guide_f32(const float* first, const float* last, const float* weight
                       int32_t channels, int32_t last_h, int32_t last_w, int32_t src_x0, int32_t src_y0, int32_t src_w, int32_t src_h,
                       void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Multi-reference image batches (VRGDG_MultiReferenceConditioning, VRGDG_MultiReferenceConditioningFromPaths and
+ * VRGDG_ImageBatchMultiFromPaths, VRGDG_GeneralNodes2.py:3801-4145 of the reference), csrc/vrg_refbatch.hip and
+ * csrc/vrg_refbatch_math.hpp: many pictures of unrelated sizes and channel counts, each resampled as
+ * comfy.utils.common_upscale(picture.movedim(-1, 1), dst_w, dst_h, method, crop) resamples it -- F.interpolate over the rectangle
+ * (src_x0, src_y0, src_rw, src_rh) of the channels-last view, taps clamped to the rectangle, EVERY channel, the result NOT clamped --
+ * into its own place of one output buffer, all in ONE launch.  A record is one output picture, or a run of `frames` pictures of one
+ * geometry: source frame f starts at src_offset + f * src_h * src_w * src_c, output frame f at dst_offset + f * dst_h * dst_w * dst_c.
+ * Channels src_c .. dst_c - 1 are the reference's F.pad(value=1.0) before the resize: a plane of 1.0f through the same filter.
+ * VRG_REFBATCH_COPY moves the rectangle unfiltered, bit for bit (dst_h x dst_w is the rectangle's size); VRG_REFBATCH_BYTES does the same
+ * from bytes, out = (float)byte / 255.0f correctly rounded.  The filters are evaluated even where source and target sizes agree.
+ * Workgroups map to (record, frame, tile of VRG_REFBATCH_TILE floats) through first_tile, the running sum of
+ * frames * ceil(dst_h * dst_w * dst_c / VRG_REFBATCH_TILE) over the earlier records, which the caller fills in; `tiles` is the sum over
+ * all records.  Every float of every output picture is written exactly once and none is read; pictures that start on the 16-byte grid
+ * take 16-byte stores, the others 4-byte stores; sources are never written.  src_f32, out: device fp32, 4-byte aligned; src_u8: device
+ * bytes, any alignment; either source may be null when no record reads it.  `desc` of the launch is device memory.
+ * vrg_refbatch_check refuses ON THE HOST what the launch refuses: VRG_ERR_BAD_ARG for sizes below 1, negative offsets or frames, channel
+ * counts other than 3 or 4 (or dst_c < src_c), a rectangle outside its picture, an unknown method, a copy whose sizes differ, a span
+ * outside its buffer, a first_tile that is not the running sum, and outputs that overlap; VRG_ERR_UNSUPPORTED for pictures of more than
+ * 2^31 - 1 elements, more than 2^31 - 1 tiles, and an area window of more than 65536 source pixels under one output pixel.  The kernel
+ * follows no record that breaks these rules or leaves the buffers; it cannot see an overlap.  Zero records succeed without a launch.
+ * vrg_refbatch_quantise_u8 is the fp32 -> byte step of comfy's lanczos (np.clip(255. * x, 0, 255).astype(np.uint8): the product in fp32,
+ * truncated; NaN, which numpy leaves undefined, becomes 0) for a table of VRG_REFBATCH_COPY records with dst_c == src_c, one launch:
+ * dst_offset and `dst_bytes` count bytes there.  The bytes are then resampled by vrg_pil_resize_u8.
+ * ------------------------------------------------------------------------------------------- */
+#define VRG_REFBATCH_TILE 1024
+typedef enum vrg_refbatch_method {
+    VRG_REFBATCH_BICUBIC = 0, VRG_REFBATCH_BILINEAR = 1, VRG_REFBATCH_AREA = 2, VRG_REFBATCH_NEAREST_EXACT = 3,
+    VRG_REFBATCH_COPY = 4, VRG_REFBATCH_BYTES = 5
+} vrg_refbatch_method;
+
+typedef struct vrg_refbatch_desc {
+    int64_t src_offset;                        /* first element of the first source frame: floats of src_f32, bytes of src_u8 */
+    int64_t dst_offset;                        /* first element of the first output frame */
+    int32_t src_h, src_w, src_c;               /* a source frame: [src_h][src_w][src_c] */
+    int32_t src_x0, src_y0, src_rw, src_rh;    /* the rectangle of it that is resampled */
+    int32_t dst_h, dst_w, dst_c;               /* an output frame: [dst_h][dst_w][dst_c] */
+    int32_t method;                            /* vrg_refbatch_method */
+    int32_t frames;
+    int32_t first_tile;
+    int32_t reserved;
+} vrg_refbatch_desc;
+
+int vrg_refbatch_check(const vrg_refbatch_desc* desc_host, int64_t n, int64_t src_floats, int64_t src_bytes, int64_t out_elems);
+int vrg_refbatch_f32(const float* src_f32, int64_t src_floats, const uint8_t* src_u8, int64_t src_bytes, const vrg_refbatch_desc* desc,
+                     int64_t n, int64_t tiles, float* out, int64_t out_floats, void* stream);
+int vrg_refbatch_quantise_u8(const float* src_f32, int64_t src_floats, const vrg_refbatch_desc* desc, int64_t n, int64_t tiles,
+                             uint8_t* dst, int64_t dst_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
