@@ -88,7 +88,7 @@ __device__ __forceinline__ void apply_march_body(uint32_t vblock, uint32_t vgrid
         AmRow r;
         const float xi[3] = {v.r, v.g, v.b};
         float o[3];
-        chain_apply_stages<STAGES>(D, FC, xi, n0, o, PT);
+        chain_apply_stages<STAGES, !GENERAL>(D, FC, xi, n0, o, PT);      // !GENERAL: the NaN patches of the row's clamps stay behind their scalar branch (clamp01_3)
         r.c[0] = o[0]; r.c[1] = o[1]; r.c[2] = o[2];                              // replicate border = the clamped coordinate's own value
         if (zero) {
             // zero border (the reference's use_gpu flag): pixels outside the frame count as 0.  A wave-uniform branch that the optimiser must
@@ -112,7 +112,7 @@ __device__ __forceinline__ void apply_march_body(uint32_t vblock, uint32_t vgrid
             const float p[3][3][3] = {{{a.l[0], a.c[0], a.r[0]}, {b.l[0], b.c[0], b.r[0]}, {c.l[0], c.c[0], c.r[0]}},
                                       {{a.l[1], a.c[1], a.r[1]}, {b.l[1], b.c[1], b.r[1]}, {c.l[1], c.c[1], c.r[1]}},
                                       {{a.l[2], a.c[2], a.r[2]}, {b.l[2], b.c[2], b.r[2]}, {c.l[2], c.c[2], c.r[2]}}};
-            stencil_value3_unit(D.stencil_op, p, D.strength, D.zero_border, res);
+            stencil_value3_unit<!GENERAL>(D.stencil_op, p, D.strength, D.zero_border, res);
         } else {
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) {

@@ -45,7 +45,8 @@ __device__ __forceinline__ FrameCtx frame_ctx(const ChainK& D, int64_t f) {
 }
 
 // grain (with the pixel's three raw normals n) -> LUT -> colour match for a pixel of the frame described by C
-template <int STAGES, class MATH>
+// KEEP_BRANCH: clamp01_3's, for the colour match from a stored Lab image (the apply march)
+template <int STAGES, bool KEEP_BRANCH = false, class MATH>
 __device__ __forceinline__ void chain_apply_stages(const ChainK& D, const FrameCtx& C, const float xin[3], const float n[3], float o[3],
                                                    const MATH& PT, const f32x4* lut_nodes = nullptr) {
     float v[3] = {xin[0], xin[1], xin[2]};
@@ -63,7 +64,7 @@ __device__ __forceinline__ void chain_apply_stages(const ChainK& D, const FrameC
     if (STAGES & VRG_STAGE_COLORMATCH) {
         float g[3];
         if (STAGES & VRG_STAGE_FROM_LAB)
-            colormatch_from_lab(v, C.ims, C.rms, D.cm.K, D.cm.T, g, PT, &C.sr);     // the input pixel is already Lab
+            colormatch_from_lab<KEEP_BRANCH>(v, C.ims, C.rms, D.cm.K, D.cm.T, g, PT, &C.sr);     // the input pixel is already Lab
         else
             colormatch_pixel(v, C.ims, C.rms, D.cm.K, D.cm.T, g, PT, &C.sr);
         v[0] = g[0]; v[1] = g[1]; v[2] = g[2];

@@ -61,12 +61,19 @@ VRG_HD float clamp01(float v) {
 // clamp01 of a pixel's three values.  The NaN pass-through costs a compare and a select per value; a NaN in any of the three makes their
 // SUM a NaN (so does +Inf next to -Inf), so one comparison of the sum and a wave-uniform branch decide for the pixel: v_med3_f32 alone
 // when no lane of the wave holds a NaN (every frame of a video), clamp01 otherwise.  Same values for every input.
+// KEEP_BRANCH: the optimiser finds the rare side cheap enough to speculate and flattens the branch into selects -- per pixel three more
+// v_cmp_u_f32, three VCC selects, three selects on the ballot and their wait states run in EVERY wave, ~55 issue units beside the ~9 of the
+// test itself (profiles/r07_isa_cost_*_finite.txt).  An empty volatile asm on the rare side cannot be speculated and keeps the branch a
+// scalar one (s_cbranch on the ballot, no exec mask): the finite wave runs the three clamps and the test, nothing else.  Opt-in per
+// caller (pass 2 of the headline, the apply march without conditional blocks); the default is the code every other kernel had.
+template <bool KEEP_BRANCH = false>
 VRG_HD void clamp01_3(const float v[3], float o[3]) {
 #if defined(__HIP_DEVICE_COMPILE__)
     const float s = (v[0] + v[1]) + v[2];
     const float a = v[0], b = v[1], c = v[2];
     float x = __builtin_amdgcn_fmed3f(a, 0.0f, 1.0f), y = __builtin_amdgcn_fmed3f(b, 0.0f, 1.0f), z = __builtin_amdgcn_fmed3f(c, 0.0f, 1.0f);
     if (__builtin_amdgcn_ballot_w64(s != s) != 0) {      // the rare side patches the three results in place: no copies where the sides meet
+        if (KEEP_BRANCH) asm volatile("; vrg_rare: NaN patch of clamp01_3");      // (a comment: tools/isa_cost.py finds the block by it)
         x = (a != a) ? a : x;
         y = (b != b) ? b : y;
         z = (c != c) ? c : z;
@@ -269,7 +276,7 @@ VRG_HD void grain_pixel(const float x[3], const float n[3], float I, float S, fl
 VRG_HD void grain_pixel_nan_branch(const float x[3], const float n[3], float I, float S, float T, float o[3]) {
     const float r[3] = {grain_element_raw(x[0], n[0], n[1], 0, I, S, T), grain_element_raw(x[1], n[1], n[1], 1, I, S, T),
                         grain_element_raw(x[2], n[2], n[1], 2, I, S, T)};
-    clamp01_3(r, o);
+    clamp01_3(r, o);         // (the kept branch was measured here too: pass 1 -0.5 .. -0.8 %, inside the spread -- LABNOTES 000.1; not taken)
 }
 
 // ------------------------------------------------------------------------------------------
@@ -540,12 +547,13 @@ VRG_HD uint8_t sharpen_grain_byte(const float p[3][3], float strength, int zero_
 
 // The three channels of a pixel whose taps are in [0, 1] or NaN (the colour transfer's output): the same values with the three clamps behind
 // one NaN test (clamp01_3) and the unsharp mean without its Inf pass-through
+template <bool KEEP_BRANCH = false>
 VRG_HD void stencil_value3_unit(int op, const float p[3][3][3], float strength, int zero_border, float o[3]) {
     float raw[3];
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch)
         raw[ch] = op == 0 ? unsharp_raw<true>(p[ch], strength) : (op == 1 ? laplacian_raw(p[ch], strength, zero_border) : sobel_raw(p[ch], strength, zero_border));
-    clamp01_3(raw, o);
+    clamp01_3<KEEP_BRANCH>(raw, o);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1219,7 +1227,8 @@ VRG_HD float lab_finv(float f, const MATH& T) {
     return f > 0.2068966f ? cube : sc;
 }
 
-template <class MATH>
+// KEEP_BRANCH: clamp01_3's (the apply march asks for it; every other caller keeps the default)
+template <bool KEEP_BRANCH = false, class MATH>
 VRG_HD void lab_to_rgb(const float lab[3], float rgb[3], const MATH& T) {
     const float l16 = lab[0] + 16.0f;
     const float fy = VRG_CM_DIVS(l16, 116.0, T);
@@ -1237,7 +1246,7 @@ VRG_HD void lab_to_rgb(const float lab[3], float rgb[3], const MATH& T) {
     const float lin[3] = {lr, lg, lb};
     float s3[3];
     linear_to_srgb3(lin, s3, T);
-    clamp01_3(s3, rgb);
+    clamp01_3<KEEP_BRANCH>(s3, rgb);
 }
 
 // matched = (lab-mu)/sigma*sigma_ref + mu_ref ; blended = K*matched + T*lab (nodes.py:112-113)
@@ -1332,7 +1341,7 @@ VRG_HD void cm_normalise3(const float lab[3], const float* img_ms, float z[3], c
 
 // ms: {mean, std+1e-5} per channel.  Lab of the pixel -> matched, blended, back to RGB.
 // SR: the frame's SigmaRecip (device policy only), or nullptr: every quotient by the division
-template <class MATH>
+template <bool KEEP_BRANCH = false, class MATH>
 VRG_HD void colormatch_from_lab(const float lab[3], const float* img_ms, const float* ref_ms, float K, float T, float o[3],
                                 const MATH& PT, const SigmaRecip* SR = nullptr) {
     float z[3], bl[3];
@@ -1345,7 +1354,7 @@ VRG_HD void colormatch_from_lab(const float lab[3], const float* img_ms, const f
         const float b = T * lab[c];
         bl[c] = a + b;
     }
-    lab_to_rgb(bl, o, PT);
+    lab_to_rgb<KEEP_BRANCH>(bl, o, PT);
     // final .clamp(0,1) of nodes.py:121 is idempotent after lab_to_rgb's clip
 }
 

@@ -23,6 +23,8 @@ ap.add_argument("--label", default="", help="price the lines from this label to 
                 "blocks that are skipped at run time (the powers' transcriptions) are counted as if executed: an upper bound")
 ap.add_argument("--exclude-after", default="", help="with --label: comma-separated substrings; a line range s_cbranch_execz X .. X: that holds one of them in any line is left out "
                 "(0x3e76c4e1 = a coefficient of ocml's epln: the transcriptions of powf; v_div_fmas_f32: the IEEE divisions behind the unscaled / FMA forms)")
+ap.add_argument("--exclude-marked", default="", help="with --label: leave out every BASIC BLOCK (label or branch .. next label or branch) that holds an asm comment line "
+                "starting with this word, e.g. vrg_rare: the NaN patch of clamp01_3<true>, a block behind a scalar branch that a finite wave skips")
 ap.add_argument("extra", nargs="*")
 a, unknown = ap.parse_known_args()
 extra = list(a.extra) + unknown
@@ -53,7 +55,11 @@ for m in re.finditer(r"^(_Z\w+):[^\n]*\n(.*?)s_endpgm", text, flags=re.S | re.M)
 if body is None:
     raise SystemExit(f"kernel {a.kernel!r} not found")
 lines = []
+MARK = "#marked"
 for l in body.split("\n"):
+    if a.exclude_marked and l.strip().startswith("; " + a.exclude_marked):
+        lines.append(MARK)
+        continue
     l = l.split(";")[0].split("//")[0].rstrip()
     if not l.strip() or l.strip().startswith("."):
         if re.match(r"^\.LBB\w+:", l.strip()):
@@ -103,7 +109,16 @@ if a.label:
                 out.append(seq[k]); k += 1
             return out
         body = strip(body)
-    ops = [l for l in body if not l.endswith(":")]
+    if a.exclude_marked:
+        edge = [k for k, l in enumerate(body) if l.endswith(":") or re.match(r"s_c?branch", l)]
+        drop = set()
+        for k in (k for k, l in enumerate(body) if l == MARK):
+            lo = max([e for e in edge if e < k], default=-1) + 1
+            hi = min([e for e in edge if e > k], default=len(body))
+            drop.update(range(lo, hi + (1 if hi < len(body) and body[hi].startswith("s_branch") else 0)))
+        print(f"# --exclude-marked {a.exclude_marked}: {sum(1 for l in body if l == MARK)} blocks, {len(drop)} lines left out")
+        body = [l for k, l in enumerate(body) if k not in drop]
+    ops = [l for l in body if not l.endswith(":") and l != MARK]
 else:
     i, j = inner[a.loop]
     ops = [l for l in lines[i:j + 1] if not l.endswith(":")]
