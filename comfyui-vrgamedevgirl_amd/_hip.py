@@ -181,6 +181,12 @@ class RefbatchDesc(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class AssembleDesc(C.Structure):
+    """vrg_assemble_desc"""
+    _fields_ = [("src", C.c_void_p * 16), ("overlay", C.c_void_p * 16), ("frames", C.c_int32 * 16), ("height", C.c_int32 * 16),
+                ("width", C.c_int32 * 16), ("channels", C.c_int32 * 16), ("n_src", C.c_int32), ("bytes", C.c_int32)]
+
+
 GRID_COPY, GRID_FAST, GRID_FAST_2X2, GRID_GENERAL, GRID_LINEAR = 0, 1, 2, 3, 4
 THUMB_SIDE = 320                # include/vrgdg_hip.h: VRG_THUMB_SIDE
 THUMB_MAX_SIDE = 32767          # include/vrgdg_hip.h: VRG_THUMB_MAX_SIDE
@@ -192,6 +198,8 @@ PIL_FILTER_LANCZOS, PIL_FILTER_BICUBIC = 1, 3      # include/vrgdg_hip.h: VRG_PI
 FLF_CHUNK = 32                  # frames one workgroup writes (csrc/vrg_flf_math.hpp: FLF_CHUNK)
 REFBATCH_TILE = 1024            # include/vrgdg_hip.h: VRG_REFBATCH_TILE
 REFBATCH_BICUBIC, REFBATCH_BILINEAR, REFBATCH_AREA, REFBATCH_NEAREST_EXACT, REFBATCH_COPY, REFBATCH_BYTES = 0, 1, 2, 3, 4, 5
+ASSEMBLE_MAX_SOURCES = 16       # include/vrgdg_hip.h: VRG_ASSEMBLE_MAX_SOURCES
+ASSEMBLE_BAR = 60               # include/vrgdg_hip.h: VRG_ASSEMBLE_BAR (rows of the label bar)
 FACEFIX_STATS_WORDS = 12        # uint64 per frame (csrc/vrg_facefix_math.hpp: FF_STATS_WORDS)
 
 _F3 = C.c_float * 3
@@ -312,6 +320,9 @@ _SIGNATURES = {
     "vrg_refbatch_check": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "vrg_refbatch_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int64, _P, C.c_int64, _P]),
     "vrg_refbatch_quantise_u8": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int64, _P, C.c_int64, _P]),
+    "vrg_assemble_check": (C.c_int, [C.POINTER(AssembleDesc), _P, C.c_int64, _P, _P, C.c_int32]),
+    "vrg_assemble_f32": (C.c_int, [C.POINTER(AssembleDesc), _P, C.c_int64, _P, _P]),
+    "vrg_assemble_labelled_u8": (C.c_int, [C.POINTER(AssembleDesc), _P, C.c_int64, _P, _P, _P]),
 }
 
 # include/vrgdg_hip_debug.h: self-tests and probes -- for the test suite and the measurement tools, not part of the drop-in boundary

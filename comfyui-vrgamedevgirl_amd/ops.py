@@ -3594,3 +3594,233 @@ def reference_bytes_to_images(pictures) -> list:
                         _hip.REFBATCH_BYTES, 1) for s, t, at in zip(srcs, items, offsets)]
         _refbatch_launch(dev, jobs, buf)
     return [buf[at:at + t.numel()].view(1, *t.shape) for t, at in zip(items, offsets)]
+
+
+# ---------------------------------------------------------------------------------------------
+# Music-video assembly (VRGDG_CombinevideosV2 / V3, HumoAutomation.py:50-133 and :892-1030; VRGDG_CombinevideosV5,
+# HumoAutomationExtra2.py:309-498; VRGDG_PadVideoWithLastFrame, GeneralVideoNodes.py:1945-1987; VRGDG_LoadVideos, nodes.py:1327-1377 of the
+# reference): which frame of which clip becomes which output frame is planned on the host, the frames are moved by ONE launch of
+# csrc/vrg_assemble.hip -- and V5's labelled MP4 bytes come out of the same read
+# ---------------------------------------------------------------------------------------------
+ASSEMBLE_SLOTS = _hip.ASSEMBLE_MAX_SOURCES       # video_1 .. video_16
+ASSEMBLE_BAR = _hip.ASSEMBLE_BAR                 # rows of V5's label bar
+ASSEMBLE_MODES = ("v2", "v3", "v5", "pad", "load")
+ASSEMBLE_ENTRY = np.dtype([("source", "<i4"), ("frame", "<i4")])                     # vrg_assemble_entry
+
+
+def _assemble_shape(entry):
+    return None if entry is None else ((int(entry), 0, 0, 0) if isinstance(entry, (int, np.integer)) else tuple(int(v) for v in entry))
+
+
+def assemble_plan(mode, shapes, fps=25.0, audio_meta=None, index=0, total_sets=1, groups_in_last_set=16, pad_frames=1, pad_front=False) -> list:
+    """The host side of the assembly nodes, no GPU needed: the ``(source, frame)`` pair of every output frame, in order.  ``shapes`` holds
+    one entry per input slot (``video_1`` first) -- a shape tuple, a frame count, or None for a slot that is not connected -- and
+    ``source`` is the slot's index in it.  The reference's integer arithmetic, expression for expression:
+
+    ``"v2"``: durations padded with 0.0 or cut to 16; a clip's target is ``max(1, int(round(dur * float(fps))))`` for ``dur > 0`` (a value
+    ``float()`` refuses counts as 0) and its own length otherwise; longer clips are trimmed, shorter ones repeat their last frame.
+    ``"v3"`` / ``"v5"``: ``durations_frames`` before ``durations``; ``max(1, int(round(value)))`` or ``max(1, int(round(fps * value)))``
+    (Python's ``round``: half to even, on the double); missing durations are 0.0, a target of 1; on the last run
+    (``index == total_sets - 1``) only slots up to ``max(1, min(groups_in_last_set, 16))`` are looked at and a slot above
+    ``groups_in_last_set`` is skipped; clips are trimmed, never padded.  The plan may be empty (the reference's ``torch.cat`` then fails).
+    ``"pad"``: one clip; ``pad_frames`` copies of frame 0 in front (``pad_front``) or of the last frame behind it; ``pad_frames <= 0`` or an
+    empty clip: the clip as it is.  ``"load"``: the clips one after another.
+    The reference's errors and their texts are kept: no videos, ``ndim != 4``, ``audio_meta`` that is no dict, no durations."""
+    if mode not in ASSEMBLE_MODES:
+        raise ValueError(f"assemble_plan: unknown mode {mode!r} (one of {', '.join(ASSEMBLE_MODES)})")
+    shapes = [_assemble_shape(s) for s in shapes]
+    if mode == "load":
+        return [(i, f) for i, s in enumerate(shapes) if s is not None for f in range(s[0])]
+    if mode == "pad":
+        frames = shapes[0][0]
+        body = [(0, f) for f in range(frames)]
+        if frames == 0 or pad_frames <= 0:
+            return body
+        pad = [(0, 0 if pad_front else frames - 1)] * int(pad_frames)
+        return pad + body if pad_front else body + pad
+    if len(shapes) > ASSEMBLE_SLOTS:
+        raise ValueError(f"assemble_plan: {len(shapes)} slots ({ASSEMBLE_SLOTS} at the most)")
+    if mode == "v2":
+        if isinstance(audio_meta, dict) and isinstance(audio_meta.get("durations"), (list, tuple)):
+            durations = (list(audio_meta["durations"]) + [0.0] * ASSEMBLE_SLOTS)[:ASSEMBLE_SLOTS]
+        else:
+            durations = [0.0] * ASSEMBLE_SLOTS
+        vids = [(i + 1, s) for i, s in enumerate(shapes) if s is not None]
+        if len(vids) < 1:
+            raise ValueError("Provide at least one videos (e.g., video_1).")
+        plan = []
+        for slot, shape in vids:
+            if len(shape) != 4:
+                raise ValueError(f"video_{slot} must have shape (frames,H,W,C), got {shape}")
+            cur = shape[0]
+            try:
+                dur = float(durations[slot - 1])
+            except Exception:
+                dur = 0.0
+            tgt = max(1, int(round(dur * float(fps)))) if dur > 0.0 else int(cur)
+            plan += [(slot - 1, f) for f in range(min(cur, tgt))]
+            if 0 < cur < tgt:
+                plan += [(slot - 1, cur - 1)] * (tgt - cur)
+        return plan
+    tag = "[CombineV3]" if mode == "v3" else "[CombineV5]"
+    last_run = index == total_sets - 1
+    if not isinstance(audio_meta, dict):
+        raise ValueError(f"{tag} audio_meta must be a dict")
+    if audio_meta.get("durations_frames") is not None:
+        durations, is_frames = list(audio_meta["durations_frames"]), True
+    elif audio_meta.get("durations") is not None:
+        durations, is_frames = list(audio_meta["durations"]), False
+    else:
+        raise ValueError("[CombineV3] audio_meta missing 'durations' or 'durations_frames' list" if mode == "v3"
+                         else "[CombineV5] audio_meta missing durations info")
+    durations = (durations + [0.0] * ASSEMBLE_SLOTS)[:ASSEMBLE_SLOTS]
+    limit = max(1, min(groups_in_last_set, ASSEMBLE_SLOTS)) if last_run else ASSEMBLE_SLOTS
+    vids = [(i + 1, s) for i, s in enumerate(shapes[:limit]) if s is not None]
+    if not vids:
+        raise ValueError("[CombineV3] No video inputs detected. Connect at least one video_x input." if mode == "v3"
+                         else "[CombineV5] No video inputs detected.")
+    plan = []
+    for slot, shape in vids:
+        if mode == "v3" and len(shape) != 4:
+            raise ValueError(f"video_{slot} must have shape (frames,H,W,C), got {shape}")
+        value = float(durations[slot - 1])
+        tgt = max(1, int(round(value))) if is_frames else max(1, int(round(fps * value)))
+        if last_run and slot > groups_in_last_set:
+            continue
+        if len(shape) != 4:
+            raise ValueError(f"Expected (frames,H,W,C), got {shape}")
+        plan += [(slot - 1, f) for f in range(min(shape[0], tgt))]
+    return plan
+
+
+@dataclass
+class _Assembly:
+    """one launch, ready: the descriptor, the device table and what keeps their memory alive"""
+    device: torch.device
+    desc: "_hip.AssembleDesc"
+    table: torch.Tensor
+    frames: int
+    shape: tuple                 # (height, width, channels)
+    host_fed: bool               # every clip came from the CPU: the results go to the intermediate device
+    rows: np.ndarray             # the table on the host
+    keep: list
+
+
+def _assemble_prepare(videos, plan, overlays, what) -> _Assembly:
+    from . import _devices
+    if isinstance(videos, torch.Tensor):
+        videos = [videos]
+    videos = list(videos)
+    entries = np.asarray(plan, dtype=np.int64).reshape(-1, 2)
+    used = sorted(set(int(s) for s in entries[:, 0]))
+    if not len(entries):
+        raise ValueError(f"{what}: the plan is empty")
+    if len(used) > ASSEMBLE_SLOTS:
+        raise ValueError(f"{what}: the plan names {len(used)} clips ({ASSEMBLE_SLOTS} at the most)")
+    for s in used:
+        if s < 0 or s >= len(videos) or not isinstance(videos[s], torch.Tensor) or videos[s].ndim != 4:
+            raise ValueError(f"{what}: the plan names clip {s}, which is no [frames, height, width, channels] tensor")
+    clips = {s: videos[s].detach() for s in used}
+    kinds = {t.dtype == torch.uint8 for t in clips.values()}
+    if len(kinds) > 1:
+        raise ValueError(f"{what}: uint8 and float clips cannot be joined")
+    is_bytes = kinds.pop()
+    if not is_bytes and any(not t.dtype.is_floating_point for t in clips.values()):
+        raise ValueError(f"{what}: clips must be float (IMAGE) or uint8 R,G,B tensors")
+    shape = tuple(int(v) for v in clips[used[0]].shape[1:])
+    for s, t in clips.items():
+        if tuple(int(v) for v in t.shape[1:]) != shape:
+            raise ValueError(f"{what}: clip {s} is {tuple(t.shape[1:])}, clip {used[0]} is {shape}: height, width and channels must agree")
+        lo, hi = int(entries[entries[:, 0] == s, 1].min()), int(entries[entries[:, 0] == s, 1].max())
+        if lo < 0 or hi >= int(t.shape[0]):
+            raise ValueError(f"{what}: the plan names frames {lo} .. {hi} of clip {s}, which has {int(t.shape[0])}")
+    on = [t.device for t in clips.values() if t.is_cuda]
+    dev = on[0] if on else _devices.compute_device()
+    if any(d != dev for d in on):
+        raise RuntimeError(f"{what}: the clips live on two GPUs")
+    desc, keep, rows = _hip.AssembleDesc(), [], np.zeros(len(entries), dtype=ASSEMBLE_ENTRY)
+    desc.n_src, desc.bytes = len(used), int(is_bytes)
+    with torch.cuda.device(dev):
+        for k, s in enumerate(used):
+            t, mine = clips[s], entries[:, 0] == s
+            first = 0
+            if not t.is_cuda:                                      # only the frames the plan keeps cross PCIe
+                first, last = int(entries[mine, 1].min()), int(entries[mine, 1].max())
+                t = t[first:last + 1].to(dev)
+            if not is_bytes and t.dtype != torch.float32:
+                t = t.to(torch.float32)
+            t = t.contiguous()
+            keep.append(t)
+            rows["source"][mine], rows["frame"][mine] = k, entries[mine, 1] - first
+            desc.src[k], desc.frames[k] = t.data_ptr(), int(t.shape[0])
+            desc.height[k], desc.width[k], desc.channels[k] = shape
+            if overlays is not None and s < len(overlays) and overlays[s] is not None:
+                o = overlays[s] if isinstance(overlays[s], torch.Tensor) else torch.from_numpy(np.ascontiguousarray(overlays[s]))
+                if o.dtype != torch.uint8 or tuple(o.shape) != (ASSEMBLE_BAR, shape[1], 3):
+                    raise ValueError(f"{what}: overlay {s} must be uint8 [{ASSEMBLE_BAR}, {shape[1]}, 3] (B,G,R)")
+                o = o.detach().to(dev).contiguous()
+                keep.append(o)
+                desc.overlay[k] = o.data_ptr()
+        table = _upload_records(rows, dev)
+    return _Assembly(dev, desc, table, len(entries), shape, not on, rows, keep)
+
+
+def _assemble_out(out, shape, dtype, dev, what, name):
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    if (not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != dtype or tuple(out.shape) != tuple(shape)
+            or not out.is_contiguous()):
+        raise ValueError(f"{what}: {name} must be a contiguous {str(dtype).replace('torch.', '')} {list(shape)} tensor on {dev}")
+    return out
+
+
+def _assemble_check(a: _Assembly, out_f32, out_u8, labelled, what):
+    rc = _host_lib().vrg_assemble_check(C.byref(a.desc), C.c_void_p(a.rows.ctypes.data), a.frames, None if out_f32 is None else _hip.ptr(out_f32),
+                                        None if out_u8 is None else _hip.ptr(out_u8), int(labelled))
+    if rc == _hip.VRG_ERR_BAD_ARG:
+        raise ValueError(f"{what}: vrg_assemble_check refuses the call (clip shapes, channels, or an output that overlaps a clip)")
+    if rc != _hip.VRG_OK:
+        raise RuntimeError(f"{what}: a frame of {a.shape} is larger than one launch takes (2^31 - 1 elements)")
+
+
+def assemble_frames(videos, plan, out=None) -> torch.Tensor:
+    """``torch.cat`` of the trimmed and padded clips of the reference's assembly nodes as ONE launch: output frame ``i`` is frame
+    ``plan[i][1]`` of ``videos[plan[i][0]]`` (``ops.assemble_plan``).  ``videos``: up to 16 named clips ``[F, H, W, C]`` of one frame
+    shape; float clips are copied bit for bit (fp32; other float types are widened by torch first), uint8 R,G,B clips become
+    ``byte / 255`` in fp32.  Clips on the GPU are read where they lie and the batch stays there; of CPU clips only the frames the plan keeps
+    are uploaded, and when every clip came from the CPU the batch is returned on the intermediate device.  ``out``: an optional
+    contiguous fp32 ``[N, H, W, C]`` device tensor that overlaps no clip.  Inputs are never written."""
+    from . import _devices
+    what = "assemble_frames"
+    a = _assemble_prepare(videos, plan, None, what)
+    with torch.cuda.device(a.device):
+        dst = _assemble_out(out, (a.frames, *a.shape), torch.float32, a.device, what, "out")
+        _assemble_check(a, dst, None, False, what)
+        _hip.check(_hip.lib().vrg_assemble_f32(C.byref(a.desc), _hip.ptr(a.table), a.frames, _hip.ptr(dst), _hip.current_stream()),
+                   "vrg_assemble_f32")
+    return dst.to(_devices.intermediate_device()) if a.host_fed and out is None else dst
+
+
+def assemble_labelled_bytes(videos, plan, overlays=None, clean_out=None):
+    """What ``VRGDG_CombinevideosV5`` hands its MP4 writer, ``[N, H + 60, W, 3]`` uint8 in B,G,R, for the frames of ``plan``: per value
+    ``q1 = trunc(x * 255)``, ``q2 = trunc((q1 / 255) * 255)`` in fp32 with both roundings kept, under every frame a 60-row bar that is black
+    or holds ``overlays[source]`` (uint8 ``[60, W, 3]`` B,G,R: the label pixels, made on the host).  Equal to the reference for finite
+    ``0 <= x * 255 < 256``; outside that range bytes saturate to 0 / 255 and NaN gives 0.  ``clean_out``: True, or a contiguous fp32
+    ``[N, H, W, 3]`` device tensor, to get ``assemble_frames``' batch from the same read of the clips.  Returns ``(bytes, clean or None)``;
+    device and upload rules as for ``assemble_frames``."""
+    from . import _devices
+    what = "assemble_labelled_bytes"
+    a = _assemble_prepare(videos, plan, overlays, what)
+    if a.shape[2] != 3:
+        raise ValueError(f"{what}: labelled output takes 3-channel clips, got {a.shape[2]}")
+    with torch.cuda.device(a.device):
+        given = isinstance(clean_out, torch.Tensor)
+        clean = _assemble_out(clean_out if given else None, (a.frames, *a.shape), torch.float32, a.device, what, "clean_out") if given or clean_out else None
+        data = torch.empty((a.frames, a.shape[0] + ASSEMBLE_BAR, a.shape[1], 3), dtype=torch.uint8, device=a.device)
+        _assemble_check(a, clean, data, True, what)
+        _hip.check(_hip.lib().vrg_assemble_labelled_u8(C.byref(a.desc), _hip.ptr(a.table), a.frames, None if clean is None else _hip.ptr(clean),
+                                                       _hip.ptr(data), _hip.current_stream()), "vrg_assemble_labelled_u8")
+    if a.host_fed:
+        to = _devices.intermediate_device()
+        return data.to(to), (clean if clean is None or given else clean.to(to))
+    return data, clean

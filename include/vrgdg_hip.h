@@ -1068,6 +1068,47 @@ int vrg_refbatch_f32(const float* src_f32, int64_t src_floats, const uint8_t* sr
 int vrg_refbatch_quantise_u8(const float* src_f32, int64_t src_floats, const vrg_refbatch_desc* desc, int64_t n, int64_t tiles,
                              uint8_t* dst, int64_t dst_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Music-video assembly (VRGDG_CombinevideosV2 / V3, HumoAutomation.py:50-133 and :892-1030; VRGDG_CombinevideosV5,
+ * HumoAutomationExtra2.py:309-498; VRGDG_PadVideoWithLastFrame, GeneralVideoNodes.py:1945-1987; VRGDG_LoadVideos, nodes.py:1327-1377 of
+ * the reference), csrc/vrg_assemble.hip and csrc/vrg_assemble_math.hpp: up to VRG_ASSEMBLE_MAX_SOURCES clips of one frame shape,
+ * trimmed, padded and joined into one batch by ONE launch.  `map` holds one (source, frame) entry per output frame: output frame f is
+ * frame map[f].frame of clip map[f].source.  The clips' base pointers travel by value in the descriptor; `map` of a launch is device
+ * memory, 4-byte aligned.
+ * vrg_assemble_f32: out = [n_out][height][width][channels] fp32.  fp32 clips (bytes == 0) are copied bit for bit: NaN payloads, +-Inf,
+ * -0.0 and subnormals pass.  uint8 R,G,B clips (bytes == 1, any alignment) give (float)byte / 255.0f correctly rounded.
+ * vrg_assemble_labelled_u8 (channels == 3): out_u8 = [n_out][height + VRG_ASSEMBLE_BAR][width][3] bytes in B,G,R -- what the reference
+ * hands its MP4 writer for the labelled copy: per value q1 = trunc(x * 255f), f = (float)q1 / 255f, q2 = trunc(f * 255f), q2 stored, both
+ * roundings kept; the bar rows are 0, or byte by byte q2 of the clip's overlay[source] = [VRG_ASSEMBLE_BAR][width][3] bytes B,G,R in
+ * device memory (null: a black bar).  Parity with the reference is claimed for finite x with 0 <= x * 255 < 256; outside that range the
+ * bytes saturate to 0 / 255 and NaN gives 0.  out_f32, where not null, receives the batch vrg_assemble_f32 writes, from the same read.
+ * Two routes, the same bits: 16-byte loads and stores when every base pointer and the frame size in bytes are multiples of 16, 4-byte
+ * (bytes: 1-byte) ones otherwise.  Every element of the outputs is written exactly once and none is read; sources are never written.
+ * vrg_assemble_check refuses ON THE HOST what the launches refuse (map_host, where not null, is checked too): VRG_ERR_BAD_ARG for no
+ * or more than 16 clips, clips whose height, width or channels differ or are below 1, a map entry outside its clip, outputs that
+ * overlap a clip, an overlay or each other, a labelled call with channels != 3, fp32 pointers off the 4-byte grid;
+ * VRG_ERR_UNSUPPORTED for frames of more than 2^31 - 1 elements (frames are addressed with 64 bits).  The kernels follow no entry that
+ * leaves its clip.  Zero output frames succeed without a launch.
+ * ------------------------------------------------------------------------------------------- */
+#define VRG_ASSEMBLE_MAX_SOURCES 16
+#define VRG_ASSEMBLE_BAR 60
+typedef struct vrg_assemble_desc {
+    const void* src[VRG_ASSEMBLE_MAX_SOURCES];          /* [frames][height][width][channels], fp32 or bytes, device memory */
+    const uint8_t* overlay[VRG_ASSEMBLE_MAX_SOURCES];   /* labelled launches: the bar of this clip's frames, or null */
+    int32_t frames[VRG_ASSEMBLE_MAX_SOURCES];
+    int32_t height[VRG_ASSEMBLE_MAX_SOURCES], width[VRG_ASSEMBLE_MAX_SOURCES], channels[VRG_ASSEMBLE_MAX_SOURCES];
+    int32_t n_src;
+    int32_t bytes;                                      /* 0: fp32 clips; 1: uint8 R,G,B clips */
+} vrg_assemble_desc;
+
+typedef struct vrg_assemble_entry { int32_t source, frame; } vrg_assemble_entry;
+
+int vrg_assemble_check(const vrg_assemble_desc* desc, const vrg_assemble_entry* map_host, int64_t n_out, const float* out_f32,
+                       const uint8_t* out_u8, int32_t labelled);
+int vrg_assemble_f32(const vrg_assemble_desc* desc, const vrg_assemble_entry* map, int64_t n_out, float* out, void* stream);
+int vrg_assemble_labelled_u8(const vrg_assemble_desc* desc, const vrg_assemble_entry* map, int64_t n_out, float* out_f32, uint8_t* out_u8,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif
