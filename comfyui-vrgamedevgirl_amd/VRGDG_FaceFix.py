@@ -25,7 +25,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _hip
+from . import _hip, ops
 from ._devices import compute_device
 
 NODE_CLASS_MAPPINGS = {}
@@ -33,16 +33,14 @@ NODE_DISPLAY_NAME_MAPPINGS = {}
 
 DEFAULT_FEATHER = 18
 DEFAULT_COLOR_MATCH = 0.65
-_TAP = np.dtype([("s", "<i4"), ("w", "<i2", (8,))])
-_BOX_DESC = np.dtype([("frame", "<i4"), ("left", "<i4"), ("top", "<i4"), ("box_w", "<i4"), ("box_h", "<i4"), ("reserved", "<i4"),
-                      ("taps_offset", "<i8")])
-_MASK_DESC = np.dtype([("width", "<i4"), ("height", "<i4"), ("span_offset", "<i8"), ("mask_offset", "<i8")])
-_FF_DESC = np.dtype([("enhanced_index", "<i4"), ("left", "<i4"), ("top", "<i4"), ("box_w", "<i4"), ("box_h", "<i4"), ("strength", "<f4"),
-                     ("mask_offset", "<i8"), ("taps_offset", "<i8"), ("bytes_offset", "<i8")])
-assert _BOX_DESC.itemsize == C.sizeof(_hip.FaceFixBoxDesc) and _MASK_DESC.itemsize == C.sizeof(_hip.FaceFixMaskDesc)
-assert _FF_DESC.itemsize == C.sizeof(_hip.FaceFixDesc)
+_TAP = _hip.record_dtype(_hip.LzTap)
+_BOX_DESC = _hip.record_dtype(_hip.FaceFixBoxDesc)
+_MASK_DESC = _hip.record_dtype(_hip.FaceFixMaskDesc)
+_FF_DESC = _hip.record_dtype(_hip.FaceFixDesc)
 
 _host = _hip.host_library       # the library for its HOST table functions (no GPU needed); far_face_repair imports the name
+_lanczos_taps = ops.lanczos4_taps
+_upload = _hip.upload_records   # records and the byte / int32 tables that go with them; far_face_repair imports the name
 
 
 # ------------------------------------------------------------------------------------------------
@@ -96,12 +94,6 @@ def gauss_coeffs(feather: int) -> np.ndarray:
     coeffs = np.zeros(gauss_taps(feather), dtype=np.float32)
     _hip.check(_host().vrg_ff_gauss_coeffs(feather, C.c_void_p(coeffs.ctypes.data)), "vrg_ff_gauss_coeffs")
     return coeffs
-
-
-def _lanczos_taps(in_h, in_w, out_h, out_w) -> np.ndarray:
-    table = np.zeros(out_w + out_h, dtype=_TAP)
-    _hip.check(_host().vrg_lanczos4_taps(in_h, in_w, out_h, out_w, C.c_void_p(table.ctypes.data)), "vrg_lanczos4_taps")
-    return table
 
 
 # ------------------------------------------------------------------------------------------------
@@ -167,10 +159,6 @@ def _boxes(crop_boxes, frames, height, width):
             raise ValueError(f"crop box of frame {index} does not lie inside the {width} x {height} frame")
         out.append((left, top, w, h))
     return out
-
-
-def _upload(array: np.ndarray, device) -> torch.Tensor:
-    return torch.from_numpy(np.ascontiguousarray(array).view(np.uint8).reshape(-1).copy()).to(device)
 
 
 def _tap_tables(sizes, in_size_of, out_size_of):

@@ -8,8 +8,12 @@ it is opened the first time a test or a tool asks the handle for one of its name
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
 import threading
+
+import numpy as np
+import torch
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VRGDG_HIP_LIB") or os.path.join(PKG_DIR, "libvrgdg_hip.so")   # override: A/B builds (tools/build_variant.py, tools/ab_interleaved.py)
@@ -30,15 +34,21 @@ COMPOSITE_STATS_WORDS = 16
 ABI_VERSION = 8
 
 
-class NoiseDesc(C.Structure):
-    """vrg_noise_desc"""
+class Record(C.Structure):
+    """A record the host fills for a kernel: each subclass is the ONLY Python declaration of the struct `c_name` of `c_header` (a path from
+    the repository's root).  The numpy layouts derive from it (record_dtype); tests/test_abi.py compiles the header and compares them."""
+    c_name, c_header = None, "include/vrgdg_hip.h"
+
+
+class NoiseDesc(Record):
+    c_name = "vrg_noise_desc"
     _fields_ = [("seed0", C.c_uint64), ("seed_stride", C.c_uint64), ("offset0", C.c_uint64),
                 ("offset_stride", C.c_uint64), ("chunk0", C.c_int64), ("chunk_frames", C.c_int32),
                 ("grid_threads", C.c_uint32)]
 
 
-class ChainDesc(C.Structure):
-    """vrg_chain_desc"""
+class ChainDesc(Record):
+    c_name = "vrg_chain_desc"
     _fields_ = [("stages", C.c_int32), ("variant", C.c_int32),
                 ("intensity", C.c_float), ("sat", C.c_float), ("one_minus_sat", C.c_float),
                 ("noise", NoiseDesc),
@@ -51,8 +61,8 @@ class ChainDesc(C.Structure):
                 ("cm_math", C.c_int32)]
 
 
-class AdjustDesc(C.Structure):
-    """vrg_adjust_desc"""
+class AdjustDesc(Record):
+    c_name = "vrg_adjust_desc"
     _fields_ = [("enabled", C.c_int32), ("shift", C.c_float * 3), ("exposure", C.c_float),
                 ("contrast", C.c_float), ("saturation", C.c_float),
                 ("highlights", C.c_float), ("shadows", C.c_float), ("whites", C.c_float), ("blacks", C.c_float),
@@ -63,8 +73,8 @@ class AdjustDesc(C.Structure):
                 ("div_mode", C.c_int32)]
 
 
-class CompositeDesc(C.Structure):
-    """vrg_composite_desc"""
+class CompositeDesc(Record):
+    c_name = "vrg_composite_desc"
     _fields_ = [("rule", C.c_int32), ("flags", C.c_int32),
                 ("original_index", C.c_int32), ("crop_index", C.c_int32), ("mask_index", C.c_int32),
                 ("left", C.c_int32), ("top", C.c_int32), ("box_w", C.c_int32), ("box_h", C.c_int32),
@@ -72,14 +82,14 @@ class CompositeDesc(C.Structure):
                 ("match_strength", C.c_float), ("threshold", C.c_float), ("p", C.c_float * 7)]
 
 
-class CropDesc(C.Structure):
-    """vrg_crop_desc"""
+class CropDesc(Record):
+    c_name = "vrg_crop_desc"
     _fields_ = [("src_offset", C.c_int64), ("row_pitch", C.c_int32), ("pixel_stride", C.c_int32),
                 ("box_w", C.c_int32), ("box_h", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
-class WarpDesc(C.Structure):
-    """vrg_warp_desc"""
+class WarpDesc(Record):
+    c_name = "vrg_warp_desc"
     _fields_ = [("m", C.c_double * 6), ("src_offset", C.c_int64), ("src_w", C.c_int32), ("src_h", C.c_int32),
                 ("set", C.c_int32), ("reserved", C.c_int32)]
 
@@ -87,55 +97,55 @@ class WarpDesc(C.Structure):
 WARP_TABLE_BYTES = 1024 * 64 * 2
 
 
-class FaceFixBoxDesc(C.Structure):
-    """vrg_ff_box_desc"""
+class FaceFixBoxDesc(Record):
+    c_name = "vrg_ff_box_desc"
     _fields_ = [("frame", C.c_int32), ("left", C.c_int32), ("top", C.c_int32), ("box_w", C.c_int32), ("box_h", C.c_int32),
                 ("reserved", C.c_int32), ("taps_offset", C.c_int64)]
 
 
-class FaceFixMaskDesc(C.Structure):
-    """vrg_ff_mask_desc"""
+class FaceFixMaskDesc(Record):
+    c_name = "vrg_ff_mask_desc"
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("span_offset", C.c_int64), ("mask_offset", C.c_int64)]
 
 
-class FaceFixDesc(C.Structure):
-    """vrg_ff_desc"""
+class FaceFixDesc(Record):
+    c_name = "vrg_ff_desc"
     _fields_ = [("enhanced_index", C.c_int32), ("left", C.c_int32), ("top", C.c_int32), ("box_w", C.c_int32), ("box_h", C.c_int32),
                 ("strength", C.c_float), ("mask_offset", C.c_int64), ("taps_offset", C.c_int64), ("bytes_offset", C.c_int64)]
 
 
-class DetectDesc(C.Structure):
-    """vrg_detect_desc"""
+class DetectDesc(Record):
+    c_name = "vrg_detect_desc"
     _fields_ = [("frame", C.c_int32), ("transform", C.c_int32), ("left", C.c_int32), ("top", C.c_int32), ("right", C.c_int32),
                 ("bottom", C.c_int32)]
 
 
-class DetectFrameDesc(C.Structure):
-    """vrg_detect_frame_desc"""
+class DetectFrameDesc(Record):
+    c_name = "vrg_detect_frame_desc"
     _fields_ = [("frame", C.c_int32), ("transform", C.c_int32)]
 
 
-class PilResizeDesc(C.Structure):
-    """vrg_pil_resize_desc"""
+class PilResizeDesc(Record):
+    c_name = "vrg_pil_resize_desc"
     _fields_ = [("src_offset", C.c_int64), ("dst_offset", C.c_int64), ("tmp_offset", C.c_int64), ("h_table", C.c_int64), ("v_table", C.c_int64),
                 ("in_w", C.c_int32), ("in_h", C.c_int32), ("out_w", C.c_int32), ("out_h", C.c_int32), ("h_ksize", C.c_int32),
                 ("v_ksize", C.c_int32)]
 
 
-class PilMaskDesc(C.Structure):
-    """vrg_pil_mask_desc"""
+class PilMaskDesc(Record):
+    c_name = "vrg_pil_mask_desc"
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("radius", C.c_int32), ("ww", C.c_uint32), ("fw", C.c_uint32),
                 ("reserved", C.c_int32), ("span_offset", C.c_int64), ("mask_offset", C.c_int64)]
 
 
-class PilBoxDesc(C.Structure):
-    """vrg_pil_box_desc"""
+class PilBoxDesc(Record):
+    c_name = "vrg_pil_box_desc"
     _fields_ = [("left", C.c_int32), ("top", C.c_int32), ("box_w", C.c_int32), ("box_h", C.c_int32), ("color_match", C.c_int32),
                 ("reserved", C.c_int32), ("mask_offset", C.c_int64), ("rep_offset", C.c_int64)]
 
 
-class GridDesc(C.Structure):
-    """vrg_grid_desc"""
+class GridDesc(Record):
+    c_name = "vrg_grid_desc"
     _fields_ = [("src", C.c_void_p), ("xtab", C.c_void_p), ("ytab", C.c_void_p), ("overlay", C.c_void_p),
                 ("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32), ("mode", C.c_int32),
                 ("frame", C.c_int32), ("dst_x", C.c_int32), ("dst_y", C.c_int32),
@@ -143,14 +153,14 @@ class GridDesc(C.Structure):
                 ("band", C.c_int32), ("cps", C.c_int32), ("inv", C.c_float)]
 
 
-class ThumbDesc(C.Structure):
-    """vrg_thumb_desc"""
+class ThumbDesc(Record):
+    c_name = "vrg_thumb_desc"
     _fields_ = [("xtab", C.c_void_p), ("ytab", C.c_void_p), ("offset", C.c_int64), ("which", C.c_int32),
                 ("box_w", C.c_int32), ("box_h", C.c_int32), ("mode", C.c_int32), ("cps", C.c_int32), ("inv", C.c_float)]
 
 
-class SheetPanel(C.Structure):
-    """vrg_sheet_panel"""
+class SheetPanel(Record):
+    c_name = "vrg_sheet_panel"
     _fields_ = [("src", C.c_void_p), ("h_table", C.c_int64), ("v_table", C.c_int64), ("span_offset", C.c_int64), ("tmp_offset", C.c_int64),
                 ("src_h", C.c_int32), ("src_w", C.c_int32), ("channels", C.c_int32), ("new_w", C.c_int32), ("new_h", C.c_int32),
                 ("h_ksize", C.c_int32), ("v_ksize", C.c_int32), ("win_x", C.c_int32), ("win_y", C.c_int32), ("pic_w", C.c_int32),
@@ -159,32 +169,64 @@ class SheetPanel(C.Structure):
                 ("reserved", C.c_int32)]
 
 
-class MsrDesc(C.Structure):
-    """vrg_msr_desc"""
+class MsrDesc(Record):
+    c_name = "vrg_msr_desc"
     _fields_ = [("src", C.c_void_p), ("in_h", C.c_int32), ("in_w", C.c_int32), ("taps", C.c_int32), ("first_frame", C.c_int32),
                 ("repeats", C.c_int32), ("fill", C.c_uint8 * 4)]
 
 
-class ThumbEntry(C.Structure):
-    """vrg_thumb_entry"""
+class ThumbEntry(Record):
+    c_name = "vrg_thumb_entry"
     _fields_ = [("left_offset", C.c_int64), ("right_offset", C.c_int64), ("tmp_offset", C.c_int64), ("h_table", C.c_int64), ("v_table", C.c_int64),
                 ("left_w", C.c_int32), ("left_h", C.c_int32), ("right_w", C.c_int32), ("right_h", C.c_int32), ("fx", C.c_int32), ("fy", C.c_int32),
                 ("red_w", C.c_int32), ("red_h", C.c_int32), ("out_w", C.c_int32), ("out_h", C.c_int32), ("h_ksize", C.c_int32),
                 ("v_ksize", C.c_int32), ("dst_x", C.c_int32), ("dst_y", C.c_int32), ("cps", C.c_int32), ("reserved", C.c_int32)]
 
 
-class RefbatchDesc(C.Structure):
-    """vrg_refbatch_desc"""
+class RefbatchDesc(Record):
+    c_name = "vrg_refbatch_desc"
     _fields_ = [("src_offset", C.c_int64), ("dst_offset", C.c_int64), ("src_h", C.c_int32), ("src_w", C.c_int32), ("src_c", C.c_int32),
                 ("src_x0", C.c_int32), ("src_y0", C.c_int32), ("src_rw", C.c_int32), ("src_rh", C.c_int32), ("dst_h", C.c_int32),
                 ("dst_w", C.c_int32), ("dst_c", C.c_int32), ("method", C.c_int32), ("frames", C.c_int32), ("first_tile", C.c_int32),
                 ("reserved", C.c_int32)]
 
 
-class AssembleDesc(C.Structure):
-    """vrg_assemble_desc"""
+class AssembleDesc(Record):
+    c_name = "vrg_assemble_desc"
     _fields_ = [("src", C.c_void_p * 16), ("overlay", C.c_void_p * 16), ("frames", C.c_int32 * 16), ("height", C.c_int32 * 16),
                 ("width", C.c_int32 * 16), ("channels", C.c_int32 * 16), ("n_src", C.c_int32), ("bytes", C.c_int32)]
+
+
+class AssembleEntry(Record):
+    c_name = "vrg_assemble_entry"
+    _fields_ = [("source", C.c_int32), ("frame", C.c_int32)]
+
+
+class AreaCell(Record):          # one cell of the tables of vrg_area_taps / vrg_grid_taps / vrg_linear_taps
+    c_name, c_header = "vrg::AreaCell", "comfyui-vrgamedevgirl_amd/csrc/vrg_area_math.hpp"
+    _fields_ = [("first", C.c_int32), ("count", C.c_int32), ("w_first", C.c_float), ("w_mid", C.c_float), ("w_last", C.c_float)]
+
+
+class LzTap(Record):             # one record of the table of vrg_lanczos4_taps
+    c_name, c_header = "vrg::LzTap", "comfyui-vrgamedevgirl_amd/csrc/vrg_lanczos_math.hpp"
+    _fields_ = [("s", C.c_int32), ("w", C.c_int16 * 8)]
+
+
+record_dtype = functools.lru_cache(maxsize=None)(np.dtype)      # record_dtype(Record): its structured dtype, the fields at their offsets
+
+
+def upload_records(records, device, count=None, trailing=(), out=None):
+    """The one way records reach a kernel: the first `count` (default all) of `records` -- a structured numpy array or a ctypes array of
+    a Record -- then the arrays of `trailing` (side tables that ride in the same upload), as one flat uint8 tensor on `device`, or in the
+    preallocated device tensor `out` of that size.  A synchronous copy from pageable memory: the host arrays are free once it returns."""
+    if isinstance(records, np.ndarray):
+        host = np.ascontiguousarray(records).reshape(-1)[:count].view(np.uint8)
+    else:
+        host = np.frombuffer(records, np.uint8, -1 if count is None else count * C.sizeof(records._type_))
+    if trailing or not host.flags.writeable:        # (torch takes no read-only array)
+        host = np.concatenate([host, *[np.ascontiguousarray(t).reshape(-1).view(np.uint8) for t in trailing]])
+    host = torch.from_numpy(host)
+    return host.to(device) if out is None else out.copy_(host)
 
 
 GRID_COPY, GRID_FAST, GRID_FAST_2X2, GRID_GENERAL, GRID_LINEAR = 0, 1, 2, 3, 4

@@ -42,16 +42,10 @@ MAX_FEATHER = 4096
 
 FaceBox = namedtuple("FaceBox", "x y w h score")
 
-_RESIZE_DESC = np.dtype([("src_offset", "<i8"), ("dst_offset", "<i8"), ("tmp_offset", "<i8"), ("h_table", "<i8"), ("v_table", "<i8"),
-                         ("in_w", "<i4"), ("in_h", "<i4"), ("out_w", "<i4"), ("out_h", "<i4"), ("h_ksize", "<i4"), ("v_ksize", "<i4")])
-_MASK_DESC = np.dtype([("width", "<i4"), ("height", "<i4"), ("radius", "<i4"), ("ww", "<u4"), ("fw", "<u4"), ("reserved", "<i4"),
-                       ("span_offset", "<i8"), ("mask_offset", "<i8")])
-_BOX_DESC = np.dtype([("left", "<i4"), ("top", "<i4"), ("box_w", "<i4"), ("box_h", "<i4"), ("color_match", "<i4"), ("reserved", "<i4"),
-                      ("mask_offset", "<i8"), ("rep_offset", "<i8")])
-assert _RESIZE_DESC.itemsize == C.sizeof(_hip.PilResizeDesc) and _MASK_DESC.itemsize == C.sizeof(_hip.PilMaskDesc)
-assert _BOX_DESC.itemsize == C.sizeof(_hip.PilBoxDesc)
-_THUMB_ENTRY = np.dtype([(name, "<i8" if ctype is C.c_int64 else "<i4") for name, ctype in _hip.ThumbEntry._fields_])
-assert _THUMB_ENTRY.itemsize == C.sizeof(_hip.ThumbEntry)
+_RESIZE_DESC = _hip.record_dtype(_hip.PilResizeDesc)
+_MASK_DESC = _hip.record_dtype(_hip.PilMaskDesc)
+_BOX_DESC = _hip.record_dtype(_hip.PilBoxDesc)
+_THUMB_ENTRY = _hip.record_dtype(_hip.ThumbEntry)
 
 SHEET_CANVAS = (24, 24, 24)
 NO_FRAMES = "No frames were available for the contact sheet."

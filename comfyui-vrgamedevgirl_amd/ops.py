@@ -388,7 +388,7 @@ def _sharpen_then_seeded_grain_u8(frames_bgr, sharpen_strength, zero_border, gra
 # The stand-alone enhancer's upscale (cv2.resize(..., INTER_LANCZOS4) on decoded bytes, reference
 # VRGDG_StandaloneVideoEnhancerNodes.py:213-230) and the upscale fused into sharpen -> grain
 # ---------------------------------------------------------------------------------------------
-LANCZOS_TAP_BYTES = 20          # one record of the table: int32 s, eight int16 weights (csrc/vrg_lanczos_math.hpp: LzTap)
+LANCZOS_TAP_BYTES = C.sizeof(_hip.LzTap)          # one record of the table: int32 s, eight int16 weights
 _host_lib = _hip.host_library   # the library for its HOST table functions (no GPU needed)
 
 
@@ -419,11 +419,11 @@ _lanczos_tables: dict = {}      # (in_h, in_w, out_h, out_w, device) -> the uplo
 
 
 def _uploaded(cache: dict, key, build, device) -> torch.Tensor:
-    """``cache[key]``: on a miss the byte table of ``build()`` (a numpy array), uploaded to ``device``.  A cache that holds 64 tables is
+    """``cache[key]``: on a miss the table of ``build()`` (a numpy array of records), uploaded to ``device`` as bytes.  A cache that holds 64 tables is
     cleared first: a handful of geometries per job; never grows without bound."""
     t = cache.get(key)
     if t is None:
-        t = torch.from_numpy(build()).to(device)
+        t = _hip.upload_records(build(), device)
         with _upload_lock:
             if len(cache) >= 64:
                 cache.clear()
@@ -437,15 +437,13 @@ def lanczos4_taps(in_h: int, in_w: int, out_h: int, out_w: int) -> np.ndarray:
     in_h, in_w, out_h, out_w = int(in_h), int(in_w), int(out_h), int(out_w)
     if min(in_h, in_w, out_h, out_w) < 1:
         raise ValueError("lanczos4_taps: sizes must be at least 1")
-    table = np.zeros(out_w + out_h, dtype=np.dtype([("s", "<i4"), ("w", "<i2", (8,))]))
-    assert table.dtype.itemsize == LANCZOS_TAP_BYTES
+    table = np.zeros(out_w + out_h, dtype=_hip.record_dtype(_hip.LzTap))
     _hip.check(_host_lib().vrg_lanczos4_taps(in_h, in_w, out_h, out_w, C.c_void_p(table.ctypes.data)), "vrg_lanczos4_taps")
     return table
 
 
 def _lanczos_table(in_h, in_w, out_h, out_w, device) -> torch.Tensor:
-    return _uploaded(_lanczos_tables, (in_h, in_w, out_h, out_w, str(device)),
-                     lambda: lanczos4_taps(in_h, in_w, out_h, out_w).view(np.uint8).copy(), device)
+    return _uploaded(_lanczos_tables, (in_h, in_w, out_h, out_w, str(device)), lambda: lanczos4_taps(in_h, in_w, out_h, out_w), device)
 
 
 def _lanczos_sizes(x, out_w, out_h):
@@ -975,8 +973,7 @@ def _composite_prepare(originals, crops, entries, rule, color_match, user_mask):
         if d.flags & _hip.COMPOSITE_USER_MASK and not 0 <= d.mask_index < n_mask:
             raise ValueError(f"entry {f} names frame {d.mask_index} of a user mask of {n_mask}")
     # one upload: the records, then the list of frames to measure
-    raw = bytes(memoryview(table))[:frames * C.sizeof(_hip.CompositeDesc)] + np.asarray(match, dtype=np.int32).tobytes()
-    dev_table = torch.frombuffer(bytearray(raw) or bytearray(4), dtype=torch.uint8).to(o.device)
+    dev_table = _hip.upload_records(table, o.device, frames, [np.asarray(match if frames else [0], dtype=np.int32)])  # never empty
     geom = (frames, int(o.shape[0]), int(c.shape[0]), n_mask, int(c.shape[1]), int(c.shape[2]), int(c.shape[3]), int(o.shape[1]),
             int(o.shape[2]), int(o.shape[3]), mask_h, mask_w, mask_stride, nc)
     stats = torch.zeros((max(frames, 1), _hip.COMPOSITE_STATS_WORDS), dtype=torch.int32, device=o.device)
@@ -1169,8 +1166,7 @@ def face_bytes(crops: torch.Tensor, entries, height: int, width: int, originals:
     source = torch.zeros_like(generated) if o is not None else None
     if frames == 0 or total == 0:
         return FaceBytes(generated, source, offsets, sizes)
-    raw = bytes(memoryview(table))[:frames * C.sizeof(_hip.CompositeDesc)] + np.asarray(offsets, dtype=np.int64).tobytes()
-    dev_table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(c.device)
+    dev_table = _hip.upload_records(table, c.device, frames, [np.asarray(offsets, dtype=np.int64)])
     offsets_ptr = C.c_void_p(dev_table.data_ptr() + frames * C.sizeof(_hip.CompositeDesc))
     _hip.check(_hip.lib().vrg_face_bytes_u8(_hip.ptr(c), _hip.ptr(o) if o is not None else None, _hip.ptr(dev_table), offsets_ptr,
                                            _hip.ptr(generated), _hip.ptr(source) if source is not None else None, total, max_pixels,
@@ -1181,9 +1177,7 @@ def face_bytes(crops: torch.Tensor, entries, height: int, width: int, originals:
 
 
 THUMB_SIDE = _hip.THUMB_SIDE    # the landmark network's input is 320 x 320
-THUMB_DESC = np.dtype([("xtab", "<u8"), ("ytab", "<u8"), ("offset", "<i8"), ("which", "<i4"), ("box_w", "<i4"), ("box_h", "<i4"),
-                       ("mode", "<i4"), ("cps", "<i4"), ("inv", "<f4")])                         # vrg_thumb_desc
-assert THUMB_DESC.itemsize == C.sizeof(_hip.ThumbDesc) == 48
+THUMB_DESC = _hip.record_dtype(_hip.ThumbDesc)
 _THUMB_WHICH = {"generated": 0, "source": 1}
 
 
@@ -1253,7 +1247,7 @@ def _face_thumbs(faces, names, source):
     n_bytes = int(g.numel())
     lib = _hip.lib()
     _hip.check(lib.vrg_face_thumbs_check(C.c_void_p(desc.ctypes.data), len(desc), n_bytes, int(src is not None)), "vrg_face_thumbs_check")
-    records.copy_(torch.from_numpy(np.concatenate([desc.view(np.uint8), tables])))
+    _hip.upload_records(desc, g.device, trailing=[tables], out=records)
     _hip.check(lib.vrg_face_thumbs_u8(_hip.ptr(g), _hip.ptr(src) if src is not None else None, n_bytes, _hip.ptr(records), len(desc),
                                       _hip.ptr(out), _hip.current_stream()), "vrg_face_thumbs_u8")
     return out, index
@@ -1275,7 +1269,7 @@ def warp_affine_u8(frames_u8: torch.Tensor, transforms, out_w: int, out_h: int) 
     out = torch.empty((F, out_h, out_w, 3), dtype=torch.uint8, device=x.device)
     if F == 0:
         return out
-    rec = torch.frombuffer(bytearray(bytes(memoryview(table))[:F * C.sizeof(_hip.WarpDesc)]), dtype=torch.uint8).to(x.device)
+    rec = _hip.upload_records(table, x.device, F)
     _hip.check(_hip.lib().vrg_warp_affine_u8(_hip.ptr(x), x.numel(), _hip.ptr(out), _hip.ptr(rec), _hip.ptr(_warp_table(x.device)), F,
                                             out_h, out_w, _hip.current_stream()), "vrg_warp_affine_u8")
     return out
@@ -1318,7 +1312,7 @@ def aligned_composite_frames(originals: torch.Tensor, crops: torch.Tensor, entri
         mask_out = torch.empty(shape[:3], dtype=torch.float32, device=o.device)
     if out.data_ptr() in (o.data_ptr(), c.data_ptr()):
         raise ValueError("out must not be an input")
-    rec = torch.frombuffer(bytearray(bytes(memoryview(records))[:frames * C.sizeof(_hip.WarpDesc)]), dtype=torch.uint8).to(o.device)
+    rec = _hip.upload_records(records, o.device, frames)
     g = generated.generated
     _hip.check(_hip.lib().vrg_composite_warp_apply_f32(_hip.ptr(c), _hip.ptr(o), None, _hip.ptr(dev_table), _hip.ptr(stats), _hip.ptr(rec),
                                                       _hip.ptr(g), g.numel(), _hip.ptr(_warp_table(o.device)), _hip.ptr(out),
@@ -1331,9 +1325,7 @@ def aligned_composite_frames(originals: torch.Tensor, crops: torch.Tensor, entri
 # ------------------------------------------------------------------------------------------------
 
 CROP_SIZE = (512, 512)           # the reference's F.interpolate(size=(512, 512))
-_CROP_DESC = np.dtype([("src_offset", "<i8"), ("row_pitch", "<i4"), ("pixel_stride", "<i4"), ("box_w", "<i4"), ("box_h", "<i4"),
-                       ("reserved", "<i4", (2,))])
-assert _CROP_DESC.itemsize == C.sizeof(_hip.CropDesc)
+_CROP_DESC = _hip.record_dtype(_hip.CropDesc)
 
 
 @dataclass(frozen=True)
@@ -1440,7 +1432,7 @@ def crop_resize(source: torch.Tensor, records, size=CROP_SIZE, out: Optional[tor
         return out
     if out.data_ptr() == source.data_ptr():
         raise ValueError("out must not be the source")
-    dev_table = torch.from_numpy(table.view(np.uint8)).to(source.device)
+    dev_table = _hip.upload_records(table, source.device)
     _hip.check(_hip.lib().vrg_crop_resize_f32(_hip.ptr(source), source.numel(), _hip.ptr(out), _hip.ptr(dev_table), len(records), size_h, size_w,
                                              _hip.current_stream()), "vrg_crop_resize_f32")
     return out
@@ -1524,7 +1516,7 @@ def crop_host_bytes(plan: CropPlan) -> int:
 # INTER_AREA thumbnails of the quantised frames, their hue / saturation histograms, four integers per consecutive pair
 # ------------------------------------------------------------------------------------------------
 CUT_THUMB = 64                  # the thumbnail is 64 x 64 x 3 bytes
-AREA_CELL = np.dtype([("first", "<i4"), ("count", "<i4"), ("w_first", "<f4"), ("w_mid", "<f4"), ("w_last", "<f4")])      # csrc/vrg_area_math.hpp: AreaCell
+AREA_CELL = _hip.record_dtype(_hip.AreaCell)
 _area_tables: dict = {}         # (height, width, device) -> the uploaded table
 
 
@@ -1551,7 +1543,7 @@ def area_taps(in_h: int, in_w: int) -> np.ndarray:
 
 
 def _area_table(in_h, in_w, device) -> torch.Tensor:
-    return _uploaded(_area_tables, (in_h, in_w, str(device)), lambda: area_taps(in_h, in_w).view(np.uint8).copy(), device)
+    return _uploaded(_area_tables, (in_h, in_w, str(device)), lambda: area_taps(in_h, in_w), device)
 
 
 @_on_device
@@ -1632,9 +1624,7 @@ def cut_pair_sums(thumbs: torch.Tensor, hist: Optional[torch.Tensor] = None) -> 
 # ------------------------------------------------------------------------------------------------
 GRID_MODES = ("copy", "fast", "fast 2x2", "general", "linear")          # include/vrgdg_hip.h, enum vrg_grid_mode
 GRID_ROW_VALUES = 4096          # source values one wave stages at a time (csrc/vrg_grid_math.hpp): the most one column's taps may cover
-GRID_DESC = np.dtype([("src", "<u8"), ("xtab", "<u8"), ("ytab", "<u8"), ("overlay", "<u8"), ("height", "<i4"), ("width", "<i4"),
-                      ("channels", "<i4"), ("mode", "<i4"), ("frame", "<i4"), ("dst_x", "<i4"), ("dst_y", "<i4"), ("new_w", "<i4"),
-                      ("new_h", "<i4"), ("x_off", "<i4"), ("y_off", "<i4"), ("band", "<i4"), ("cps", "<i4"), ("inv", "<f4")])      # vrg_grid_desc
+GRID_DESC = _hip.record_dtype(_hip.GridDesc)
 _grid_tables: dict = {}         # (n_in, n_out, mode, device) -> the uploaded table of one axis; at most 256, the oldest leaves first
 _grid_lock = threading.Lock()
 
@@ -1721,7 +1711,7 @@ def _grid_table(n_in, n_out, mode, table, device) -> torch.Tensor:
     key = (n_in, n_out, mode, str(device))
     t = _grid_tables.get(key)
     if t is None:
-        t = torch.from_numpy(table.view(np.uint8).copy()).to(device)
+        t = _hip.upload_records(table, device)
         with _grid_lock:
             while len(_grid_tables) >= 256:
                 _grid_tables.pop(next(iter(_grid_tables)))
@@ -1788,7 +1778,7 @@ def _grid_launch(plan: GridPlan, out: torch.Tensor, jobs, dev_overlays, has_over
     lib = _hip.lib()
     geometry = (frames, plan.cell_w, plan.cell_h, plan.grid_w, plan.grid_h)
     _hip.check(lib.vrg_grid_check(C.c_void_p(desc.ctypes.data), len(desc), int(byte_sources), *geometry), "vrg_grid_check")
-    dev_desc = torch.from_numpy(desc.view(np.uint8)).to(out.device)
+    dev_desc = _hip.upload_records(desc, out.device)
     entry = lib.vrg_grid_tiles_u8 if byte_sources else lib.vrg_grid_tiles_f32
     _hip.check(entry(_hip.ptr(dev_desc), len(desc), _hip.ptr(out), *geometry, _hip.current_stream()),
                "vrg_grid_tiles_u8" if byte_sources else "vrg_grid_tiles_f32")
@@ -1899,9 +1889,7 @@ def video_grid_bytes(batches, index, cell_w: int, cell_h: int, columns: int, ban
 DETECT_BLOB = 300               # the network's input is 300 x 300
 DETECT_MIN_SIDE = 8             # a region with a smaller side is refused (the Builder skips those)
 DETECT_MAX_SIDE = 32767         # positions of the warp are int16
-DETECT_DESC = np.dtype([("frame", "<i4"), ("transform", "<i4"), ("left", "<i4"), ("top", "<i4"), ("right", "<i4"), ("bottom", "<i4")])
-DETECT_FRAME_DESC = np.dtype([("frame", "<i4"), ("transform", "<i4")])
-assert DETECT_DESC.itemsize == C.sizeof(_hip.DetectDesc) and DETECT_FRAME_DESC.itemsize == C.sizeof(_hip.DetectFrameDesc)
+DETECT_DESC, DETECT_FRAME_DESC = _hip.record_dtype(_hip.DetectDesc), _hip.record_dtype(_hip.DetectFrameDesc)
 
 
 def linear_taps(n_in: int, n_out: int = DETECT_BLOB) -> dict:
@@ -1990,10 +1978,6 @@ def _detect_run(frames, records, launch, out):
     return out
 
 
-def _upload_records(array: np.ndarray, device) -> torch.Tensor:
-    return torch.from_numpy(np.ascontiguousarray(array).view(np.uint8).reshape(-1).copy()).to(device)
-
-
 def detect_blobs(frames: torch.Tensor, descriptors, transforms) -> torch.Tensor:
     """``blobFromImage(cv2.resize(rotated[top:bottom, left:right], (300, 300)), 1.0, (300, 300), (104, 177, 123))`` for every descriptor
     ``(frame, transform, left, top, right, bottom)`` (DETECT_DESC records or rows of six integers), where ``rotated`` is
@@ -2015,7 +1999,7 @@ def detect_blobs(frames: torch.Tensor, descriptors, transforms) -> torch.Tensor:
         tr = torch.from_numpy(t.copy()).to(dev) if len(t) else None
 
         def launch(x, records, rows):
-            rec = _upload_records(records, x.device)
+            rec = _hip.upload_records(records, x.device)
             n, h, w, c = (int(v) for v in x.shape)
             if x.dtype == torch.uint8:
                 st = _hip.lib().vrg_detect_blobs_u8(_hip.ptr(x), n, h, w, _hip.ptr(tr) if tr is not None else None, len(t), _hip.ptr(rec), records.size,
@@ -2047,7 +2031,7 @@ def warp_linear_bytes(frames: torch.Tensor, descriptors, transforms) -> torch.Te
         tr = torch.from_numpy(t.copy()).to(dev) if len(t) else None
 
         def launch(x, records, rows):
-            rec = _upload_records(records, x.device)
+            rec = _hip.upload_records(records, x.device)
             n, h, w, c = (int(v) for v in x.shape)
             st = _hip.lib().vrg_warp_linear_u8(_hip.ptr(x), 0 if x.dtype == torch.uint8 else c, n, h, w, _hip.ptr(tr) if tr is not None else None,
                                                len(t), _hip.ptr(rec), records.size, _hip.ptr(rows), _hip.current_stream())
@@ -2834,12 +2818,7 @@ class HipEvent:
 # with Pillow's LANCZOS and pasted as panels onto a coloured canvas, in two launches (csrc/vrg_sheet.hip, arithmetic
 # csrc/vrg_sheet_math.hpp)
 # ------------------------------------------------------------------------------------------------
-SHEET_PANEL = np.dtype([("src", "<u8"), ("h_table", "<i8"), ("v_table", "<i8"), ("span_offset", "<i8"), ("tmp_offset", "<i8"), ("src_h", "<i4"),
-                        ("src_w", "<i4"), ("channels", "<i4"), ("new_w", "<i4"), ("new_h", "<i4"), ("h_ksize", "<i4"), ("v_ksize", "<i4"),
-                        ("win_x", "<i4"), ("win_y", "<i4"), ("pic_w", "<i4"), ("pic_h", "<i4"), ("row0", "<i4"), ("rows", "<i4"), ("left", "<i4"),
-                        ("top", "<i4"), ("w", "<i4"), ("h", "<i4"), ("pic_x", "<i4"), ("pic_y", "<i4"), ("cps", "<i4"), ("cell", "u1", (4,)),
-                        ("reserved", "<i4")])                                   # vrg_sheet_panel
-assert SHEET_PANEL.itemsize == C.sizeof(_hip.SheetPanel) == 128
+SHEET_PANEL = _hip.record_dtype(_hip.SheetPanel)          # the record; the SheetPanel below is the caller's description of a panel
 SHEET_FITS = ("contain_pad", "cover_crop", "resize")
 
 
@@ -3034,7 +3013,7 @@ def reference_sheet(sources, panels, canvas_size, background=(0, 0, 0), *, out_b
         def run_rows(which):
             part = np.ascontiguousarray(rec[which])
             plan.check(part, byte_sources)
-            d = torch.from_numpy(part.view(np.uint8).reshape(-1)).to(dev)
+            d = _hip.upload_records(part, dev)
             _hip.check(rows(_hip.ptr(d), len(part), _hip.ptr(tables), plan.table_ints, _hip.ptr(tmp), plan.tmp_bytes, plan.max_segments,
                             plan.max_rows, _hip.current_stream()), "vrg_sheet_rows")
 
@@ -3061,7 +3040,7 @@ def reference_sheet(sources, panels, canvas_size, background=(0, 0, 0), *, out_b
         if marks:
             marks[1].record()
         plan.check(rec, byte_sources)
-        d = torch.from_numpy(rec.view(np.uint8).reshape(-1)).to(dev)
+        d = _hip.upload_records(rec, dev)
         r, g, b = plan.background
         _hip.check(compose(_hip.ptr(d), len(rec), int(byte_sources), _hip.ptr(tables), plan.table_ints, _hip.ptr(spans), plan.n_spans, _hip.ptr(tmp),
                            plan.tmp_bytes, _hip.ptr(out), plan.width, plan.height, r | (g << 8) | (b << 16), _hip.current_stream()),
@@ -3077,8 +3056,7 @@ def reference_sheet(sources, panels, canvas_size, background=(0, 0, 0), *, out_b
 # The LTX MSR reference frames (vrgdg_ltx_msr_reference_builder.py of the reference): a few byte stills, each stretched with cv2's byte
 # Lanczos-4 and repeated into a run of fp32 / 255 frames, in one launch (csrc/vrg_msr.hip)
 # ---------------------------------------------------------------------------------------------
-MSR_DESC = np.dtype([("src", "<u8"), ("in_h", "<i4"), ("in_w", "<i4"), ("taps", "<i4"), ("first_frame", "<i4"), ("repeats", "<i4"),
-                     ("fill", "u1", (4,))])           # vrg_msr_desc
+MSR_DESC = _hip.record_dtype(_hip.MsrDesc)
 _msr_tables: dict = {}          # (distinct source sizes, out_h, out_w, device) -> the uploaded table
 
 
@@ -3190,7 +3168,7 @@ def msr_reference_frames(pictures, size, frame_count: int, background=None) -> t
                 desc["src"][i] = p.data_ptr()
         plan.check(desc)
         table = _msr_table(plan, dev)
-        d = torch.from_numpy(desc.view(np.uint8).reshape(-1)).to(dev)
+        d = _hip.upload_records(desc, dev)
         _hip.check(_hip.lib().vrg_msr_frames_f32(_hip.ptr(d), len(desc), _hip.ptr(table), plan.n_taps, _hip.ptr(out), plan.frames, plan.height,
                                                  plan.width, _hip.current_stream()), "vrg_msr_frames_f32")
     return out
@@ -3320,10 +3298,7 @@ def flf_guide_frames(first, last, frame_count: int, transition_start=0.05, trans
 REFBATCH_METHODS = ("nearest-exact", "bilinear", "area", "bicubic", "lanczos")          # the reference's upscale_methods, in its order
 _REFBATCH_FILTERS = {"bicubic": _hip.REFBATCH_BICUBIC, "bilinear": _hip.REFBATCH_BILINEAR, "area": _hip.REFBATCH_AREA,
                      "nearest-exact": _hip.REFBATCH_NEAREST_EXACT}
-REFBATCH_DESC = np.dtype([("src_offset", "<i8"), ("dst_offset", "<i8"), ("src_h", "<i4"), ("src_w", "<i4"), ("src_c", "<i4"), ("src_x0", "<i4"),
-                          ("src_y0", "<i4"), ("src_rw", "<i4"), ("src_rh", "<i4"), ("dst_h", "<i4"), ("dst_w", "<i4"), ("dst_c", "<i4"),
-                          ("method", "<i4"), ("frames", "<i4"), ("first_tile", "<i4"), ("reserved", "<i4")])           # vrg_refbatch_desc
-assert REFBATCH_DESC.itemsize == C.sizeof(_hip.RefbatchDesc)
+REFBATCH_DESC = _hip.record_dtype(_hip.RefbatchDesc)
 
 
 def total_pixels_size(height: int, width: int, megapixels, resolution_steps=1) -> tuple:
@@ -3393,7 +3368,7 @@ def _refbatch_launch(dev, jobs, out: torch.Tensor):
     if not jobs:
         return
     desc, tiles, (f_base, f_floats), (b_base, b_bytes) = refbatch_table(jobs, out.numel())
-    table = _upload_records(desc, dev)
+    table = _hip.upload_records(desc, dev)
     if out.dtype == torch.uint8:
         _hip.check(_hip.lib().vrg_refbatch_quantise_u8(C.c_void_p(f_base), f_floats, _hip.ptr(table), len(jobs), tiles, _hip.ptr(out), out.numel(),
                                                        _hip.current_stream()), "vrg_refbatch_quantise_u8")
@@ -3605,7 +3580,7 @@ def reference_bytes_to_images(pictures) -> list:
 ASSEMBLE_SLOTS = _hip.ASSEMBLE_MAX_SOURCES       # video_1 .. video_16
 ASSEMBLE_BAR = _hip.ASSEMBLE_BAR                 # rows of V5's label bar
 ASSEMBLE_MODES = ("v2", "v3", "v5", "pad", "load")
-ASSEMBLE_ENTRY = np.dtype([("source", "<i4"), ("frame", "<i4")])                     # vrg_assemble_entry
+ASSEMBLE_ENTRY = _hip.record_dtype(_hip.AssembleEntry)
 
 
 def _assemble_shape(entry):
@@ -3761,7 +3736,7 @@ def _assemble_prepare(videos, plan, overlays, what) -> _Assembly:
                 o = o.detach().to(dev).contiguous()
                 keep.append(o)
                 desc.overlay[k] = o.data_ptr()
-        table = _upload_records(rows, dev)
+        table = _hip.upload_records(rows, dev)
     return _Assembly(dev, desc, table, len(entries), shape, not on, rows, keep)
 
 

@@ -14,7 +14,7 @@ import subprocess
 
 import numpy as np
 
-from conftest import GOLDEN, PKG_DIR, ROOT
+from conftest import GOLDEN, PKG_DIR, ROOT, load_package
 
 F32 = np.float32
 U8P = np.ctypeslib.ndpointer(dtype=np.uint8, flags="C_CONTIGUOUS")
@@ -23,7 +23,8 @@ I32P = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
 I64P = np.ctypeslib.ndpointer(dtype=np.int64, flags="C_CONTIGUOUS")
 YARDSTICK_MAX_LEVELS = 1
 YARDSTICK_MAX_SHARE = 0.01
-CELL = np.dtype([("first", "<i4"), ("count", "<i4"), ("w_first", "<f4"), ("w_mid", "<f4"), ("w_last", "<f4")])
+_hip = load_package()._hip
+CELL = _hip.record_dtype(_hip.AreaCell)
 
 # (height, width, channels): the sizes of the issue
 SIZES = ((2160, 3840, 3), (1080, 1920, 3), (720, 1280, 3), (480, 854, 3), (512, 512, 3), (128, 128, 3), (64, 64, 3), (65, 67, 3), (64, 4096, 3),

@@ -14,13 +14,14 @@ import subprocess
 
 import numpy as np
 
-from conftest import GOLDEN, PKG_DIR, ROOT
+from conftest import GOLDEN, PKG_DIR, ROOT, load_package
 from cut_support import smooth_frames, uniform_frames
 
 F32 = np.float32
 COPY, FAST, FAST_2X2, GENERAL, LINEAR = 0, 1, 2, 3, 4
 MODE_NAMES = {COPY: "copy", FAST: "fast", FAST_2X2: "fast 2x2", GENERAL: "general", LINEAR: "linear"}
-CELL = np.dtype([("first", "<i4"), ("count", "<i4"), ("w_first", "<f4"), ("w_mid", "<f4"), ("w_last", "<f4")])
+_hip = load_package()._hip
+CELL = _hip.record_dtype(_hip.AreaCell)
 LABEL_BAND = 40
 
 # source (H, W) -> tile (h, w), the rule it takes

@@ -3,6 +3,8 @@ works without a GPU (no compute calls here)."""
 import ctypes as C
 import os
 import re
+import shutil
+import subprocess
 
 import pytest
 
@@ -52,11 +54,102 @@ def test_header_symbols_are_exported(hip):
     assert not (declared & debug)
 
 
-def test_struct_layouts_match_the_header(hip):
+# every arithmetic type of C (and, appended below, every struct of the header) is named, so what is left is a pointer
+_C_KINDS = ("float: 'f', double: 'f', long double: 'f', int8_t: 'i', int16_t: 'i', int32_t: 'i', int64_t: 'i', long long: 'i', char: 'i', "
+            "uint8_t: 'u', uint16_t: 'u', uint32_t: 'u', uint64_t: 'u', unsigned long long: 'u', _Bool: 'u'")
+_CXX_KIND = """#include <type_traits>
+template <class T> constexpr char kind() {
+    using U = std::remove_cv_t<std::remove_reference_t<T>>;
+    return std::is_pointer_v<U> ? 'p' : std::is_floating_point_v<U> ? 'f' : std::is_class_v<U> ? 's' : std::is_signed_v<U> ? 'i' :
+           std::is_unsigned_v<U> ? 'u' : '?';
+}
+#define KIND(x) kind<decltype(x)>()
+"""
+
+
+def _ctypes_kind(ctype):
+    """'i' signed integer, 'u' unsigned integer, 'f' float / double, 'p' pointer, 's' struct -- of the field, or of an array field's elements"""
+    while issubclass(ctype, C.Array):
+        ctype = ctype._type_
+    if issubclass(ctype, C.Structure):
+        return "s"
+    code = ctype._type_
+    return "p" if code == "P" else "f" if code in "fd" else "i" if code in "bhilq" else "u" if code in "BHILQ" else "?"
+
+
+def _header_members(text, c_name):
+    """the member names of `struct <c_name> { ... }` in the header's text (comments removed), in the order they are declared"""
+    body = re.search(r"\bstruct\s+%s\s*\{([^{}]*)\}" % re.escape(c_name.split("::")[-1]), text)
+    assert body, f"no struct {c_name} in its header"
+    names = []
+    for declaration in body.group(1).split(";"):
+        for declarator in declaration.split(","):
+            if declarator.strip():
+                names.append(re.search(r"(\w+)\s*(?:\[[^\]]*\]\s*)*$", declarator.strip()).group(1))
+    return names
+
+
+def _compiled_layout(header, records, tmp_path):
+    """{"<c_name>": sizeof, "<c_name>.<member>": (offsetof, sizeof, kind)} of `records` as the compiler lays out ROOT/<header>: a program
+    generated from the ctypes field names -- C for a .h (which must stay plain C), C++ for the headers of csrc/"""
+    plain_c = header.endswith(".h")
+    lines = ["#include <stddef.h>", "#include <stdint.h>", "#include <stdio.h>"]
+    if not plain_c:         # as tests/host_math/*.cpp: the hardware transcendentals of vrg_pixel_math.hpp have no host form of their own
+        lines += ["#include <math.h>", "#define VRG_HW_LOG2(x) log2f(x)", "#define VRG_HW_SIN_REV(x) sinf(x)", "#define VRG_HW_COS_REV(x) cosf(x)",
+                  "#define VRG_HW_EXP2(x) exp2f(x)", "#define VRG_HW_RCP(x) (1.0f / (x))"]
+    lines.append(f'#include "{os.path.basename(header)}"')
+    if plain_c:
+        structs = ", ".join(f"{r.c_name}: 's'" for r in records)
+        lines.append(f"#define KIND(x) _Generic((x), {_C_KINDS}, {structs}, default: 'p')")
+    else:
+        lines.append(_CXX_KIND)
+    lines.append("int main(void) {")
+    for r in records:
+        lines.append(f'    {{ static {r.c_name} r; printf("{r.c_name} %zu\\n", sizeof r);')
+        for name, ctype in r._fields_:
+            element = f"r.{name}" + "[0]" * issubclass(ctype, C.Array)
+            lines.append(f'      printf("{r.c_name}.{name} %zu %zu %c\\n", offsetof({r.c_name}, {name}), sizeof r.{name}, KIND({element}));')
+        lines.append("    }")
+    lines += ["    return 0;", "}"]
+    src = tmp_path / ("layout.c" if plain_c else "layout.cpp")
+    src.write_text("\n".join(lines) + "\n")
+    exe = tmp_path / ("layout_c" if plain_c else "layout_cxx")
+    compiler = ["gcc", "-std=c11"] if plain_c else ["g++", "-std=c++17"]
+    subprocess.run(compiler + ["-I", os.path.dirname(os.path.join(ROOT, header)), str(src), "-o", str(exe)], check=True)
+    out = {}
+    for line in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines():
+        key, *values = line.split()
+        out[key] = int(values[0]) if len(values) == 1 else (int(values[0]), int(values[1]), values[2])
+    return out
+
+
+@pytest.mark.skipif(shutil.which("gcc") is None or shutil.which("g++") is None, reason="gcc / g++ not available")
+def test_struct_layouts_match_the_header(pkg, tmp_path):
+    """Every record of _hip.py against the struct the kernels are compiled with: the same members in the same order (so none hides in
+    padding), each at the same offset, of the same size and the same kind (signed, unsigned, float, pointer, struct); the same size
+    overall; and no `typedef struct vrg_*` of the header without its record.  The numpy layouts are np.dtype(record), so they follow."""
+    from comfyui_vrgamedevgirl_amd import _hip
+    records = _hip.Record.__subclasses__()
+    assert len(records) >= 24 and len({r.c_name for r in records}) == len(records)
+    for header in sorted({r.c_header for r in records}):
+        mine = [r for r in records if r.c_header == header]
+        text = open(os.path.join(ROOT, header)).read()
+        text = re.sub(r"/\*.*?\*/|//[^\n]*", "", text, flags=re.S)
+        compiled = _compiled_layout(header, mine, tmp_path)
+        for r in mine:
+            assert _header_members(text, r.c_name) == [name for name, _ in r._fields_], r.c_name
+            assert compiled[r.c_name] == C.sizeof(r), r.c_name
+            for name, ctype in r._fields_:
+                field = getattr(r, name)
+                assert compiled[f"{r.c_name}.{name}"] == (field.offset, field.size, _ctypes_kind(ctype)), f"{r.c_name}.{name}"
+            assert _hip.record_dtype(r).itemsize == C.sizeof(r)
+            assert [_hip.record_dtype(r).fields[name][1] for name, _ in r._fields_] == [getattr(r, name).offset for name, _ in r._fields_]
+        if header == "include/vrgdg_hip.h":
+            assert set(re.findall(r"typedef\s+struct\s+(vrg_\w+)", text)) == {r.c_name for r in mine}
     # vrg_noise_desc: 4*u64 + i64 + i32 + u32 = 48 bytes
-    assert C.sizeof(hip.NoiseDesc) == 48
-    assert hip.ChainDesc.noise.offset % 8 == 0 and hip.ChainDesc.lut.offset % 8 == 0
-    assert hip.ChainDesc.img_ms.offset % 8 == 0
+    assert C.sizeof(_hip.NoiseDesc) == 48
+    assert _hip.ChainDesc.noise.offset % 8 == 0 and _hip.ChainDesc.lut.offset % 8 == 0
+    assert _hip.ChainDesc.img_ms.offset % 8 == 0
 
 
 def test_versions_and_error_strings(hip):
