@@ -44,6 +44,20 @@ def _as_gpu_u8(frames) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(a)).to(compute_device())
 
 
+_SUMS_FRAMES = 65535          # frames per vrg_u8_channel_sums call (one frame per blockIdx.y)
+
+
+def _channel_sums(x):
+    """``[F,H,W,3]`` uint8 frames on the GPU -> int64 ``[F,3,2]``: the sum and the sum of squares of every channel of every frame, exact."""
+    F, H, W, _ = x.shape
+    sums = torch.empty((F, 3, 2), dtype=torch.int64, device=x.device)
+    for f0 in range(0, F, _SUMS_FRAMES):
+        nf = min(_SUMS_FRAMES, F - f0)
+        _hip.check(_hip.lib().vrg_u8_channel_sums(_hip.ptr(x[f0:f0 + nf]), nf, H, W, _hip.ptr(sums[f0:f0 + nf]), _hip.current_stream()),
+                   "vrg_u8_channel_sums")
+    return sums
+
+
 def _frame_channel_stats(frame_bgr):
     """``ImageStat.Stat(image.convert("RGB")).mean[:3] / .stddev[:3]`` (:4382-4389) of one decoded B,G,R frame, in
     R,G,B order: exact 64-bit sums on the GPU, then ImageStat's own double arithmetic
@@ -52,9 +66,7 @@ def _frame_channel_stats(frame_bgr):
     if x.shape[0] != 1:
         raise ValueError("one frame expected")
     _, H, W, _ = x.shape
-    sums = torch.empty((1, 3, 2), dtype=torch.int64, device=x.device)
-    _hip.check(_hip.lib().vrg_u8_channel_sums(_hip.ptr(x), 1, H, W, _hip.ptr(sums), _hip.current_stream()), "vrg_u8_channel_sums")
-    s = sums.cpu().tolist()[0]
+    s = _channel_sums(x).cpu().tolist()[0]
     n = H * W
     mean, std = [], []
     for c in (2, 1, 0):                                   # memory order is B,G,R

@@ -303,10 +303,11 @@ static int launch_stats(const float* in, int64_t frames, int32_t H, int32_t W, c
     const int64_t ppf = (int64_t)H * W;
     const int bpf = stats_blocks_per_frame(ppf);
     double* partials = reinterpret_cast<double*>(scratch);
-    return launch_chunks(frames, [&](int64_t f0, int64_t nf) {
+    // a launch takes whole noise chunks: the kernels count chunks from the launch's first frame
+    return launch_chunks(frames, (STAGES & VRG_STAGE_GRAIN) ? D.noise.chunk_frames : 1, [&](int64_t f0, int64_t nf) {
         ChainK d = D;
         if (STAGES & VRG_STAGE_GRAIN) {
-            if (f0 % D.noise.chunk_frames) return VRG_ERR_UNSUPPORTED;
+            if (f0 % D.noise.chunk_frames) return VRG_ERR_UNSUPPORTED;     // (cannot happen: launch_chunks' alignment)
             d.noise.chunk0 += f0 / D.noise.chunk_frames;
         }
         const px3* src = reinterpret_cast<const px3*>(in) + f0 * ppf;
@@ -341,19 +342,17 @@ static int launch_chain(const void* in, void* out, int64_t frames, int32_t H, in
     const int tx = (W + TILE_W - 1) / TILE_W, ty = (H + TILE_H - 1) / TILE_H;
     const int64_t tpf = (int64_t)tx * ty;
     // frames per launch: 2-D grid y limit for the point-wise kernel, 32-bit work-item count for the tile kernel
-    int64_t step = 32768;
+    int64_t step = LAUNCH_RECORDS;
     if (sharpen) {
         step = (1ll << 23) / tpf;
         if (step < 1) return VRG_ERR_UNSUPPORTED;
     }
-    if (STAGES & VRG_STAGE_GRAIN) {
-        if (step < D.noise.chunk_frames) return VRG_ERR_UNSUPPORTED;
-        step -= step % D.noise.chunk_frames;
-    }
-    if ((STAGES & VRG_STAGE_COLORMATCH) && D.cm.ref_frames != 1) {
-        if (step < D.cm.ref_frames) return VRG_ERR_UNSUPPORTED;
-        step -= step % D.cm.ref_frames;     // (both alignments together are only needed when ref_frames divides chunk_frames)
-    }
+    // a launch takes whole noise chunks and whole rounds of the reference statistics, like launch_stats and vrg_colormatch_apply_f32: with
+    // both, their least common multiple
+    int64_t align = (STAGES & VRG_STAGE_GRAIN) ? D.noise.chunk_frames : 1;
+    if (STAGES & VRG_STAGE_COLORMATCH) align = chunk_lcm(align, D.cm.ref_frames);
+    if (frames > step) step = aligned_step(step, align);
+    if (step < 1) return VRG_ERR_UNSUPPORTED;
     for (int64_t f0 = 0; f0 < frames; f0 += step) {
         const int64_t nf = frames - f0 < step ? frames - f0 : step;
         ChainK d = D;

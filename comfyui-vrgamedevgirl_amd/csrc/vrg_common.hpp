@@ -33,15 +33,31 @@ VRG_HD bool span_fits(int64_t offset, int64_t need, int64_t size) { return offse
 // blockIdx.y / blockIdx.z take one record each, at most this many per launch
 constexpr int64_t LAUNCH_RECORDS = 32768;
 
-// launch(first, count) for consecutive chunks of [0, n), each at most LAUNCH_RECORDS long; stops at the first return that is not VRG_OK
+// The largest multiple of `align` that is at most `limit` records: the chunk length for which every chunk starts on a multiple of `align`
+// (records that share state in groups of `align`: f % ref_frames, the frames of one Philox chunk).  0: no such length, align > limit.
+VRG_HD int64_t aligned_step(int64_t limit, int64_t align) { return align < 1 || align > limit ? 0 : limit - limit % align; }
+// The alignment that holds two at once (both at least 1 and below 2^31: no overflow).
+VRG_HD int64_t chunk_lcm(int64_t a, int64_t b) {
+    int64_t x = a, y = b;
+    while (y) { const int64_t t = x % y; x = y; y = t; }
+    return a / x * b;
+}
+
+// launch(first, count) for consecutive chunks of [0, n), each at most LAUNCH_RECORDS long and each starting on a multiple of `align`; stops at
+// the first return that is not VRG_OK.  A call of more than one chunk whose alignment no chunk can hold is VRG_ERR_UNSUPPORTED.
 template <class Launch>
-inline int launch_chunks(int64_t n, Launch launch) {
-    for (int64_t first = 0; first < n; first += LAUNCH_RECORDS) {
-        const int rc = launch(first, n - first < LAUNCH_RECORDS ? n - first : LAUNCH_RECORDS);
+inline int launch_chunks(int64_t n, int64_t align, Launch launch) {
+    if (align < 1) return VRG_ERR_BAD_ARG;
+    const int64_t step = n <= LAUNCH_RECORDS ? LAUNCH_RECORDS : aligned_step(LAUNCH_RECORDS, align);
+    if (step < 1) return VRG_ERR_UNSUPPORTED;
+    for (int64_t first = 0; first < n; first += step) {
+        const int rc = launch(first, n - first < step ? n - first : step);
         if (rc != VRG_OK) return rc;
     }
     return VRG_OK;
 }
+template <class Launch>
+inline int launch_chunks(int64_t n, Launch launch) { return launch_chunks(n, 1, launch); }
 
 // Device copy of vrg_noise_desc plus the per-call geometry the noise mapping needs.
 struct NoiseK {

@@ -804,12 +804,11 @@ int vrg_colormatch_apply_f32(const float* in, float* out, int64_t frames, int32_
     if (ppf > 0x7fffffff) return VRG_ERR_UNSUPPORTED;
     CmK cm{img_ms, ref_ms, ref_frames, k, one_minus_k};
     const uint32_t bx = (uint32_t)((ppf + 255) / 256);
-    return launch_chunks(frames, [&](int64_t f0, int64_t nf) {
+    // the kernels index ref_ms with f % ref_frames relative to the chunk start: chunks start on multiples of ref_frames
+    return launch_chunks(frames, ref_frames, [&](int64_t f0, int64_t nf) {
         CmK c = cm;
         c.img_ms = img_ms + f0 * 6;
-        // ref frame index uses f % ref_frames relative to the call start; 32768 is a multiple of any
-        // chunk size only if ref_frames divides it -- keep the mapping exact by offsetting explicitly.
-        if (ref_frames != 1 && (f0 % ref_frames) != 0) return VRG_ERR_UNSUPPORTED;
+        if (f0 % ref_frames) return VRG_ERR_UNSUPPORTED;     // (cannot happen: launch_chunks' alignment)
         if (ppf * 12 < ((int64_t)1 << 31)) {
             const dim3 g4((uint32_t)((ppf + 1023) / 1024), (uint32_t)nf);
             if (cm_math == VRG_CM_MATH_FAST)

@@ -324,6 +324,10 @@ def build_host_lib(directory):
     lib.hm_span_fits.argtypes = [C.c_int64] * 3
     lib.hm_launch_chunks.restype = C.c_int32
     lib.hm_launch_chunks.argtypes = [C.c_int64, C.c_int32, C.c_int32, I64P, C.c_int32, I32P]
+    lib.hm_launch_chunks_aligned.restype = C.c_int32
+    lib.hm_launch_chunks_aligned.argtypes = [C.c_int64, C.c_int64, I64P, C.c_int32, I32P]
+    lib.hm_chunk_lcm.restype = C.c_int64
+    lib.hm_chunk_lcm.argtypes = [C.c_int64, C.c_int64]
     return lib
 
 

@@ -163,4 +163,19 @@ int32_t hm_launch_chunks(int64_t n, int32_t fail_call, int32_t code, int64_t* ch
     });
 }
 
+// the aligned form: every chunk starts on a multiple of `align`
+int32_t hm_launch_chunks_aligned(int64_t n, int64_t align, int64_t* chunks, int32_t capacity, int32_t* calls) {
+    *calls = 0;
+    return launch_chunks(n, align, [&](int64_t first, int64_t count) {
+        if (*calls < capacity) {
+            chunks[2 * *calls] = first;
+            chunks[2 * *calls + 1] = count;
+        }
+        ++*calls;
+        return (int)VRG_OK;
+    });
+}
+
+int64_t hm_chunk_lcm(int64_t a, int64_t b) { return chunk_lcm(a, b); }
+
 }  // extern "C"

@@ -200,6 +200,40 @@ def test_a_failing_launch_stops_the_chunks_and_returns_its_code(hm_far):
     assert hm_far.hm_launch_chunks(32771, 1, 2, chunks, 4, calls) == 2 and int(calls[0]) == 1
 
 
+@pytest.mark.parametrize("align", [1, 2, 3, 5, 7, 32768])
+def test_the_aligned_launch_chunks_tile_the_records_and_start_on_the_alignment(hm_far, align):
+    """Records that share state in groups of `align` (f % ref_frames, the frames of one Philox chunk): every launch starts on a group."""
+    for n in (0, 1, align, 32768, 32769, 3 * 32768 + 5):
+        chunks, calls = np.full((8, 2), -1, np.int64), np.zeros(1, np.int32)
+        assert hm_far.hm_launch_chunks_aligned(n, align, chunks, 8, calls) == 0, n
+        k = int(calls[0])
+        step = 32768 - 32768 % align
+        assert k == (0 if n == 0 else 1 if n <= 32768 else -(-n // step)) and k <= 8, n
+        first, count = chunks[:k, 0], chunks[:k, 1]
+        assert (count >= 1).all() and (count <= 32768).all() and int(count.sum()) == n, n
+        assert list(first) == [int(count[:i].sum()) for i in range(k)], n           # in order, from 0, nothing left out or done twice
+        assert not (first % align).any(), n
+        assert (chunks[k:] == -1).all(), n
+
+
+def test_an_alignment_no_launch_can_hold_is_refused_past_one_launch(hm_far):
+    chunks, calls = np.full((4, 2), -1, np.int64), np.zeros(1, np.int32)
+    for n in (32769, 32771, 2 * 32769):
+        assert hm_far.hm_launch_chunks_aligned(n, 32769, chunks, 4, calls) == 2 and int(calls[0]) == 0, n      # VRG_ERR_UNSUPPORTED, nothing launched
+    for n in (1, 32767, 32768):
+        assert hm_far.hm_launch_chunks_aligned(n, 32769, chunks, 4, calls) == 0 and int(calls[0]) == 1, n
+        assert chunks[0].tolist() == [0, n]
+    assert hm_far.hm_launch_chunks_aligned(0, 32769, chunks, 4, calls) == 0 and int(calls[0]) == 0
+    assert hm_far.hm_launch_chunks_aligned(5, 0, chunks, 4, calls) == 1 and int(calls[0]) == 0                  # VRG_ERR_BAD_ARG
+
+
+def test_the_alignment_of_two_is_their_least_common_multiple(hm_far):
+    import math
+    for a in (1, 2, 3, 4, 6, 7, 32768, 2**31 - 1):
+        for b in (1, 2, 3, 5, 6, 9, 32767, 2**31 - 1):
+            assert hm_far.hm_chunk_lcm(a, b) == math.lcm(a, b), (a, b)
+
+
 def test_span_fits_at_its_edges(hm_far):
     fits = lambda offset, need, size: bool(hm_far.hm_span_fits(offset, need, size))
     size = 100
