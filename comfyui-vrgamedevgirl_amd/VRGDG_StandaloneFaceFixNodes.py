@@ -37,6 +37,12 @@ read once, 12 B per pixel); two small launches turn the thumbnails into hue / sa
 consecutive pair, and the host finishes the score in double (cut_scores_from_sums).  CPU frames go up through the staging pipeline of
 _devices; nothing but 32 bytes per pair comes back.  The `shot_id` values are what face_crop_sequence(..., per_shot=True) consumes.
 
+`VRGDGFaceFixLoadAnchorsMetaBatch` and `VRGDGFaceFixStoreAnchors` carry the 512 x 512 anchors to the image model and back: the Meta Batch
+protocol and the decode seam `image_loader` are in _anchors.py, a call's chunk of decoded bytes becomes fp32 in one launch
+(ops.anchor_frames); the store quantises and swaps to B,G,R in one launch (ops.anchor_store_bytes), downloads once and hands every
+frame to the seam `png_writer(path, bgr_bytes)` -- cv2.imwrite in the reference; the default writes the same pixels through Pillow.
+They are listed in ANCHOR_NODE_CLASS_MAPPINGS / ANCHOR_NODE_DISPLAY_NAME_MAPPINGS.
+
 What is NOT here: detection and tracking (cv2 DNN, candidate choice, anchor selection and the anchor PNG dump) and
 with them the Prepare / Collect node classes -- a shot-aware Prepare node calls shot_boundaries once before its detection loop and
 face_crop_sequence once after it, INTEGRATION.md shows the lines; the landmark detector of the aligned composite (YuNet, the RANSAC similarity fit and the .onnx asset); and
@@ -57,7 +63,7 @@ import sys
 import numpy as np
 import torch
 
-from . import ops
+from . import _anchors, ops
 from ._devices import compute_device, intermediate_device, stream_frames_with_masks
 
 FACE_FIX_CONTEXT = "VRGDG_FACE_FIX_CONTEXT"
@@ -790,4 +796,118 @@ LANDMARK_NODE_CLASS_MAPPINGS = {
 
 LANDMARK_NODE_DISPLAY_NAME_MAPPINGS = {
     "VRGDGFaceFixCompositeLandmarkAligned": "Face Fix - Composite Landmark Aligned",
+}
+
+
+# ------------------------------------------------------------------------------------------------
+# the anchor round trip: Load Anchors (Meta Batch) -> the image model -> Store Enhanced Anchors
+# ------------------------------------------------------------------------------------------------
+image_loader = _anchors.image_loader      # the decode seam of the Load node: path -> [h, w, 3] uint8 R,G,B
+
+_NO_ANCHOR_FOLDER = "Prepared Face Fix anchor folder was not found: {}"
+_NO_ANCHOR_FILES = "No anchor images were found in {}"
+_NO_ANCHORS_LEFT = "The Face Fix Meta Batch has no anchor images left to load."
+
+
+def png_writer(path, bgr_bytes):
+    """The encode seam of the Store node: ``[h, w, 3]`` uint8 in B,G,R, what ``cv2.imwrite(path, ...)`` takes.  The default needs no cv2:
+    it swaps back to R,G,B and writes the same pixels with Pillow.  A caller may bind ``cv2.imwrite`` instead."""
+    from PIL import Image
+    Image.fromarray(np.ascontiguousarray(bgr_bytes[..., ::-1]), "RGB").save(path)
+
+
+def _progress(index, total, label, checkpoints=10):
+    done = index + 1
+    if total > 0 and (done in (1, total) or done % max(total // checkpoints, 1) == 0):
+        _log(f"{label}: {done}/{total}")
+
+
+class VRGDGFaceFixLoadAnchorsMetaBatch:
+    @classmethod
+    def INPUT_TYPES(cls):
+        return {
+            "required": {
+                "face_fix_context": (FACE_FIX_CONTEXT, {"tooltip": "Connect Face Fix - Prepare Video and Anchors: face_fix_context. It contains the automatically generated anchor-source folder."}),
+                "meta_batch": ("VHS_BatchManager", {"tooltip": "Connect VHS Meta Batch Manager. Set frames_per_batch from Prepare's anchor_count so all anchors follow the same managed loading behavior used by the tested Z-Image workflow."}),
+            },
+            "hidden": {"unique_id": "UNIQUE_ID"},
+        }
+
+    RETURN_TYPES = ("IMAGE", "MASK", "INT", FACE_FIX_CONTEXT)
+    RETURN_NAMES = ("anchor_images", "mask", "batch_frame_count", "face_fix_context")
+    RETURN_TOOLTIPS = (
+        "The current Meta Batch of 512×512 source anchors. Connect this to the Z-Image pixels/VAE Encode input.",
+        "Blank compatibility mask supplied for workflows that require a MASK output.",
+        "Number of anchors loaded in this Meta Batch execution.",
+        "The unchanged Face Fix context. Connect this to Store Enhanced Anchors to preserve execution order.",
+    )
+    FUNCTION = "load"
+    CATEGORY = "VRGameDevGirl/Face Fix"
+    DESCRIPTION = "Loads prepared Face Fix anchors through VHS Meta Batch without manually selecting a folder."
+
+    def load(self, face_fix_context, meta_batch, unique_id):
+        directory = str(face_fix_context.get("anchor_sources_folder") or "")
+        _log(f"Meta Batch anchor loader started. Job={face_fix_context.get('job_id', 'unknown')}; "
+             f"frames_per_batch={getattr(meta_batch, 'frames_per_batch', '?')}; folder={directory}")
+        if not os.path.isdir(directory):
+            raise FileNotFoundError(_NO_ANCHOR_FOLDER.format(directory))
+        images, masks, count = _anchors.load_chunk(directory, meta_batch, unique_id, lambda path: image_loader(path), _NO_ANCHOR_FILES,
+                                                   _NO_ANCHORS_LEFT)
+        _log(f"Meta Batch anchor loader returned {count} image(s) at {int(images.shape[2])}x{int(images.shape[1])}. "
+             f"closed={getattr(meta_batch, 'has_closed_inputs', False)}")
+        return images, masks, count, face_fix_context
+
+
+class VRGDGFaceFixStoreAnchors:
+    @classmethod
+    def INPUT_TYPES(cls):
+        return {"required": {
+            "enhanced_anchors": ("IMAGE", {"tooltip": "Connect the decoded IMAGE output from Z-Image. The number and order must exactly match the anchors loaded by the Face Fix Meta Batch node."}),
+            "face_fix_context": (FACE_FIX_CONTEXT, {"tooltip": "Connect Face Fix - Load Anchors (Meta Batch): face_fix_context. This links the enhanced results to the correct Face Fix job and anchor ordering."}),
+        }}
+
+    RETURN_TYPES = ("STRING", "STRING", "INT", FACE_FIX_CONTEXT)
+    RETURN_NAMES = ("enhanced_anchor_folder", "anchor_indices", "anchor_count", "face_fix_context")
+    RETURN_TOOLTIPS = (
+        "Automatically managed folder containing the numbered Z-Image enhanced anchors for LTX.",
+        "Comma-separated LTX conditioning positions corresponding to the saved anchors.",
+        "Number of enhanced anchors validated and saved.",
+        "Updated job context containing the enhanced-anchor folder. Connect this to Collect LTX Inputs: enhanced_anchor_context.",
+    )
+    FUNCTION = "store"
+    CATEGORY = "VRGameDevGirl/Face Fix"
+    OUTPUT_NODE = True
+    DESCRIPTION = "Saves the enhanced anchor batch in deterministic order for LTX conditioning."
+
+    def store(self, enhanced_anchors, face_fix_context):
+        import folder_paths
+        context = dict(face_fix_context)
+        indices = list(context.get("anchor_indices") or [])
+        received = int(enhanced_anchors.shape[0])
+        _log(f"Store Enhanced Anchors started. Job={context.get('job_id', 'unknown')}; received={received}, expected={len(indices)}.")
+        if received != len(indices):
+            raise ValueError(f"Z-Image returned {received} anchors; expected {len(indices)}.")
+        folder = os.path.join(folder_paths.get_output_directory(), "face_fix_standalone", context["job_id"], "enhanced_anchors_512")
+        os.makedirs(folder, exist_ok=True)
+        for entry in list(os.scandir(folder)):
+            if entry.name.lower().endswith(".png"):
+                os.remove(entry.path)
+        frames = _anchors.stored_bytes(enhanced_anchors, bgr=True) if received else ()
+        for order, frame in enumerate(frames):
+            png_writer(os.path.join(folder, "anchor_%04d.png" % order), frame)
+            _progress(order, len(frames), "Saving enhanced anchors")
+        context["enhanced_anchor_folder"] = folder
+        _log(f"Store Enhanced Anchors finished: {len(indices)} image(s) saved to {folder}")
+        return folder, ",".join(str(value) for value in indices), len(indices), context
+
+
+ANCHOR_NODE_CLASS_MAPPINGS = {
+    "VRGDGFaceFixLoadAnchorsMetaBatch": VRGDGFaceFixLoadAnchorsMetaBatch,
+    "VRGDGFaceFixStoreAnchors": VRGDGFaceFixStoreAnchors,
+}
+
+
+ANCHOR_NODE_DISPLAY_NAME_MAPPINGS = {
+    "VRGDGFaceFixLoadAnchorsMetaBatch": "Face Fix - Load Anchors (Meta Batch)",
+    "VRGDGFaceFixStoreAnchors": "Face Fix - Store Enhanced Anchors",
 }

@@ -6,15 +6,23 @@ resize + blend + clamp of the node is ONE pass over the originals (ops.restore_f
 kernels and temporaries.  CPU tensors (what ComfyUI hands a node) go through the host-fed pipeline of _devices (staging ring, pieces
 along the frame axis, upload / kernel / download overlapped); device tensors are processed where they are.
 
-What is NOT here: the Prepare node (it has a module of its own, VRGDG_VideoEnhancePrepare.py), the anchor
-and collect nodes, and the registration in the package's NODE_CLASS_MAPPINGS: INTEGRATION.md shows the two lines that merge this
-module's mapping.  The node is eager: it is not part of the deferred graph fusion of nodes.py.
+The anchor round trip between Prepare and Restore is here too: `VRGDGVideoEnhanceLoadAnchorsMetaBatch` (the anchor files of a job through
+VHS Meta Batch: the protocol and the decode seam `image_loader` are in _anchors.py, the pixels come from ops.anchor_frames, one launch a
+call), `VRGDGVideoEnhanceStoreAnchors` (ops.anchor_store_bytes, one page-locked download, then the PNG writer `_save_image_batch` of
+VRGDG_VideoEnhancePrepare.py) and `VRGDGVideoEnhanceCollectLTXInputs` (host logic only).  They are listed in ANCHOR_NODE_CLASS_MAPPINGS /
+ANCHOR_NODE_DISPLAY_NAME_MAPPINGS: this module's NODE_CLASS_MAPPINGS keeps its one key (an existing test pins that set).
+
+What is NOT here: the Prepare node (it has a module of its own, VRGDG_VideoEnhancePrepare.py) and the registration
+in the package's NODE_CLASS_MAPPINGS: INTEGRATION.md shows the lines that merge this module's mappings.  The nodes are eager: they are
+not part of the deferred graph fusion of nodes.py.
 """
 from __future__ import annotations
 
+import os
+
 import torch
 
-from . import ops
+from . import _anchors, ops
 from ._devices import compute_device, intermediate_device, piece_frames, stream_frames
 
 VIDEO_ENHANCE_CONTEXT = "VRGDG_VIDEO_ENHANCE_CONTEXT"
@@ -144,4 +152,149 @@ NODE_CLASS_MAPPINGS = {
 
 NODE_DISPLAY_NAME_MAPPINGS = {
     "VRGDGVideoEnhanceRestoreOriginal": "Video Enhance - Restore Original Resolution",
+}
+
+
+# ------------------------------------------------------------------------------------------------
+# the anchor round trip: Load Anchors (Meta Batch) -> the image model -> Store Enhanced Anchors -> Collect LTX Inputs
+# ------------------------------------------------------------------------------------------------
+image_loader = _anchors.image_loader      # the decode seam of the Load node: path -> [h, w, 3] uint8 R,G,B
+
+_NO_ANCHOR_FOLDER = "Prepared Video Enhance anchor folder was not found: {}"
+_NO_ANCHOR_FILES = "No Video Enhance anchor images were found in {}"
+_NO_ANCHORS_LEFT = "The Video Enhance Meta Batch has no anchor images left to load."
+_SAFE_REACH = 8                           # how far from an anchor a conditioning position is looked for
+_LTX_PERIOD, _LTX_REFUSED = 8, 1          # LTX takes no conditioning position p with p % 8 == 1
+
+
+def _save_image_batch(images_or_bytes, folder, prefix):
+    """the PNG writer seam: VRGDG_VideoEnhancePrepare._save_image_batch (image files of an earlier run in `folder` go first)"""
+    from .VRGDG_VideoEnhancePrepare import _save_image_batch as save
+    save(images_or_bytes, folder, prefix)
+
+
+def _count_error(got, expected):
+    return ValueError(f"Z-Image returned {got} anchors; expected {expected}.")
+
+
+def _joined(indices):
+    return ",".join(str(value) for value in indices)
+
+
+class VRGDGVideoEnhanceLoadAnchorsMetaBatch:
+    @classmethod
+    def INPUT_TYPES(cls):
+        return {
+            "required": {
+                "video_enhance_context": (VIDEO_ENHANCE_CONTEXT, {"tooltip": "Connect Prepare Video and Anchors context. It contains the automatically generated full-frame anchor folder."}),
+                "meta_batch": ("VHS_BatchManager", {"tooltip": "Connect VHS Meta Batch Manager and set frames_per_batch from Prepare anchor_count so Z-Image receives the managed anchor sequence in one queued workflow."}),
+            },
+            "hidden": {"unique_id": "UNIQUE_ID"},
+        }
+
+    RETURN_TYPES = ("IMAGE", "MASK", "INT", VIDEO_ENHANCE_CONTEXT)
+    RETURN_NAMES = ("anchor_images", "mask", "batch_frame_count", "video_enhance_context")
+    FUNCTION = "load"
+    CATEGORY = "VRGameDevGirl/Video Enhance"
+    DESCRIPTION = "Loads full-frame Video Enhance anchors through VHS Meta Batch for sequential Z-Image enhancement."
+
+    def load(self, video_enhance_context, meta_batch, unique_id):
+        directory = str(video_enhance_context.get("anchor_sources_folder") or "")
+        if not os.path.isdir(directory):
+            raise FileNotFoundError(_NO_ANCHOR_FOLDER.format(directory))
+        images, masks, count = _anchors.load_chunk(directory, meta_batch, unique_id, lambda path: image_loader(path), _NO_ANCHOR_FILES,
+                                                   _NO_ANCHORS_LEFT)
+        _log(f"Meta Batch returned {count} anchor(s) at {int(images.shape[2])}x{int(images.shape[1])}.")
+        return images, masks, count, video_enhance_context
+
+
+class VRGDGVideoEnhanceStoreAnchors:
+    @classmethod
+    def INPUT_TYPES(cls):
+        return {"required": {
+            "enhanced_anchors": ("IMAGE", {"tooltip": "Connect the decoded Z-Image IMAGE result. Its count and order must match the anchors loaded through Meta Batch."}),
+            "video_enhance_context": (VIDEO_ENHANCE_CONTEXT, {"tooltip": "Connect the context from Load Anchors (Meta Batch) so enhanced results are stored in the correct job."}),
+        }}
+
+    RETURN_TYPES = ("STRING", "STRING", "INT", VIDEO_ENHANCE_CONTEXT)
+    RETURN_NAMES = ("enhanced_anchor_folder", "anchor_indices", "anchor_count", "video_enhance_context")
+    FUNCTION = "store"
+    CATEGORY = "VRGameDevGirl/Video Enhance"
+    OUTPUT_NODE = True
+    DESCRIPTION = "Stores enhanced full-frame anchors in deterministic order for LTX conditioning."
+
+    def store(self, enhanced_anchors, video_enhance_context):
+        context = dict(video_enhance_context)
+        indices = list(context.get("anchor_indices") or [])
+        if int(enhanced_anchors.shape[0]) != len(indices):
+            raise _count_error(enhanced_anchors.shape[0], len(indices))
+        folder = os.path.join(context["job_folder"], "enhanced_anchors")
+        no_frames = torch.zeros((0, 1, 1, 3), dtype=torch.uint8)                  # an empty batch still clears the folder
+        _save_image_batch(_anchors.stored_bytes(enhanced_anchors) if indices else no_frames, folder, "anchor")
+        context["enhanced_anchor_folder"] = folder
+        _log(f"Stored {len(indices)} enhanced anchor(s) in {folder}")
+        return folder, _joined(indices), len(indices), context
+
+
+class VRGDGVideoEnhanceCollectLTXInputs:
+    @classmethod
+    def INPUT_TYPES(cls):
+        return {"required": {
+            "prepared_video_context": (VIDEO_ENHANCE_CONTEXT, {"tooltip": "Connect Prepare Video and Anchors context. This proves the temporary full-frame LTX MP4 exists."}),
+            "enhanced_anchor_context": (VIDEO_ENHANCE_CONTEXT, {"tooltip": "Connect Store Enhanced Anchors context. This proves all Z-Image anchor results were saved."}),
+        }}
+
+    RETURN_TYPES = ("STRING", "STRING", "STRING", "INT", "INT", "INT", VIDEO_ENHANCE_CONTEXT)
+    RETURN_NAMES = ("ltx_video_path", "enhanced_anchor_folder", "anchor_indices", "anchor_count", "ltx_width", "ltx_height", "video_enhance_context")
+    FUNCTION = "collect"
+    CATEGORY = "VRGameDevGirl/Video Enhance"
+    DESCRIPTION = "Validates both Video Enhance branches, adjusts LTX-incompatible conditioning positions, and exposes the paths and dimensions required by the LTX workflow."
+
+    @staticmethod
+    def _safe_indices(indices, frame_count):
+        """Every anchor position moved to the nearest frame LTX takes: the position itself, else 1 below, 1 above, 2 below, ... up to 8
+        away, inside the video, not taken by an earlier anchor and not 1 modulo 8."""
+        taken, safe = set(), []
+        for anchor in indices:
+            near = [anchor] + [anchor + sign * step for step in range(1, _SAFE_REACH + 1) for sign in (-1, 1)]
+            fits = [p for p in near if 0 <= p < frame_count and p not in taken and p % _LTX_PERIOD != _LTX_REFUSED]
+            if not fits:
+                raise ValueError(f"Could not find a safe LTX conditioning position near anchor {anchor}.")
+            taken.add(fits[0])
+            safe.append(fits[0])
+        return safe
+
+    def collect(self, prepared_video_context, enhanced_anchor_context):
+        prepared, enhanced = prepared_video_context, enhanced_anchor_context
+        job = str(prepared.get("job_id") or "")
+        if not job or job != str(enhanced.get("job_id") or ""):
+            raise ValueError("The prepared video and enhanced anchors belong to different Video Enhance jobs.")
+        video_path, folder = str(prepared.get("ltx_video_path") or ""), str(enhanced.get("enhanced_anchor_folder") or "")
+        indices = list(enhanced.get("anchor_indices") or [])
+        if not os.path.isfile(video_path):
+            raise FileNotFoundError(f"The Video Enhance LTX working video is missing: {video_path}")
+        if not os.path.isdir(folder):
+            raise FileNotFoundError(f"The enhanced Video Enhance anchor folder is missing: {folder}")
+        stored = [name for name in os.listdir(folder) if name.lower().endswith(".png")]
+        if len(stored) != len(indices):
+            raise ValueError(f"Enhanced anchor folder contains {len(stored)} images; expected {len(indices)}.")
+        safe = self._safe_indices(indices, int(prepared.get("frame_count") or 0))
+        moved = [f"{old}->{new}" for old, new in zip(indices, safe) if old != new]
+        if moved:
+            _log("Adjusted LTX-incompatible anchor position(s): " + ", ".join(moved))
+        context = dict(prepared, enhanced_anchor_folder=folder, anchor_indices=safe)
+        return video_path, folder, _joined(safe), len(safe), int(context["ltx_width"]), int(context["ltx_height"]), context
+
+
+ANCHOR_NODE_CLASS_MAPPINGS = {
+    "VRGDGVideoEnhanceLoadAnchorsMetaBatch": VRGDGVideoEnhanceLoadAnchorsMetaBatch,
+    "VRGDGVideoEnhanceStoreAnchors": VRGDGVideoEnhanceStoreAnchors,
+    "VRGDGVideoEnhanceCollectLTXInputs": VRGDGVideoEnhanceCollectLTXInputs,
+}
+
+
+ANCHOR_NODE_DISPLAY_NAME_MAPPINGS = {
+    "VRGDGVideoEnhanceLoadAnchorsMetaBatch": "Video Enhance - Load Anchors (Meta Batch)",
+    "VRGDGVideoEnhanceStoreAnchors": "Video Enhance - Store Enhanced Anchors",
+    "VRGDGVideoEnhanceCollectLTXInputs": "Video Enhance - Collect LTX Inputs",
 }

@@ -202,6 +202,12 @@ class AssembleEntry(Record):
     _fields_ = [("source", C.c_int32), ("frame", C.c_int32)]
 
 
+class AnchorDesc(Record):
+    c_name = "vrg_anchor_desc"
+    _fields_ = [("src_offset", C.c_int64), ("h_table", C.c_int64), ("v_table", C.c_int64), ("in_w", C.c_int32), ("in_h", C.c_int32),
+                ("h_ksize", C.c_int32), ("v_ksize", C.c_int32)]
+
+
 class AreaCell(Record):          # one cell of the tables of vrg_area_taps / vrg_grid_taps / vrg_linear_taps
     c_name, c_header = "vrg::AreaCell", "comfyui-vrgamedevgirl_amd/csrc/vrg_area_math.hpp"
     _fields_ = [("first", C.c_int32), ("count", C.c_int32), ("w_first", C.c_float), ("w_mid", C.c_float), ("w_last", C.c_float)]
@@ -242,6 +248,7 @@ REFBATCH_TILE = 1024            # include/vrgdg_hip.h: VRG_REFBATCH_TILE
 REFBATCH_BICUBIC, REFBATCH_BILINEAR, REFBATCH_AREA, REFBATCH_NEAREST_EXACT, REFBATCH_COPY, REFBATCH_BYTES = 0, 1, 2, 3, 4, 5
 ASSEMBLE_MAX_SOURCES = 16       # include/vrgdg_hip.h: VRG_ASSEMBLE_MAX_SOURCES
 ASSEMBLE_BAR = 60               # include/vrgdg_hip.h: VRG_ASSEMBLE_BAR (rows of the label bar)
+ANCHOR_RGB, ANCHOR_BGR = 0, 1      # include/vrgdg_hip.h: VRG_ANCHOR_RGB / VRG_ANCHOR_BGR
 FACEFIX_STATS_WORDS = 12        # uint64 per frame (csrc/vrg_facefix_math.hpp: FF_STATS_WORDS)
 
 _F3 = C.c_float * 3
@@ -365,6 +372,9 @@ _SIGNATURES = {
     "vrg_assemble_check": (C.c_int, [C.POINTER(AssembleDesc), _P, C.c_int64, _P, _P, C.c_int32]),
     "vrg_assemble_f32": (C.c_int, [C.POINTER(AssembleDesc), _P, C.c_int64, _P, _P]),
     "vrg_assemble_labelled_u8": (C.c_int, [C.POINTER(AssembleDesc), _P, C.c_int64, _P, _P, _P]),
+    "vrg_anchor_check": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+    "vrg_anchor_frames_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, C.c_int32, C.c_int32, _P]),
+    "vrg_anchor_store_u8": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
 }
 
 # include/vrgdg_hip_debug.h: self-tests and probes -- for the test suite and the measurement tools, not part of the drop-in boundary

@@ -3799,3 +3799,117 @@ def assemble_labelled_bytes(videos, plan, overlays=None, clean_out=None):
         to = _devices.intermediate_device()
         return data.to(to), (clean if clean is None or given else clean.to(to))
     return data, clean
+
+
+# ---------------------------------------------------------------------------------------------
+# The anchor round trip of the Video Enhance and Face Fix pipelines (VRGDG_VideoEnhanceNodes.py:143-167, :295-319 and
+# VRGDG_StandaloneFaceFixNodes.py:27-51, :658-702 of the reference): decoded anchor stills to the fp32 batch of the image model in one
+# launch, the model's fp32 output to the bytes of the PNG files in one launch (csrc/vrg_anchor.hip)
+# ---------------------------------------------------------------------------------------------
+ANCHOR_DESC = _hip.record_dtype(_hip.AnchorDesc)
+_NO_ANCHOR_PICTURES = "anchor_frames: at least one picture is needed"
+_NO_ANCHOR_IMAGES = "anchor_store_bytes: at least one image is needed"
+
+
+def _anchor_picture(p, i):
+    if isinstance(p, np.ndarray):
+        p = torch.from_numpy(np.ascontiguousarray(p) if p.flags.writeable else np.array(p))                 # Pillow's arrays are read-only
+    if not isinstance(p, torch.Tensor) or p.dtype != torch.uint8 or p.ndim != 3 or int(p.shape[2]) != 3 or min(int(v) for v in p.shape[:2]) < 1:
+        raise ValueError(f"anchor_frames: picture {i} must be a non-empty [height, width, 3] uint8 tensor or array")
+    return p.detach()
+
+
+def anchor_plan(shapes, size=None):
+    """``(records, tables, src_bytes, (height, width))`` for pictures of ``shapes`` = [(height, width), ...] packed back to back: the
+    ANCHOR_DESC records, the int32 axis tables of ``Image.resize(.., LANCZOS)`` they index (one per distinct (n_in, n_out); none for an
+    axis that keeps its size) and the bytes of the packed pictures.  The size is ``size`` = (width, height), by default the first picture's.
+    Host only."""
+    shapes = [(int(h), int(w)) for h, w in shapes]
+    if not shapes:
+        raise ValueError(_NO_ANCHOR_PICTURES)
+    height, width = shapes[0] if size is None else (int(size[1]), int(size[0]))
+    if height < 1 or width < 1:
+        raise ValueError("anchor_frames: size must be at least 1 x 1")
+    desc = np.zeros(len(shapes), dtype=ANCHOR_DESC)
+    tables, table_at, n_ints, at = [], {}, 0, 0
+    for i, (h, w) in enumerate(shapes):
+        where, ks = [0, 0], [0, 0]
+        for axis, (n_in, n_out) in enumerate(((w, width), (h, height))):
+            if n_in == n_out:
+                continue
+            if (n_in, n_out) not in table_at:
+                ksize, table = pil_axis_table(_hip.PIL_FILTER_LANCZOS, n_in, n_out)
+                table_at[(n_in, n_out)] = (n_ints, ksize)
+                tables.append(table)
+                n_ints += len(table)
+            where[axis], ks[axis] = table_at[(n_in, n_out)]
+        desc[i] = (at, where[0], where[1], w, h, ks[0], ks[1])
+        at += h * w * 3
+    return desc, (np.concatenate(tables) if tables else np.zeros(0, np.int32)), at, (height, width)
+
+
+def anchor_check(desc, tables, src_bytes: int, height: int, width: int) -> None:
+    """the host refusal of records the kernel would not follow (vrg_anchor_check): ValueError, before any launch"""
+    desc = np.ascontiguousarray(desc)
+    tables = np.ascontiguousarray(tables, dtype=np.int32)
+    rc = _host_lib().vrg_anchor_check(C.c_void_p(desc.ctypes.data), len(desc), C.c_void_p(tables.ctypes.data) if tables.size else None,
+                                      int(tables.size), int(src_bytes), int(height), int(width))
+    if rc == _hip.VRG_ERR_BAD_ARG:
+        raise ValueError("anchor_frames: vrg_anchor_check refuses the records (a picture or a table outside its buffer, or a tap outside its axis)")
+    if rc != _hip.VRG_OK:
+        raise RuntimeError(f"anchor_frames: not built -- a picture more than 100 times as tall as wide whose height shrinks (Pillow resizes "
+                           f"those vertically first), or a frame of {height} x {width} is larger than one launch takes")
+
+
+def _anchor_out(out, shape, dtype, dev, what):
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    if (not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != dtype or tuple(out.shape) != tuple(shape)
+            or not out.is_contiguous()):
+        raise ValueError(f"{what}: out must be a contiguous {str(dtype).replace('torch.', '')} {list(shape)} tensor on {dev}")
+    return out
+
+
+def anchor_frames(pictures, out: Optional[torch.Tensor] = None, size=None) -> torch.Tensor:
+    """``np.stack([np.asarray(Image.fromarray(p).resize((W, H), Image.Resampling.LANCZOS), dtype=np.float32) / 255.0 for p in pictures])``
+    -- what the reference's Load Anchors nodes yield file by file -- as one launch: ``pictures`` are ``[h, w, 3]`` uint8 R,G,B tensors or
+    arrays of any sizes, on the GPU or on the CPU (the CPU ones go up as bytes, in one upload), ``(W, H)`` is the first picture's size --
+    or ``size``, for a later chunk of a sequence whose first picture came with an earlier call.
+    Returns the ``[n, H, W, 3]`` fp32 device tensor, or writes ``out`` (contiguous, of that shape, on that device).  The records are
+    checked on the host before the launch.  Inputs are never written."""
+    from . import _devices
+    what = "anchor_frames"
+    pics = [_anchor_picture(p, i) for i, p in enumerate(pictures)]
+    desc, tables, src_bytes, (height, width) = anchor_plan([tuple(p.shape[:2]) for p in pics], size)
+    on = [p.device for p in pics if p.is_cuda]
+    dev = on[0] if on else (out.device if isinstance(out, torch.Tensor) and out.is_cuda else _devices.compute_device())
+    if any(d != dev for d in on):
+        raise RuntimeError(f"{what}: the pictures live on more than one GPU")
+    anchor_check(desc, tables, src_bytes, height, width)
+    with torch.cuda.device(dev):
+        dst = _anchor_out(out, (len(pics), height, width, 3), torch.float32, dev, what)
+        flat = [p.contiguous().reshape(-1) for p in pics]
+        src = torch.cat(flat).to(dev) if not on else torch.cat([f.to(dev) for f in flat])
+        table = _hip.upload_records(desc, dev, trailing=(tables,))
+        at = len(desc) * ANCHOR_DESC.itemsize
+        _hip.check(_hip.lib().vrg_anchor_frames_f32(_hip.ptr(src), src_bytes, _hip.ptr(table), len(desc),
+                                                    C.c_void_p(table.data_ptr() + at) if tables.size else None, int(tables.size),
+                                                    _hip.ptr(dst), height, width, _hip.current_stream()), "vrg_anchor_frames_f32")
+    return dst
+
+
+@_on_device
+def anchor_store_bytes(images: torch.Tensor, bgr: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``(images[..., :3].clamp(0, 1) * 255).round().astype("uint8")`` of the reference's Store Anchors nodes for a device-resident fp32
+    ``[N, H, W, C]`` batch, ``C >= 3``, as one launch: ``[N, H, W, 3]`` uint8 on the same device, R,G,B or -- ``bgr=True``, what
+    ``cv2.imwrite`` takes -- B,G,R.  NaN gives 0 (numpy on x86).  ``out``: an optional contiguous uint8 tensor of that shape."""
+    what = "anchor_store_bytes"
+    x = _check_frames(images)
+    if int(x.shape[0]) < 1 or min(int(v) for v in x.shape[1:3]) < 1:
+        raise ValueError(_NO_ANCHOR_IMAGES)
+    if int(x.shape[3]) < 3:
+        raise ValueError(f"{what}: images must have at least 3 channels, got {int(x.shape[3])}")
+    dst = _anchor_out(out, (*x.shape[:3], 3), torch.uint8, x.device, what)
+    _hip.check(_hip.lib().vrg_anchor_store_u8(_hip.ptr(x), _hip.ptr(dst), x.numel() // int(x.shape[3]), int(x.shape[3]),
+                                              _hip.ANCHOR_BGR if bgr else _hip.ANCHOR_RGB, _hip.current_stream()), "vrg_anchor_store_u8")
+    return dst

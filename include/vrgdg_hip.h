@@ -1109,6 +1109,42 @@ int vrg_assemble_f32(const vrg_assemble_desc* desc, const vrg_assemble_entry* ma
 int vrg_assemble_labelled_u8(const vrg_assemble_desc* desc, const vrg_assemble_entry* map, int64_t n_out, float* out_f32, uint8_t* out_u8,
                              void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The anchor round trip of the Video Enhance and Face Fix pipelines (the Load Anchors (Meta Batch) and Store Enhanced Anchors nodes of
+ * VRGDG_VideoEnhanceNodes.py and VRGDG_StandaloneFaceFixNodes.py of the reference), csrc/vrg_anchor.hip and csrc/vrg_anchor_math.hpp.
+ *
+ * vrg_anchor_frames_f32: n decoded R,G,B byte pictures of unrelated sizes, packed in `src`, one record each, become
+ * out = [n][out_h][out_w][3] fp32 (4-byte aligned) in one launch: picture i is Image.resize((out_w, out_h), LANCZOS) of Pillow on its
+ * bytes -- horizontal pass, rounded byte image, vertical pass, from the tables of vrg_pil_lanczos_table; an axis whose size stays has no
+ * pass and a picture of the output's size is its own bytes -- and each byte becomes (float)byte / 255.0f, correctly rounded.  The resized
+ * bytes never reach memory.  16-byte non-temporal stores where the address allows them, 4-byte stores elsewhere; every float of `out` is
+ * written exactly once and none is read; `src` may lie at any byte address and is never written.  Any sizes >= 1 and any ratio.
+ * vrg_anchor_check refuses ON THE HOST (VRG_ERR_BAD_ARG) a record whose picture leaves `src`, whose table leaves `tables`, whose ksize is
+ * below 1 on an axis that changes, or whose table holds a record that reaches outside its axis; the kernel follows no such record
+ * either (its frame is then left unwritten).  Not built, refused with VRG_ERR_UNSUPPORTED: a picture more than 100 times as tall as wide
+ * whose height shrinks (Image.resize takes those vertically first).  `src`, `desc` (8-byte aligned) and `tables` (4-byte aligned) of the launch are device memory.
+ *
+ * vrg_anchor_store_u8: in = [pixels][channels] fp32 (channels >= 3, only the first three are read), out = [pixels][3] bytes at any
+ * address: (uint8)rint(clamp(x, 0, 1) * 255.0f), the product in fp32, ties to even -- numpy's (x.clip(0, 1) * 255).round().astype("uint8")
+ * -- in R,G,B order (VRG_ANCHOR_RGB) or B,G,R (VRG_ANCHOR_BGR).  NaN gives 0, what numpy yields on x86.  The bytes are written as a flat
+ * run of 16-byte non-temporal pieces with single bytes in front of the first 16-byte boundary and behind the last piece.
+ * ------------------------------------------------------------------------------------------- */
+#define VRG_ANCHOR_RGB 0
+#define VRG_ANCHOR_BGR 1
+
+typedef struct vrg_anchor_desc {   /* one decoded picture */
+    int64_t src_offset;            /* its [in_h][in_w][3] bytes in `src` */
+    int64_t h_table, v_table;      /* index in `tables` of the axis table (bounds [n_out][2], weights [n_out][ksize]); unused where the axis stays */
+    int32_t in_w, in_h;
+    int32_t h_ksize, v_ksize;
+} vrg_anchor_desc;
+
+int vrg_anchor_check(const vrg_anchor_desc* desc_host, int64_t n, const int32_t* tables_host, int64_t table_ints, int64_t src_bytes,
+                     int32_t out_h, int32_t out_w);
+int vrg_anchor_frames_f32(const uint8_t* src, int64_t src_bytes, const vrg_anchor_desc* desc, int64_t n, const int32_t* tables,
+                          int64_t table_ints, float* out, int32_t out_h, int32_t out_w, void* stream);
+int vrg_anchor_store_u8(const float* in, uint8_t* out, int64_t pixels, int32_t channels, int32_t order, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
