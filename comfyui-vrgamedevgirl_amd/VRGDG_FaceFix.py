@@ -14,13 +14,19 @@
                       round() and kept when x2 > x and y2 > y.  The implementation is shared with VRGDG_StandaloneFaceFixNodes
                       (csrc/vrg_detect.hip); the network is a seam (``forward``), None by default.
 
-Device-resident inputs stay on the device; CPU inputs (a uint8 tensor, a list of numpy frames) are uploaded whole and the result is
-downloaded whole (the staging helpers of VRGDG_LUTVideoTools).  The detector network, tracking, PNG / video I/O, manifests, ffmpeg and the
+``crop_frames_packed`` / ``composite_boxes_packed`` / ``composite_frames_packed`` / ``packed_plan`` / ``last_transfer``
+                      the same pixels for frames that stay on the HOST, which is all the two routes ever hold: only the boxes cross
+                      the bus, gathered into one page-locked buffer each way (csrc/vrg_facefix_packed.hip).
+
+Device-resident inputs stay on the device; ``crop_frames`` and ``composite_frames`` upload CPU inputs (a uint8 tensor, a list of numpy
+frames) whole and download the result whole (the staging helpers of VRGDG_LUTVideoTools); the packed functions take CPU inputs only and
+move the boxes.  The detector network, tracking, PNG / video I/O, manifests, ffmpeg and the
 aiohttp routes are out of scope.  The arithmetic is csrc/vrg_facefix_math.hpp; the library is reached through ``_hip`` only.
 """
 from __future__ import annotations
 
 import ctypes as C
+import threading
 
 import numpy as np
 import torch
@@ -322,6 +328,205 @@ class CompositePlan:
                                                   self.capacity, _hip.ptr(self.stats), _hip.ptr(self.out), int(x.shape[0]), int(x.shape[1]),
                                                   int(x.shape[2]), _hip.current_stream()), "vrg_ff_composite_u8")
         return self.out
+
+
+# ------------------------------------------------------------------------------------------------
+# frames that stay on the host: only the boxes cross the bus (csrc/vrg_facefix_packed.hip)
+# ------------------------------------------------------------------------------------------------
+_PACKED_DESC = _hip.record_dtype(_hip.FaceFixPackedDesc)
+_transfer = threading.local()
+
+
+class PackedPlan:
+    """Host integers of one packed call, one entry per ACTIVE frame (a box, and strength > 0 where strengths are given), in frame order:
+    ``frames`` the frame indices, ``box_index`` each one's position among the frames that have a box, ``boxes`` (left, top, w, h),
+    ``strengths`` (clamped; 1.0 without strengths), ``offsets`` the byte offset of the box's dense [h][w][3] block in the packed buffers,
+    ``tile_prefix`` int64 [n + 1]: 0 and the running sum of ceil(w * h / 256), ``tiles`` its last entry; ``n_boxes`` frames with a box.
+    ``bytes_up`` = ``bytes_down`` = the bytes of all active boxes: what the composite moves each way for the originals (the repaired
+    frames and the small tables go up besides; a crop brings n * S * S * 3 bytes down).  ``frame_bytes`` = frames * H * W * 3."""
+
+    def __init__(self, frames, box_index, boxes, strengths, n_boxes, frame_bytes):
+        self.frames, self.box_index, self.boxes, self.strengths, self.n_boxes, self.frame_bytes = frames, box_index, boxes, strengths, n_boxes, frame_bytes
+        sizes = [w * h * 3 for _, _, w, h in boxes]
+        self.offsets = [int(v) for v in np.cumsum([0] + sizes[:-1])] if sizes else []
+        tile = _hip.FACEFIX_PACKED_TILE
+        self.tile_prefix = np.concatenate([[0], np.cumsum([(w * h + tile - 1) // tile for _, _, w, h in boxes], dtype=np.int64)]).astype(np.int64)
+        self.tiles = int(self.tile_prefix[-1])
+        self.bytes_up = self.bytes_down = int(sum(sizes))
+
+
+def packed_plan(frames, height, width, crop_boxes, strengths=None) -> PackedPlan:
+    """The plan of a packed call on ``frames`` frames of ``height`` x ``width``: ``crop_boxes`` as ``crop_frames`` takes them (the same
+    ValueErrors), ``strengths`` as ``composite_frames`` takes them or None (a crop: every box is active).  No pixels, no device."""
+    frames, height, width = int(frames), int(height), int(width)
+    boxes = _boxes(crop_boxes, frames, height, width)
+    strength = None if strengths is None else _strengths(strengths, frames)
+    used, k = [], 0
+    for f, box in enumerate(boxes):
+        if box is None:
+            continue
+        index, k = k, k + 1
+        s = 1.0 if strength is None else strength[f]
+        if s > 0.0:
+            used.append((f, index, box, s))
+    return PackedPlan([u[0] for u in used], [u[1] for u in used], [u[2] for u in used], [u[3] for u in used], k, frames * height * width * 3)
+
+
+def last_transfer() -> dict:
+    """The bytes the last packed call of this thread moved: ``bytes_up`` / ``bytes_down`` the boxes' pixels (the plan's counts; for a
+    crop ``bytes_down`` is n * S * S * 3), ``enhanced_up`` the repaired frames, ``tables_up`` records and tables.  For tests and tools."""
+    return dict(getattr(_transfer, "value", None) or {"bytes_up": 0, "bytes_down": 0, "enhanced_up": 0, "tables_up": 0})
+
+
+def _host_arrays(frames, name, whole):
+    """-> one HxWx3 numpy view per frame of a CPU batch (a uint8 tensor or numpy frames), the caller's own memory"""
+    if hasattr(frames, "u8") or (isinstance(frames, torch.Tensor) and frames.is_cuda):
+        raise TypeError(f"{name} is on the GPU already: the packed route is for decoded frames on the host, use {whole}")
+    _peek(frames, name)
+    return list(frames.numpy()) if isinstance(frames, torch.Tensor) else [np.asarray(f) for f in frames]
+
+
+def _pack_boxes(arrays, plan, stage):
+    """every active box of ``arrays`` as a dense block at its offset of ``stage`` (a uint8 numpy array of at least plan.bytes_up)"""
+    for f, (left, top, w, h), offset in zip(plan.frames, plan.boxes, plan.offsets):
+        stage[offset:offset + w * h * 3].reshape(h, w, 3)[...] = arrays[f][top:top + h, left:left + w]
+
+
+def _paste_boxes(arrays, plan, results):
+    for f, (left, top, w, h), block in zip(plan.frames, plan.boxes, results):
+        arrays[f][top:top + h, left:left + w] = block
+
+
+def _staging(nbytes):
+    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, pin_memory=True)
+
+
+def _download(dev):
+    """a device tensor -> a page-locked host tensor of its shape, complete on return"""
+    host = torch.empty(dev.shape, dtype=dev.dtype, pin_memory=True)
+    host.copy_(dev, non_blocking=True)
+    torch.cuda.current_stream(dev.device).synchronize()
+    return host
+
+
+def crop_frames_packed(frames_u8, crop_boxes, enhance_size):
+    """``crop_frames`` for frames on the host (a CPU uint8 tensor or a list of numpy frames): the boxes are gathered into one page-locked
+    buffer, uploaded once, resized in one launch and downloaded once -> ``[n, S, S, 3]`` in the caller's form.  Frames on the GPU
+    (a CUDA tensor, DecodedFrames) raise TypeError: ``crop_frames`` keeps them there."""
+    size = int(enhance_size)
+    if size < 1:
+        raise ValueError("enhance_size must be at least 1")
+    arrays = _host_arrays(frames_u8, "frames", "crop_frames")
+    plan = packed_plan(*_peek(frames_u8, "frames"), crop_boxes)
+    n, as_tensor = len(plan.frames), isinstance(frames_u8, torch.Tensor)
+    if n == 0:
+        _transfer.value = None
+        return torch.empty((0, size, size, 3), dtype=torch.uint8) if as_tensor else []
+    stage = _staging(plan.bytes_up)
+    _pack_boxes(arrays, plan, stage.numpy())
+    table, offsets = _tap_tables([(b[3], b[2]) for b in plan.boxes], lambda s: s, lambda s: (size, size))
+    desc = np.zeros(n, dtype=_PACKED_DESC)
+    for i, ((_, _, w, h), offset) in enumerate(zip(plan.boxes, plan.offsets)):
+        desc[i] = (offset, 0, w, h, 0, 0.0, 0, offsets[(h, w)], 0)
+    _hip.check(_host().vrg_ff_packed_check(C.c_void_p(desc.ctypes.data), n, None, plan.bytes_up, 0, 0, 0, len(table), 0, size, size),
+               "vrg_ff_packed_check")
+    device = compute_device()
+    with torch.cuda.device(device):
+        src = stage[:plan.bytes_up].to(device, non_blocking=True)
+        taps, dev_desc = _upload(table, device), _upload(desc, device)
+        out = torch.empty((n, size, size, 3), dtype=torch.uint8, device=device)
+        _hip.check(_hip.lib().vrg_lanczos4_packed_u8(_hip.ptr(src), plan.bytes_up, _hip.ptr(dev_desc), n, _hip.ptr(out), size, size,
+                                                     _hip.ptr(taps), len(table), _hip.current_stream()), "vrg_lanczos4_packed_u8")
+        host = _download(out)
+    _transfer.value = {"bytes_up": plan.bytes_up, "bytes_down": out.numel(), "enhanced_up": 0, "tables_up": table.nbytes + desc.nbytes}
+    return host.clone() if as_tensor else list(host.numpy())
+
+
+def composite_boxes_packed(originals_u8, enhanced_u8, crop_boxes, strengths, feather=DEFAULT_FEATHER, color_match=DEFAULT_COLOR_MATCH):
+    """The pixels of ``composite_frames`` for frames on the host, boxes only: the active boxes of ``originals_u8`` and their repaired
+    frames go up in one page-locked buffer, the composited boxes come down in one -> one ``[h, w, 3]`` array per active frame, in the
+    order of ``packed_plan(...).frames`` (views of the download).  Nothing outside a box crosses the bus; no input is written."""
+    feather = max(0, min(256, int(feather)))
+    color_match = max(0.0, min(1.0, float(color_match)))
+    arrays = _host_arrays(originals_u8, "originals", "composite_frames")
+    F, H, W = _peek(originals_u8, "originals")
+    plan = packed_plan(F, H, W, crop_boxes, strengths)
+    n = len(plan.frames)
+    if n == 0:
+        _transfer.value = None
+        return []
+    enhanced = _host_arrays(enhanced_u8, "enhanced", "composite_frames")
+    EF, EH, EW = _peek(enhanced_u8, "enhanced")
+    if EF not in (plan.n_boxes, F):
+        raise ValueError(f"enhanced must hold one frame per box ({plan.n_boxes}) or per original frame ({F}), got {EF}")
+    picks = plan.box_index if EF == plan.n_boxes else plan.frames
+    enh_bytes, enh_at = EH * EW * 3, -(-plan.bytes_up // 16) * 16
+    stage = _staging(enh_at + n * enh_bytes)
+    staged = stage.numpy()
+    _pack_boxes(arrays, plan, staged)
+    for i, pick in enumerate(picks):                                        # the repaired frame of record i is frame i of the upload
+        staged[enh_at + i * enh_bytes:enh_at + (i + 1) * enh_bytes].reshape(EH, EW, 3)[...] = enhanced[pick]
+    spans, records, mask_offsets, mask_floats, largest = _mask_tables([(b[2], b[3]) for b in plan.boxes], feather)
+    table, tap_offsets = _tap_tables([(b[3], b[2]) for b in plan.boxes], lambda s: (EH, EW), lambda s: s)
+    desc = np.zeros(n, dtype=_PACKED_DESC)
+    for i, ((_, _, w, h), offset, s) in enumerate(zip(plan.boxes, plan.offsets, plan.strengths)):
+        desc[i] = (offset, offset, w, h, i, s, mask_offsets[(w, h)], tap_offsets[(h, w)], offset)
+    total = plan.bytes_up
+    _hip.check(_host().vrg_ff_packed_check(C.c_void_p(desc.ctypes.data), n, C.c_void_p(plan.tile_prefix.ctypes.data), total, total, n,
+                                           mask_floats, len(table), total, 0, 0), "vrg_ff_packed_check")
+    device = compute_device()
+    with torch.cuda.device(device):
+        dev = stage[:enh_at + n * enh_bytes].to(device, non_blocking=True)
+        src, enh = C.c_void_p(dev.data_ptr()), C.c_void_p(dev.data_ptr() + enh_at)
+        dev_desc = _upload(desc, device, trailing=(plan.tile_prefix,))
+        prefix = C.c_void_p(dev_desc.data_ptr() + desc.nbytes)
+        taps = _upload(table, device)
+        masks = _run_masks(spans, records, mask_floats, largest, feather, device)
+        face = torch.empty(total, dtype=torch.uint8, device=device)
+        stats = torch.empty(n * _hip.FACEFIX_STATS_WORDS, dtype=torch.int64, device=device)
+        out = torch.empty(total, dtype=torch.uint8, device=device)
+        lib, stream = _hip.lib(), _hip.current_stream()
+        _hip.check(lib.vrg_ff_packed_resize_stats_u8(src, total, enh, n, EH, EW, _hip.ptr(masks), mask_floats, _hip.ptr(dev_desc), prefix, n,
+                                                     plan.tiles, _hip.ptr(taps), len(table), _hip.ptr(face), total, _hip.ptr(stats), color_match,
+                                                     stream), "vrg_ff_packed_resize_stats_u8")
+        _hip.check(lib.vrg_ff_packed_composite_u8(src, total, _hip.ptr(masks), mask_floats, _hip.ptr(dev_desc), prefix, n, plan.tiles,
+                                                  _hip.ptr(face), total, _hip.ptr(stats), _hip.ptr(out), total, stream),
+                   "vrg_ff_packed_composite_u8")
+        host = _download(out).numpy()
+    tables = desc.nbytes + plan.tile_prefix.nbytes + table.nbytes + spans.nbytes + records.nbytes + (4 * gauss_taps(feather) if feather > 0 else 0)
+    _transfer.value = {"bytes_up": plan.bytes_up, "bytes_down": plan.bytes_down, "enhanced_up": n * enh_bytes, "tables_up": tables}
+    return [host[offset:offset + w * h * 3].reshape(h, w, 3) for (_, _, w, h), offset in zip(plan.boxes, plan.offsets)]
+
+
+def _host_copy(dst, src):
+    """src -> dst, two numpy arrays of one shape: the threaded copy of vrg_host_copy where both are dense"""
+    if dst.flags.c_contiguous and src.flags.c_contiguous:
+        _hip.check(_host().vrg_host_copy(C.c_void_p(dst.ctypes.data), C.c_void_p(src.ctypes.data), src.nbytes, 0), "vrg_host_copy")
+    else:
+        dst[...] = src
+
+
+def composite_frames_packed(originals_u8, enhanced_u8, crop_boxes, strengths, feather=DEFAULT_FEATHER, color_match=DEFAULT_COLOR_MATCH, *,
+                            inplace=False):
+    """``composite_frames`` for frames on the host: ``composite_boxes_packed`` pasted into a host copy of ``originals_u8`` (the
+    reference's ``original.copy()``; the result has the originals' form), or -- ``inplace=True`` -- into the caller's own frames, which
+    are returned.  ``originals_u8`` is never written unless ``inplace=True``."""
+    arrays = _host_arrays(originals_u8, "originals", "composite_frames")
+    plan = packed_plan(*_peek(originals_u8, "originals"), crop_boxes, strengths)
+    results = composite_boxes_packed(originals_u8, enhanced_u8, crop_boxes, strengths, feather, color_match)
+    if inplace:
+        out, target = originals_u8, arrays
+    elif isinstance(originals_u8, torch.Tensor):
+        out = torch.empty(originals_u8.shape, dtype=torch.uint8)
+        if out.numel():
+            _host_copy(out.numpy(), originals_u8.numpy())
+        target = list(out.numpy())
+    else:
+        out = target = [np.empty(a.shape, dtype=np.uint8) for a in arrays]
+        for dst, src in zip(target, arrays):
+            _host_copy(dst, src)
+    _paste_boxes(target, plan, results)
+    return out
 
 
 # ------------------------------------------------------------------------------------------------

@@ -114,6 +114,13 @@ class FaceFixDesc(Record):
                 ("strength", C.c_float), ("mask_offset", C.c_int64), ("taps_offset", C.c_int64), ("bytes_offset", C.c_int64)]
 
 
+class FaceFixPackedDesc(Record):
+    c_name = "vrg_ff_packed_desc"
+    _fields_ = [("src_offset", C.c_int64), ("dst_offset", C.c_int64), ("box_w", C.c_int32), ("box_h", C.c_int32),
+                ("enhanced_index", C.c_int32), ("strength", C.c_float), ("mask_offset", C.c_int64), ("taps_offset", C.c_int64),
+                ("bytes_offset", C.c_int64)]
+
+
 class DetectDesc(Record):
     c_name = "vrg_detect_desc"
     _fields_ = [("frame", C.c_int32), ("transform", C.c_int32), ("left", C.c_int32), ("top", C.c_int32), ("right", C.c_int32),
@@ -250,6 +257,7 @@ ASSEMBLE_MAX_SOURCES = 16       # include/vrgdg_hip.h: VRG_ASSEMBLE_MAX_SOURCES
 ASSEMBLE_BAR = 60               # include/vrgdg_hip.h: VRG_ASSEMBLE_BAR (rows of the label bar)
 ANCHOR_RGB, ANCHOR_BGR = 0, 1      # include/vrgdg_hip.h: VRG_ANCHOR_RGB / VRG_ANCHOR_BGR
 FACEFIX_STATS_WORDS = 12        # uint64 per frame (csrc/vrg_facefix_math.hpp: FF_STATS_WORDS)
+FACEFIX_PACKED_TILE = 256       # include/vrgdg_hip.h: VRG_FF_PACKED_TILE (box pixels of one workgroup)
 
 _F3 = C.c_float * 3
 _P = C.c_void_p
@@ -326,6 +334,11 @@ _SIGNATURES = {
     "vrg_ff_resize_stats_u8": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int64] + [C.c_int32] * 4 +
                                [C.c_int64, C.c_float, _P]),
     "vrg_ff_composite_u8": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
+    "vrg_ff_packed_check": (C.c_int, [_P, C.c_int64, _P] + [C.c_int64] * 6 + [C.c_int32, C.c_int32]),
+    "vrg_lanczos4_packed_u8": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P]),
+    "vrg_ff_packed_resize_stats_u8": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P, C.c_int64, C.c_int64,
+                                                _P, C.c_int64, _P, C.c_int64, _P, C.c_float, _P]),
+    "vrg_ff_packed_composite_u8": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, _P]),
     "vrg_pil_lanczos_ksize": (C.c_int32, [C.c_int32, C.c_int32]),
     "vrg_pil_lanczos_table": (C.c_int, [C.c_int32, C.c_int32, _P, _P]),
     "vrg_pil_box_parameters": (C.c_int, [C.c_float, _P]),

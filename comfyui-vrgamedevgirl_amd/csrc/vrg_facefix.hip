@@ -138,15 +138,7 @@ __global__ __launch_bounds__(256) void k_ff_resize_stats(const uint8_t* __restri
 __global__ __launch_bounds__(256) void k_ff_finish(unsigned long long* __restrict__ stats, int64_t frames, float color_match) {
     const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (f >= frames) return;
-    unsigned long long* rec = stats + f * FF_STATS_WORDS;
-    uint64_t sums[FF_STAT_SUMS];
-#pragma unroll
-    for (int i = 0; i < FF_STAT_SUMS; ++i) sums[i] = rec[i];
-    float shift[3];
-    const bool matched = ff_shifts(sums, color_match, shift);
-    rec[7] = matched ? 1ull : 0ull;
-    rec[8] = (unsigned long long)f32_bits(shift[0]) | ((unsigned long long)f32_bits(shift[1]) << 32);
-    rec[9] = (unsigned long long)f32_bits(shift[2]);
+    ff_finish_record(stats + f * FF_STATS_WORDS, color_match);
 }
 
 // the composite as a policy of move_bytes: the face bytes of the resize scratch, shifted, blended under the float mask and the strength
@@ -165,12 +157,7 @@ struct FfMover {
         fr.shift[0] = fr.shift[1] = fr.shift[2] = 0.0f;
     }
     __device__ __forceinline__ void load_stats(Frame& fr, int64_t f) const {
-        const unsigned long long* rec = stats + f * FF_STATS_WORDS;
-        fr.matched = rec[7] != 0ull;
-        const unsigned long long a = rec[8], b = rec[9];
-        fr.shift[0] = f32_from_bits((uint32_t)a);
-        fr.shift[1] = f32_from_bits((uint32_t)(a >> 32));
-        fr.shift[2] = f32_from_bits((uint32_t)b);
+        fr.matched = ff_read_record(stats + f * FF_STATS_WORDS, fr.shift);
     }
     __device__ __forceinline__ ByteBox box(const Frame& fr) const { return ByteBox{fr.d.left, fr.d.top, fr.d.box_w, fr.d.box_h, g.W}; }
     __device__ __forceinline__ uint8_t byte(const Frame& fr, int32_t r, uint8_t v) const {

@@ -349,6 +349,26 @@ VRG_HD bool ff_shifts(const uint64_t (&sums)[FF_STAT_SUMS], float strength, floa
     return true;
 }
 
+// the last five words of a frame's FF_STATS_WORDS record from its seven sums: matched, the three fp32 shifts
+VRG_HD void ff_finish_record(unsigned long long* rec, float color_match) {
+    uint64_t sums[FF_STAT_SUMS];
+    for (int i = 0; i < FF_STAT_SUMS; ++i) sums[i] = rec[i];
+    float shift[3];
+    const bool matched = ff_shifts(sums, color_match, shift);
+    rec[7] = matched ? 1ull : 0ull;
+    rec[8] = (unsigned long long)f32_bits(shift[0]) | ((unsigned long long)f32_bits(shift[1]) << 32);
+    rec[9] = (unsigned long long)f32_bits(shift[2]);
+}
+
+// ... and read back: -> matched
+VRG_HD bool ff_read_record(const unsigned long long* rec, float (&shift)[3]) {
+    const unsigned long long a = rec[8], b = rec[9];
+    shift[0] = f32_from_bits((uint32_t)a);
+    shift[1] = f32_from_bits((uint32_t)(a >> 32));
+    shift[2] = f32_from_bits((uint32_t)b);
+    return rec[7] != 0ull;
+}
+
 VRG_HD uint8_t ff_trunc_byte(float v) {
     v = v < 0.0f ? 0.0f : (v > 255.0f ? 255.0f : v);
     return (uint8_t)(int32_t)v;

@@ -1,0 +1,212 @@
+// vrg_facefix_packed.hip -- the Builder's Face Fix (csrc/vrg_facefix.hip) for frames that live on the host: only the boxes cross the bus.
+// gfx950 only.  Where a workgroup works and which records it follows: csrc/vrg_facefix_packed_math.hpp; the arithmetic of a pixel is that of
+// the whole-frame kernels (csrc/vrg_facefix_math.hpp, csrc/vrg_lanczos_math.hpp), called with other addresses.
+//
+// Shape of the work.  The host gathers every box into one packed buffer ([box_h][box_w][3] blocks back to back) and uploads it with the
+// records and their tile prefix; the results come back packed the same way.  Each grid is one-dimensional.
+//   k_ffp_lanczos        prepare: thread = one output pixel of one record, lz_pixel on the box's block (row pitch = box_w, so the taps clamp
+//                        to the box by construction).  Every record has out_h * out_w pixels: the workgroup index divides into
+//                        (record, part); no table.
+//   k_ffp_resize_stats   finalize, first half: workgroup = one tile of 256 box pixels, found in the prefix table (ffp_find).  The repaired
+//                        frame resized to the box into the byte scratch; with colour matching the selected count and six byte sums: lane
+//                        values -> wave butterfly -> LDS -> one 64-bit integer atomic per sum and workgroup, as k_ff_resize_stats.
+//   k_ffp_finish         the means and shifts of every record, on the device (ff_finish_record).
+//   k_ffp_composite      finalize, second half: the same tiles; a pixel's three bytes read from the box's block, shifted, blended under
+//                        the mask and written to the block of the packed result.  A record that may not be blended copies its block.
+// All three are tap- or latency-bound on a few hundred KB; nothing here is tuned.
+#include "vrg_facefix_packed_math.hpp"
+#include "vrg_lanczos_math.hpp"
+
+namespace vrg {
+
+__global__ __launch_bounds__(256) void k_ffp_lanczos(const uint8_t* __restrict__ src, const vrg_ff_packed_desc* __restrict__ desc,
+                                                      uint8_t* __restrict__ out, int32_t out_h, int32_t out_w, uint32_t parts,
+                                                      const LzTap* __restrict__ taps, FfpGeom g) {
+    const uint32_t rec = blockIdx.x / parts;                              // < n: the grid is n * parts
+    const int32_t n = out_h * out_w;
+    const int32_t p = (int32_t)((blockIdx.x - rec * parts) * 256 + threadIdx.x);
+    if (p >= n) return;
+    const vrg_ff_packed_desc d = desc[rec];                               // wave-uniform
+    uint8_t* dst = out + ((int64_t)rec * n + p) * 3;
+    uint8_t o[3] = {0, 0, 0};
+    if (ffp_crop_ok(d, g, out_h, out_w)) {
+        const int32_t y = p / out_w, x = p - y * out_w;
+        const uint8_t* box = src + d.src_offset;
+        const int32_t bw = d.box_w;
+        const LzTap cx = taps[d.taps_offset + x], ry = taps[d.taps_offset + out_w + y];
+        lz_pixel(cx, ry, d.box_w, d.box_h, [&](int32_t sy, int32_t sx, int c) { return box[((int64_t)sy * bw + sx) * 3 + c]; }, o);
+    }
+    dst[0] = o[0]; dst[1] = o[1]; dst[2] = o[2];
+}
+
+__global__ __launch_bounds__(256) void k_ffp_resize_stats(const uint8_t* __restrict__ src, const uint8_t* __restrict__ enhanced,
+                                                           const float* __restrict__ masks, const vrg_ff_packed_desc* __restrict__ desc,
+                                                           const int64_t* __restrict__ prefix, const LzTap* __restrict__ taps,
+                                                           uint8_t* __restrict__ bytes, unsigned long long* __restrict__ stats, FfpGeom g,
+                                                           int32_t measure) {
+    const int64_t rec = ffp_find(prefix, g.n, (int64_t)blockIdx.x);
+    const vrg_ff_packed_desc d = desc[rec];                               // workgroup-uniform, and so is every return before the sums
+    if (!ffp_blend_ok(d, g, true) || (measure && !ffp_src_ok(d, g))) return;
+    int64_t p0;
+    int32_t count;
+    if (!ffp_place(d, prefix[rec], (int64_t)blockIdx.x, p0, count)) return;
+    uint32_t acc[FF_STAT_SUMS];
+#pragma unroll
+    for (int i = 0; i < FF_STAT_SUMS; ++i) acc[i] = 0u;
+    if ((int32_t)threadIdx.x < count) {
+        const int64_t p = p0 + threadIdx.x;
+        const int32_t dy = (int32_t)(p / d.box_w), dx = (int32_t)(p - (int64_t)dy * d.box_w);
+        const uint8_t* ef = enhanced + (int64_t)d.enhanced_index * g.enh_h * g.enh_w * 3;
+        const LzTap cx = taps[d.taps_offset + dx], ry = taps[d.taps_offset + d.box_w + dy];
+        uint8_t o[3];
+        const int32_t ew = g.enh_w;
+        lz_pixel(cx, ry, g.enh_w, g.enh_h, [&](int32_t sy, int32_t sx, int c) { return ef[((int64_t)sy * ew + sx) * 3 + c]; }, o);
+        uint8_t* dst = bytes + d.bytes_offset + p * 3;
+        dst[0] = o[0]; dst[1] = o[1]; dst[2] = o[2];
+        if (measure && ff_selected(masks[d.mask_offset + p])) {
+            const uint8_t* t = src + d.src_offset + p * 3;
+            acc[0] = 1u;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                acc[1 + c] = o[c];
+                acc[4 + c] = t[c];
+            }
+        }
+    }
+    if (!measure) return;                                                // uniform
+    __shared__ uint32_t part[4][FF_STAT_SUMS];
+    block_sum_4waves(acc, part);
+    if (threadIdx.x < FF_STAT_SUMS) {
+        const int t = threadIdx.x;
+        const uint32_t s = part[0][t] + part[1][t] + part[2][t] + part[3][t];             // <= 256 * 255
+        if (s) atomicAdd(stats + rec * FF_STATS_WORDS + t, (unsigned long long)s);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_ffp_finish(unsigned long long* __restrict__ stats, int64_t n, float color_match) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    ff_finish_record(stats + i * FF_STATS_WORDS, color_match);
+}
+
+__global__ __launch_bounds__(256) void k_ffp_composite(const uint8_t* __restrict__ src, const float* __restrict__ masks,
+                                                        const vrg_ff_packed_desc* __restrict__ desc, const int64_t* __restrict__ prefix,
+                                                        const uint8_t* __restrict__ bytes, const unsigned long long* __restrict__ stats,
+                                                        uint8_t* __restrict__ out, FfpGeom g) {
+    const int64_t rec = ffp_find(prefix, g.n, (int64_t)blockIdx.x);
+    const vrg_ff_packed_desc d = desc[rec];                               // workgroup-uniform
+    if (!ffp_blocks_ok(d, g)) return;                                     // nowhere to read or to write
+    int64_t p0;
+    int32_t count;
+    if (!ffp_place(d, prefix[rec], (int64_t)blockIdx.x, p0, count) || (int32_t)threadIdx.x >= count) return;
+    const int64_t p = p0 + threadIdx.x;
+    const uint8_t* t = src + d.src_offset + p * 3;
+    uint8_t o[3] = {t[0], t[1], t[2]};
+    if (ffp_blend_ok(d, g, false)) {
+        float shift[3];
+        const bool matched = ff_read_record(stats + rec * FF_STATS_WORDS, shift);
+        const float alpha = masks[d.mask_offset + p];
+        const uint8_t* fb = bytes + d.bytes_offset + p * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            uint8_t face = fb[c];
+            if (matched) face = ff_shift_byte(face, shift[c]);
+            o[c] = ff_blend_byte(o[c], face, alpha, d.strength);
+        }
+    }
+    uint8_t* dst = out + d.dst_offset + p * 3;
+    dst[0] = o[0]; dst[1] = o[1]; dst[2] = o[2];
+}
+
+}  // namespace vrg
+
+using namespace vrg;
+
+namespace {
+
+bool sizes_ok(int64_t n, int64_t src_bytes, int64_t a = 0, int64_t b = 0, int64_t c = 0, int64_t e = 0) {
+    return n >= 0 && src_bytes >= 0 && a >= 0 && b >= 0 && c >= 0 && e >= 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vrg_ff_packed_check(const vrg_ff_packed_desc* desc_host, int64_t n, const int64_t* tile_prefix_host, int64_t src_bytes, int64_t out_bytes,
+                        int64_t enhanced_frames, int64_t mask_floats, int64_t n_taps, int64_t capacity, int32_t out_h, int32_t out_w) {
+    const bool crop = out_h > 0 || out_w > 0;
+    if (!sizes_ok(n, src_bytes, out_bytes, enhanced_frames, mask_floats, n_taps) || capacity < 0 || out_h < 0 || out_w < 0 ||
+        (crop && (out_h < 1 || out_w < 1)))
+        return VRG_ERR_BAD_ARG;
+    if (n == 0) return VRG_OK;
+    if (!desc_host || (!crop && !tile_prefix_host)) return VRG_ERR_BAD_ARG;
+    const FfpGeom g{n, src_bytes, out_bytes, enhanced_frames, mask_floats, n_taps, capacity, 0, 0};
+    for (int64_t i = 0; i < n; ++i) {
+        const vrg_ff_packed_desc& d = desc_host[i];
+        if (crop ? !ffp_crop_ok(d, g, out_h, out_w) : !(ffp_blocks_ok(d, g) && ffp_blend_ok(d, g, true))) return VRG_ERR_BAD_ARG;
+    }
+    if (tile_prefix_host && !ffp_prefix_ok(desc_host, n, tile_prefix_host)) return VRG_ERR_BAD_ARG;
+    return VRG_OK;
+}
+
+int vrg_lanczos4_packed_u8(const uint8_t* src, int64_t src_bytes, const vrg_ff_packed_desc* desc, int64_t n, uint8_t* out, int32_t out_h,
+                           int32_t out_w, const void* taps, int64_t n_taps, void* stream) {
+    if (!src || !out || src == out || !desc || !taps || (reinterpret_cast<uintptr_t>(taps) & 3u) != 0 || !sizes_ok(n, src_bytes, n_taps) ||
+        out_h < 1 || out_w < 1)
+        return VRG_ERR_BAD_ARG;
+    if (n == 0) return VRG_OK;
+    if ((int64_t)out_h * out_w * 3 > 0x7fffffffll) return VRG_ERR_UNSUPPORTED;
+    const int64_t parts = ((int64_t)out_h * out_w + 255) / 256;
+    if (n > 0x7fffffffll / parts) return VRG_ERR_UNSUPPORTED;
+    const FfpGeom g{n, src_bytes, 0, 0, 0, n_taps, 0, 0, 0};
+    hipLaunchKernelGGL(k_ffp_lanczos, dim3((uint32_t)(n * parts)), dim3(256), 0, (hipStream_t)stream, src, desc, out, out_h, out_w,
+                       (uint32_t)parts, reinterpret_cast<const LzTap*>(taps), g);
+    VRG_CHECK_LAUNCH();
+    return VRG_OK;
+}
+
+int vrg_ff_packed_resize_stats_u8(const uint8_t* src, int64_t src_bytes, const uint8_t* enhanced, int64_t enhanced_frames, int32_t enh_h,
+                                  int32_t enh_w, const float* masks, int64_t mask_floats, const vrg_ff_packed_desc* desc,
+                                  const int64_t* tile_prefix, int64_t n, int64_t tiles, const void* taps, int64_t n_taps, uint8_t* bytes,
+                                  int64_t capacity, void* stats, float color_match, void* stream) {
+    if (!sizes_ok(n, src_bytes, enhanced_frames, mask_floats, n_taps, capacity) || tiles < 0) return VRG_ERR_BAD_ARG;
+    if (n == 0) return VRG_OK;
+    if (!src || !enhanced || !masks || !desc || !tile_prefix || (reinterpret_cast<uintptr_t>(tile_prefix) & 7u) != 0 || !taps ||
+        (reinterpret_cast<uintptr_t>(taps) & 3u) != 0 || !bytes || !stats || (reinterpret_cast<uintptr_t>(stats) & 7u) != 0 || bytes == src ||
+        bytes == enhanced || enh_h < 1 || enh_w < 1)
+        return VRG_ERR_BAD_ARG;
+    if ((int64_t)enh_h * enh_w * 3 > 0x7fffffffll || tiles > 0x7fffffffll) return VRG_ERR_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(stats, 0, (size_t)n * FF_STATS_WORDS * sizeof(uint64_t), st) != hipSuccess) return VRG_ERR_LAUNCH;
+    const FfpGeom g{n, src_bytes, 0, enhanced_frames, mask_floats, n_taps, capacity, enh_h, enh_w};
+    const int32_t measure = color_match > 0.0f ? 1 : 0;
+    if (tiles > 0) {
+        hipLaunchKernelGGL(k_ffp_resize_stats, dim3((uint32_t)tiles), dim3(256), 0, st, src, enhanced, masks, desc, tile_prefix,
+                           reinterpret_cast<const LzTap*>(taps), bytes, (unsigned long long*)stats, g, measure);
+        VRG_CHECK_LAUNCH();
+    }
+    if (measure) {
+        hipLaunchKernelGGL(k_ffp_finish, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, (unsigned long long*)stats, n, color_match);
+        VRG_CHECK_LAUNCH();
+    }
+    return VRG_OK;
+}
+
+int vrg_ff_packed_composite_u8(const uint8_t* src, int64_t src_bytes, const float* masks, int64_t mask_floats, const vrg_ff_packed_desc* desc,
+                               const int64_t* tile_prefix, int64_t n, int64_t tiles, const uint8_t* bytes, int64_t capacity, const void* stats,
+                               uint8_t* out, int64_t out_bytes, void* stream) {
+    if (!sizes_ok(n, src_bytes, mask_floats, capacity, out_bytes) || tiles < 0) return VRG_ERR_BAD_ARG;
+    if (n == 0) return VRG_OK;
+    if (!src || !masks || !desc || !tile_prefix || (reinterpret_cast<uintptr_t>(tile_prefix) & 7u) != 0 || !bytes || !stats ||
+        (reinterpret_cast<uintptr_t>(stats) & 7u) != 0 || !out || out == src || out == bytes)
+        return VRG_ERR_BAD_ARG;
+    if (tiles > 0x7fffffffll) return VRG_ERR_UNSUPPORTED;
+    if (tiles == 0) return VRG_OK;
+    const FfpGeom g{n, src_bytes, out_bytes, 0, mask_floats, 0, capacity, 0, 0};
+    hipLaunchKernelGGL(k_ffp_composite, dim3((uint32_t)tiles), dim3(256), 0, (hipStream_t)stream, src, masks, desc, tile_prefix, bytes,
+                       (const unsigned long long*)stats, out, g);
+    VRG_CHECK_LAUNCH();
+    return VRG_OK;
+}
+
+}  // extern "C"

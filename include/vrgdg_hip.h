@@ -609,6 +609,56 @@ int vrg_ff_composite_u8(const uint8_t* originals, const float* masks, int64_t ma
                         int64_t capacity, const void* stats, uint8_t* out, int64_t frames, int32_t height, int32_t width, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The same pixels for frames that live on the HOST (csrc/vrg_facefix_packed.hip): only the boxes cross the bus.  `src` is one buffer of
+ * `src_bytes` bytes that holds each box's original bytes as a dense [box_h][box_w][3] block at its record's src_offset; the composite
+ * writes each box's result as such a block at dst_offset of `out` (`out_bytes` bytes).  The masks, the Lanczos records, the byte scratch
+ * and the statistics are those of the entry points above; `stats` holds 12 uint64 per RECORD.
+ *
+ * Grids are one-dimensional.  A workgroup of the statistics and composite launches is one tile of VRG_FF_PACKED_TILE box pixels; it
+ * finds its record in `tile_prefix` (device, n + 1 int64, 8-byte aligned): tile_prefix[i] = the first tile of record i,
+ * tile_prefix[n] = `tiles`, the grid.  vrg_lanczos4_packed_u8 writes out_h * out_w pixels for every record, so its workgroups divide.
+ *
+ * vrg_ff_packed_check refuses ON THE HOST (VRG_ERR_BAD_ARG) what the launches do not follow: a box below 1 x 1 or of 2^31 bytes or more,
+ * a span (src, taps; and for the composite dst, mask, bytes) that leaves the stated sizes, an enhanced_index outside enhanced_frames,
+ * a strength that is not > 0, a tile_prefix that is not the running sum of ceil(box_w * box_h / 256) from 0.  out_h, out_w >= 1: the
+ * records of vrg_lanczos4_packed_u8 (taps: out_w + out_h records; tile_prefix may be NULL; dst, mask, bytes, strength, enhanced_index
+ * are not read).  out_h == out_w == 0: the records of the other two (taps: box_w + box_h records).  n == 0 is fine.
+ * On the device a record that fails these checks writes zeros (vrg_lanczos4_packed_u8), is skipped (statistics), or -- where its src
+ * and dst blocks lie inside the buffers -- comes out as a copy of its original bytes (composite; otherwise nothing is written).
+ * ------------------------------------------------------------------------------------------- */
+#define VRG_FF_PACKED_TILE 256
+
+typedef struct vrg_ff_packed_desc {
+    int64_t src_offset;                /* bytes from `src` to the box's [box_h][box_w][3] original bytes */
+    int64_t dst_offset;                /* bytes from `out` of the composite to the box's [box_h][box_w][3] result */
+    int32_t box_w, box_h;
+    int32_t enhanced_index;
+    float strength;                    /* composite_strength in (0, 1] */
+    int64_t mask_offset;               /* floats from `masks` to the [box_h][box_w] mask */
+    int64_t taps_offset;               /* records from `taps`: (box_h, box_w) -> (out_h, out_w), or (enh_h, enh_w) -> (box_h, box_w) */
+    int64_t bytes_offset;              /* bytes from `bytes` to this record's [box_h][box_w][3] resized face */
+} vrg_ff_packed_desc;
+
+int vrg_ff_packed_check(const vrg_ff_packed_desc* desc_host, int64_t n, const int64_t* tile_prefix_host, int64_t src_bytes, int64_t out_bytes,
+                        int64_t enhanced_frames, int64_t mask_floats, int64_t n_taps, int64_t capacity, int32_t out_h, int32_t out_w);
+
+/* out[i] = cv2.resize(box i, (out_w, out_h), INTER_LANCZOS4) for n records ([n][out_h][out_w][3]), one launch; taps clamp to the box. */
+int vrg_lanczos4_packed_u8(const uint8_t* src, int64_t src_bytes, const vrg_ff_packed_desc* desc, int64_t n, uint8_t* out, int32_t out_h,
+                           int32_t out_w, const void* taps, int64_t n_taps, void* stream);
+
+/* enhanced[enhanced_index] ([enhanced_frames][enh_h][enh_w][3]) resized to the box into `bytes`, and -- when color_match > 0 -- stats[i]
+ * in the layout of vrg_ff_resize_stats_u8 (zeroed here; the means and shifts are finished on the device). */
+int vrg_ff_packed_resize_stats_u8(const uint8_t* src, int64_t src_bytes, const uint8_t* enhanced, int64_t enhanced_frames, int32_t enh_h,
+                                  int32_t enh_w, const float* masks, int64_t mask_floats, const vrg_ff_packed_desc* desc,
+                                  const int64_t* tile_prefix, int64_t n, int64_t tiles, const void* taps, int64_t n_taps, uint8_t* bytes,
+                                  int64_t capacity, void* stats, float color_match, void* stream);
+
+/* out[dst_offset ..] = the composite of vrg_ff_composite_u8 inside the box, for every record.  out != src, which is never written. */
+int vrg_ff_packed_composite_u8(const uint8_t* src, int64_t src_bytes, const float* masks, int64_t mask_floats, const vrg_ff_packed_desc* desc,
+                               const int64_t* tile_prefix, int64_t n, int64_t tiles, const uint8_t* bytes, int64_t capacity, const void* stats,
+                               uint8_t* out, int64_t out_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The input of the Face Fix face detector (`_detect_with_rotation` / `_detect`, VRGDG_StandaloneFaceFixNodes.py:95-185 and
  * VRGDG_FaceFix.py:67-157 of the reference), restated in csrc/vrg_detect_math.hpp: frames quantised to B,G,R bytes, rotated about the frame
  * centre (cv2.warpAffine, INTER_LINEAR, BORDER_REPLICATE, the classic fixed-point path), cut into regions, each resized to 300 x 300
