@@ -565,9 +565,18 @@ class _Pending:
             _LAZY.enforce(self)                   # this result holds HBM now: older ones may have to go to the host (outside the locks)
         return pieces
 
+    def _order_after_recipe(self):
+        """A device-resident result is read where it lies: the reader's current stream waits for the recipe, which may have run on another
+        thread under that thread's stream."""
+        if self.host.is_cuda and self.pieces:
+            cur = torch.cuda.current_stream(self.device)
+            for _s, _e, _gpu, ran in self.pieces:
+                cur.wait_event(ran)
+
     def materialise(self):
         with _STAGING.lock, self.lock:   # (self.host is the plain tensor under the LazyFrames: nothing in here re-enters __torch_function__)
             if self.done:
+                self._order_after_recipe()
                 _LAZY.forget(self)
                 return
             # the buffer was created where the node ran -- under ComfyUI inside torch.inference_mode() -- and is written here, possibly from
@@ -577,6 +586,7 @@ class _Pending:
                     self._run_recipe(to_host=True)
                 if not self.host.is_cuda and not self._on_host:
                     self._download()
+            self._order_after_recipe()
             self.done = True
         _LAZY.forget(self)
         owner = self.owner() if self.owner is not None else None

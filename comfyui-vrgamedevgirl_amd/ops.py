@@ -420,7 +420,9 @@ _lanczos_tables: dict = {}      # (in_h, in_w, out_h, out_w, device) -> the uplo
 
 def _uploaded(cache: dict, key, build, device) -> torch.Tensor:
     """``cache[key]``: on a miss the table of ``build()`` (a numpy array of records), uploaded to ``device`` as bytes.  A cache that holds 64 tables is
-    cleared first: a handful of geometries per job; never grows without bound."""
+    cleared first: a handful of geometries per job; never grows without bound.  The table is marked as used on the caller's current stream:
+    a cache cleared under another stream drops it while this caller's launch may still be queued, and the allocator then keeps the block
+    until that launch is done."""
     t = cache.get(key)
     if t is None:
         t = _hip.upload_records(build(), device)
@@ -428,6 +430,8 @@ def _uploaded(cache: dict, key, build, device) -> torch.Tensor:
             if len(cache) >= 64:
                 cache.clear()
             cache[key] = t
+    if t.is_cuda:
+        t.record_stream(torch.cuda.current_stream(t.device))
     return t
 
 
@@ -1716,6 +1720,8 @@ def _grid_table(n_in, n_out, mode, table, device) -> torch.Tensor:
             while len(_grid_tables) >= 256:
                 _grid_tables.pop(next(iter(_grid_tables)))
             _grid_tables[key] = t
+    if t.is_cuda:
+        t.record_stream(torch.cuda.current_stream(t.device))          # as in _uploaded: an evicted table outlives the launches that read it
     return t
 
 
