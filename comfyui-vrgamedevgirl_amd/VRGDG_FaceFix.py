@@ -71,11 +71,16 @@ def _square_crop_box(face_box, width, height, padding):
     return (max(0, left), max(0, top), min(width, right), min(height, bottom))
 
 
+def _blend_settings(feather, color_match):
+    """(feather, color_match) clamped as finalize_face_fix clamps them (:930-931)"""
+    return max(0, min(256, int(feather))), max(0.0, min(1.0, float(color_match)))
+
+
 def settings_from_payload(payload) -> dict:
     """``feather`` and ``color_match`` as finalize_face_fix reads them (:930-931): a missing or zero value falls back to the default
     (the reference's ``or``), then the clamp."""
-    return {"feather": max(0, min(256, int(payload.get("feather") or DEFAULT_FEATHER))),
-            "color_match": max(0.0, min(1.0, float(payload.get("color_match") or DEFAULT_COLOR_MATCH)))}
+    feather, color_match = _blend_settings(payload.get("feather") or DEFAULT_FEATHER, payload.get("color_match") or DEFAULT_COLOR_MATCH)
+    return {"feather": feather, "color_match": color_match}
 
 
 def ellipse_spans(width: int, height: int) -> np.ndarray:
@@ -167,6 +172,13 @@ def _boxes(crop_boxes, frames, height, width):
     return out
 
 
+def _active(boxes, strengths=None):
+    """[(frame, box_index, box, strength)] of the ACTIVE frames, in frame order: a box, and strength > 0 where strengths are given (1.0
+    without); ``box_index`` = the frame's position among the frames that have a box"""
+    with_box = [f for f, box in enumerate(boxes) if box is not None]
+    return [(f, k, boxes[f], 1.0 if strengths is None else strengths[f]) for k, f in enumerate(with_box) if strengths is None or strengths[f] > 0.0]
+
+
 def _tap_tables(sizes, in_size_of, out_size_of):
     """the concatenated Lanczos records of the distinct sizes: -> (table, {size: offset in records})"""
     offsets, parts, total = {}, [], 0
@@ -219,6 +231,12 @@ def _mask_tables(sizes, feather):
     return np.concatenate(spans), np.array(records, dtype=_MASK_DESC), offsets, total, largest
 
 
+def _composite_tables(boxes, enh_size, feather):
+    """active ``boxes`` (left, top, w, h), repaired frames of ``enh_size`` (height, width) -> (spans, mask records, mask offsets, mask_floats,
+    largest, tap table, tap offsets)"""
+    return (*_mask_tables([(b[2], b[3]) for b in boxes] or [(1, 1)], feather), *_tap_tables([(b[3], b[2]) for b in boxes], lambda s: enh_size, lambda s: s))
+
+
 def _run_masks(spans, records, total, largest, feather, device):
     """the launches of vrg_ff_masks_f32 -> the packed masks on the device"""
     masks = torch.empty(max(total, 1), dtype=torch.float32, device=device)
@@ -257,8 +275,7 @@ def composite_frames(originals_u8, enhanced_u8, crop_boxes, strengths, feather=D
     original frame) resized to its box, colour matched, blended under the soft ellipse times ``strengths[f]`` and pasted into a copy of
     ``originals_u8``, which is never written.  Frames without a box or with strength <= 0 come back unchanged.  The result has the shape
     and the form of ``originals_u8``."""
-    feather = max(0, min(256, int(feather)))
-    color_match = max(0.0, min(1.0, float(color_match)))
+    feather, color_match = _blend_settings(feather, color_match)
     boxes = _boxes(crop_boxes, *_peek(originals_u8, "originals"))
     strength = _strengths(strengths, len(boxes))
     x, back = _frames_in(originals_u8, "originals")
@@ -288,21 +305,13 @@ class CompositePlan:
 
     def __init__(self, x, e, boxes, strength, per_box, feather, color_match):
         self.x, self.e, self.feather, self.color_match = x, e, feather, color_match
-        F, EH, EW = int(x.shape[0]), int(e.shape[1]), int(e.shape[2])
+        F, active = int(x.shape[0]), _active(boxes, strength)
         desc = np.zeros(F, dtype=_FF_DESC)
-        active, k = [], 0
-        for f, box in enumerate(boxes):
-            if box is None:
-                continue
-            index, k = (k if per_box else f), k + 1
-            if strength[f] > 0.0:
-                active.append((f, index, box))
-        sizes = [(b[2], b[3]) for _, _, b in active] or [(1, 1)]
-        self.spans, self.records, mask_offsets, self.mask_floats, self.largest = _mask_tables(sizes, feather)
-        table, tap_offsets = _tap_tables([(b[3], b[2]) for _, _, b in active], lambda s: (EH, EW), lambda s: s)
+        self.spans, self.records, mask_offsets, self.mask_floats, self.largest, table, tap_offsets = _composite_tables(
+            [a[2] for a in active], (int(e.shape[1]), int(e.shape[2])), feather)
         capacity = 0
-        for f, index, (left, top, w, h) in active:
-            desc[f] = (index, left, top, w, h, strength[f], mask_offsets[(w, h)], tap_offsets[(h, w)], capacity)
+        for f, index, (left, top, w, h), s in active:
+            desc[f] = (index if per_box else f, left, top, w, h, s, mask_offsets[(w, h)], tap_offsets[(h, w)], capacity)
             capacity += w * h * 3
         self.capacity, self.n_taps, self.active = capacity, len(table), len(active)
         self.taps, self.desc = _upload(table, x.device), _upload(desc, x.device)
@@ -360,16 +369,8 @@ def packed_plan(frames, height, width, crop_boxes, strengths=None) -> PackedPlan
     ValueErrors), ``strengths`` as ``composite_frames`` takes them or None (a crop: every box is active).  No pixels, no device."""
     frames, height, width = int(frames), int(height), int(width)
     boxes = _boxes(crop_boxes, frames, height, width)
-    strength = None if strengths is None else _strengths(strengths, frames)
-    used, k = [], 0
-    for f, box in enumerate(boxes):
-        if box is None:
-            continue
-        index, k = k, k + 1
-        s = 1.0 if strength is None else strength[f]
-        if s > 0.0:
-            used.append((f, index, box, s))
-    return PackedPlan([u[0] for u in used], [u[1] for u in used], [u[2] for u in used], [u[3] for u in used], k, frames * height * width * 3)
+    used = _active(boxes, None if strengths is None else _strengths(strengths, frames))
+    return PackedPlan(*([u[i] for u in used] for i in range(4)), sum(b is not None for b in boxes), frames * height * width * 3)
 
 
 def last_transfer() -> dict:
@@ -446,8 +447,7 @@ def composite_boxes_packed(originals_u8, enhanced_u8, crop_boxes, strengths, fea
     """The pixels of ``composite_frames`` for frames on the host, boxes only: the active boxes of ``originals_u8`` and their repaired
     frames go up in one page-locked buffer, the composited boxes come down in one -> one ``[h, w, 3]`` array per active frame, in the
     order of ``packed_plan(...).frames`` (views of the download).  Nothing outside a box crosses the bus; no input is written."""
-    feather = max(0, min(256, int(feather)))
-    color_match = max(0.0, min(1.0, float(color_match)))
+    feather, color_match = _blend_settings(feather, color_match)
     arrays = _host_arrays(originals_u8, "originals", "composite_frames")
     F, H, W = _peek(originals_u8, "originals")
     plan = packed_plan(F, H, W, crop_boxes, strengths)
@@ -466,8 +466,7 @@ def composite_boxes_packed(originals_u8, enhanced_u8, crop_boxes, strengths, fea
     _pack_boxes(arrays, plan, staged)
     for i, pick in enumerate(picks):                                        # the repaired frame of record i is frame i of the upload
         staged[enh_at + i * enh_bytes:enh_at + (i + 1) * enh_bytes].reshape(EH, EW, 3)[...] = enhanced[pick]
-    spans, records, mask_offsets, mask_floats, largest = _mask_tables([(b[2], b[3]) for b in plan.boxes], feather)
-    table, tap_offsets = _tap_tables([(b[3], b[2]) for b in plan.boxes], lambda s: (EH, EW), lambda s: s)
+    spans, records, mask_offsets, mask_floats, largest, table, tap_offsets = _composite_tables(plan.boxes, (EH, EW), feather)
     desc = np.zeros(n, dtype=_PACKED_DESC)
     for i, ((_, _, w, h), offset, s) in enumerate(zip(plan.boxes, plan.offsets, plan.strengths)):
         desc[i] = (offset, offset, w, h, i, s, mask_offsets[(w, h)], tap_offsets[(h, w)], offset)

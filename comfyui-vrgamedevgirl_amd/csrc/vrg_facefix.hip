@@ -1,5 +1,6 @@
 // vrg_facefix.hip -- the pixels of the AI Video Builder's Face Fix (reference VRGDG_FaceFix.py: prepare_face_fix :473-476,
-// finalize_face_fix :937-957) on decoded B,G,R bytes.  gfx950 only.  Arithmetic: csrc/vrg_facefix_math.hpp, csrc/vrg_lanczos_math.hpp.
+// finalize_face_fix :937-957) on decoded B,G,R bytes.  gfx950 only.  Arithmetic: csrc/vrg_facefix_math.hpp, csrc/vrg_lanczos_math.hpp; the
+// body of a pixel, a byte, a record check and a workgroup's sums is csrc/vrg_facefix_body.hpp, shared with csrc/vrg_facefix_packed.hip.
 //
 // Shape of the work.  A job is a batch of byte frames and one square box per frame, a few per cent of a 4K frame up to all of its height.
 //   k_lanczos4_boxes     prepare: one launch, blockIdx.y = the output frame, so its record (source frame, box, where its Lanczos records
@@ -12,14 +13,13 @@
 //   k_ff_resize_stats    finalize, first half: the repaired frame resized to its box (lz_pixel again) into a packed byte scratch, and in
 //                        the same launch the selected count and six byte sums of the frame: lane values -> wave butterfly -> LDS -> one
 //                        64-bit integer atomic per sum and workgroup (integer addition: the same bits in any order).
-//   k_ff_finish          the means and shifts of every frame, on the device: the host never waits.
+//   k_ff_finish          the means and shifts of every record, on the device: the host never waits.  Both routes launch it (ff_stats_end).
 //   k_ff_composite       finalize, second half: ONE pass over the output batch as a flat run of bytes, 16 per thread.  A piece that
 //                        misses the box (nearly all of a frame) is one 16-byte non-temporal load and store; a piece that touches it is
 //                        rebuilt byte by byte in registers; pieces that cross a frame boundary or are not 16-byte aligned go byte by byte
 //                        (move_bytes of csrc/vrg_byte_mover.hpp, shared with the far-face paste).
 #include "vrg_byte_mover.hpp"
-#include "vrg_facefix_math.hpp"
-#include "vrg_lanczos_math.hpp"
+#include "vrg_facefix_body.hpp"
 
 namespace vrg {
 
@@ -35,15 +35,11 @@ __device__ __forceinline__ bool ff_box_ok(const vrg_ff_box_desc& d, int64_t in_f
     return span_fits(d.taps_offset, (int64_t)out_w + out_h, n_taps);
 }
 
-// the record of the composite: `resized` = the checks of the passes that read the resize source as well
+// the record of the composite: the box inside the frame, and ff_blend_ok
 __device__ __forceinline__ bool ff_desc_ok(const vrg_ff_desc& d, const FfGeom& g, bool resized) {
-    if (!(d.strength > 0.0f) || d.left < 0 || d.top < 0 || d.box_w < 1 || d.box_h < 1) return false;
+    if (d.left < 0 || d.top < 0 || d.box_w < 1 || d.box_h < 1) return false;
     if ((int64_t)d.left + d.box_w > g.W || (int64_t)d.top + d.box_h > g.H) return false;
-    const int64_t px = (int64_t)d.box_w * d.box_h;
-    if (!span_fits(d.mask_offset, px, g.mask_floats) || !span_fits(d.bytes_offset, px * 3, g.capacity)) return false;
-    if (!resized) return true;
-    if (d.enhanced_index < 0 || d.enhanced_index >= g.enhanced_frames) return false;
-    return span_fits(d.taps_offset, (int64_t)d.box_w + d.box_h, g.n_taps);
+    return ff_blend_ok(d, g, (int64_t)d.box_w * d.box_h, resized);
 }
 
 __global__ __launch_bounds__(256) void k_lanczos4_boxes(const uint8_t* __restrict__ in, int64_t in_frames, int32_t H, int32_t W,
@@ -57,9 +53,8 @@ __global__ __launch_bounds__(256) void k_lanczos4_boxes(const uint8_t* __restric
     uint8_t o[3] = {0, 0, 0};
     if (ff_box_ok(d, in_frames, H, W, n_taps, out_h, out_w)) {
         const int32_t y = p / out_w, x = p - y * out_w;
-        const uint8_t* box = in + (((int64_t)d.frame * H + d.top) * W + d.left) * 3;
-        const LzTap cx = taps[d.taps_offset + x], ry = taps[d.taps_offset + out_w + y];
-        lz_pixel(cx, ry, d.box_w, d.box_h, [&](int32_t sy, int32_t sx, int c) { return box[((int64_t)sy * W + sx) * 3 + c]; }, o);
+        ff_crop_pixel(in + (((int64_t)d.frame * H + d.top) * W + d.left) * 3, W, d.box_w, d.box_h, taps[d.taps_offset + x],
+                      taps[d.taps_offset + out_w + y], o);
     }
     dst[0] = o[0]; dst[1] = o[1]; dst[2] = o[2];
 }
@@ -103,36 +98,14 @@ __global__ __launch_bounds__(256) void k_ff_resize_stats(const uint8_t* __restri
     const int64_t n = (int64_t)d.box_w * d.box_h;
     if ((int64_t)blockIdx.x * 256 >= n) return;
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    uint32_t acc[FF_STAT_SUMS];
-#pragma unroll
-    for (int i = 0; i < FF_STAT_SUMS; ++i) acc[i] = 0u;
+    uint32_t acc[FF_STAT_SUMS] = {};
     if (p < n) {
         const int32_t dy = (int32_t)(p / d.box_w), dx = (int32_t)(p - (int64_t)dy * d.box_w);
-        const uint8_t* ef = enhanced + (int64_t)d.enhanced_index * g.enh_h * g.enh_w * 3;
-        const LzTap cx = taps[d.taps_offset + dx], ry = taps[d.taps_offset + d.box_w + dy];
-        uint8_t o[3];
-        const int32_t ew = g.enh_w;
-        lz_pixel(cx, ry, g.enh_w, g.enh_h, [&](int32_t sy, int32_t sx, int c) { return ef[((int64_t)sy * ew + sx) * 3 + c]; }, o);
-        uint8_t* dst = bytes + d.bytes_offset + p * 3;
-        dst[0] = o[0]; dst[1] = o[1]; dst[2] = o[2];
-        if (measure && ff_selected(masks[d.mask_offset + p])) {
-            const uint8_t* t = originals + ((f * g.H + d.top + dy) * (int64_t)g.W + d.left + dx) * 3;
-            acc[0] = 1u;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                acc[1 + c] = o[c];
-                acc[4 + c] = t[c];
-            }
-        }
+        ff_resize_pixel(enhanced + (int64_t)d.enhanced_index * g.enh_h * g.enh_w * 3, g.enh_h, g.enh_w, taps[d.taps_offset + dx],
+                        taps[d.taps_offset + d.box_w + dy], bytes + d.bytes_offset + p * 3, masks + d.mask_offset + p,
+                        originals + ((f * g.H + d.top + dy) * (int64_t)g.W + d.left + dx) * 3, measure, acc);
     }
-    if (!measure) return;                                                // uniform
-    __shared__ uint32_t part[4][FF_STAT_SUMS];
-    block_sum_4waves(acc, part);
-    if (threadIdx.x < FF_STAT_SUMS) {
-        const int t = threadIdx.x;
-        const uint32_t s = part[0][t] + part[1][t] + part[2][t] + part[3][t];             // <= 256 * 255
-        if (s) atomicAdd(stats + f * FF_STATS_WORDS + t, (unsigned long long)s);
-    }
+    if (measure) ff_block_stats(acc, stats + f * FF_STATS_WORDS);       // uniform
 }
 
 __global__ __launch_bounds__(256) void k_ff_finish(unsigned long long* __restrict__ stats, int64_t frames, float color_match) {
@@ -164,9 +137,7 @@ struct FfMover {
         int64_t i;
         int32_t c;
         if (!byte_in_box(box(fr), r, i, c)) return v;
-        uint8_t face = bytes[fr.d.bytes_offset + i * 3 + c];
-        if (fr.matched) face = ff_shift_byte(face, fr.shift[c]);
-        return ff_blend_byte(v, face, masks[fr.d.mask_offset + i], fr.d.strength);
+        return ff_composite_byte(v, bytes[fr.d.bytes_offset + i * 3 + c], fr.matched, fr.shift[c], masks[fr.d.mask_offset + i], fr.d.strength);
     }
 };
 
@@ -175,6 +146,17 @@ __global__ __launch_bounds__(256) void k_ff_composite(const uint8_t* __restrict_
                                                        const unsigned long long* __restrict__ stats, uint8_t* __restrict__ out, FfGeom g,
                                                        int64_t frame_bytes, int64_t total, int32_t aligned) {
     move_bytes(FfMover{masks, desc, bytes, stats, g}, originals, out, frame_bytes, total, aligned);
+}
+
+int ff_stats_begin(void* stats, int64_t n, void* stream) {
+    return hipMemsetAsync(stats, 0, (size_t)n * FF_STATS_WORDS * sizeof(uint64_t), (hipStream_t)stream) == hipSuccess ? VRG_OK : VRG_ERR_LAUNCH;
+}
+
+int ff_stats_end(void* stats, int64_t n, float color_match, void* stream) {
+    if (!(color_match > 0.0f)) return VRG_OK;
+    hipLaunchKernelGGL(k_ff_finish, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (unsigned long long*)stats, n, color_match);
+    VRG_CHECK_LAUNCH();
+    return VRG_OK;
 }
 
 }  // namespace vrg
@@ -245,25 +227,21 @@ int vrg_ff_resize_stats_u8(const uint8_t* originals, const uint8_t* enhanced, co
         return VRG_ERR_BAD_ARG;
     if ((int64_t)height * width * 3 > 0x7fffffffll || (int64_t)enh_h * enh_w * 3 > 0x7fffffffll || max_box_pixels > 0x7fffffffll)
         return VRG_ERR_UNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(stats, 0, (size_t)frames * FF_STATS_WORDS * sizeof(uint64_t), st) != hipSuccess) return VRG_ERR_LAUNCH;
+    int rc = ff_stats_begin(stats, frames, stream);
+    if (rc != VRG_OK) return rc;
     const FfGeom g{frames, enhanced_frames, mask_floats, n_taps, capacity, height, width, enh_h, enh_w};
     const int32_t measure = color_match > 0.0f ? 1 : 0;
     if (max_box_pixels > 0) {
         const uint32_t parts = (uint32_t)((max_box_pixels + 255) / 256);
-        const int rc = launch_chunks(frames, [&](int64_t f0, int64_t nf) {
-            hipLaunchKernelGGL(k_ff_resize_stats, dim3(parts, (uint32_t)nf), dim3(256), 0, st, originals, enhanced, masks, desc,
+        rc = launch_chunks(frames, [&](int64_t f0, int64_t nf) {
+            hipLaunchKernelGGL(k_ff_resize_stats, dim3(parts, (uint32_t)nf), dim3(256), 0, (hipStream_t)stream, originals, enhanced, masks, desc,
                                reinterpret_cast<const LzTap*>(taps), bytes, (unsigned long long*)stats, g, f0, measure);
             VRG_CHECK_LAUNCH();
             return VRG_OK;
         });
         if (rc != VRG_OK) return rc;
     }
-    if (measure) {
-        hipLaunchKernelGGL(k_ff_finish, dim3((uint32_t)((frames + 255) / 256)), dim3(256), 0, st, (unsigned long long*)stats, frames, color_match);
-        VRG_CHECK_LAUNCH();
-    }
-    return VRG_OK;
+    return ff_stats_end(stats, frames, color_match, stream);
 }
 
 int vrg_ff_composite_u8(const uint8_t* originals, const float* masks, int64_t mask_floats, const vrg_ff_desc* desc, const uint8_t* bytes,

@@ -1,6 +1,6 @@
 // vrg_facefix_packed.hip -- the Builder's Face Fix (csrc/vrg_facefix.hip) for frames that live on the host: only the boxes cross the bus.
-// gfx950 only.  Where a workgroup works and which records it follows: csrc/vrg_facefix_packed_math.hpp; the arithmetic of a pixel is that of
-// the whole-frame kernels (csrc/vrg_facefix_math.hpp, csrc/vrg_lanczos_math.hpp), called with other addresses.
+// gfx950 only.  Where a workgroup works and which records it follows: csrc/vrg_facefix_packed_math.hpp; what it does to a pixel, a byte
+// and its sums is csrc/vrg_facefix_body.hpp, the body of the whole-frame kernels, called with other addresses.
 //
 // Shape of the work.  The host gathers every box into one packed buffer ([box_h][box_w][3] blocks back to back) and uploads it with the
 // records and their tile prefix; the results come back packed the same way.  Each grid is one-dimensional.
@@ -10,12 +10,11 @@
 //   k_ffp_resize_stats   finalize, first half: workgroup = one tile of 256 box pixels, found in the prefix table (ffp_find).  The repaired
 //                        frame resized to the box into the byte scratch; with colour matching the selected count and six byte sums: lane
 //                        values -> wave butterfly -> LDS -> one 64-bit integer atomic per sum and workgroup, as k_ff_resize_stats.
-//   k_ffp_finish         the means and shifts of every record, on the device (ff_finish_record).
+//                        The means and shifts of every record follow on the device: k_ff_finish of csrc/vrg_facefix.hip (ff_stats_end).
 //   k_ffp_composite      finalize, second half: the same tiles; a pixel's three bytes read from the box's block, shifted, blended under
 //                        the mask and written to the block of the packed result.  A record that may not be blended copies its block.
 // All three are tap- or latency-bound on a few hundred KB; nothing here is tuned.
 #include "vrg_facefix_packed_math.hpp"
-#include "vrg_lanczos_math.hpp"
 
 namespace vrg {
 
@@ -31,10 +30,7 @@ __global__ __launch_bounds__(256) void k_ffp_lanczos(const uint8_t* __restrict__
     uint8_t o[3] = {0, 0, 0};
     if (ffp_crop_ok(d, g, out_h, out_w)) {
         const int32_t y = p / out_w, x = p - y * out_w;
-        const uint8_t* box = src + d.src_offset;
-        const int32_t bw = d.box_w;
-        const LzTap cx = taps[d.taps_offset + x], ry = taps[d.taps_offset + out_w + y];
-        lz_pixel(cx, ry, d.box_w, d.box_h, [&](int32_t sy, int32_t sx, int c) { return box[((int64_t)sy * bw + sx) * 3 + c]; }, o);
+        ff_crop_pixel(src + d.src_offset, d.box_w, d.box_w, d.box_h, taps[d.taps_offset + x], taps[d.taps_offset + out_w + y], o);
     }
     dst[0] = o[0]; dst[1] = o[1]; dst[2] = o[2];
 }
@@ -50,43 +46,15 @@ __global__ __launch_bounds__(256) void k_ffp_resize_stats(const uint8_t* __restr
     int64_t p0;
     int32_t count;
     if (!ffp_place(d, prefix[rec], (int64_t)blockIdx.x, p0, count)) return;
-    uint32_t acc[FF_STAT_SUMS];
-#pragma unroll
-    for (int i = 0; i < FF_STAT_SUMS; ++i) acc[i] = 0u;
+    uint32_t acc[FF_STAT_SUMS] = {};
     if ((int32_t)threadIdx.x < count) {
         const int64_t p = p0 + threadIdx.x;
         const int32_t dy = (int32_t)(p / d.box_w), dx = (int32_t)(p - (int64_t)dy * d.box_w);
-        const uint8_t* ef = enhanced + (int64_t)d.enhanced_index * g.enh_h * g.enh_w * 3;
-        const LzTap cx = taps[d.taps_offset + dx], ry = taps[d.taps_offset + d.box_w + dy];
-        uint8_t o[3];
-        const int32_t ew = g.enh_w;
-        lz_pixel(cx, ry, g.enh_w, g.enh_h, [&](int32_t sy, int32_t sx, int c) { return ef[((int64_t)sy * ew + sx) * 3 + c]; }, o);
-        uint8_t* dst = bytes + d.bytes_offset + p * 3;
-        dst[0] = o[0]; dst[1] = o[1]; dst[2] = o[2];
-        if (measure && ff_selected(masks[d.mask_offset + p])) {
-            const uint8_t* t = src + d.src_offset + p * 3;
-            acc[0] = 1u;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                acc[1 + c] = o[c];
-                acc[4 + c] = t[c];
-            }
-        }
+        ff_resize_pixel(enhanced + (int64_t)d.enhanced_index * g.enh_h * g.enh_w * 3, g.enh_h, g.enh_w, taps[d.taps_offset + dx],
+                        taps[d.taps_offset + d.box_w + dy], bytes + d.bytes_offset + p * 3, masks + d.mask_offset + p,
+                        src + d.src_offset + p * 3, measure, acc);
     }
-    if (!measure) return;                                                // uniform
-    __shared__ uint32_t part[4][FF_STAT_SUMS];
-    block_sum_4waves(acc, part);
-    if (threadIdx.x < FF_STAT_SUMS) {
-        const int t = threadIdx.x;
-        const uint32_t s = part[0][t] + part[1][t] + part[2][t] + part[3][t];             // <= 256 * 255
-        if (s) atomicAdd(stats + rec * FF_STATS_WORDS + t, (unsigned long long)s);
-    }
-}
-
-__global__ __launch_bounds__(256) void k_ffp_finish(unsigned long long* __restrict__ stats, int64_t n, float color_match) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    ff_finish_record(stats + i * FF_STATS_WORDS, color_match);
+    if (measure) ff_block_stats(acc, stats + rec * FF_STATS_WORDS);     // uniform
 }
 
 __global__ __launch_bounds__(256) void k_ffp_composite(const uint8_t* __restrict__ src, const float* __restrict__ masks,
@@ -108,11 +76,7 @@ __global__ __launch_bounds__(256) void k_ffp_composite(const uint8_t* __restrict
         const float alpha = masks[d.mask_offset + p];
         const uint8_t* fb = bytes + d.bytes_offset + p * 3;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            uint8_t face = fb[c];
-            if (matched) face = ff_shift_byte(face, shift[c]);
-            o[c] = ff_blend_byte(o[c], face, alpha, d.strength);
-        }
+        for (int c = 0; c < 3; ++c) o[c] = ff_composite_byte(o[c], fb[c], matched, shift[c], alpha, d.strength);
     }
     uint8_t* dst = out + d.dst_offset + p * 3;
     dst[0] = o[0]; dst[1] = o[1]; dst[2] = o[2];
@@ -176,20 +140,15 @@ int vrg_ff_packed_resize_stats_u8(const uint8_t* src, int64_t src_bytes, const u
         bytes == enhanced || enh_h < 1 || enh_w < 1)
         return VRG_ERR_BAD_ARG;
     if ((int64_t)enh_h * enh_w * 3 > 0x7fffffffll || tiles > 0x7fffffffll) return VRG_ERR_UNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(stats, 0, (size_t)n * FF_STATS_WORDS * sizeof(uint64_t), st) != hipSuccess) return VRG_ERR_LAUNCH;
+    const int rc = ff_stats_begin(stats, n, stream);
+    if (rc != VRG_OK) return rc;
     const FfpGeom g{n, src_bytes, 0, enhanced_frames, mask_floats, n_taps, capacity, enh_h, enh_w};
-    const int32_t measure = color_match > 0.0f ? 1 : 0;
     if (tiles > 0) {
-        hipLaunchKernelGGL(k_ffp_resize_stats, dim3((uint32_t)tiles), dim3(256), 0, st, src, enhanced, masks, desc, tile_prefix,
-                           reinterpret_cast<const LzTap*>(taps), bytes, (unsigned long long*)stats, g, measure);
+        hipLaunchKernelGGL(k_ffp_resize_stats, dim3((uint32_t)tiles), dim3(256), 0, (hipStream_t)stream, src, enhanced, masks, desc, tile_prefix,
+                           reinterpret_cast<const LzTap*>(taps), bytes, (unsigned long long*)stats, g, color_match > 0.0f ? 1 : 0);
         VRG_CHECK_LAUNCH();
     }
-    if (measure) {
-        hipLaunchKernelGGL(k_ffp_finish, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, (unsigned long long*)stats, n, color_match);
-        VRG_CHECK_LAUNCH();
-    }
-    return VRG_OK;
+    return ff_stats_end(stats, n, color_match, stream);
 }
 
 int vrg_ff_packed_composite_u8(const uint8_t* src, int64_t src_bytes, const float* masks, int64_t mask_floats, const vrg_ff_packed_desc* desc,

@@ -7,11 +7,10 @@
 // Records without tiles (a box below 1 x 1) repeat the value of their successor, so the owner of a tile is the LAST record whose prefix is
 // not above it (ffp_find; the search of rb_find in csrc/vrg_refbatch.hip on a table of its own).  A kernel never trusts the table: the tile
 // index inside the record is checked against the record's own tile count (ffp_place), and every span against the stated sizes
-// (ffp_*_ok).  vrg_ff_packed_check applies the same rules on the host.  The per-pixel arithmetic is csrc/vrg_facefix_math.hpp and
-// csrc/vrg_lanczos_math.hpp, unchanged.
+// (ffp_*_ok).  vrg_ff_packed_check applies the same rules on the host.  The per-pixel body and the blend checks are
+// csrc/vrg_facefix_body.hpp, shared with the whole-frame kernels.
 #pragma once
-#include "vrg_common.hpp"
-#include "vrg_facefix_math.hpp"
+#include "vrg_facefix_body.hpp"
 
 namespace vrg {
 
@@ -69,15 +68,8 @@ VRG_HD bool ffp_blocks_ok(const vrg_ff_packed_desc& d, const FfpGeom& g) {
     return ffp_src_ok(d, g) && span_fits(d.dst_offset, ffp_pixels(d) * 3, g.out_bytes);
 }
 
-// ... and to blend: the checks of ff_desc_ok on packed records; `resized` = the checks of the pass that reads the resize source as well
-VRG_HD bool ffp_blend_ok(const vrg_ff_packed_desc& d, const FfpGeom& g, bool resized) {
-    const int64_t px = ffp_pixels(d);
-    if (!(d.strength > 0.0f) || px < 1) return false;
-    if (!span_fits(d.mask_offset, px, g.mask_floats) || !span_fits(d.bytes_offset, px * 3, g.capacity)) return false;
-    if (!resized) return true;
-    if (d.enhanced_index < 0 || d.enhanced_index >= g.enhanced_frames) return false;
-    return span_fits(d.taps_offset, (int64_t)d.box_w + d.box_h, g.n_taps);
-}
+// ... and to blend: ff_blend_ok on the pixels ffp_pixels allows
+VRG_HD bool ffp_blend_ok(const vrg_ff_packed_desc& d, const FfpGeom& g, bool resized) { return ff_blend_ok(d, g, ffp_pixels(d), resized); }
 
 // prefix[0 .. n] is the running sum of the records' tile counts
 inline bool ffp_prefix_ok(const vrg_ff_packed_desc* desc, int64_t n, const int64_t* prefix) {

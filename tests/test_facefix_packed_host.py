@@ -1,5 +1,6 @@
 """The packed Builder Face Fix (frames on the host, only the boxes cross the bus) without a GPU: the plan's integers, the tile search of
-csrc/vrg_facefix_packed_math.hpp compiled for the host (tests/host_math/facefix_packed_check.cpp), the refusals of vrg_ff_packed_check
+csrc/vrg_facefix_packed_math.hpp compiled for the host (tests/host_math/facefix_packed_check.cpp), the body shared with the whole-frame
+kernels under both addressings (csrc/vrg_facefix_body.hpp, tests/host_math/facefix_body_check.cpp), the refusals of vrg_ff_packed_check
 and of the three launches, header <-> _hip._SIGNATURES <-> library, the public signatures, and packing / pasting with the device step
 replaced by the numpy restatement of tests/facefix_builder_support.py."""
 import ctypes as C
@@ -121,6 +122,67 @@ def test_tiles_cover_the_box_once(hm, w, h):
     assert hm.hm_ffp_place(w, h, first, first - 1, out) == 0 and hm.hm_ffp_place(w, h, first, first + tiles, out) == 0
     for bad in ((0, 5), (5, 0), (-1, 5), (46341, 46341)):                    # no box, or 2^31 bytes and more: no tiles
         assert hm.hm_ffp_tiles(*bad) == 0 and hm.hm_ffp_place(*bad, 0, 0, out) == 0
+
+
+# ---- the shared body under both addressings --------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def body(tmp_path_factory):
+    out = os.path.join(str(tmp_path_factory.mktemp("facefix_body_check")), "libfacefix_body_check.so")
+    src = os.path.join(ROOT, "tests", "host_math", "facefix_body_check.cpp")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-I", os.path.join(PKG_DIR, "csrc"), src, "-o", out],
+                   check=True)
+    lib = C.CDLL(out)
+    lib.hm_ffb_box.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_float, C.c_float,
+                               C.c_int32, C.c_void_p, C.c_void_p, I64P, C.c_void_p]
+    lib.hm_ffb_box.restype = None
+    return lib
+
+
+BODY_FRAME = (48, 64, 3)
+BODY_ENHANCED = (20, 24, 3)
+BODY_CROP = 12
+BODY_BOXES = {"17x16_two_tiles": (5, 7, 17, 16), "1x1": (30, 20, 1, 1), "16x16_corner": (48, 32, 16, 16), "23x19": (11, 3, 23, 19)}      # left, top, w, h
+
+
+def _body_run(lib, base, offset, pitch, w, h, enhanced, mask, cm, strength):
+    """the box whose first byte is base[offset:], rows `pitch` pixels apart -> (crop, resized, sums, out)"""
+    crop = np.zeros((BODY_CROP, BODY_CROP, 3), dtype=np.uint8)
+    resized, out, sums = np.zeros((h, w, 3), dtype=np.uint8), np.zeros((h, w, 3), dtype=np.uint8), np.zeros(7, dtype=np.int64)
+    lib.hm_ffb_box(base.ctypes.data + offset, pitch, w, h, enhanced.ctypes.data, enhanced.shape[0], enhanced.shape[1], mask.ctypes.data, cm, strength,
+                   BODY_CROP, crop.ctypes.data, resized.ctypes.data, sums, out.ctypes.data)
+    return crop, resized, sums, out
+
+
+@pytest.mark.parametrize("cm", (0.0, 0.65))
+@pytest.mark.parametrize("feather", (0, 3))
+@pytest.mark.parametrize("name", sorted(BODY_BOXES))
+def test_shared_body_agrees_under_both_addressings(body, name, feather, cm):
+    """csrc/vrg_facefix_body.hpp on the same pixels as k_lanczos4_boxes / k_ff_resize_stats / FfMover address them (a box inside a frame,
+    pitch = the frame's width) and as the packed kernels do (a dense block, pitch = box_w)"""
+    left, top, w, h = BODY_BOXES[name]
+    H, W, _ = BODY_FRAME
+    assert left + w <= W and top + h <= H
+    rng = np.random.Generator(np.random.PCG64(77))
+    frame = rng.integers(0, 256, size=BODY_FRAME, dtype=np.uint8)
+    enhanced = rng.integers(0, 256, size=BODY_ENHANCED, dtype=np.uint8)
+    dense = np.ascontiguousarray(frame[top:top + h, left:left + w])
+    mask = np.ascontiguousarray(FS.soft_ellipse_mask(w, h, feather), dtype=np.float32)
+    strength = 0.75
+    in_frame = _body_run(body, frame, (top * W + left) * 3, W, w, h, enhanced, mask, cm, strength)
+    packed = _body_run(body, dense, 0, w, w, h, enhanced, mask, cm, strength)
+    for what, a, b in zip(("crop", "resized", "sums", "composite"), in_frame, packed):
+        assert np.array_equal(a, b), (name, feather, cm, what)
+    crop, resized, sums, out = packed
+    selected = mask > np.float32(0.35)
+    want = [int(selected.sum())] + [int(img[..., c][selected].astype(np.int64).sum()) for img in (resized, dense) for c in range(3)]
+    assert sums.tolist() == (want if cm > 0 else [0] * 7), (name, feather, cm)         # colour match off: nothing is measured
+    assert want[0] > 0
+    # ... and the bytes are those of the numpy restatement of the route
+    assert np.array_equal(crop, FS.crops(frame[None], [(left, top, left + w, top + h)], BODY_CROP)[0])
+    assert np.array_equal(resized, np.asarray(FS.LS.restated(enhanced[None], w, h))[0])
+    face, _ = FS.color_match(resized, dense, mask, cm)
+    assert np.array_equal(out, FS.blend(dense, face, mask, strength))
+    assert not np.array_equal(out, dense)
 
 
 # ---- the C ABI ----------------------------------------------------------------------------------------------------------------------------
