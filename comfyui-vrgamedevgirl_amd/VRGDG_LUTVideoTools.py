@@ -7,17 +7,13 @@ import torch
 
 from . import ops
 from .VRGDG_IV_Adjustments import LUTS_DIR, VRGDG_LUTS  # noqa: F401  (names the routes import)
-from ._devices import compute_device
-
-
-def _on_gpu(t: torch.Tensor) -> torch.Tensor:
-    return t if t.is_cuda else t.to(compute_device())
+from ._devices import compute_device, resident
 
 
 def _apply_lut_tensor(image_tensor, lut_name, strength, device):
     """LUT + strength blend for one decoded batch; result stays on the GPU (the caller converts to uint8)."""
     lut_data = VRGDG_LUTS._load_lut(lut_name)
-    src = _on_gpu(image_tensor).to(torch.float32)
+    src = resident(image_tensor).to(torch.float32)
     return ops.lut3d(src, ops.upload_lut(lut_data, src.device), strength)
 
 
@@ -26,7 +22,7 @@ def _apply_film_grain_tensor(image_tensor, grain_intensity=0.04, saturation_mix=
     ``torch.randn`` draw from a fresh generator seeded with it (callers pass seed + frame_offset per batch)."""
     intensity = max(0.0, min(1.0, float(grain_intensity)))
     saturation = max(0.0, min(1.0, float(saturation_mix)))
-    src = _on_gpu(image_tensor).to(torch.float32)
+    src = resident(image_tensor).to(torch.float32)
     gen = None
     if seed not in (None, ""):
         gen = torch.Generator(device=src.device)
@@ -71,7 +67,7 @@ def _apply_adjust_tensor(image_tensor, settings=None, device="cpu"):
     """13-slider Adjust for one decoded batch (:307-391 of the reference): one or two HIP passes
     (csrc/vrg_adjust.hip); result stays on the GPU."""
     adjust = _normalize_adjust_settings(settings)
-    src = _on_gpu(image_tensor).to(torch.float32)
+    src = resident(image_tensor).to(torch.float32)
     return ops.adjust(src, ops.adjust_terms(adjust, device_math=_is_gpu_device(device)))
 
 
@@ -116,7 +112,7 @@ def _frames_to_tensor(frames):
 
 def _tensor_to_frames(tensor):
     """fp32 RGB tensor -> list of BGR uint8 frames (``clip(x * 255, 0, 255).astype(uint8)``: truncation)."""
-    return _unstack_frames(ops.f32_to_frames_u8(_on_gpu(tensor.detach()).to(torch.float32)))
+    return _unstack_frames(ops.f32_to_frames_u8(resident(tensor.detach()).to(torch.float32)))
 
 
 def _process_video_batch(batch, writer, lut_name, strength, target_device):

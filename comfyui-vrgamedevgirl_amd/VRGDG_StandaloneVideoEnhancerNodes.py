@@ -10,7 +10,7 @@ from __future__ import annotations
 import torch
 
 from . import ops
-from ._devices import compute_device
+from ._devices import resident
 
 
 class DecodedFrames:
@@ -73,8 +73,7 @@ def _apply_effects_batch(images, settings, frame_start=0):
                                             float(settings.get("grain_intensity", 0.04)) if grain_on else 0.0,
                                             float(settings.get("saturation_mix", 0.5)), int(settings.get("seed", 42)), int(frame_start))
         return DecodedFrames(out)
-    batch = images if images.is_cuda else images.to(compute_device())
-    batch = batch.to(torch.float32)
+    batch = resident(images).to(torch.float32)
     sharpen, grain = bool(settings.get("sharpen_enabled", True)), bool(settings.get("grain_enabled", False))
     strength, intensity = float(settings.get("sharpen_strength", 0.5)), float(settings.get("grain_intensity", 0.04))
     if sharpen and grain and strength > 0 and intensity > 0:

@@ -41,7 +41,7 @@ def _as_gpu_u8(frames) -> torch.Tensor:
         a = a[None]
     if a.dtype != np.uint8 or a.ndim != 4 or a.shape[-1] != 3:
         raise ValueError("frames must be uint8 HxWx3")
-    return torch.from_numpy(np.ascontiguousarray(a)).to(compute_device())
+    return ops._as_tensor(a).to(compute_device())
 
 
 _SUMS_FRAMES = 65535          # frames per vrg_u8_channel_sums call (one frame per blockIdx.y)

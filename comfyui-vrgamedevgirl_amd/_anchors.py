@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import ops
-from ._devices import compute_device
+from ._devices import resident
 
 IMAGE_SUFFIXES = (".png", ".jpg", ".jpeg", ".webp", ".bmp")
 
@@ -78,9 +78,9 @@ def stored_bytes(images, bgr=False) -> np.ndarray:
     x = images.detach()
     if x.dtype != torch.float32:
         x = x.float()
-    dev = x.device if x.is_cuda else compute_device()
-    with torch.cuda.device(dev):
-        data = ops.anchor_store_bytes(x.to(dev), bgr=bgr)
+    x = resident(x)
+    with torch.cuda.device(x.device):
+        data = ops.anchor_store_bytes(x, bgr=bgr)
         try:
             host = torch.empty(data.shape, dtype=torch.uint8, pin_memory=True)
         except RuntimeError:

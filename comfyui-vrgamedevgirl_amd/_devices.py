@@ -781,6 +781,11 @@ def pending_of(t):
     return None
 
 
+def resident(t: torch.Tensor) -> torch.Tensor:
+    """`t` where it lies if that is a GPU, else uploaded to the compute device (type unchanged)."""
+    return t if t.is_cuda else t.to(compute_device())
+
+
 def on_device(t: torch.Tensor, device: torch.device) -> torch.Tensor:
     """`t` on `device` (fp32 frames): the pending device pieces of a LazyFrames of that device as they are (no download, no upload; a
     recipe that has not run runs into HBM), anything else through `.to()`."""

@@ -132,16 +132,93 @@ def _check_side(t: torch.Tensor, name: str, like: torch.Tensor, shape_tail=None,
     return t
 
 
-def _out_like(x: torch.Tensor, out: Optional[torch.Tensor]) -> torch.Tensor:
-    """The destination of an operator: a fresh tensor, or the caller's (contiguous, shaped and typed like the frames, same device, not
-    the frames themselves -- the stencils read neighbours of what they write)."""
+def _checked_out(out, shape, dtype, device, what: str, name: str = "out") -> torch.Tensor:
+    """The destination of an operator: a fresh tensor of `shape`, `dtype` on `device`, or the caller's `out` -- the kernels write it
+    through a raw pointer, so it must be a contiguous tensor of exactly that shape and type on that device (`name`: its argument)."""
     if out is None:
-        return torch.empty_like(x)
-    if out.shape != x.shape or out.dtype != x.dtype or not out.is_contiguous() or out.device != x.device:
-        raise ValueError("out must be a contiguous tensor shaped and typed like the frames on the same device")
-    if out.data_ptr() == x.data_ptr() and x.numel():
-        raise ValueError("out must not alias the input frames")
+        return torch.empty(tuple(shape), dtype=dtype, device=device)
+    if (not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(shape) or out.dtype != dtype or out.device != device
+            or not out.is_contiguous()):
+        raise ValueError(f"{what}: {name} must be a contiguous {str(dtype).replace('torch.', '')} {list(shape)} tensor on {device}")
     return out
+
+
+def _out_like(x: torch.Tensor, out: Optional[torch.Tensor], what: str) -> torch.Tensor:
+    """_checked_out for a result shaped and typed like the (checked, contiguous) frames `x`, which `out` must not be -- the stencils
+    read neighbours of what they write."""
+    out = _checked_out(out, x.shape, x.dtype, x.device, what)
+    if out.data_ptr() == x.data_ptr() and x.numel():
+        raise ValueError(f"{what}: out must not alias the input frames")
+    return out
+
+
+def _placement(devices, what: str, noun: str, *, ring: bool, prefer: Optional[torch.device] = None) -> torch.device:
+    """The GPU a call whose inputs live on `devices` (one torch.device per input, CPU ones included) runs on.  Inputs on two GPUs
+    are refused under both rules; `what` names the operator and `noun` its inputs in the message.
+
+    ring=False, the follow rule: CPU inputs follow the resident ones -- the operator uploads them itself with `.to(device)`, which
+    reaches any GPU.  With nothing resident the call runs on `prefer` (the device of a resident `out`) or the compute device.
+
+    ring=True, the ring rule: CPU inputs always go to the compute device, because `_devices.upload_frames` stages them through the
+    page-locked ring, which uploads there and nowhere else (the grid and the sheet; the MSR frames and the first/last guide upload with
+    `.to()` and simply inherited the rule).  Resident inputs on another GPU next to CPU ones are therefore refused, not moved."""
+    from . import _devices
+    on = [d for d in devices if d.type == "cuda"]
+    if on and not (ring and len(on) < len(devices)):
+        dev = on[0]
+    else:
+        dev = prefer if prefer is not None and not on else _devices.compute_device()
+        if on and on[0] != dev:
+            raise RuntimeError(f"{what}: CPU {noun} go to {dev}, the CUDA {noun} live on {on[0]}; move them there")
+    if any(d != dev for d in on):
+        raise RuntimeError(f"{what}: the {noun} live on more than one GPU")
+    return dev
+
+
+def _as_tensor(p):
+    """A caller's numpy picture as a tensor over the same memory -- over a copy where the array is not contiguous or read-only (torch
+    takes no read-only array) -- and a tensor detached; anything else as it is, for the caller's own refusal."""
+    if isinstance(p, np.ndarray):
+        p = torch.from_numpy(np.ascontiguousarray(p) if p.flags.writeable else np.array(p))                 # Pillow's arrays are read-only
+    return p.detach() if isinstance(p, torch.Tensor) else p
+
+
+def _byte_picture(p, what: str, *, allow_empty: bool) -> torch.Tensor:
+    """One decoded picture (numpy array or tensor, never written) as a detached [height, width, 3] uint8 tensor"""
+    p = _as_tensor(p)
+    if (not isinstance(p, torch.Tensor) or p.dtype != torch.uint8 or p.ndim != 3 or int(p.shape[2]) != 3
+            or not (allow_empty or min(int(v) for v in p.shape[:2]) >= 1)):
+        raise ValueError(f"{what} must be a {'' if allow_empty else 'non-empty '}[height, width, 3] uint8 tensor or array")
+    return p
+
+
+def _refuse(rc: int, what: str, bad_arg: str, unsupported: str) -> None:
+    """The return code of a host check (no device, so without the error strings _hip.check asks the library for) as the exception of
+    the operator `what`: a ValueError for records that are wrong, a RuntimeError for a call that is larger than the kernels take."""
+    if rc == _hip.VRG_ERR_BAD_ARG:
+        raise ValueError(f"{what}: {bad_arg}")
+    if rc != _hip.VRG_OK:
+        raise RuntimeError(f"{what}: {unsupported}")
+
+
+_upload_lock = threading.Lock()
+
+
+def _uploaded(cache: dict, key, build, device, limit: int = 64) -> torch.Tensor:
+    """``cache[key]``: on a miss the table of ``build()`` (a numpy array of records), uploaded to ``device`` as bytes.  A cache that holds ``limit``
+    tables is cleared first: a handful of geometries per job; never grows without bound.  The table is marked as used on the caller's current stream:
+    a cache cleared under another stream drops it while this caller's launch may still be queued, and the allocator then keeps the block
+    until that launch is done."""
+    t = cache.get(key)
+    if t is None:
+        t = _hip.upload_records(build(), device)
+        with _upload_lock:
+            if len(cache) >= limit:
+                cache.clear()
+            cache[key] = t
+    if t.is_cuda:
+        t.record_stream(torch.cuda.current_stream(t.device))
+    return t
 
 
 # ------------------------------------------------------------------------------------------------
@@ -265,7 +342,7 @@ def film_grain(images: torch.Tensor, grain_intensity: float, saturation_mix: flo
     generator state: chunks of `chunk_frames` frames each draw one ``torch.randn`` (0 = one draw for all)."""
     x = _check_frames(images, channels=3)
     F, H, W, _ = x.shape
-    out = _out_like(x, out)
+    out = _out_like(x, out, "film_grain")
     if F == 0:
         return out
     fe = H * W * 3
@@ -414,25 +491,9 @@ def pil_axis_table(number: int, n_in: int, n_out: int, box=None):
         raise (ValueError if status == 1 else RuntimeError)(f"pil_axis_table: {lib.vrg_error_string(status).decode()}")
     table.setflags(write=False)
     return ksize, table
-_upload_lock = threading.Lock()
+
+
 _lanczos_tables: dict = {}      # (in_h, in_w, out_h, out_w, device) -> the uploaded table
-
-
-def _uploaded(cache: dict, key, build, device) -> torch.Tensor:
-    """``cache[key]``: on a miss the table of ``build()`` (a numpy array of records), uploaded to ``device`` as bytes.  A cache that holds 64 tables is
-    cleared first: a handful of geometries per job; never grows without bound.  The table is marked as used on the caller's current stream:
-    a cache cleared under another stream drops it while this caller's launch may still be queued, and the allocator then keeps the block
-    until that launch is done."""
-    t = cache.get(key)
-    if t is None:
-        t = _hip.upload_records(build(), device)
-        with _upload_lock:
-            if len(cache) >= 64:
-                cache.clear()
-            cache[key] = t
-    if t.is_cuda:
-        t.record_stream(torch.cuda.current_stream(t.device))
-    return t
 
 
 def lanczos4_taps(in_h: int, in_w: int, out_h: int, out_w: int) -> np.ndarray:
@@ -586,11 +647,11 @@ def lut3d(image: torch.Tensor, lut: DeviceLut, strength: float = 10.0, out: Opti
     mode, B, omB = blend_terms(strength)
     if mode == 0:
         if out is not None:
-            _out_like(x, out).copy_(x)
+            _out_like(x, out, "lut3d").copy_(x)
             return out
         return x
     _check_side(lut.table, "LUT record table", x)
-    out = _out_like(x, out)
+    out = _out_like(x, out, "lut3d")
     px = x.numel() // x.shape[-1]
     if px == 0:
         return out
@@ -636,7 +697,7 @@ def stencil3x3(images: torch.Tensor, op: str, strength: float, zero_border: bool
     """unsharp / laplacian / sobel.  zero_border=False is the reference's default numpy path (edge replicate);
     True is its ``use_gpu`` path (zero padding, and for laplacian/sobel the conv2d sign/epsilon conventions)."""
     x = _check_frames(images)
-    out = _out_like(x, out)
+    out = _out_like(x, out, "stencil3x3")
     F, H, W, Cn = x.shape
     if x.numel() == 0:
         return out
@@ -731,10 +792,7 @@ def resize_geometry_frames(images: torch.Tensor, geometry: ResizeGeometry, resiz
     x = _check_resize_source(images, "images")
     shape = (int(x.shape[0]), geometry.out_h, geometry.out_w, 3)
     args = _geometry_args(x, geometry)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
-        raise ValueError(f"out must be a contiguous float32 tensor shaped {shape} on the frames' device")
+    out = _checked_out(out, shape, torch.float32, x.device, "resize_geometry_frames")
     _hip.check(_hip.lib().vrg_resize_f32(_hip.ptr(x), _hip.ptr(out), shape[0], *args, RESIZE_METHODS[interpolation_mode(resize_method)],
                                         _hip.current_stream()), "vrg_resize_f32")
     return out
@@ -803,7 +861,7 @@ def restore_frames(work: torch.Tensor, originals: torch.Tensor, source_width, so
     usable = min(frames if frame_count is None else int(frame_count), int(w.shape[0]))
     if usable > frames:
         raise ValueError(f"{usable} restored frames for {frames} original frames")
-    out = _out_like(o, out)
+    out = _out_like(o, out, "restore_frames")
     if o.numel() == 0:
         return out
     strength = float(strength)
@@ -1022,13 +1080,8 @@ def composite_frames(originals: torch.Tensor, crops: torch.Tensor, entries, rule
     o, c, m, dev_table, match, max_pixels, geom, stats = _composite_prepare(originals, crops, entries, rule, color_match, user_mask)
     frames = len(entries)
     shape = (frames, int(o.shape[1]), int(o.shape[2]), int(o.shape[3]))
-    for name, t, want in (("out", out, shape), ("mask_out", mask_out, shape[:3])):
-        if t is not None and (tuple(t.shape) != want or t.dtype != torch.float32 or not t.is_contiguous() or t.device != o.device):
-            raise ValueError(f"{name} must be a contiguous float32 tensor shaped {want} on the frames' device")
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=o.device)
-    if mask_out is None:
-        mask_out = torch.empty(shape[:3], dtype=torch.float32, device=o.device)
+    out = _checked_out(out, shape, torch.float32, o.device, "composite_frames")
+    mask_out = _checked_out(mask_out, shape[:3], torch.float32, o.device, "composite_frames", "mask_out")
     if out.data_ptr() in (o.data_ptr(), c.data_ptr()):
         raise ValueError("out must not be an input")
     if frames == 0:
@@ -1044,7 +1097,6 @@ def composite_frames(originals: torch.Tensor, crops: torch.Tensor, entries, rule
 # landmark-aligned Face Fix composite (VRGDG_StandaloneFaceFixNodes.py:1015-1054): the face as bytes, cv2's byte Lanczos-4 affine warp
 # (csrc/vrg_warp_math.hpp), the warp fused into the composite pass
 # ------------------------------------------------------------------------------------------------
-_warp_lock = threading.Lock()
 _warp_host_table = None
 _warp_tables: dict = {}          # device -> the uploaded phase table
 
@@ -1062,15 +1114,7 @@ def warp_phase_table() -> np.ndarray:
 
 
 def _warp_table(device) -> torch.Tensor:
-    key = str(device)
-    t = _warp_tables.get(key)
-    if t is None:
-        with _warp_lock:
-            t = _warp_tables.get(key)
-            if t is None:
-                t = torch.from_numpy(warp_phase_table().reshape(-1).copy()).to(device)
-                _warp_tables[key] = t
-    return t
+    return _uploaded(_warp_tables, str(device), warp_phase_table, device)
 
 
 def _box_size(box):
@@ -1307,13 +1351,8 @@ def aligned_composite_frames(originals: torch.Tensor, crops: torch.Tensor, entri
         generated = face_bytes(c, entries, o.shape[1], o.shape[2])
     frames = len(entries)
     shape = (frames, int(o.shape[1]), int(o.shape[2]), int(o.shape[3]))
-    for name, t, want in (("out", out, shape), ("mask_out", mask_out, shape[:3])):
-        if t is not None and (tuple(t.shape) != want or t.dtype != torch.float32 or not t.is_contiguous() or t.device != o.device):
-            raise ValueError(f"{name} must be a contiguous float32 tensor shaped {want} on the frames' device")
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=o.device)
-    if mask_out is None:
-        mask_out = torch.empty(shape[:3], dtype=torch.float32, device=o.device)
+    out = _checked_out(out, shape, torch.float32, o.device, "aligned_composite_frames")
+    mask_out = _checked_out(mask_out, shape[:3], torch.float32, o.device, "aligned_composite_frames", "mask_out")
     if out.data_ptr() in (o.data_ptr(), c.data_ptr()):
         raise ValueError("out must not be an input")
     rec = _hip.upload_records(records, o.device, frames)
@@ -1427,11 +1466,7 @@ def crop_resize(source: torch.Tensor, records, size=CROP_SIZE, out: Optional[tor
             raise ValueError(f"crop record {k} {tuple(int(v) for v in rec[k])} reaches float {int(last[k])} of a source of {source.numel()}; refused")
         for k, name in enumerate(("src_offset", "row_pitch", "pixel_stride", "box_w", "box_h")):
             table[name] = rec[:, k]
-    shape = (len(records), size_h, size_w, 3)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=source.device)
-    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != source.device:
-        raise ValueError(f"out must be a contiguous float32 tensor shaped {shape} on the frames' device")
+    out = _checked_out(out, (len(records), size_h, size_w, 3), torch.float32, source.device, "crop_resize")
     if len(records) == 0:
         return out
     if out.data_ptr() == source.data_ptr():
@@ -1562,11 +1597,7 @@ def cut_thumbnails(frames: torch.Tensor, out: Optional[torch.Tensor] = None) -> 
     if Cn > 4:
         x = x[..., :3].contiguous()
         Cn = 3
-    shape = (F, CUT_THUMB, CUT_THUMB, 3)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.uint8, device=x.device)
-    elif tuple(out.shape) != shape or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != x.device:
-        raise ValueError(f"out must be a contiguous uint8 tensor shaped {shape} on the frames' device")
+    out = _checked_out(out, (F, CUT_THUMB, CUT_THUMB, 3), torch.uint8, x.device, "cut_thumbnails")
     if F == 0:
         return out
     taps = _area_table(H, W, x.device)
@@ -1629,8 +1660,7 @@ def cut_pair_sums(thumbs: torch.Tensor, hist: Optional[torch.Tensor] = None) -> 
 GRID_MODES = ("copy", "fast", "fast 2x2", "general", "linear")          # include/vrgdg_hip.h, enum vrg_grid_mode
 GRID_ROW_VALUES = 4096          # source values one wave stages at a time (csrc/vrg_grid_math.hpp): the most one column's taps may cover
 GRID_DESC = _hip.record_dtype(_hip.GridDesc)
-_grid_tables: dict = {}         # (n_in, n_out, mode, device) -> the uploaded table of one axis; at most 256, the oldest leaves first
-_grid_lock = threading.Lock()
+_grid_tables: dict = {}         # (n_in, n_out, mode, device) -> the uploaded table of one axis; at most 256
 
 
 @dataclass(frozen=True)
@@ -1712,17 +1742,7 @@ def grid_plan(sizes, cell_w: int, cell_h: int, columns: int, band: int = 0) -> G
 
 
 def _grid_table(n_in, n_out, mode, table, device) -> torch.Tensor:
-    key = (n_in, n_out, mode, str(device))
-    t = _grid_tables.get(key)
-    if t is None:
-        t = _hip.upload_records(table, device)
-        with _grid_lock:
-            while len(_grid_tables) >= 256:
-                _grid_tables.pop(next(iter(_grid_tables)))
-            _grid_tables[key] = t
-    if t.is_cuda:
-        t.record_stream(torch.cuda.current_stream(t.device))          # as in _uploaded: an evicted table outlives the launches that read it
-    return t
+    return _uploaded(_grid_tables, (n_in, n_out, mode, str(device)), lambda: table, device, limit=256)
 
 
 def _grid_overlays(plan: GridPlan, overlays, device):
@@ -1809,37 +1829,20 @@ def _grid_batches(batches, dtype):
     return out
 
 
-def _grid_out(plan: GridPlan, frames: int, device, out):
-    shape = (frames, plan.grid_h, plan.grid_w, 3)
-    if out is None:
-        return torch.empty(shape, dtype=torch.float32, device=device)
-    if tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != device:
-        raise ValueError(f"out must be a contiguous float32 tensor shaped {shape} on {device}")
-    return out
-
-
 def _grid_run(batches, index, plan, overlays, out, byte_sources):
     """Device-resident batches and the empty cells in one launch; every CPU batch through the page-locked ring in pieces along its frames,
     one launch per piece for its tile alone.  index[i][f]: the frame of batch i that output frame f shows (-1: none)."""
     from . import _devices
     frames = len(index[0])
-    dev = next((b.device for b in batches if b is not None and b.is_cuda), None)
-    if any(b is not None and not b.is_cuda for b in batches):
-        if dev is not None and dev != _devices.compute_device():             # the page-locked ring uploads to the compute device
-            raise RuntimeError(f"video grid: CPU batches go to {_devices.compute_device()}, the CUDA batches live on {dev}; move them there")
-        dev = _devices.compute_device()
-    elif dev is None:
-        dev = _devices.compute_device()
+    dev = _placement([b.device for b in batches if b is not None], "video grid", "batches", ring=True)     # every CUDA batch lives on it
     with torch.cuda.device(dev):
-        out = _grid_out(plan, frames, dev, out)
+        out = _checked_out(out, (frames, plan.grid_h, plan.grid_w, 3), torch.float32, dev, "video grid")
         dev_overlays, has = _grid_overlays(plan, overlays, dev)
         jobs = [(None, cell, None, 0, np.full(frames, -1)) for cell in range(len(batches), plan.rows * plan.columns)]
         for i, b in enumerate(batches):
             if b is None:
                 jobs.append((i, i, None, 0, index[i]))
             elif b.is_cuda:
-                if b.device != dev:
-                    raise RuntimeError(f"video grid: batch {i} lives on {b.device}, the grid on {dev}")
                 jobs.append((i, i, b.contiguous(), 0, index[i]))
         _grid_launch(plan, out, jobs, dev_overlays, has, byte_sources)
         for i, b in enumerate(batches):
@@ -2096,10 +2099,7 @@ def adjust(images: torch.Tensor, terms: "_hip.AdjustDesc", out: torch.Tensor | N
     x = _check_frames(images, dtype=torch.uint8 if u8 else torch.float32)
     if x.shape[-1] != 3:
         raise ValueError("adjust expects 3-channel frames")
-    if out is None:
-        out = torch.empty_like(x)
-    elif out.shape != x.shape or out.dtype != x.dtype or not out.is_contiguous() or out.device != x.device:
-        raise ValueError("out must be a contiguous tensor shaped and typed like the frames on the same device")
+    out = _checked_out(out, x.shape, x.dtype, x.device, "adjust")
     F, H, W, _ = x.shape
     if x.numel() == 0:
         return out
@@ -2513,7 +2513,7 @@ def color_match(images: torch.Tensor, reference_image: torch.Tensor, match_stren
     img_ms = finalize_stats(lab_stats(x, cm_math))
     res = colormatch_apply(x, img_ms, ref_ms, match_strength, cm_math)
     if out is not None:
-        _out_like(x, out).copy_(res)
+        _out_like(x, out, "color_match").copy_(res)
         return out
     return res
 
@@ -2629,10 +2629,7 @@ def fused_chain(images: torch.Tensor, spec: ChainSpec, generator: Optional[torch
         raise ValueError("uint8 frames: colour match is not part of the video routes (convert to fp32 first)")
     esize = 1 if u8 else 4
     F, H, W, _ = x.shape
-    if out is None:
-        out = torch.empty_like(x)
-    elif out.shape != x.shape or out.dtype != x.dtype or not out.is_contiguous() or out.device != x.device:
-        raise ValueError("out must be a contiguous tensor shaped and typed like images on the same device")
+    out = _checked_out(out, x.shape, x.dtype, x.device, "fused_chain")
     if F == 0:
         return out
     fe = H * W * 3
@@ -2868,13 +2865,8 @@ def rounded_spans(width: int, height: int, radius: int) -> np.ndarray:
     return spans
 
 
-def _sheet_rc(rc: int, what: str):
-    """_hip.check without the device its error strings need"""
-    if rc == _hip.VRG_ERR_BAD_ARG:
-        raise ValueError(f"{what}: invalid argument")
-    if rc != _hip.VRG_OK:
-        raise RuntimeError(f"{what}: " + ("not supported: a side above 32767, or the taps of one column do not fit the staging buffer"
-                                          if rc == _hip.VRG_ERR_UNSUPPORTED else f"error {rc}"))
+#: what _refuse says for vrg_sheet_fit, vrg_sheet_plan and vrg_sheet_check (they return nothing but OK, BAD_ARG and UNSUPPORTED)
+_SHEET_REFUSALS = ("invalid argument", "not supported: a side above 32767, or the taps of one column do not fit the staging buffer")
 
 
 class SheetPlan:
@@ -2906,7 +2898,7 @@ class SheetPlan:
             if p.fit == "resize":
                 fit[:] = (w, h, 0, 0, w, h, 0, 0)
             else:
-                _sheet_rc(lib.vrg_sheet_fit(sw, sh, w, h, int(p.fit == "cover_crop"), C.c_void_p(fit.ctypes.data)), "vrg_sheet_fit")
+                _refuse(lib.vrg_sheet_fit(sw, sh, w, h, int(p.fit == "cover_crop"), C.c_void_p(fit.ctypes.data)), "vrg_sheet_fit", *_SHEET_REFUSALS)
             r = rec[i]
             r["src_h"], r["src_w"], r["channels"] = sh, sw, sc
             r["left"], r["top"], r["w"], r["h"] = left, top, w, h
@@ -2937,7 +2929,8 @@ class SheetPlan:
         self.spans = np.concatenate(spans) if spans else np.zeros((1, 2), np.int32)
         self.n_spans = n_spans
         if len(rec):
-            _sheet_rc(lib.vrg_sheet_plan(C.c_void_p(rec.ctypes.data), len(rec), C.c_void_p(self.tables.ctypes.data), n_ints), "vrg_sheet_plan")
+            _refuse(lib.vrg_sheet_plan(C.c_void_p(rec.ctypes.data), len(rec), C.c_void_p(self.tables.ctypes.data), n_ints), "vrg_sheet_plan",
+                    *_SHEET_REFUSALS)
         for r in rec:
             r["tmp_offset"] = tmp_bytes
             tmp_bytes += int(r["rows"]) * int(r["pic_w"]) * 3
@@ -2948,8 +2941,8 @@ class SheetPlan:
     def check(self, records, byte_sources: bool):
         """vrg_sheet_check of `records` (this plan's, with their source pointers set) on the host"""
         records = np.ascontiguousarray(records)
-        _sheet_rc(_host_lib().vrg_sheet_check(C.c_void_p(records.ctypes.data), len(records), int(byte_sources), C.c_void_p(self.tables.ctypes.data),
-                                              self.table_ints, self.n_spans, self.tmp_bytes), "vrg_sheet_check")
+        _refuse(_host_lib().vrg_sheet_check(C.c_void_p(records.ctypes.data), len(records), int(byte_sources), C.c_void_p(self.tables.ctypes.data),
+                                            self.table_ints, self.n_spans, self.tmp_bytes), "vrg_sheet_check", *_SHEET_REFUSALS)
 
 
 def _sheet_colour(value, name):
@@ -2962,11 +2955,9 @@ def _sheet_colour(value, name):
 def _sheet_sources(sources):
     out = []
     for i, s in enumerate(sources):
-        if isinstance(s, np.ndarray):
-            s = torch.from_numpy(np.ascontiguousarray(s) if s.flags.writeable else np.array(s))             # Pillow's arrays are read-only
+        s = _as_tensor(s)
         if not isinstance(s, torch.Tensor):
             raise ValueError(f"reference sheet: source {i} must be a tensor")
-        s = s.detach()
         if s.ndim == 4 and int(s.shape[0]) == 1:
             s = s[0]
         if s.ndim == 2:
@@ -2997,13 +2988,7 @@ def reference_sheet(sources, panels, canvas_size, background=(0, 0, 0), *, out_b
     plan = SheetPlan([tuple(s.shape) for s in srcs], panels, canvas_size, background)
     if not len(plan.records):
         raise ValueError("reference sheet: no panels")
-    dev = next((s.device for s in srcs if s.is_cuda), None)
-    if dev is None or any(not s.is_cuda for s in srcs):
-        if dev is not None and dev != _devices.compute_device():
-            raise RuntimeError(f"reference sheet: CPU sources go to {_devices.compute_device()}, the CUDA sources live on {dev}; move them there")
-        dev = _devices.compute_device()
-    if any(s.is_cuda and s.device != dev for s in srcs):
-        raise RuntimeError("reference sheet: the sources live on more than one GPU")
+    dev = _placement([s.device for s in srcs], "reference sheet", "sources", ring=True)
     lib = _hip.lib()
     rows = lib.vrg_sheet_rows_u8 if byte_sources else lib.vrg_sheet_rows_f32
     compose = lib.vrg_sheet_compose_u8 if out_bytes else lib.vrg_sheet_compose_f32
@@ -3132,35 +3117,21 @@ def _msr_table(plan: MsrPlan, device) -> torch.Tensor:
     return _uploaded(_msr_tables, (plan.sizes, plan.height, plan.width, str(device)), plan.table, device)
 
 
-def _msr_picture(p, i):
-    if isinstance(p, np.ndarray):
-        p = torch.from_numpy(np.ascontiguousarray(p) if p.flags.writeable else np.array(p))                 # Pillow's arrays are read-only
-    if not isinstance(p, torch.Tensor) or p.dtype != torch.uint8 or p.ndim != 3 or int(p.shape[2]) != 3:
-        raise ValueError(f"msr reference frames: picture {i} must be a [height, width, 3] uint8 tensor or array")
-    return p.detach()
-
-
 def msr_reference_frames(pictures, size, frame_count: int, background=None) -> torch.Tensor:
     """``np.stack(_expand_frames([cv2.resize(p, size, INTER_LANCZOS4) for p in pictures + [background]], frame_count)).astype(np.float32)
     / 255.0`` of the reference's MSR builder as one launch: ``pictures`` are ``[h, w, 3]`` uint8 R,G,B tensors or arrays of any sizes, on
     the GPU or on the CPU (uploaded as bytes), ``size`` = (width, height), ``background`` a further picture, an (R, G, B) tuple for a
     constant colour, or None.  A picture that already has the size is taken unfiltered.  Returns the ``[frame_count, height, width, 3]``
     fp32 device tensor; every distinct picture is filtered once, whatever its repeats.  Inputs are never written."""
-    from . import _devices
-    pics = [_msr_picture(p, i) for i, p in enumerate(pictures)]
+    what = "msr reference frames"
+    pics = [_byte_picture(p, f"{what}: picture {i}", allow_empty=True) for i, p in enumerate(pictures)]      # msr_plan refuses the empty ones
     fill = None
     if isinstance(background, (tuple, list)):
         fill = tuple(background)
     elif background is not None:
-        pics.append(_msr_picture(background, "background"))
+        pics.append(_byte_picture(background, f"{what}: picture background", allow_empty=True))
     plan = msr_plan([tuple(p.shape[:2]) for p in pics], size, frame_count, fill)
-    dev = next((p.device for p in pics if p.is_cuda), None)
-    if dev is None or any(not p.is_cuda for p in pics):
-        if dev is not None and dev != _devices.compute_device():
-            raise RuntimeError(f"msr reference frames: CPU pictures go to {_devices.compute_device()}, the CUDA pictures live on {dev}; move them there")
-        dev = _devices.compute_device()
-    if any(p.is_cuda and p.device != dev for p in pics):
-        raise RuntimeError("msr reference frames: the pictures live on more than one GPU")
+    dev = _placement([p.device for p in pics], what, "pictures", ring=True)
     desc = plan.desc.copy()
     with torch.cuda.device(dev):
         out = torch.empty((plan.frames, plan.height, plan.width, 3), dtype=torch.float32, device=dev)
@@ -3183,7 +3154,7 @@ def msr_reference_frames(pictures, size, frame_count: int, background=None) -> t
 def bytes_to_image(picture) -> torch.Tensor:
     """``np.asarray(picture, dtype=np.float32) / 255.0`` as ``[1, h, w, 3]`` fp32 on the device (the reference's _pil_to_image_tensor): the
     launch of msr_reference_frames with one descriptor, no filter, one frame."""
-    p = _msr_picture(picture, 0)
+    p = _byte_picture(picture, "msr reference frames: picture 0", allow_empty=True)
     return msr_reference_frames([p], (int(p.shape[1]), int(p.shape[0])), 1)
 
 
@@ -3258,11 +3229,9 @@ def flf_plan(first_shape, last_shape, frame_count: int, transition_start=0.05, t
         raise ValueError("first/last guide: pictures must be at least 1 x 1")
     weights = flf_weights(frame_count, transition_start, transition_end, curve)
     rect = (0, 0, last_w, last_h) if (last_h, last_w) == (h, w) else center_crop_rect(last_w, last_h, w, h)
-    rc = _host_lib().vrg_flf_check(len(weights), h, w, c, last_h, last_w, *rect)
-    if rc == _hip.VRG_ERR_BAD_ARG:
-        raise ValueError(f"first/last guide: vrg_flf_check refuses {last_w} x {last_h} -> {w} x {h}, rectangle {rect}")
-    if rc != _hip.VRG_OK:
-        raise RuntimeError(f"first/last guide: {len(weights)} frames of {w} x {h} x {c} are more than one launch takes")
+    _refuse(_host_lib().vrg_flf_check(len(weights), h, w, c, last_h, last_w, *rect), "first/last guide",
+            f"vrg_flf_check refuses {last_w} x {last_h} -> {w} x {h}, rectangle {rect}",
+            f"{len(weights)} frames of {w} x {h} x {c} are more than one launch takes")
     return rect, weights
 
 
@@ -3274,22 +3243,11 @@ def flf_guide_frames(first, last, frame_count: int, transition_start=0.05, trans
     from . import _devices
     a, b = _flf_picture(first, "first"), _flf_picture(last, "last")
     rect, weights = flf_plan(tuple(a.shape[1:]), tuple(b.shape[1:]), frame_count, transition_start, transition_end, curve)
-    dev = next((t.device for t in (a, b) if t.is_cuda), None)
-    if dev is None or not (a.is_cuda and b.is_cuda):
-        if dev is not None and dev != _devices.compute_device():
-            raise RuntimeError(f"first/last guide: a CPU picture goes to {_devices.compute_device()}, the CUDA picture lives on {dev}; move it there")
-        dev = _devices.compute_device()
-    if any(t.is_cuda and t.device != dev for t in (a, b)):
-        raise RuntimeError("first/last guide: the pictures live on two GPUs")
+    dev = _placement([a.device, b.device], "first/last guide", "pictures", ring=True)
     frames, (h, w, c) = len(weights), (int(v) for v in a.shape[1:])
-    if out is not None:
-        if (not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.float32 or tuple(out.shape) != (frames, h, w, c)
-                or not out.is_contiguous()):
-            raise ValueError(f"first/last guide: out must be a contiguous fp32 [{frames}, {h}, {w}, {c}] tensor on {dev}")
+    out = _checked_out(out, (frames, h, w, c), torch.float32, dev, "first/last guide")
     with torch.cuda.device(dev):
         a, b = (t.contiguous() if t.is_cuda else _devices.on_device(t, dev).contiguous() for t in (a, b))
-        if out is None:
-            out = torch.empty((frames, h, w, c), dtype=torch.float32, device=dev)
         wd = torch.from_numpy(weights).to(dev)
         _hip.check(_hip.lib().vrg_flf_guide_f32(_hip.ptr(a), _hip.ptr(b), _hip.ptr(wd), _hip.ptr(out), frames, h, w, c, int(b.shape[1]),
                                                 int(b.shape[2]), *rect, _hip.current_stream()), "vrg_flf_guide_f32")
@@ -3360,12 +3318,9 @@ def refbatch_table(jobs, out_elems: int):
             raise RuntimeError("reference batch: more tiles than one launch takes")
         desc[i] = (offset, int(j.dst_offset), *j.src_shape, *j.rect, *j.dst_shape, int(j.method), int(j.frames), tiles, 0)
         tiles += int(j.frames) * -(-int(np.prod(j.dst_shape, dtype=np.int64)) // _hip.REFBATCH_TILE)
-    rc = _host_lib().vrg_refbatch_check(C.c_void_p(desc.ctypes.data), len(jobs), spans[torch.float32][1], spans[torch.uint8][1], int(out_elems))
-    if rc == _hip.VRG_ERR_BAD_ARG:
-        raise ValueError("reference batch: vrg_refbatch_check refuses the records (sizes, channel counts, rectangles or overlapping outputs)")
-    if rc != _hip.VRG_OK:
-        raise RuntimeError("reference batch: a picture is larger than one launch takes (2^31 - 1 elements a picture, 65536 source pixels "
-                           "under one area pixel)")
+    _refuse(_host_lib().vrg_refbatch_check(C.c_void_p(desc.ctypes.data), len(jobs), spans[torch.float32][1], spans[torch.uint8][1], int(out_elems)),
+            "reference batch", "vrg_refbatch_check refuses the records (sizes, channel counts, rectangles or overlapping outputs)",
+            "a picture is larger than one launch takes (2^31 - 1 elements a picture, 65536 source pixels under one area pixel)")
     return desc, tiles, spans[torch.float32], spans[torch.uint8]
 
 
@@ -3402,11 +3357,7 @@ def _refbatch_pictures(images, what):
 
 def _refbatch_place(images, what):
     """device tensors as they are, all CPU pictures in ONE upload"""
-    from . import _devices
-    on = [t.device for t in images if t.is_cuda]
-    dev = on[0] if on else _devices.compute_device()
-    if any(d != dev for d in on):
-        raise RuntimeError(f"{what}: the pictures live on two GPUs")
+    dev = _placement([t.device for t in images], what, "pictures", ring=False)
     pics = [t.detach() for t in images]
     host = [i for i, t in enumerate(pics) if not t.is_cuda]
     with torch.cuda.device(dev):
@@ -3530,10 +3481,8 @@ def batch_reference_images(images, upscale_method="bilinear", out=None) -> torch
     frame = height * width * channels
     offsets = np.concatenate([[0], np.cumsum([int(t.shape[0]) * frame for t in pics])])
     shape = (int(sum(int(t.shape[0]) for t in pics)), height, width, channels)
-    if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or not out.is_contiguous()):
-        raise ValueError(f"{what}: out must be a contiguous fp32 {list(shape)} tensor")
     with torch.cuda.device(dev):
-        buf = _refbatch_out(None if out is None else out.view(-1), int(offsets[-1]), dev, what)
+        buf = _refbatch_out(None, int(offsets[-1]), dev, what) if out is None else _checked_out(out, shape, torch.float32, dev, what).view(-1)
         jobs, lanczos = [], []
         for t, fit, at in zip(pics, fits, offsets[:-1]):
             frames, h, w, c = (int(v) for v in t.shape)
@@ -3688,7 +3637,6 @@ class _Assembly:
 
 
 def _assemble_prepare(videos, plan, overlays, what) -> _Assembly:
-    from . import _devices
     if isinstance(videos, torch.Tensor):
         videos = [videos]
     videos = list(videos)
@@ -3715,10 +3663,8 @@ def _assemble_prepare(videos, plan, overlays, what) -> _Assembly:
         lo, hi = int(entries[entries[:, 0] == s, 1].min()), int(entries[entries[:, 0] == s, 1].max())
         if lo < 0 or hi >= int(t.shape[0]):
             raise ValueError(f"{what}: the plan names frames {lo} .. {hi} of clip {s}, which has {int(t.shape[0])}")
-    on = [t.device for t in clips.values() if t.is_cuda]
-    dev = on[0] if on else _devices.compute_device()
-    if any(d != dev for d in on):
-        raise RuntimeError(f"{what}: the clips live on two GPUs")
+    dev = _placement([t.device for t in clips.values()], what, "clips", ring=False)
+    host_fed = not any(t.is_cuda for t in clips.values())
     desc, keep, rows = _hip.AssembleDesc(), [], np.zeros(len(entries), dtype=ASSEMBLE_ENTRY)
     desc.n_src, desc.bytes = len(used), int(is_bytes)
     with torch.cuda.device(dev):
@@ -3743,25 +3689,14 @@ def _assemble_prepare(videos, plan, overlays, what) -> _Assembly:
                 keep.append(o)
                 desc.overlay[k] = o.data_ptr()
         table = _hip.upload_records(rows, dev)
-    return _Assembly(dev, desc, table, len(entries), shape, not on, rows, keep)
-
-
-def _assemble_out(out, shape, dtype, dev, what, name):
-    if out is None:
-        return torch.empty(shape, dtype=dtype, device=dev)
-    if (not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != dtype or tuple(out.shape) != tuple(shape)
-            or not out.is_contiguous()):
-        raise ValueError(f"{what}: {name} must be a contiguous {str(dtype).replace('torch.', '')} {list(shape)} tensor on {dev}")
-    return out
+    return _Assembly(dev, desc, table, len(entries), shape, host_fed, rows, keep)
 
 
 def _assemble_check(a: _Assembly, out_f32, out_u8, labelled, what):
-    rc = _host_lib().vrg_assemble_check(C.byref(a.desc), C.c_void_p(a.rows.ctypes.data), a.frames, None if out_f32 is None else _hip.ptr(out_f32),
-                                        None if out_u8 is None else _hip.ptr(out_u8), int(labelled))
-    if rc == _hip.VRG_ERR_BAD_ARG:
-        raise ValueError(f"{what}: vrg_assemble_check refuses the call (clip shapes, channels, or an output that overlaps a clip)")
-    if rc != _hip.VRG_OK:
-        raise RuntimeError(f"{what}: a frame of {a.shape} is larger than one launch takes (2^31 - 1 elements)")
+    _refuse(_host_lib().vrg_assemble_check(C.byref(a.desc), C.c_void_p(a.rows.ctypes.data), a.frames, None if out_f32 is None else _hip.ptr(out_f32),
+                                           None if out_u8 is None else _hip.ptr(out_u8), int(labelled)),
+            what, "vrg_assemble_check refuses the call (clip shapes, channels, or an output that overlaps a clip)",
+            f"a frame of {a.shape} is larger than one launch takes (2^31 - 1 elements)")
 
 
 def assemble_frames(videos, plan, out=None) -> torch.Tensor:
@@ -3775,7 +3710,7 @@ def assemble_frames(videos, plan, out=None) -> torch.Tensor:
     what = "assemble_frames"
     a = _assemble_prepare(videos, plan, None, what)
     with torch.cuda.device(a.device):
-        dst = _assemble_out(out, (a.frames, *a.shape), torch.float32, a.device, what, "out")
+        dst = _checked_out(out, (a.frames, *a.shape), torch.float32, a.device, what)
         _assemble_check(a, dst, None, False, what)
         _hip.check(_hip.lib().vrg_assemble_f32(C.byref(a.desc), _hip.ptr(a.table), a.frames, _hip.ptr(dst), _hip.current_stream()),
                    "vrg_assemble_f32")
@@ -3796,7 +3731,7 @@ def assemble_labelled_bytes(videos, plan, overlays=None, clean_out=None):
         raise ValueError(f"{what}: labelled output takes 3-channel clips, got {a.shape[2]}")
     with torch.cuda.device(a.device):
         given = isinstance(clean_out, torch.Tensor)
-        clean = _assemble_out(clean_out if given else None, (a.frames, *a.shape), torch.float32, a.device, what, "clean_out") if given or clean_out else None
+        clean = _checked_out(clean_out if given else None, (a.frames, *a.shape), torch.float32, a.device, what, "clean_out") if given or clean_out else None
         data = torch.empty((a.frames, a.shape[0] + ASSEMBLE_BAR, a.shape[1], 3), dtype=torch.uint8, device=a.device)
         _assemble_check(a, clean, data, True, what)
         _hip.check(_hip.lib().vrg_assemble_labelled_u8(C.byref(a.desc), _hip.ptr(a.table), a.frames, None if clean is None else _hip.ptr(clean),
@@ -3815,14 +3750,6 @@ def assemble_labelled_bytes(videos, plan, overlays=None, clean_out=None):
 ANCHOR_DESC = _hip.record_dtype(_hip.AnchorDesc)
 _NO_ANCHOR_PICTURES = "anchor_frames: at least one picture is needed"
 _NO_ANCHOR_IMAGES = "anchor_store_bytes: at least one image is needed"
-
-
-def _anchor_picture(p, i):
-    if isinstance(p, np.ndarray):
-        p = torch.from_numpy(np.ascontiguousarray(p) if p.flags.writeable else np.array(p))                 # Pillow's arrays are read-only
-    if not isinstance(p, torch.Tensor) or p.dtype != torch.uint8 or p.ndim != 3 or int(p.shape[2]) != 3 or min(int(v) for v in p.shape[:2]) < 1:
-        raise ValueError(f"anchor_frames: picture {i} must be a non-empty [height, width, 3] uint8 tensor or array")
-    return p.detach()
 
 
 def anchor_plan(shapes, size=None):
@@ -3858,22 +3785,11 @@ def anchor_check(desc, tables, src_bytes: int, height: int, width: int) -> None:
     """the host refusal of records the kernel would not follow (vrg_anchor_check): ValueError, before any launch"""
     desc = np.ascontiguousarray(desc)
     tables = np.ascontiguousarray(tables, dtype=np.int32)
-    rc = _host_lib().vrg_anchor_check(C.c_void_p(desc.ctypes.data), len(desc), C.c_void_p(tables.ctypes.data) if tables.size else None,
-                                      int(tables.size), int(src_bytes), int(height), int(width))
-    if rc == _hip.VRG_ERR_BAD_ARG:
-        raise ValueError("anchor_frames: vrg_anchor_check refuses the records (a picture or a table outside its buffer, or a tap outside its axis)")
-    if rc != _hip.VRG_OK:
-        raise RuntimeError(f"anchor_frames: not built -- a picture more than 100 times as tall as wide whose height shrinks (Pillow resizes "
-                           f"those vertically first), or a frame of {height} x {width} is larger than one launch takes")
-
-
-def _anchor_out(out, shape, dtype, dev, what):
-    if out is None:
-        return torch.empty(shape, dtype=dtype, device=dev)
-    if (not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != dtype or tuple(out.shape) != tuple(shape)
-            or not out.is_contiguous()):
-        raise ValueError(f"{what}: out must be a contiguous {str(dtype).replace('torch.', '')} {list(shape)} tensor on {dev}")
-    return out
+    _refuse(_host_lib().vrg_anchor_check(C.c_void_p(desc.ctypes.data), len(desc), C.c_void_p(tables.ctypes.data) if tables.size else None,
+                                         int(tables.size), int(src_bytes), int(height), int(width)),
+            "anchor_frames", "vrg_anchor_check refuses the records (a picture or a table outside its buffer, or a tap outside its axis)",
+            "not built -- a picture more than 100 times as tall as wide whose height shrinks (Pillow resizes those vertically first), "
+            f"or a frame of {height} x {width} is larger than one launch takes")
 
 
 def anchor_frames(pictures, out: Optional[torch.Tensor] = None, size=None) -> torch.Tensor:
@@ -3883,19 +3799,16 @@ def anchor_frames(pictures, out: Optional[torch.Tensor] = None, size=None) -> to
     or ``size``, for a later chunk of a sequence whose first picture came with an earlier call.
     Returns the ``[n, H, W, 3]`` fp32 device tensor, or writes ``out`` (contiguous, of that shape, on that device).  The records are
     checked on the host before the launch.  Inputs are never written."""
-    from . import _devices
     what = "anchor_frames"
-    pics = [_anchor_picture(p, i) for i, p in enumerate(pictures)]
+    pics = [_byte_picture(p, f"{what}: picture {i}", allow_empty=False) for i, p in enumerate(pictures)]
     desc, tables, src_bytes, (height, width) = anchor_plan([tuple(p.shape[:2]) for p in pics], size)
-    on = [p.device for p in pics if p.is_cuda]
-    dev = on[0] if on else (out.device if isinstance(out, torch.Tensor) and out.is_cuda else _devices.compute_device())
-    if any(d != dev for d in on):
-        raise RuntimeError(f"{what}: the pictures live on more than one GPU")
+    dev = _placement([p.device for p in pics], what, "pictures", ring=False,
+                     prefer=out.device if isinstance(out, torch.Tensor) and out.is_cuda else None)
     anchor_check(desc, tables, src_bytes, height, width)
     with torch.cuda.device(dev):
-        dst = _anchor_out(out, (len(pics), height, width, 3), torch.float32, dev, what)
+        dst = _checked_out(out, (len(pics), height, width, 3), torch.float32, dev, what)
         flat = [p.contiguous().reshape(-1) for p in pics]
-        src = torch.cat(flat).to(dev) if not on else torch.cat([f.to(dev) for f in flat])
+        src = torch.cat([f.to(dev) for f in flat]) if any(p.is_cuda for p in pics) else torch.cat(flat).to(dev)
         table = _hip.upload_records(desc, dev, trailing=(tables,))
         at = len(desc) * ANCHOR_DESC.itemsize
         _hip.check(_hip.lib().vrg_anchor_frames_f32(_hip.ptr(src), src_bytes, _hip.ptr(table), len(desc),
@@ -3915,7 +3828,7 @@ def anchor_store_bytes(images: torch.Tensor, bgr: bool = False, out: Optional[to
         raise ValueError(_NO_ANCHOR_IMAGES)
     if int(x.shape[3]) < 3:
         raise ValueError(f"{what}: images must have at least 3 channels, got {int(x.shape[3])}")
-    dst = _anchor_out(out, (*x.shape[:3], 3), torch.uint8, x.device, what)
+    dst = _checked_out(out, (*x.shape[:3], 3), torch.uint8, x.device, what)
     _hip.check(_hip.lib().vrg_anchor_store_u8(_hip.ptr(x), _hip.ptr(dst), x.numel() // int(x.shape[3]), int(x.shape[3]),
                                               _hip.ANCHOR_BGR if bgr else _hip.ANCHOR_RGB, _hip.current_stream()), "vrg_anchor_store_u8")
     return dst

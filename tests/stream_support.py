@@ -492,9 +492,9 @@ HOST_SYNCING = {
     "upscale_sharpen_then_seeded_grain[first]": "ops.py _uploaded: _hip.upload_records(build(), device) on a cache miss",
     "cut_score[first]": "ops.py _uploaded: _hip.upload_records(build(), device) on a cache miss",
     "warp_affine_u8": "ops.py warp_affine_u8: rec = _hip.upload_records(table, x.device, F)",
-    "warp_affine_u8[first]": "ops.py _warp_table: torch.from_numpy(...).to(device), then warp_affine_u8's records",
+    "warp_affine_u8[first]": "ops.py _uploaded: _hip.upload_records(build(), device) on a cache miss, then warp_affine_u8's records",
     "video_grid": "ops.py _grid_launch: dev_desc = _hip.upload_records(desc, out.device)",
-    "video_grid[first]": "ops.py _grid_table: _hip.upload_records(table, device), then _grid_launch's records",
+    "video_grid[first]": "ops.py _uploaded: _hip.upload_records(build(), device) on a cache miss, then _grid_launch's records",
     "video_grid_bytes": "ops.py _grid_launch: dev_desc = _hip.upload_records(desc, out.device)",
     "msr_reference_frames": "ops.py msr_reference_frames: d = _hip.upload_records(desc, dev)",
     "prepare_frames": "ops.py prepare_frames: torch.tensor(listed, dtype=torch.int32).to(x.device)",
