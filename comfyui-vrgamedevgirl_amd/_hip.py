@@ -151,6 +151,12 @@ class PilBoxDesc(Record):
                 ("reserved", C.c_int32), ("mask_offset", C.c_int64), ("rep_offset", C.c_int64)]
 
 
+class PilPackedDesc(Record):
+    c_name = "vrg_pil_packed_desc"
+    _fields_ = [("src_offset", C.c_int64), ("dst_offset", C.c_int64), ("box_w", C.c_int32), ("box_h", C.c_int32), ("color_match", C.c_int32),
+                ("reserved", C.c_int32), ("mask_offset", C.c_int64), ("rep_offset", C.c_int64)]
+
+
 class GridDesc(Record):
     c_name = "vrg_grid_desc"
     _fields_ = [("src", C.c_void_p), ("xtab", C.c_void_p), ("ytab", C.c_void_p), ("overlay", C.c_void_p),
@@ -258,6 +264,7 @@ ASSEMBLE_BAR = 60               # include/vrgdg_hip.h: VRG_ASSEMBLE_BAR (rows of
 ANCHOR_RGB, ANCHOR_BGR = 0, 1      # include/vrgdg_hip.h: VRG_ANCHOR_RGB / VRG_ANCHOR_BGR
 FACEFIX_STATS_WORDS = 12        # uint64 per frame (csrc/vrg_facefix_math.hpp: FF_STATS_WORDS)
 FACEFIX_PACKED_TILE = 256       # include/vrgdg_hip.h: VRG_FF_PACKED_TILE (box pixels of one workgroup)
+PIL_PACKED_TILE = 256           # include/vrgdg_hip.h: VRG_PIL_PACKED_TILE (box pixels of one workgroup of the packed far-face paste)
 
 _F3 = C.c_float * 3
 _P = C.c_void_p
@@ -346,6 +353,9 @@ _SIGNATURES = {
     "vrg_pil_mask_u8": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P]),
     "vrg_np_masked_means_f32": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_float, _P]),
     "vrg_pil_paste_u8": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
+    "vrg_pil_packed_check": (C.c_int, [_P, C.c_int64, _P] + [C.c_int64] * 4),
+    "vrg_np_packed_masked_means_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, C.c_float, _P]),
+    "vrg_pil_packed_paste_u8": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, C.c_int64, _P, _P, C.c_int64, _P]),
     "vrg_linear_taps": (C.c_int, [C.c_int32, C.c_int32, _P, _P]),
     "vrg_detect_check": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64]),
     "vrg_detect_blobs_f32": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P, _P]),

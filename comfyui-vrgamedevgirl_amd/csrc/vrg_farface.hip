@@ -13,12 +13,12 @@
 //   k_np_means            numpy's sequential fp32 means: one workgroup per frame walks its box in chunks of NP_CHUNK pixels; a lane folds
 //                         NP_RUN consecutive pixels into six maps, the maps are reduced pairwise in order through LDS, and the chunk is
 //                         applied at once unless a sum would reach its next power of two -- then one lane per sum walks the chunk with
-//                         real fp32 adds.
+//                         real fp32 adds (np_means_block of csrc/vrg_farface_body.hpp, shared with csrc/vrg_farface_packed.hip).
 //   k_pil_paste           ONE pass over the output batch as a flat run of bytes, 16 per thread: a piece that misses the box is one 16-byte
 //                         non-temporal load and store, a piece that touches it is rebuilt byte by byte (move_bytes of
 //                         csrc/vrg_byte_mover.hpp, shared with vrg_ff_composite_u8).
 #include "vrg_byte_mover.hpp"
-#include "vrg_pil_math.hpp"
+#include "vrg_farface_body.hpp"
 
 namespace vrg {
 
@@ -185,85 +185,15 @@ __device__ __forceinline__ bool pil_box_ok(const vrg_pil_box_desc& d, const PilG
 __global__ __launch_bounds__(256) void k_np_means(const uint8_t* __restrict__ originals, const uint8_t* __restrict__ repaired,
                                                    const uint8_t* __restrict__ masks, const vrg_pil_box_desc* __restrict__ desc,
                                                    uint32_t* __restrict__ stats, PilGeom g, float strength) {
-    __shared__ uint8_t stage[6][NP_CHUNK];                               // the chunk's values (0 where not selected), for the walk
-    __shared__ NpMap maps[256][6];
-    __shared__ uint64_t acc[6];
-    __shared__ uint32_t counts[4];
     const int64_t f = blockIdx.x;
-    const int32_t t = threadIdx.x;
     const vrg_pil_box_desc d = desc[f];                                  // uniform
     uint32_t* rec = stats + f * PIL_STATS_WORDS;
     if (!pil_box_ok(d, g) || !d.color_match) {
-        if (t < PIL_STATS_WORDS) rec[t] = 0u;
+        if (threadIdx.x < PIL_STATS_WORDS) rec[threadIdx.x] = 0u;
         return;
     }
-    const int64_t n = (int64_t)d.box_w * d.box_h;
-    const uint8_t* frame = originals + ((f * g.H + d.top) * (int64_t)g.W + d.left) * 3;
-    const uint8_t* rep = repaired + d.rep_offset;
-    const uint8_t* mask = masks + d.mask_offset;
-    if (t < 6) acc[t] = 0ull;
-    uint32_t count = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < n; base += NP_CHUNK) {
-        uint32_t sh[6];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) sh[k] = np_ulp_shift(acc[k]);
-        NpMap m[6];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) m[k].d[0] = m[k].d[1] = 0u;
-#pragma unroll
-        for (int e = 0; e < NP_RUN; ++e) {
-            const int32_t i = t * NP_RUN + e;
-            const int64_t p = base + i;
-            uint8_t v[6] = {0, 0, 0, 0, 0, 0};
-            if (p < n && mask[p] >= PIL_SELECT_FROM) {
-                const int32_t dy = (int32_t)(p / d.box_w), dx = (int32_t)(p - (int64_t)dy * d.box_w);
-                const uint8_t* o = frame + ((int64_t)dy * g.W + dx) * 3;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    v[c] = o[c];
-                    v[3 + c] = rep[p * 3 + c];
-                }
-                ++count;
-            }
-#pragma unroll
-            for (int k = 0; k < 6; ++k) {
-                stage[k][i] = v[k];
-                np_map_push(m[k], v[k], sh[k]);
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 6; ++k) maps[t][k] = m[k];
-        __syncthreads();
-        for (int s = 1; s < 256; s <<= 1) {                              // in order: (t) then (t + s)
-            if ((t & (2 * s - 1)) == 0) {
-#pragma unroll
-                for (int k = 0; k < 6; ++k) maps[t][k] = np_map_then(maps[t][k], maps[t + s][k], sh[k]);
-            }
-            __syncthreads();
-        }
-        if (t < 6) {
-            uint64_t a = acc[t];
-            const uint32_t mine = np_ulp_shift(a);
-            if (!np_apply(a, maps[0][t], mine)) {
-                const int32_t len = (int32_t)(n - base < NP_CHUNK ? n - base : NP_CHUNK);
-                a = np_walk(a, stage[t], len, 1);
-            }
-            acc[t] = a;
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) count += (uint32_t)__shfl_xor((int)count, off, 64);
-    if ((t & 63) == 0) counts[t >> 6] = count;
-    __syncthreads();
-    if (t == 0) {
-        uint64_t sums[6];
-        for (int k = 0; k < 6; ++k) sums[k] = acc[k];
-        uint32_t out[PIL_STATS_WORDS];
-        np_finish(counts[0] + counts[1] + counts[2] + counts[3], sums, strength, out);
-        for (int i = 0; i < PIL_STATS_WORDS; ++i) rec[i] = out[i];
-    }
+    const PilFrameOrig orig{originals + ((f * g.H + d.top) * (int64_t)g.W + d.left) * 3, d.box_w, g.W};
+    np_means_block(orig, repaired + d.rep_offset, masks + d.mask_offset, (int64_t)d.box_w * d.box_h, strength, rec);
 }
 
 // the paste as a policy of move_bytes: the repaired bytes, shifted where the box asked for the colour match, pasted under the byte mask
@@ -282,19 +212,14 @@ struct PilMover {
         fr.shift[0] = fr.shift[1] = fr.shift[2] = 0.0f;
     }
     __device__ __forceinline__ void load_stats(Frame& fr, int64_t f) const {
-        if (!fr.d.color_match) return;
-        const uint32_t* rec = stats + f * PIL_STATS_WORDS;
-        fr.matched = rec[10] != 0u;
-        for (int c = 0; c < 3; ++c) fr.shift[c] = f32_from_bits(rec[7 + c]);
+        if (fr.d.color_match) fr.matched = pil_read_shift(stats + f * PIL_STATS_WORDS, fr.shift);
     }
     __device__ __forceinline__ ByteBox box(const Frame& fr) const { return ByteBox{fr.d.left, fr.d.top, fr.d.box_w, fr.d.box_h, g.W}; }
     __device__ __forceinline__ uint8_t byte(const Frame& fr, int32_t r, uint8_t v) const {
         int64_t i;
         int32_t c;
         if (!byte_in_box(box(fr), r, i, c)) return v;
-        uint8_t face = repaired[fr.d.rep_offset + i * 3 + c];
-        if (fr.matched) face = pil_shift_byte(face, fr.shift[c]);
-        return pil_paste_byte(v, face, masks[fr.d.mask_offset + i]);
+        return pil_face_byte(v, repaired[fr.d.rep_offset + i * 3 + c], fr.matched, fr.shift[c], masks[fr.d.mask_offset + i]);
     }
 };
 

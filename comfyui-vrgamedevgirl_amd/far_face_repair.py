@@ -10,20 +10,25 @@ under the reference's names.
                                              with Pillow's LANCZOS, the mask, the optional colour match and ``Image.paste`` into a copy of
                                              the frame -- a handful of launches for the batch, no host round trip in between.
 ``pil_lanczos_resize``                       ``Image.resize(size, Image.Resampling.LANCZOS)`` for a batch of RGB or L images of any sizes.
+``composite_frames_packed``                  the same for frames that stay on the HOST (a CPU tensor, numpy frames): only the boxes cross the
+``composite_boxes_packed``                   bus -- the boxes of the originals and the repaired crops go up in one page-locked buffer, the
+                                             composited boxes come down in one (csrc/vrg_farface_packed.hip); ``packed_plan`` gives the
+                                             offsets and byte counts without a device, ``last_transfer`` what the last call moved.
 ``contact_sheet``                            :374-408 -- original and fixed frame side by side, ``Image.thumbnail`` (``Image.reduce`` and a
                                              BICUBIC resize over the fractional box) and the paste into the cells of the sheet: two launches.
 ``pil_thumbnail`` / ``pil_reduce``           ``Image.thumbnail`` and ``Image.reduce`` for a batch of RGB images of any sizes, on the same kernels.
 
 Every step equals Pillow / numpy byte for byte (csrc/vrg_pil_math.hpp).  The channel order is the caller's: the arithmetic treats the three
-channels alike.  Device-resident inputs stay on the device; CPU inputs are uploaded whole and the result comes back in the form the frames
-came in.  Detection, PNG / video / JPEG I/O, manifests and ``rebuild_video`` are out of scope.  The library is reached through ``_hip`` only;
-Pillow is needed for the ellipse outline alone.
+channels alike.  Device-resident inputs stay on the device; CPU inputs of ``composite_frames`` are uploaded whole and the result comes back in
+the form the frames came in -- ``composite_frames_packed`` moves the boxes alone.  Detection, PNG / video / JPEG I/O, manifests and
+``rebuild_video`` are out of scope.  The library is reached through ``_hip`` only; Pillow is needed for the ellipse outline alone.
 """
 from __future__ import annotations
 
 import ctypes as C
 import functools
 import math
+import threading
 from collections import namedtuple
 
 import numpy as np
@@ -31,7 +36,8 @@ import torch
 
 from . import _hip, ops
 from ._devices import compute_device
-from .VRGDG_FaceFix import _boxes, _frames_in, _host, _peek, _upload
+from .VRGDG_FaceFix import (_boxes, _download, _frames_in, _host, _host_arrays, _host_copy, _pack_boxes, _paste_boxes, _peek, _staging,
+                            _upload)
 
 NODE_CLASS_MAPPINGS = {}
 NODE_DISPLAY_NAME_MAPPINGS = {}
@@ -46,6 +52,8 @@ _RESIZE_DESC = _hip.record_dtype(_hip.PilResizeDesc)
 _MASK_DESC = _hip.record_dtype(_hip.PilMaskDesc)
 _BOX_DESC = _hip.record_dtype(_hip.PilBoxDesc)
 _THUMB_ENTRY = _hip.record_dtype(_hip.ThumbEntry)
+_PACKED_DESC = _hip.record_dtype(_hip.PilPackedDesc)
+_transfer = threading.local()
 
 SHEET_CANVAS = (24, 24, 24)
 NO_FRAMES = "No frames were available for the contact sheet."
@@ -343,17 +351,8 @@ class CompositePlan:
         self.x, self.color_match = x, bool(color_match)
         used = [(f, b) for f, b in enumerate(boxes) if b is not None]
         src, offsets = _pack(repaired, device)
-        self.resize = ResizePlan(src, offsets, [(int(r.shape[1]), int(r.shape[0]), b[2], b[3]) for r, (_, b) in zip(repaired, used)], 3, device)
-        if feather >= 0:
-            self.mask_plan, self.mask_resize = MaskPlan([(b[2], b[3]) for _, b in used], feather, device), None
-            mask_offsets = [self.mask_plan.offsets[(b[2], b[3])] for _, b in used]
-            self.mask_bytes = self.mask_plan.total
-        else:
-            msrc, moffsets = _pack(masks, device)
-            self.mask_plan = None
-            self.mask_resize = ResizePlan(msrc, moffsets, [(int(m.shape[1]), int(m.shape[0]), b[2], b[3]) for m, (_, b) in zip(masks, used)], 1,
-                                          device)
-            mask_offsets, self.mask_bytes = self.mask_resize.offsets, self.mask_resize.dst_bytes
+        msrc, moffsets = _pack(masks, device) if feather < 0 else (None, None)
+        mask_offsets = self._plans([b for _, b in used], feather, device, repaired, src, offsets, masks, msrc, moffsets)
         desc = np.zeros(int(x.shape[0]), dtype=_BOX_DESC)
         for k, (f, (left, top, w, h)) in enumerate(used):
             desc[f] = (left, top, w, h, int(self.color_match), 0, mask_offsets[k], self.resize.offsets[k])
@@ -361,6 +360,19 @@ class CompositePlan:
         self.stats = torch.zeros(int(x.shape[0]) * _hip.PIL_STATS_WORDS, dtype=torch.int32, device=device)
         self.out = torch.empty_like(x)
         self.rep = self.masks = None
+
+    def _plans(self, boxes, feather, device, repaired, src, offsets, masks, msrc, moffsets):
+        """the resize of the crops (`repaired[k]` at ``offsets[k]`` of the device buffer ``src``) and the masks of ``boxes`` -- fresh, or the
+        saved ones (``masks[k]`` at ``moffsets[k]`` of ``msrc``) resized as L -> the mask's offset per box"""
+        self.resize = ResizePlan(src, offsets, [(int(r.shape[1]), int(r.shape[0]), b[2], b[3]) for r, b in zip(repaired, boxes)], 3, device)
+        if feather >= 0:
+            self.mask_plan, self.mask_resize = MaskPlan([(b[2], b[3]) for b in boxes], feather, device), None
+            self.mask_bytes = self.mask_plan.total
+            return [self.mask_plan.offsets[(b[2], b[3])] for b in boxes]
+        self.mask_plan = None
+        self.mask_resize = ResizePlan(msrc, moffsets, [(int(m.shape[1]), int(m.shape[0]), b[2], b[3]) for m, b in zip(masks, boxes)], 1, device)
+        self.mask_bytes = self.mask_resize.dst_bytes
+        return self.mask_resize.offsets
 
     def run_resize(self):
         self.rep = self.resize.run()
@@ -374,15 +386,22 @@ class CompositePlan:
                 _hip.ptr(self.stats))
 
     def run_means(self):
-        x = self.x
         if self.color_match:
-            _hip.check(_hip.lib().vrg_np_masked_means_f32(*self._args(), int(x.shape[0]), int(x.shape[1]), int(x.shape[2]), COLOR_MATCH_STRENGTH,
-                                                          _hip.current_stream()), "vrg_np_masked_means_f32")
+            self._means(_hip.current_stream())
 
     def run_paste(self):
+        return self._paste(_hip.current_stream())
+
+    # what the two steps launch on the stream they are handed: PackedCompositePlan launches the packed kernels instead
+    def _means(self, stream):
         x = self.x
-        _hip.check(_hip.lib().vrg_pil_paste_u8(*self._args(), _hip.ptr(self.out), int(x.shape[0]), int(x.shape[1]), int(x.shape[2]),
-                                               _hip.current_stream()), "vrg_pil_paste_u8")
+        _hip.check(_hip.lib().vrg_np_masked_means_f32(*self._args(), int(x.shape[0]), int(x.shape[1]), int(x.shape[2]), COLOR_MATCH_STRENGTH,
+                                                      stream), "vrg_np_masked_means_f32")
+
+    def _paste(self, stream):
+        x = self.x
+        _hip.check(_hip.lib().vrg_pil_paste_u8(*self._args(), _hip.ptr(self.out), int(x.shape[0]), int(x.shape[1]), int(x.shape[2]), stream),
+                   "vrg_pil_paste_u8")
         return self.out
 
 
@@ -452,6 +471,151 @@ def masked_means(original, repaired, mask) -> dict:
         rec = plan.stats.cpu().numpy().view(np.uint32)[:_hip.PIL_STATS_WORDS]
     return {"count": int(rec[0]), "original_mean": rec[1:4].view(np.float32).copy(), "repaired_mean": rec[4:7].view(np.float32).copy(),
             "shift": rec[7:10].view(np.float32).copy(), "matched": bool(rec[10])}
+
+
+# ------------------------------------------------------------------------------------------------
+# frames that stay on the host: only the boxes cross the bus (csrc/vrg_farface_packed.hip)
+# ------------------------------------------------------------------------------------------------
+class PackedPlan:
+    """Host integers of one packed call, one entry per frame that has a box, in frame order: ``frames`` the frame indices, ``boxes``
+    (left, top, w, h), ``offsets`` the byte offset of the box's dense [h][w][3] block in the packed buffers, ``tile_prefix`` int64 [n + 1]:
+    0 and the running sum of ceil(w * h / 256), ``tiles`` its last entry.  ``bytes_up`` = ``bytes_down`` = the bytes of all boxes: what the
+    composite moves each way for the originals (the repaired crops and the small tables go up besides).  ``frame_bytes`` = frames * H * W * 3."""
+
+    def __init__(self, frames, boxes, frame_bytes):
+        self.frames, self.boxes, self.frame_bytes = frames, boxes, frame_bytes
+        sizes = [w * h * 3 for _, _, w, h in boxes]
+        self.offsets = [int(v) for v in np.cumsum([0] + sizes[:-1])] if sizes else []
+        tile = _hip.PIL_PACKED_TILE
+        self.tile_prefix = np.concatenate([[0], np.cumsum([(w * h + tile - 1) // tile for _, _, w, h in boxes], dtype=np.int64)]).astype(np.int64)
+        self.tiles = int(self.tile_prefix[-1])
+        self.bytes_up = self.bytes_down = int(sum(sizes))
+
+
+def packed_plan(frames, height, width, crop_boxes) -> PackedPlan:
+    """The plan of a packed call on ``frames`` frames of ``height`` x ``width``: ``crop_boxes`` as ``composite_frames`` takes them (the
+    same ValueErrors).  No pixels, no device."""
+    frames, height, width = int(frames), int(height), int(width)
+    boxes = _boxes(crop_boxes, frames, height, width)
+    used = [(f, b) for f, b in enumerate(boxes) if b is not None]
+    return PackedPlan([f for f, _ in used], [b for _, b in used], frames * height * width * 3)
+
+
+def last_transfer() -> dict:
+    """The bytes the last packed call of this thread moved: ``bytes_up`` / ``bytes_down`` the boxes' pixels (the plan's counts),
+    ``repaired_up`` the repaired crops (and the saved masks), ``tables_up`` records and tables.  For tests and tools."""
+    return dict(getattr(_transfer, "value", None) or {"bytes_up": 0, "bytes_down": 0, "repaired_up": 0, "tables_up": 0})
+
+
+class PackedCompositePlan(CompositePlan):
+    """``CompositePlan`` on ONE upload ``dev`` (uint8, on the device): the boxes of ``plan`` as dense blocks from byte 0, the repaired crops
+    ``repaired[k]`` at ``rep_at + offsets[k]`` and -- ``feather < 0`` -- the saved masks ``masks[k]`` at ``mask_at + moffsets[k]``.  The
+    resize and the masks read views of that upload; the means and the paste are the packed kernels, on the stream ``run_means`` /
+    ``run_paste`` hand them."""
+
+    def __init__(self, dev, plan, repaired, feather, color_match, rep_at, offsets, masks, mask_at, moffsets):
+        device, total = dev.device, plan.bytes_up
+        self.x, self.color_match, self.plan, self.total = dev[:total], bool(color_match), plan, total
+        mask_offsets = self._plans(plan.boxes, feather, device, repaired, dev[rep_at:mask_at], offsets, masks, dev[mask_at:], moffsets)
+        desc = np.zeros(len(plan.boxes), dtype=_PACKED_DESC)
+        for k, ((_, _, w, h), offset) in enumerate(zip(plan.boxes, plan.offsets)):
+            desc[k] = (offset, offset, w, h, int(self.color_match), 0, mask_offsets[k], self.resize.offsets[k])
+        _host_check(_host().vrg_pil_packed_check(C.c_void_p(desc.ctypes.data), len(desc), C.c_void_p(plan.tile_prefix.ctypes.data), total,
+                                                 self.resize.dst_bytes, self.mask_bytes, total), "vrg_pil_packed_check")
+        self.desc = _upload(desc, device, trailing=(plan.tile_prefix,))
+        self.prefix = C.c_void_p(self.desc.data_ptr() + desc.nbytes)
+        self.stats = torch.zeros(len(desc) * _hip.PIL_STATS_WORDS, dtype=torch.int32, device=device)
+        self.out = torch.empty(total, dtype=torch.uint8, device=device)
+        self.rep = self.masks = None
+
+    def tables_up(self):
+        parts = [self.desc, self.resize.tables, self.resize.desc] + \
+                ([self.mask_plan.spans, self.mask_plan.records] if self.mask_plan is not None else [self.mask_resize.tables, self.mask_resize.desc])
+        return int(sum(t.numel() * t.element_size() for t in parts if t is not None))
+
+    def _packed(self):
+        return (_hip.ptr(self.x), self.total, _hip.ptr(self.rep), self.resize.dst_bytes, _hip.ptr(self.masks), self.mask_bytes, _hip.ptr(self.desc))
+
+    def _means(self, stream):
+        _hip.check(_hip.lib().vrg_np_packed_masked_means_f32(*self._packed(), _hip.ptr(self.stats), len(self.plan.boxes), COLOR_MATCH_STRENGTH,
+                                                             stream), "vrg_np_packed_masked_means_f32")
+
+    def _paste(self, stream):
+        _hip.check(_hip.lib().vrg_pil_packed_paste_u8(*self._packed(), self.prefix, len(self.plan.boxes), self.plan.tiles, _hip.ptr(self.stats),
+                                                      _hip.ptr(self.out), self.total, stream), "vrg_pil_packed_paste_u8")
+        return self.out
+
+
+def _host_images(images):
+    """the CPU images of a batch (tensors or arrays) as dense numpy arrays"""
+    return [np.ascontiguousarray(i.numpy() if isinstance(i, torch.Tensor) else i) for i in images]
+
+
+def _on_gpu(values):
+    """is a batch of crops or masks (a tensor, or a sequence of images) on the GPU, or any image of it?"""
+    if hasattr(values, "u8") or (isinstance(values, torch.Tensor) and values.is_cuda):
+        return True
+    return not isinstance(values, (torch.Tensor, np.ndarray)) and any(isinstance(v, torch.Tensor) and v.is_cuda for v in values)
+
+
+def composite_boxes_packed(originals_u8, repaired, crop_boxes, feather=DEFAULT_FEATHER, color_match=False, masks=None):
+    """The pixels of ``composite_frames`` for frames on the host (a CPU uint8 tensor [F, H, W, 3] or a list of numpy frames of one size),
+    boxes only: the boxes of ``originals_u8``, the repaired crops and -- ``feather < 0`` -- the saved masks go up in one page-locked
+    buffer, the composited boxes come down in one -> one ``[h, w, 3]`` array per frame with a box, in the order of
+    ``packed_plan(...).frames`` (views of the download).  ``repaired`` / ``masks`` as ``composite_frames`` takes them.  Nothing outside a
+    box crosses the bus; no input is written.  Frames or crops on the GPU raise TypeError: ``composite_frames`` keeps them there."""
+    arrays = _host_arrays(originals_u8, "originals", "composite_frames")
+    for values, name in ((repaired, "repaired"), (masks, "masks")):
+        if values is not None and _on_gpu(values):
+            raise TypeError(f"{name} is on the GPU already: the packed route is for decoded frames on the host, use composite_frames")
+    feather, _, rep, mk = _prepare(originals_u8, repaired, crop_boxes, feather, masks)
+    plan = packed_plan(*_peek(originals_u8, "originals"), crop_boxes)
+    if not plan.frames:
+        _transfer.value = None
+        return []
+    rep, mk = _host_images(rep), (_host_images(mk) if mk is not None else None)
+    sizes = [r.size for r in rep] + [m.size for m in mk or []]
+    rep_at = -(-plan.bytes_up // 16) * 16
+    starts = [int(v) for v in rep_at + np.cumsum([0] + sizes)]
+    mask_at = starts[len(rep)]
+    stage = _staging(starts[-1])
+    staged = stage.numpy()
+    _pack_boxes(arrays, plan, staged)
+    for image, start in zip(rep + (mk or []), starts):
+        staged[start:start + image.size] = image.reshape(-1)
+    device = compute_device()
+    with torch.cuda.device(device):
+        dev = stage[:starts[-1]].to(device, non_blocking=True)
+        work = PackedCompositePlan(dev, plan, rep, feather, color_match, rep_at, [s - rep_at for s in starts[:len(rep)]], mk, mask_at,
+                                   [s - mask_at for s in starts[len(rep):-1]])
+        work.run_resize()
+        work.run_masks()
+        work.run_means()
+        host = _download(work.run_paste()).numpy()
+    _transfer.value = {"bytes_up": plan.bytes_up, "bytes_down": plan.bytes_down, "repaired_up": starts[-1] - rep_at, "tables_up": work.tables_up()}
+    return [host[offset:offset + w * h * 3].reshape(h, w, 3) for (_, _, w, h), offset in zip(plan.boxes, plan.offsets)]
+
+
+def composite_frames_packed(originals_u8, repaired, crop_boxes, feather=DEFAULT_FEATHER, color_match=False, masks=None, *, inplace=False):
+    """``composite_frames`` for frames on the host: ``composite_boxes_packed`` pasted into a host copy of ``originals_u8`` (the
+    reference's ``original.copy()``; the result has the originals' form), or -- ``inplace=True`` -- into the caller's own frames, which
+    are returned.  ``originals_u8`` is never written unless ``inplace=True``."""
+    arrays = _host_arrays(originals_u8, "originals", "composite_frames")
+    plan = packed_plan(*_peek(originals_u8, "originals"), crop_boxes)
+    results = composite_boxes_packed(originals_u8, repaired, crop_boxes, feather, color_match, masks)
+    if inplace:
+        out, target = originals_u8, arrays
+    elif isinstance(originals_u8, torch.Tensor):
+        out = torch.empty(originals_u8.shape, dtype=torch.uint8)
+        if out.numel():
+            _host_copy(out.numpy(), originals_u8.numpy())
+        target = list(out.numpy())
+    else:
+        out = target = [np.empty(a.shape, dtype=np.uint8) for a in arrays]
+        for dst, src in zip(target, arrays):
+            _host_copy(dst, src)
+    _paste_boxes(target, plan, results)
+    return out
 
 
 # ------------------------------------------------------------------------------------------------

@@ -803,6 +803,47 @@ int vrg_pil_paste_u8(const uint8_t* originals, const uint8_t* repaired, int64_t 
                      const vrg_pil_box_desc* desc, const uint32_t* stats, uint8_t* out, int64_t frames, int32_t height, int32_t width,
                      void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The same composite for frames that live on the HOST (csrc/vrg_farface_packed.hip): only the boxes cross the bus.  `src` is one buffer
+ * of `src_bytes` bytes that holds each box's original bytes as a dense [box_h][box_w][3] block at its record's src_offset; the paste
+ * writes each box's result as such a block at dst_offset of `out` (`out_bytes` bytes).  `repaired` and `masks` are the packed outputs of
+ * vrg_pil_resize_u8 / vrg_pil_mask_u8 above, `stats` holds 12 uint32 per RECORD, laid out as vrg_np_masked_means_f32 writes them.
+ *
+ * Grids are one-dimensional.  The means are one workgroup per record.  A workgroup of the paste is one tile of VRG_PIL_PACKED_TILE box
+ * pixels; it finds its record in `tile_prefix` (device, n + 1 int64, 8-byte aligned): tile_prefix[i] = the first tile of record i,
+ * tile_prefix[n] = `tiles`, the grid (workgroups past the last tile do nothing; tiles > 2^31 - 1: VRG_ERR_UNSUPPORTED).
+ *
+ * vrg_pil_packed_check refuses ON THE HOST (VRG_ERR_BAD_ARG) what the launches do not follow: a box below 1 x 1 or of 2^31 bytes or
+ * more, a span (src, dst, rep, mask) that leaves the stated sizes, a tile_prefix that is not the running sum of
+ * ceil(box_w * box_h / VRG_PIL_PACKED_TILE) from 0.  n == 0 is fine.  On the device a record that fails these checks gets a zero
+ * statistics record; the paste writes a copy of its original bytes where its src and dst blocks lie inside the buffers and nothing
+ * otherwise.
+ * ------------------------------------------------------------------------------------------- */
+#define VRG_PIL_PACKED_TILE 256
+
+typedef struct vrg_pil_packed_desc {
+    int64_t src_offset;                /* bytes from `src` to the box's [box_h][box_w][3] original bytes */
+    int64_t dst_offset;                /* bytes from `out` of the paste to the box's [box_h][box_w][3] result */
+    int32_t box_w, box_h;
+    int32_t color_match;               /* != 0: the mean shift of color_match_repaired */
+    int32_t reserved;                  /* 0 */
+    int64_t mask_offset;               /* bytes from `masks` to the [box_h][box_w] mask */
+    int64_t rep_offset;                /* bytes from `repaired` to the [box_h][box_w][3] resized crop */
+} vrg_pil_packed_desc;
+
+int vrg_pil_packed_check(const vrg_pil_packed_desc* desc_host, int64_t n, const int64_t* tile_prefix_host, int64_t src_bytes,
+                         int64_t rep_bytes, int64_t mask_bytes, int64_t out_bytes);
+
+/* stats[i] of vrg_np_masked_means_f32 for record i: the same sequential fp32 means, the box's pixel p read at src_offset + 3 p. */
+int vrg_np_packed_masked_means_f32(const uint8_t* src, int64_t src_bytes, const uint8_t* repaired, int64_t rep_bytes, const uint8_t* masks,
+                                   int64_t mask_bytes, const vrg_pil_packed_desc* desc, uint32_t* stats, int64_t n, float strength,
+                                   void* stream);
+
+/* out[dst_offset ..] = the paste of vrg_pil_paste_u8 inside the box, for every record.  out != src, which is never written. */
+int vrg_pil_packed_paste_u8(const uint8_t* src, int64_t src_bytes, const uint8_t* repaired, int64_t rep_bytes, const uint8_t* masks,
+                            int64_t mask_bytes, const vrg_pil_packed_desc* desc, const int64_t* tile_prefix, int64_t n, int64_t tiles,
+                            const uint32_t* stats, uint8_t* out, int64_t out_bytes, void* stream);
+
 
 /* ---------------------------------------------------------------------------------------------
  * Host side of the node path (reference: nodes.py:50, 61-66 -- CPU tensors in, `images.to(device)` per batch)
