@@ -197,8 +197,17 @@ static int launch_adjust(const void* in, void* out, float* tmp, int64_t frames, 
     typedef typename IO::elem elem;
     if (!in || !out || !d || frames < 0 || height <= 0 || width <= 0) return VRG_ERR_BAD_ARG;
     if (d->div_mode != VRG_ADJUST_DIV_IEEE && d->div_mode != VRG_ADJUST_DIV_DEVICE) return VRG_ERR_BAD_ARG;
-    if (frames == 0) return VRG_OK;
     const int64_t ppf = (int64_t)height * width;
+    {   // in, out and the fp32 ring between the two boxes (when both run): the boxes read a halo that other workgroups store
+        const int box = adjust_box_size(height, width);
+        const bool ring = d->enabled && d->has_clarity && box >= 3 && d->has_sharpen;
+        const int64_t io_bytes = vrg_operand_bytes(frames, vrg_operand_bytes(ppf, (int64_t)sizeof(elem)));
+        const int64_t ring_bytes = ring ? vrg_operand_bytes(frames, vrg_operand_bytes(ppf, 12)) : 0;
+        if (vrg_ranges_overlap(in, io_bytes, out, io_bytes) || vrg_ranges_overlap(in, io_bytes, tmp, ring_bytes) ||
+            vrg_ranges_overlap(out, io_bytes, tmp, ring_bytes))
+            return VRG_ERR_BAD_ARG;
+    }
+    if (frames == 0) return VRG_OK;
     if (ppf > 0x7fffffff / 3) return VRG_ERR_UNSUPPORTED;
     AdjustK A{};
     A.enabled = d->enabled;

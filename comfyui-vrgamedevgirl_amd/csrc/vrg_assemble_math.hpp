@@ -50,12 +50,6 @@ inline uint32_t asm_grid_x(int64_t tiles, int64_t frames) {
     return (uint32_t)(gx < 1 ? 1 : gx);
 }
 
-inline bool asm_overlap(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
-    if (!a || !b || a_bytes <= 0 || b_bytes <= 0) return false;
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + (uint64_t)b_bytes && b0 < a0 + (uint64_t)a_bytes;
-}
-
 // What the launches refuse, on the host.  `map` may be null (the launches hold the table in device memory and the kernels follow no entry
 // that leaves its source); out_f32 / out_u8 may be null.
 inline int asm_check(const vrg_assemble_desc* d, const vrg_assemble_entry* map, int64_t n_out, const void* out_f32, const void* out_u8,
@@ -78,11 +72,11 @@ inline int asm_check(const vrg_assemble_desc* d, const vrg_assemble_entry* map, 
     if (n > 0x7fffffff || (labelled && n + bar > 0x7fffffff)) return VRG_ERR_UNSUPPORTED;   // in-frame offsets are 32-bit, frames 64-bit
     if (n_out > 0x7fffffffffffffffll / 4 / (n + bar)) return VRG_ERR_UNSUPPORTED;
     const int64_t f32_bytes = n_out * n * 4, u8_bytes = n_out * (n + bar);
-    if (asm_overlap(out_f32, f32_bytes, out_u8, u8_bytes)) return VRG_ERR_BAD_ARG;
+    if (vrg_ranges_overlap(out_f32, f32_bytes, out_u8, u8_bytes)) return VRG_ERR_BAD_ARG;
     for (int i = 0; i < d->n_src; ++i) {
         const int64_t src_bytes = (int64_t)d->frames[i] * n * (d->bytes ? 1 : 4);
-        if (asm_overlap(out_f32, f32_bytes, d->src[i], src_bytes) || asm_overlap(out_u8, u8_bytes, d->src[i], src_bytes)) return VRG_ERR_BAD_ARG;
-        if (labelled && (asm_overlap(out_f32, f32_bytes, d->overlay[i], bar) || asm_overlap(out_u8, u8_bytes, d->overlay[i], bar)))
+        if (vrg_ranges_overlap(out_f32, f32_bytes, d->src[i], src_bytes) || vrg_ranges_overlap(out_u8, u8_bytes, d->src[i], src_bytes)) return VRG_ERR_BAD_ARG;
+        if (labelled && (vrg_ranges_overlap(out_f32, f32_bytes, d->overlay[i], bar) || vrg_ranges_overlap(out_u8, u8_bytes, d->overlay[i], bar)))
             return VRG_ERR_BAD_ARG;
     }
     return VRG_OK;

@@ -503,6 +503,10 @@ int vrg_fused_chain_f32(const float* in, float* out, int64_t frames, int32_t hei
     if (!in || !out || !desc || frames < 0 || height <= 0 || width <= 0) return VRG_ERR_BAD_ARG;
     if (desc->stages == 0 || (desc->stages & ~31)) return VRG_ERR_BAD_ARG;
     if ((desc->stages & VRG_STAGE_FROM_LAB) && (desc->stages & 7) != VRG_STAGE_COLORMATCH) return VRG_ERR_BAD_ARG;
+    {
+        const int64_t bytes = vrg_operand_bytes(frames, vrg_operand_bytes((int64_t)height * width, 12));
+        if (vrg_ranges_overlap(in, bytes, out, bytes)) return VRG_ERR_BAD_ARG;      // stencil windows, and the marches store a last strip twice
+    }
     if (frames == 0) return VRG_OK;
     if ((int64_t)height * width > 0x7fffffff / 3) return VRG_ERR_UNSUPPORTED;
     if ((desc->stages & VRG_STAGE_COLORMATCH) && (!desc->img_ms || !desc->ref_ms || desc->ref_frames < 1)) return VRG_ERR_BAD_ARG;
@@ -588,6 +592,10 @@ int vrg_fused_chain_u8(const uint8_t* in, uint8_t* out, int64_t frames, int32_t 
                        void* stream) {
     if (!in || !out || !desc || frames < 0 || height <= 0 || width <= 0) return VRG_ERR_BAD_ARG;
     if (desc->stages == 0 || (desc->stages & ~(VRG_STAGE_GRAIN | VRG_STAGE_LUT | VRG_STAGE_SHARPEN))) return VRG_ERR_UNSUPPORTED;
+    {
+        const int64_t bytes = vrg_operand_bytes(frames, vrg_operand_bytes((int64_t)height * width, 3));
+        if (vrg_ranges_overlap(in, bytes, out, bytes)) return VRG_ERR_BAD_ARG;
+    }
     if (frames == 0) return VRG_OK;
     if ((int64_t)height * width > 0x7fffffff / 3) return VRG_ERR_UNSUPPORTED;
     ChainK D;

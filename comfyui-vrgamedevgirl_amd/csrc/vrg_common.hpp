@@ -30,6 +30,26 @@ namespace vrg {
 // Records name their data by offset into buffers that kernels read through raw pointers: do `need` elements from `offset` lie inside `size`?
 VRG_HD bool span_fits(int64_t offset, int64_t need, int64_t size) { return offset >= 0 && offset <= size && need <= size - offset; }
 
+}  // namespace vrg
+
+// The one overlap rule of the entry points (include/vrgdg_hip.h, "Operands must not overlap"): do the half-open byte ranges
+// [a, a + a_bytes) and [b, b + b_bytes) share a byte?  A range of no (or a negative number of) bytes shares none, wherever it lies, and a
+// null pointer is an operand that is not there.  Only the distance between the two starts is formed, never a + a_bytes, so a range that
+// ends at the top of the address space does not wrap.
+inline bool vrg_ranges_overlap(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
+    if (!a || !b || a_bytes <= 0 || b_bytes <= 0) return false;
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x <= y ? (uint64_t)a_bytes > (uint64_t)(y - x) : (uint64_t)b_bytes > (uint64_t)(x - y);
+}
+// count * each bytes of an operand, INT64_MAX where that product does not fit (no operand is that long: the range then reaches as far as
+// any can, which is the refusing side)
+inline int64_t vrg_operand_bytes(int64_t count, int64_t each) {
+    if (count <= 0 || each <= 0) return 0;
+    return count > INT64_MAX / each ? INT64_MAX : count * each;
+}
+
+namespace vrg {
+
 // blockIdx.y / blockIdx.z take one record each, at most this many per launch
 constexpr int64_t LAUNCH_RECORDS = 32768;
 

@@ -352,6 +352,22 @@ extern "C" int vrg_composite_stats_f32(const float* crops, const float* original
     });
 }
 
+// out and mask_out are both written, every other operand is read: no written operand may share a byte with another operand
+static bool composite_operands_overlap(const CompositeGeom& g, const float* crops, const float* originals, const float* user_mask,
+                                       const uint8_t* bytes, int64_t n_bytes, const float* out, const float* mask_out) {
+    const int64_t px = (int64_t)g.H * g.W;
+    const int64_t out_bytes = vrg_operand_bytes(g.frames, px * g.C * 4), mask_out_bytes = vrg_operand_bytes(g.frames, px * 4);
+    const void* reads[4] = {crops, originals, user_mask, bytes};
+    const int64_t read_bytes[4] = {vrg_operand_bytes(g.n_crop, (int64_t)g.crop_h * g.crop_w * g.crop_c * 4),
+                                   vrg_operand_bytes(g.n_orig, px * g.C * 4),
+                                   vrg_operand_bytes(g.n_mask, (int64_t)g.mask_h * g.mask_w * g.mask_stride * 4), n_bytes};
+    if (vrg_ranges_overlap(out, out_bytes, mask_out, mask_out_bytes)) return true;
+    for (int i = 0; i < 4; ++i)
+        if (vrg_ranges_overlap(out, out_bytes, reads[i], read_bytes[i]) || vrg_ranges_overlap(mask_out, mask_out_bytes, reads[i], read_bytes[i]))
+            return true;
+    return false;
+}
+
 extern "C" int vrg_composite_apply_f32(const float* crops, const float* originals, const float* user_mask, const vrg_composite_desc* desc,
                                        const void* stats, float* out, float* mask_out,
                                        int64_t frames, int64_t original_frames, int64_t crop_frames, int64_t mask_frames,
@@ -364,6 +380,7 @@ extern "C" int vrg_composite_apply_f32(const float* crops, const float* original
     if (frames == 0) return VRG_OK;
     if (!crops || !originals || !desc || !stats || !out || !mask_out || out == originals || out == crops || !composite_geom_ok(g, user_mask))
         return VRG_ERR_BAD_ARG;
+    if (composite_operands_overlap(g, crops, originals, user_mask, nullptr, 0, out, mask_out)) return VRG_ERR_BAD_ARG;
     if (!composite_geom_supported(g, user_mask)) return VRG_ERR_UNSUPPORTED;
     const int64_t total_px = frames * (int64_t)height * width;
     const int64_t blocks = ((total_px + 3) / 4 + 255) / 256;
@@ -394,6 +411,7 @@ extern "C" int vrg_composite_warp_apply_f32(const float* crops, const float* ori
     if (!crops || !originals || !desc || !stats || !rec || !bytes || !table || !out || !mask_out || out == originals || out == crops ||
         ((uintptr_t)table & 15) || !composite_geom_ok(g, user_mask))
         return VRG_ERR_BAD_ARG;
+    if (composite_operands_overlap(g, crops, originals, user_mask, bytes, n_bytes, out, mask_out)) return VRG_ERR_BAD_ARG;
     if (!composite_geom_supported(g, user_mask)) return VRG_ERR_UNSUPPORTED;
     const int64_t total_px = frames * (int64_t)height * width;
     const int64_t blocks = ((total_px + 3) / 4 + 255) / 256;
@@ -448,6 +466,7 @@ extern "C" int vrg_warp_affine_u8(const uint8_t* in, int64_t in_bytes, uint8_t* 
                                   int32_t out_h, int32_t out_w, void* stream) {
     if (frames < 0 || in_bytes < 0) return VRG_ERR_BAD_ARG;
     if (!in || !out || !rec || !table || in == out || ((uintptr_t)table & 15) || out_h < 1 || out_w < 1) return VRG_ERR_BAD_ARG;
+    if (vrg_ranges_overlap(in, in_bytes, out, vrg_operand_bytes(frames, (int64_t)out_h * out_w * 3))) return VRG_ERR_BAD_ARG;
     if (frames == 0) return VRG_OK;
     const int64_t px = (int64_t)out_h * out_w;
     if (px * 3 > 0x7fffffffll) return VRG_ERR_UNSUPPORTED;

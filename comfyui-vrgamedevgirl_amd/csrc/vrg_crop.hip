@@ -110,6 +110,7 @@ using namespace vrg;
 extern "C" int vrg_crop_resize_f32(const float* in, int64_t in_floats, float* out, const vrg_crop_desc* desc, int64_t n_out,
                                    int32_t size_h, int32_t size_w, void* stream) {
     if (!in || !out || !desc || in == out || in_floats < 0 || n_out < 0 || size_h < 1 || size_w < 1) return VRG_ERR_BAD_ARG;
+    if (vrg_ranges_overlap(in, vrg_operand_bytes(in_floats, 4), out, vrg_operand_bytes(n_out, (int64_t)size_h * size_w * 12))) return VRG_ERR_BAD_ARG;
     if (n_out == 0) return VRG_OK;
     if ((int64_t)size_h * size_w > 0x7fffffff / 4) return VRG_ERR_UNSUPPORTED;
     const uint32_t bx = (uint32_t)((size_w + 255) / 256), by = (uint32_t)((size_h + CROP_ROWS - 1) / CROP_ROWS);

@@ -148,8 +148,9 @@ static bool lz_tileable(int32_t in_h, int32_t out_h, int halo) {
 }
 
 static bool lz_bad_geometry(const void* in, const void* out, const void* taps, int64_t frames, int32_t in_h, int32_t in_w, int32_t out_h, int32_t out_w) {
-    return !in || !out || in == out || !taps || (reinterpret_cast<uintptr_t>(taps) & 3u) != 0 || frames < 0 || in_h < 1 || in_w < 1 || out_h < 1 ||
-           out_w < 1;
+    if (!in || !out || in == out || !taps || (reinterpret_cast<uintptr_t>(taps) & 3u) != 0 || frames < 0 || in_h < 1 || in_w < 1 || out_h < 1 || out_w < 1)
+        return true;
+    return vrg_ranges_overlap(in, vrg_operand_bytes(frames, (int64_t)in_h * in_w * 3), out, vrg_operand_bytes(frames, (int64_t)out_h * out_w * 3));
 }
 
 }  // namespace vrg

@@ -691,6 +691,7 @@ int vrg_sharpen_grain_f32(const float* in, float* out, int64_t frames, int32_t h
     GrainGeom g;
     if (!in || !out || in == out || frames < 0 || height <= 0 || width <= 0 || border < 0 || border > 1 || !grain_geom(nd, frame_elems, GRAIN_N, g))
         return VRG_ERR_BAD_ARG;
+    if (vrg_ranges_overlap(in, vrg_operand_bytes(frames, frame_elems * 4), out, vrg_operand_bytes(frames, frame_elems * 4))) return VRG_ERR_BAD_ARG;
     if (frames == 0) return VRG_OK;
     const bool aligned = (reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) % 16 == 0;
     if (nd->chunk_frames != 1 || width % 4 != 0 || (int64_t)width * 3 / 4 < 256 || frame_elems > 0x7fffffffll || !aligned)
@@ -709,6 +710,7 @@ int vrg_sharpen_grain_u8(const uint8_t* in, uint8_t* out, int64_t frames, int32_
     GrainGeom g;
     if (!in || !out || in == out || frames < 0 || height <= 0 || width <= 0 || border < 0 || border > 1 || !grain_geom(nd, frame_elems, GRAIN_N, g))
         return VRG_ERR_BAD_ARG;
+    if (vrg_ranges_overlap(in, vrg_operand_bytes(frames, frame_elems), out, vrg_operand_bytes(frames, frame_elems))) return VRG_ERR_BAD_ARG;
     if (frames == 0) return VRG_OK;
     const bool aligned = (reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) % 4 == 0;
     // several frames per noise chunk: the enhancer seeds every frame on its own (reference :233-276), nothing calls that; a batch of less than

@@ -240,7 +240,7 @@ extern "C" int vrg_prepare_frames_f32(const float* in, int64_t frames, int32_t i
         const int64_t bytes[4] = {frames * in_fe * 4, n_out * fe * 4, n_out * fe, n_out * 4};
         for (int p = 0; p < 4; ++p)
             for (int q = p + 1; q < 4; ++q)
-                if (prep_overlap(at[p], bytes[p], at[q], bytes[q])) return VRG_ERR_BAD_ARG;
+                if (vrg_ranges_overlap(at[p], bytes[p], at[q], bytes[q])) return VRG_ERR_BAD_ARG;
     }
 #if defined(VRG_LAB_VARIANT_SOURCE) && defined(LAB_PREPARE_DIRECT_BICUBIC)     /* tools/ab: bicubic through the direct form, the other side of the A/B of tools/measure_prepare.py */
     const bool staged = false;

@@ -56,13 +56,6 @@ VRG_HD int prep_ring_shift(const int32_t (&have)[4], const int32_t (&want)[4]) {
     return 4;
 }
 
-// do the byte ranges [a, a + na) and [b, b + nb) share a byte?  A null pointer is a buffer that is not there.
-inline bool prep_overlap(const void* a, int64_t na, const void* b, int64_t nb) {
-    if (!a || !b || na <= 0 || nb <= 0) return false;
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return x < y ? (uintptr_t)na > y - x : (uintptr_t)nb > x - y;
-}
-
 struct PrepPlan {
     int32_t cps, segments, bands;
 };

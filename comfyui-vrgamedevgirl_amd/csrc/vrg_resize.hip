@@ -182,6 +182,8 @@ extern "C" int vrg_resize_f32(const float* in, float* out, int64_t frames, int32
                               int32_t dst_x0, int32_t dst_y0, int32_t dst_w, int32_t dst_h, int32_t method, void* stream) {
     const ResizeGeom g{in_h, in_w, in_channels, src_x0, src_y0, src_w, src_h, out_h, out_w, dst_x0, dst_y0, dst_w, dst_h};
     if (!in || !out || in == out || frames < 0 || method < 0 || method > 3 || !rs_geom_ok(g)) return VRG_ERR_BAD_ARG;
+    if (vrg_ranges_overlap(in, vrg_operand_bytes(frames, (int64_t)in_h * in_w * in_channels * 4), out, vrg_operand_bytes(frames, (int64_t)out_h * out_w * 12)))
+        return VRG_ERR_BAD_ARG;
     if (frames == 0) return VRG_OK;
     return launch_resize<false>(in, out, frames, g, method, RestoreK{nullptr, 3, 0.0f, 0.0f}, (hipStream_t)stream);
 }
@@ -193,6 +195,10 @@ extern "C" int vrg_restore_f32(const float* work, const float* originals, float*
     const ResizeGeom g{in_h, in_w, in_channels, src_x0, src_y0, src_w, src_h, out_h, out_w, dst_x0, dst_y0, dst_w, dst_h};
     if (!work || !originals || !out || out == originals || out == work || work_frames < 0 || frames < 0 || channels < 3 || method < 0 ||
         method > 3 || !rs_geom_ok(g))
+        return VRG_ERR_BAD_ARG;
+    const int64_t out_bytes = vrg_operand_bytes(frames, (int64_t)out_h * out_w * channels * 4);           // out and originals have one shape
+    if (vrg_ranges_overlap(out, out_bytes, originals, out_bytes) ||
+        vrg_ranges_overlap(out, out_bytes, work, vrg_operand_bytes(work_frames, (int64_t)in_h * in_w * in_channels * 4)))
         return VRG_ERR_BAD_ARG;
     if (frames == 0) return VRG_OK;
     const int64_t usable = work_frames < frames ? work_frames : frames;

@@ -206,6 +206,8 @@ extern "C" int vrg_stencil3x3_f32(const float* in, float* out, int64_t frames, i
                                   int32_t op, int32_t border, float strength, void* stream) {
     if (!in || !out || frames < 0 || height <= 0 || width <= 0 || channels <= 0 || op < 0 || op > 2 || border < 0 || border > 1)
         return VRG_ERR_BAD_ARG;
+    const int64_t bytes = vrg_operand_bytes(frames, vrg_operand_bytes((int64_t)height * width, (int64_t)channels * 4));
+    if (vrg_ranges_overlap(in, bytes, out, bytes)) return VRG_ERR_BAD_ARG;          // the windows read neighbours of what other lanes store
     if (frames == 0) return VRG_OK;
     // RGB / RGBA frames with whole float4 vectors per row and 16-byte aligned bases: the streaming flat march
     const bool flat_ok = (channels == 3 || channels == 4) && ((int64_t)width * channels) % 4 == 0 && (int64_t)width * channels / 4 <= 0x7fffffff / 64 &&

@@ -67,12 +67,6 @@ __global__ __launch_bounds__(WALK_THREADS) void k_face_thumbs(const uint8_t* __r
     }
 }
 
-static bool th_overlap(const uint8_t* a, int64_t a_bytes, const uint8_t* b, int64_t b_bytes) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    if (!a || !b) return false;
-    return a0 == b0 || (a0 < b0 + (uintptr_t)b_bytes && b0 < a0 + (uintptr_t)a_bytes);
-}
-
 }  // namespace vrg
 
 using namespace vrg;
@@ -92,7 +86,7 @@ int vrg_face_thumbs_u8(const uint8_t* generated, const uint8_t* source, int64_t 
     if (n_desc == 0) return VRG_OK;
     if (!generated || !desc || !out || (reinterpret_cast<uintptr_t>(desc) & 7u) != 0 || (reinterpret_cast<uintptr_t>(out) & 15u) != 0) return VRG_ERR_BAD_ARG;
     if (n_desc > INT64_MAX / THUMB_BYTES) return VRG_ERR_BAD_ARG;
-    if (th_overlap(out, n_desc * THUMB_BYTES, generated, n_bytes) || th_overlap(out, n_desc * THUMB_BYTES, source, n_bytes)) return VRG_ERR_BAD_ARG;
+    if (vrg_ranges_overlap(out, n_desc * THUMB_BYTES, generated, n_bytes) || vrg_ranges_overlap(out, n_desc * THUMB_BYTES, source, n_bytes)) return VRG_ERR_BAD_ARG;
     return launch_chunks(n_desc, [&](int64_t first, int64_t count) -> int {
         hipLaunchKernelGGL(k_face_thumbs, dim3((uint32_t)(THUMB_SEGMENTS * THUMB_SIDE), (uint32_t)count), dim3(WALK_THREADS), 0, (hipStream_t)stream,
                            generated, source, n_bytes, desc + first, out + first * THUMB_BYTES);

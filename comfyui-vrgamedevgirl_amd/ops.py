@@ -143,12 +143,29 @@ def _checked_out(out, shape, dtype, device, what: str, name: str = "out") -> tor
     return out
 
 
-def _out_like(x: torch.Tensor, out: Optional[torch.Tensor], what: str) -> torch.Tensor:
-    """_checked_out for a result shaped and typed like the (checked, contiguous) frames `x`, which `out` must not be -- the stencils
-    read neighbours of what they write."""
+def _disjoint(what: str, writes, reads) -> None:
+    """The one overlap rule of the operators (include/vrgdg_hip.h, "Operands must not overlap"): the kernels take every operand through a
+    `__restrict__` pointer and read pixels other than the one they store, so no operand that a call writes may share a byte with one it
+    reads, or with another one it writes.  `writes` and `reads` are lists of (name, tensor or None): the checked, contiguous tensors
+    that reach the kernels, as half-open byte ranges [data_ptr(), data_ptr() + nbytes).  Only operands in one address space are
+    compared (both on the same device: what the operator uploads from the CPU itself cannot meet a resident operand); an empty
+    tensor and None overlap nothing.  ValueError, naming the operator `what` and both operands, before anything is launched."""
+    def spans(entries):
+        return [(name, t.device, t.data_ptr(), t.data_ptr() + t.nbytes) for name, t in entries
+                if isinstance(t, torch.Tensor) and t.device.type != "meta" and t.nbytes > 0]
+    w, r = spans(writes), spans(reads)
+    for i, (name, dev, lo, hi) in enumerate(w):
+        for other, other_dev, other_lo, other_hi in r + w[i + 1:]:
+            if dev == other_dev and lo < other_hi and other_lo < hi:
+                raise ValueError(f"{what}: {name} must not alias {other} (bytes {max(lo, other_lo) - lo} .. {min(hi, other_hi) - lo} of {name} "
+                                 f"lie inside {other}; the kernels read neighbours of what they write, so operands may not overlap)")
+
+
+def _out_like(x: torch.Tensor, out: Optional[torch.Tensor], what: str, name: str = "the input frames") -> torch.Tensor:
+    """_checked_out for a result shaped and typed like the (checked, contiguous) frames `x` (`name` in the message), which `out` must
+    not overlap -- the stencils read neighbours of what they write."""
     out = _checked_out(out, x.shape, x.dtype, x.device, what)
-    if out.data_ptr() == x.data_ptr() and x.numel():
-        raise ValueError(f"{what}: out must not alias the input frames")
+    _disjoint(what, [("out", out)], [(name, x)])
     return out
 
 
@@ -342,7 +359,7 @@ def film_grain(images: torch.Tensor, grain_intensity: float, saturation_mix: flo
     generator state: chunks of `chunk_frames` frames each draw one ``torch.randn`` (0 = one draw for all)."""
     x = _check_frames(images, channels=3)
     F, H, W, _ = x.shape
-    out = _out_like(x, out, "film_grain")
+    out = _out_like(x, out, "film_grain", "images")
     if F == 0:
         return out
     fe = H * W * 3
@@ -647,11 +664,11 @@ def lut3d(image: torch.Tensor, lut: DeviceLut, strength: float = 10.0, out: Opti
     mode, B, omB = blend_terms(strength)
     if mode == 0:
         if out is not None:
-            _out_like(x, out, "lut3d").copy_(x)
+            _out_like(x, out, "lut3d", "image").copy_(x)
             return out
         return x
     _check_side(lut.table, "LUT record table", x)
-    out = _out_like(x, out, "lut3d")
+    out = _out_like(x, out, "lut3d", "image")
     px = x.numel() // x.shape[-1]
     if px == 0:
         return out
@@ -697,7 +714,7 @@ def stencil3x3(images: torch.Tensor, op: str, strength: float, zero_border: bool
     """unsharp / laplacian / sobel.  zero_border=False is the reference's default numpy path (edge replicate);
     True is its ``use_gpu`` path (zero padding, and for laplacian/sobel the conv2d sign/epsilon conventions)."""
     x = _check_frames(images)
-    out = _out_like(x, out, "stencil3x3")
+    out = _out_like(x, out, "stencil3x3", "images")
     F, H, W, Cn = x.shape
     if x.numel() == 0:
         return out
@@ -793,6 +810,7 @@ def resize_geometry_frames(images: torch.Tensor, geometry: ResizeGeometry, resiz
     shape = (int(x.shape[0]), geometry.out_h, geometry.out_w, 3)
     args = _geometry_args(x, geometry)
     out = _checked_out(out, shape, torch.float32, x.device, "resize_geometry_frames")
+    _disjoint("resize_geometry_frames", [("out", out)], [("images", x)])
     _hip.check(_hip.lib().vrg_resize_f32(_hip.ptr(x), _hip.ptr(out), shape[0], *args, RESIZE_METHODS[interpolation_mode(resize_method)],
                                         _hip.current_stream()), "vrg_resize_f32")
     return out
@@ -861,7 +879,8 @@ def restore_frames(work: torch.Tensor, originals: torch.Tensor, source_width, so
     usable = min(frames if frame_count is None else int(frame_count), int(w.shape[0]))
     if usable > frames:
         raise ValueError(f"{usable} restored frames for {frames} original frames")
-    out = _out_like(o, out, "restore_frames")
+    out = _out_like(o, out, "restore_frames", "originals")
+    _disjoint("restore_frames", [("out", out)], [("work", w)])
     if o.numel() == 0:
         return out
     strength = float(strength)
@@ -1082,8 +1101,7 @@ def composite_frames(originals: torch.Tensor, crops: torch.Tensor, entries, rule
     shape = (frames, int(o.shape[1]), int(o.shape[2]), int(o.shape[3]))
     out = _checked_out(out, shape, torch.float32, o.device, "composite_frames")
     mask_out = _checked_out(mask_out, shape[:3], torch.float32, o.device, "composite_frames", "mask_out")
-    if out.data_ptr() in (o.data_ptr(), c.data_ptr()):
-        raise ValueError("out must not be an input")
+    _disjoint("composite_frames", [("out", out), ("mask_out", mask_out)], [("originals", o), ("crops", c), ("user_mask", m)])
     if frames == 0:
         return out, mask_out
     _composite_measure(o, c, m, dev_table, match, max_pixels, geom, stats)
@@ -1353,8 +1371,7 @@ def aligned_composite_frames(originals: torch.Tensor, crops: torch.Tensor, entri
     shape = (frames, int(o.shape[1]), int(o.shape[2]), int(o.shape[3]))
     out = _checked_out(out, shape, torch.float32, o.device, "aligned_composite_frames")
     mask_out = _checked_out(mask_out, shape[:3], torch.float32, o.device, "aligned_composite_frames", "mask_out")
-    if out.data_ptr() in (o.data_ptr(), c.data_ptr()):
-        raise ValueError("out must not be an input")
+    _disjoint("aligned_composite_frames", [("out", out), ("mask_out", mask_out)], [("originals", o), ("crops", c), ("generated", generated.generated)])
     rec = _hip.upload_records(records, o.device, frames)
     g = generated.generated
     _hip.check(_hip.lib().vrg_composite_warp_apply_f32(_hip.ptr(c), _hip.ptr(o), None, _hip.ptr(dev_table), _hip.ptr(stats), _hip.ptr(rec),
@@ -1467,10 +1484,9 @@ def crop_resize(source: torch.Tensor, records, size=CROP_SIZE, out: Optional[tor
         for k, name in enumerate(("src_offset", "row_pitch", "pixel_stride", "box_w", "box_h")):
             table[name] = rec[:, k]
     out = _checked_out(out, (len(records), size_h, size_w, 3), torch.float32, source.device, "crop_resize")
+    _disjoint("crop_resize", [("out", out)], [("source", source)])
     if len(records) == 0:
         return out
-    if out.data_ptr() == source.data_ptr():
-        raise ValueError("out must not be the source")
     dev_table = _hip.upload_records(table, source.device)
     _hip.check(_hip.lib().vrg_crop_resize_f32(_hip.ptr(source), source.numel(), _hip.ptr(out), _hip.ptr(dev_table), len(records), size_h, size_w,
                                              _hip.current_stream()), "vrg_crop_resize_f32")
@@ -1598,6 +1614,7 @@ def cut_thumbnails(frames: torch.Tensor, out: Optional[torch.Tensor] = None) -> 
         x = x[..., :3].contiguous()
         Cn = 3
     out = _checked_out(out, (F, CUT_THUMB, CUT_THUMB, 3), torch.uint8, x.device, "cut_thumbnails")
+    _disjoint("cut_thumbnails", [("out", out)], [("frames", x)])
     if F == 0:
         return out
     taps = _area_table(H, W, x.device)
@@ -1844,6 +1861,7 @@ def _grid_run(batches, index, plan, overlays, out, byte_sources):
                 jobs.append((i, i, None, 0, index[i]))
             elif b.is_cuda:
                 jobs.append((i, i, b.contiguous(), 0, index[i]))
+        _disjoint("video grid", [("out", out)], [(f"batch {job[0]}", job[2]) for job in jobs])
         _grid_launch(plan, out, jobs, dev_overlays, has, byte_sources)
         for i, b in enumerate(batches):
             if b is None or b.is_cuda:
@@ -2101,13 +2119,15 @@ def adjust(images: torch.Tensor, terms: "_hip.AdjustDesc", out: torch.Tensor | N
         raise ValueError("adjust expects 3-channel frames")
     out = _checked_out(out, x.shape, x.dtype, x.device, "adjust")
     F, H, W, _ = x.shape
-    if x.numel() == 0:
-        return out
     tmp = None
     if terms.enabled and terms.has_clarity and terms.has_sharpen:
         tmp = workspace if workspace is not None else torch.empty(x.shape, dtype=torch.float32, device=x.device)
-        if tmp.shape != x.shape or tmp.dtype != torch.float32 or not tmp.is_contiguous() or tmp.device != x.device:
+        if (not isinstance(tmp, torch.Tensor) or tmp.shape != x.shape or tmp.dtype != torch.float32 or not tmp.is_contiguous()
+                or tmp.device != x.device):
             raise ValueError("adjust workspace must be a contiguous float32 tensor shaped like the frames")
+    _disjoint("adjust", [("out", out), ("workspace", tmp)], [("images", x)])
+    if x.numel() == 0:
+        return out
     fn, name = (_hip.lib().vrg_adjust_u8, "vrg_adjust_u8") if u8 else (_hip.lib().vrg_adjust_f32, "vrg_adjust_f32")
     _hip.check(fn(_hip.ptr(x), _hip.ptr(out), _hip.ptr(tmp) if tmp is not None else None, F, H, W, C.byref(terms),
                   _hip.current_stream()), name)
@@ -2388,6 +2408,7 @@ def lab_stats_device(lab: torch.Tensor, chunks=1, eps: float = 1e-5, out: Option
         _check_side(out, "statistics output", x, (3, 2))
         if int(out.shape[0]) != F:
             raise ValueError("statistics output must hold one [3, 2] record per frame")
+        _disjoint("lab_stats_device", [("out", out)], [("lab", x)])
     fe = H * W * 3
     if F:
         _device_stats_selfcheck(x.device)
@@ -2503,6 +2524,8 @@ def color_match(images: torch.Tensor, reference_image: torch.Tensor, match_stren
     the reference's (CM_STATS).  `ref_event`: the event of reference_stats_async when `ref_ms` comes from it."""
     x = _check_frames(images, channels=3)
     stats = _cm_stats(cm_stats, cm_math, x.device)
+    if out is not None:
+        out = _out_like(x, out, "color_match", "images")                 # refused before anything is launched
     if ref_ms is None:
         ref_ms = reference_stats(reference_image.to(x.device), cm_math, stats)
     if cache_lab or stats == "device":
@@ -2513,7 +2536,7 @@ def color_match(images: torch.Tensor, reference_image: torch.Tensor, match_stren
     img_ms = finalize_stats(lab_stats(x, cm_math))
     res = colormatch_apply(x, img_ms, ref_ms, match_strength, cm_math)
     if out is not None:
-        _out_like(x, out, "color_match").copy_(res)
+        out.copy_(res)
         return out
     return res
 
@@ -2630,6 +2653,7 @@ def fused_chain(images: torch.Tensor, spec: ChainSpec, generator: Optional[torch
     esize = 1 if u8 else 4
     F, H, W, _ = x.shape
     out = _checked_out(out, x.shape, x.dtype, x.device, "fused_chain")
+    _disjoint("fused_chain", [("out", out), ("lab_workspace", lab_workspace)], [("images", x)])
     if F == 0:
         return out
     fe = H * W * 3
@@ -3248,6 +3272,7 @@ def flf_guide_frames(first, last, frame_count: int, transition_start=0.05, trans
     out = _checked_out(out, (frames, h, w, c), torch.float32, dev, "first/last guide")
     with torch.cuda.device(dev):
         a, b = (t.contiguous() if t.is_cuda else _devices.on_device(t, dev).contiguous() for t in (a, b))
+        _disjoint("first/last guide", [("out", out)], [("first", a), ("last", b)])
         wd = torch.from_numpy(weights).to(dev)
         _hip.check(_hip.lib().vrg_flf_guide_f32(_hip.ptr(a), _hip.ptr(b), _hip.ptr(wd), _hip.ptr(out), frames, h, w, c, int(b.shape[1]),
                                                 int(b.shape[2]), *rect, _hip.current_stream()), "vrg_flf_guide_f32")
@@ -3433,6 +3458,7 @@ def scale_reference_images(images, upscale_method="nearest-exact", megapixels=1.
         total += int(t.shape[0]) * oh * ow * int(t.shape[3])
     with torch.cuda.device(dev):
         buf = _refbatch_out(out, total, dev, what)
+        _disjoint(what, [("out", buf)], [(f"image {i}", t) for i, t in enumerate(pics)])
         if method == "lanczos":
             jobs = _refbatch_lanczos_jobs(dev, [(t, (0, 0, int(t.shape[2]), int(t.shape[1])), (ow, oh)) for t, (oh, ow) in zip(pics, sizes)])
             for j, at in zip(jobs, offsets):
@@ -3483,6 +3509,7 @@ def batch_reference_images(images, upscale_method="bilinear", out=None) -> torch
     shape = (int(sum(int(t.shape[0]) for t in pics)), height, width, channels)
     with torch.cuda.device(dev):
         buf = _refbatch_out(None, int(offsets[-1]), dev, what) if out is None else _checked_out(out, shape, torch.float32, dev, what).view(-1)
+        _disjoint(what, [("out", buf)], [(f"image {i}", t) for i, t in enumerate(pics)])
         jobs, lanczos = [], []
         for t, fit, at in zip(pics, fits, offsets[:-1]):
             frames, h, w, c = (int(v) for v in t.shape)
@@ -3634,6 +3661,7 @@ class _Assembly:
     host_fed: bool               # every clip came from the CPU: the results go to the intermediate device
     rows: np.ndarray             # the table on the host
     keep: list
+    reads: list                  # (name, tensor) of what the kernel reads: the clips and overlays as they lie on the device
 
 
 def _assemble_prepare(videos, plan, overlays, what) -> _Assembly:
@@ -3665,7 +3693,7 @@ def _assemble_prepare(videos, plan, overlays, what) -> _Assembly:
             raise ValueError(f"{what}: the plan names frames {lo} .. {hi} of clip {s}, which has {int(t.shape[0])}")
     dev = _placement([t.device for t in clips.values()], what, "clips", ring=False)
     host_fed = not any(t.is_cuda for t in clips.values())
-    desc, keep, rows = _hip.AssembleDesc(), [], np.zeros(len(entries), dtype=ASSEMBLE_ENTRY)
+    desc, keep, reads, rows = _hip.AssembleDesc(), [], [], np.zeros(len(entries), dtype=ASSEMBLE_ENTRY)
     desc.n_src, desc.bytes = len(used), int(is_bytes)
     with torch.cuda.device(dev):
         for k, s in enumerate(used):
@@ -3678,6 +3706,7 @@ def _assemble_prepare(videos, plan, overlays, what) -> _Assembly:
                 t = t.to(torch.float32)
             t = t.contiguous()
             keep.append(t)
+            reads.append((f"clip {s}", t))
             rows["source"][mine], rows["frame"][mine] = k, entries[mine, 1] - first
             desc.src[k], desc.frames[k] = t.data_ptr(), int(t.shape[0])
             desc.height[k], desc.width[k], desc.channels[k] = shape
@@ -3687,9 +3716,10 @@ def _assemble_prepare(videos, plan, overlays, what) -> _Assembly:
                     raise ValueError(f"{what}: overlay {s} must be uint8 [{ASSEMBLE_BAR}, {shape[1]}, 3] (B,G,R)")
                 o = o.detach().to(dev).contiguous()
                 keep.append(o)
+                reads.append((f"overlay {s}", o))
                 desc.overlay[k] = o.data_ptr()
         table = _hip.upload_records(rows, dev)
-    return _Assembly(dev, desc, table, len(entries), shape, host_fed, rows, keep)
+    return _Assembly(dev, desc, table, len(entries), shape, host_fed, rows, keep, reads)
 
 
 def _assemble_check(a: _Assembly, out_f32, out_u8, labelled, what):
@@ -3711,6 +3741,7 @@ def assemble_frames(videos, plan, out=None) -> torch.Tensor:
     a = _assemble_prepare(videos, plan, None, what)
     with torch.cuda.device(a.device):
         dst = _checked_out(out, (a.frames, *a.shape), torch.float32, a.device, what)
+        _disjoint(what, [("out", dst)], a.reads)
         _assemble_check(a, dst, None, False, what)
         _hip.check(_hip.lib().vrg_assemble_f32(C.byref(a.desc), _hip.ptr(a.table), a.frames, _hip.ptr(dst), _hip.current_stream()),
                    "vrg_assemble_f32")
@@ -3733,6 +3764,7 @@ def assemble_labelled_bytes(videos, plan, overlays=None, clean_out=None):
         given = isinstance(clean_out, torch.Tensor)
         clean = _checked_out(clean_out if given else None, (a.frames, *a.shape), torch.float32, a.device, what, "clean_out") if given or clean_out else None
         data = torch.empty((a.frames, a.shape[0] + ASSEMBLE_BAR, a.shape[1], 3), dtype=torch.uint8, device=a.device)
+        _disjoint(what, [("clean_out", clean)], a.reads)
         _assemble_check(a, clean, data, True, what)
         _hip.check(_hip.lib().vrg_assemble_labelled_u8(C.byref(a.desc), _hip.ptr(a.table), a.frames, None if clean is None else _hip.ptr(clean),
                                                        _hip.ptr(data), _hip.current_stream()), "vrg_assemble_labelled_u8")
@@ -3808,6 +3840,7 @@ def anchor_frames(pictures, out: Optional[torch.Tensor] = None, size=None) -> to
     with torch.cuda.device(dev):
         dst = _checked_out(out, (len(pics), height, width, 3), torch.float32, dev, what)
         flat = [p.contiguous().reshape(-1) for p in pics]
+        _disjoint(what, [("out", dst)], [(f"picture {i}", f) for i, f in enumerate(flat)])
         src = torch.cat([f.to(dev) for f in flat]) if any(p.is_cuda for p in pics) else torch.cat(flat).to(dev)
         table = _hip.upload_records(desc, dev, trailing=(tables,))
         at = len(desc) * ANCHOR_DESC.itemsize
@@ -3829,6 +3862,7 @@ def anchor_store_bytes(images: torch.Tensor, bgr: bool = False, out: Optional[to
     if int(x.shape[3]) < 3:
         raise ValueError(f"{what}: images must have at least 3 channels, got {int(x.shape[3])}")
     dst = _checked_out(out, (*x.shape[:3], 3), torch.uint8, x.device, what)
+    _disjoint(what, [("out", dst)], [("images", x)])
     _hip.check(_hip.lib().vrg_anchor_store_u8(_hip.ptr(x), _hip.ptr(dst), x.numel() // int(x.shape[3]), int(x.shape[3]),
                                               _hip.ANCHOR_BGR if bgr else _hip.ANCHOR_RGB, _hip.current_stream()), "vrg_anchor_store_u8")
     return dst

@@ -38,6 +38,14 @@ enum vrg_status {
     VRG_ERR_NO_DEVICE = 4
 };
 
+/* Operands must not overlap.  The kernels take every operand through a restrict-qualified pointer, and nearly all of them read pixels
+ * other than the one they store (3x3 and 9x9 windows, resampling taps, crop gathers; the marches store a last strip twice).  An entry
+ * point whose operand sizes follow from its scalar arguments therefore returns VRG_ERR_BAD_ARG, before it touches a device, when an
+ * operand it writes (out, mask_out, the tmp ring of vrg_adjust_*) shares a byte with an operand it reads or with another one it writes.
+ * Operands are half-open byte ranges; one of no bytes overlaps nothing, and ranges that only touch are fine.  Entry points that reach
+ * their inputs through descriptor tables check what they can; for them the caller keeps the outputs apart from every picture the
+ * records name (ops.py does, with the same rule, in ops._disjoint). */
+
 enum vrg_border {
     VRG_BORDER_REPLICATE = 0, /* reference CPU/numpy path: np.pad(mode="edge")            (nodes.py:188-192) */
     VRG_BORDER_ZERO = 1       /* reference use_gpu=True path: avg_pool2d / conv2d padding=1 (nodes.py:171, 257) */

@@ -181,7 +181,7 @@ def test_argument_validation_without_device(hip):
     nd2 = hip.NoiseDesc(seed0=1, chunk_frames=2, grid_threads=256)
     assert lib.vrg_grain_f32(one, one, 3, 4, 4, 0.1, 0.5, 0.5, C.byref(nd2), null) == 1         # ragged chunk
     # fused sharpen -> per-frame-seeded grain: in place / null / bad border are argument errors, sizes it does not take "unsupported"
-    two = C.c_void_p(32)
+    two = C.c_void_p(1 << 30)                          # 16-byte aligned and far from `one`: operands that overlap are argument errors
     assert lib.vrg_sharpen_grain_f32(one, one, 1, 8, 512, 0.5, 0, 0.1, 0.5, 0.5, C.byref(nd), null) == 1       # in == out
     assert lib.vrg_sharpen_grain_f32(null, two, 1, 8, 512, 0.5, 0, 0.1, 0.5, 0.5, C.byref(nd), null) == 1
     assert lib.vrg_sharpen_grain_f32(one, two, 1, 8, 512, 0.5, 2, 0.1, 0.5, 0.5, C.byref(nd), null) == 1       # border
@@ -199,7 +199,8 @@ def test_argument_validation_without_device(hip):
     cd = hip.ChainDesc(stages=0)
     assert lib.vrg_fused_chain_f32(one, one, 1, 4, 4, C.byref(cd), null) == 1
     cd = hip.ChainDesc(stages=8, variant=99, stencil_op=0, border=0)
-    assert lib.vrg_fused_chain_f32(one, one, 1, 4, 4, C.byref(cd), null) == 2                    # unknown variant
+    assert lib.vrg_fused_chain_f32(one, two, 1, 4, 4, C.byref(cd), null) == 2                    # unknown variant
+    assert lib.vrg_fused_chain_f32(one, one, 1, 4, 4, C.byref(cd), null) == 1                    # in == out comes first
     assert lib.vrg_fused_chain_f32(one, one, 0, 4, 4, C.byref(cd), null) == 0
 
 

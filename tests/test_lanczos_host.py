@@ -142,7 +142,7 @@ def test_refusals_without_device(pkg):
     if not os.path.exists(_hip.LIB_PATH):
         build_ext.build(verbose=False)
     lib = _hip.load_library()
-    null, a, b, t = C.c_void_p(0), C.c_void_p(64), C.c_void_p(128), C.c_void_p(256)
+    null, a, b, t = C.c_void_p(0), C.c_void_p(64), C.c_void_p(1 << 20), C.c_void_p(1 << 21)      # far apart: operands that overlap are argument errors
     nd = _hip.NoiseDesc(seed0=1, seed_stride=1, offset0=0, offset_stride=0, chunk0=0, chunk_frames=1, grid_threads=256)
 
     def plain(i=a, o=b, frames=1, ih=4, iw=4, oh=8, ow=8, taps=t):

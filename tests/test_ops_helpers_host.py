@@ -120,6 +120,17 @@ def test_out_like_is_checked_out_plus_the_alias_refusal(ops):
         ops._out_like(x, "nothing", "op")
     empty = torch.zeros((0, 3, 4, 3))
     assert ops._out_like(empty, empty, "op") is empty                  # nothing is read or written: not an alias
+    # two views of one allocation: any shared byte is refused, ranges that only touch are taken
+    buf = torch.zeros((5, 3, 4, 3))
+    flat = buf.view(-1)
+    n = x.numel()
+    for start in (1, n - 1):                                           # out one element after the input's start; out's first element the input's last
+        with pytest.raises(ValueError, match="^op: out must not alias"):
+            ops._out_like(flat[:n].view(x.shape), flat[start:start + n].view(x.shape), "op")
+    with pytest.raises(ValueError, match="^op: out must not alias"):
+        ops._out_like(buf[1:3], buf[:2], "op")                         # out's last frame is the input's first
+    assert ops._out_like(buf[:2], buf[2:4], "op").data_ptr() == buf[2:4].data_ptr()            # out starts exactly where the input ends
+    assert ops._out_like(buf[2:4], buf[:2], "op").data_ptr() == buf.data_ptr()                 # out ends exactly where the input starts
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
