@@ -47,6 +47,29 @@ class NoiseDesc(Record):
                 ("grid_threads", C.c_uint32)]
 
 
+NOISE_LEAVES_MAX = 8            # include/vrgdg_hip.h: VRG_NOISE_LEAVES_MAX
+
+
+class NoiseLeaf(Record):
+    c_name = "vrg_noise_leaf"
+    _fields_ = [("start", C.c_int64), ("size", C.c_uint32), ("grid_threads", C.c_uint32), ("offset", C.c_uint64)]
+
+
+class NoiseSplit(Record):
+    c_name = "vrg_noise_split"
+    _fields_ = [("seed", C.c_uint64), ("count", C.c_int32), ("reserved", C.c_int32), ("leaves", NoiseLeaf * NOISE_LEAVES_MAX)]
+
+    @classmethod
+    def of(cls, seed: int, leaves) -> "NoiseSplit":
+        """The record of the leaves [(start, size, grid_threads, offset), ...] a launch meets (rng.SplitStream.leaves_of)"""
+        if not 1 <= len(leaves) <= NOISE_LEAVES_MAX:
+            raise ValueError(f"a launch takes 1 to {NOISE_LEAVES_MAX} noise leaves, not {len(leaves)}")
+        rec = cls(seed=seed, count=len(leaves))
+        for i, (start, size, G, off) in enumerate(leaves):
+            rec.leaves[i] = NoiseLeaf(start=start, size=size, grid_threads=G, offset=off)
+        return rec
+
+
 class ChainDesc(Record):
     c_name = "vrg_chain_desc"
     _fields_ = [("stages", C.c_int32), ("variant", C.c_int32),
@@ -282,6 +305,11 @@ _SIGNATURES = {
                                        C.POINTER(NoiseDesc), _P]),
     "vrg_grain_f32": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float,
                                 C.POINTER(NoiseDesc), _P]),
+    "vrg_grain_split_f32": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float,
+                                      C.POINTER(NoiseSplit), _P]),
+    "vrg_fused_chain_split_f32": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.POINTER(ChainDesc), C.POINTER(NoiseSplit), _P]),
+    "vrg_fused_chain_split_u8": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.POINTER(ChainDesc), C.POINTER(NoiseSplit), _P]),
+    "vrg_chain_stats_lab_split_f32": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.POINTER(ChainDesc), C.POINTER(NoiseSplit), _P, _P, _P]),
     "vrg_grain_injected_f32": (C.c_int, [_P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, _P]),
     "vrg_lut_cells_floats": (C.c_int64, [C.c_int32]),
     "vrg_lut_prepare_f32": (C.c_int, [_P, C.c_int32, _P, _P]),

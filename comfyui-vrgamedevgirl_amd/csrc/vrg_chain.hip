@@ -24,9 +24,12 @@ __host__ __device__ inline int stats_blocks_per_frame(int64_t pixels) {
 // ----------------------------------------------------------------------------------------------
 // Point-wise chain (no sharpen): one pixel per thread.
 // ----------------------------------------------------------------------------------------------
-template <int STAGES, class IO>
+// (NS: the noise source, vrg_chain_stages.hpp -- nothing for the chunks of D.noise, or one NoiseSplitK, the leaves of a draw that torch
+// splits, as one more kernel argument: `noise_source(Sx...)` is NoSplit or that table.  The instantiations without it are what they were.)
+template <int STAGES, class IO, class... NS>
 __global__ __launch_bounds__(256) void k_chain_pointwise(const typename IO::elem* __restrict__ in, typename IO::elem* __restrict__ out,
-                                                          int32_t ppf, ChainK D) {
+                                                          int32_t ppf, ChainK D, NS... Sx) {
+    const auto& S = noise_source(Sx...);
     VRG_CM_MATH(PT, (STAGES & VRG_STAGE_COLORMATCH) != 0, (STAGES & VRG_STAGE_FASTMATH) != 0, D.dm);
     const int32_t p = blockIdx.x * 256 + threadIdx.x;
     if (p >= ppf) return;
@@ -34,7 +37,7 @@ __global__ __launch_bounds__(256) void k_chain_pointwise(const typename IO::elem
     const px3 v = IO::load_stream(in + f * ppf + p);
     const float x[3] = {v.r, v.g, v.b};
     float o[3];
-    chain_pre<STAGES>(D, frame_ctx<STAGES>(D, f), p, x, o, PT);
+    chain_pre<STAGES>(D, frame_ctx<STAGES>(D, f, S), p, x, o, PT, S);
     IO::store_stream(out + f * ppf + p, px3{o[0], o[1], o[2]});
 }
 
@@ -84,10 +87,11 @@ constexpr int LDS_PITCH = HALO_W + 1;
 // (frame, tile) = (b % 8) * ceil(total/8) + b / 8 gives every XCD one contiguous run of tiles, so that the halo
 // rows/columns a tile shares with its neighbours are re-read from the same L2 instead of from HBM (PMC: the
 // naive mapping fetched 16.9 B/px for 13.2 B/px of tile+halo reads).  Placement only affects speed.
-template <int STAGES, class IO>
+template <int STAGES, class IO, class... NS>
 __global__ __launch_bounds__(256) void k_chain_tile(const typename IO::elem* __restrict__ in, typename IO::elem* __restrict__ out,
                                                      int32_t H, int32_t W, int32_t tiles_x, int32_t tiles_per_frame, uint32_t total_work,
-                                                     ChainK D) {
+                                                     ChainK D, NS... Sx) {
+    const auto& S = noise_source(Sx...);
     __shared__ float tile[3][HALO_H][LDS_PITCH];
     VRG_CM_MATH(PT, (STAGES & VRG_STAGE_COLORMATCH) != 0, (STAGES & VRG_STAGE_FASTMATH) != 0, D.dm);
     const uint32_t per_xcd = (total_work + 7u) / 8u;
@@ -100,7 +104,7 @@ __global__ __launch_bounds__(256) void k_chain_tile(const typename IO::elem* __r
     const int32_t ppf = H * W;
     const typename IO::elem* fin = in + f * ppf;
     const bool zero = D.zero_border != 0;
-    const FrameCtx FC = frame_ctx<STAGES>(D, f);
+    const auto FC = frame_ctx<STAGES>(D, f, S);
 
 #define VRG_TILE_PRELOAD 1
     constexpr int N_IT = (HALO_H * HALO_W + 255) / 256;
@@ -133,7 +137,7 @@ __global__ __launch_bounds__(256) void k_chain_tile(const typename IO::elem* __r
                 float o[3] = {0.0f, 0.0f, 0.0f};
                 if (inside || !zero) {
                     const float xi[3] = {v[k].r, v[k].g, v[k].b};
-                    chain_pre<STAGES>(D, FC, pp[k], xi, o, PT);
+                    chain_pre<STAGES>(D, FC, pp[k], xi, o, PT, S);
                 }
                 tile[0][hy][hx] = o[0];
                 tile[1][hy][hx] = o[1];
@@ -154,7 +158,7 @@ __global__ __launch_bounds__(256) void k_chain_tile(const typename IO::elem* __r
             const int32_t p = y * W + x;
             const px3 v = IO::load(fin + p);   // plain load: halo pixels are re-read by the neighbouring tiles (L2 hits)
             const float xi[3] = {v.r, v.g, v.b};
-            chain_pre<STAGES>(D, FC, p, xi, o, PT);
+            chain_pre<STAGES>(D, FC, p, xi, o, PT, S);
         }
         tile[0][hy][hx] = o[0];
         tile[1][hy][hx] = o[1];
@@ -208,20 +212,21 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
-template <int STAGES, bool STATS = true>
+template <int STAGES, bool STATS = true, class... NS>
 __global__ __launch_bounds__(256) void k_lab_partials(const px3* __restrict__ in, int32_t ppf, int32_t bpf, ChainK D,
-                                                       double* __restrict__ partials, px3* __restrict__ lab_out) {
+                                                       double* __restrict__ partials, px3* __restrict__ lab_out, NS... Sx) {
+    const auto& S = noise_source(Sx...);
     __shared__ double red[STATS ? 4 : 1][6];
     VRG_CM_MATH(PT, true, (STAGES & VRG_STAGE_FASTMATH) != 0, D.dm);
     const int64_t f = blockIdx.y;
     const px3* fin = in + f * ppf;
-    const FrameCtx FC = frame_ctx<STAGES>(D, f);
+    const auto FC = frame_ctx<STAGES>(D, f, S);
     float pivot[3];
     {
         const px3 v0 = fin[0];
         const float x0[3] = {v0.r, v0.g, v0.b};
         float pre[3];
-        chain_pre<STAGES>(D, FC, 0, x0, pre, PT);
+        chain_pre<STAGES>(D, FC, 0, x0, pre, PT, S);
         rgb_to_lab(pre, pivot, PT);
     }
     const int32_t per = (ppf + bpf - 1) / bpf;
@@ -232,7 +237,7 @@ __global__ __launch_bounds__(256) void k_lab_partials(const px3* __restrict__ in
         const px3 v = load_px_stream(fin + p);
         const float x[3] = {v.r, v.g, v.b};
         float pre[3], lab[3];
-        chain_pre<STAGES>(D, FC, p, x, pre, PT);
+        chain_pre<STAGES>(D, FC, p, x, pre, PT, S);
         rgb_to_lab(pre, lab, PT);
         if (lab_out) store_px_stream(lab_out + f * ppf + p, px3{lab[0], lab[1], lab[2]});
 #pragma unroll
@@ -257,9 +262,10 @@ __global__ __launch_bounds__(256) void k_lab_partials(const px3* __restrict__ in
     }
 }
 
-template <int STAGES>
+template <int STAGES, class... NS>
 __global__ __launch_bounds__(64) void k_lab_merge(const px3* __restrict__ in, int32_t ppf, int32_t bpf, ChainK D,
-                                                   const double* __restrict__ partials, double* __restrict__ stats) {
+                                                   const double* __restrict__ partials, double* __restrict__ stats, NS... Sx) {
+    const auto& S = noise_source(Sx...);
     VRG_CM_MATH(PT, true, (STAGES & VRG_STAGE_FASTMATH) != 0, D.dm);
     const int64_t f = blockIdx.x;
     float pivot[3];
@@ -267,7 +273,7 @@ __global__ __launch_bounds__(64) void k_lab_merge(const px3* __restrict__ in, in
         const px3 v0 = in[f * ppf];
         const float x0[3] = {v0.r, v0.g, v0.b};
         float pre[3];
-        chain_pre<STAGES>(D, frame_ctx<STAGES>(D, f), 0, x0, pre, PT);
+        chain_pre<STAGES>(D, frame_ctx<STAGES>(D, f, S), 0, x0, pre, PT, S);
         rgb_to_lab(pre, pivot, PT);
     }
     if (threadIdx.x < 3) {
@@ -378,6 +384,80 @@ static int launch_chain(const void* in, void* out, int64_t frames, int32_t H, in
         }
         if (hipGetLastError() != hipSuccess) return VRG_ERR_LAUNCH;
     }
+    return VRG_OK;
+}
+
+// The same launches with the noise of a split draw (no colour-match stage: pass 2 has no grain left).  Any frame may start a launch: the
+// table's starts move with it.
+template <int STAGES, class IO>
+static int launch_chain_split(const void* in, void* out, int64_t frames, int32_t H, int32_t W, const ChainK& D, const NoiseSplitK& S, bool sharpen,
+                              hipStream_t st) {
+    static_assert((STAGES & VRG_STAGE_GRAIN) && !(STAGES & VRG_STAGE_COLORMATCH), "split noise: grain (-> LUT) (-> stencil)");
+    const int64_t ppf = (int64_t)H * W;
+    const int tx = (W + TILE_W - 1) / TILE_W, ty = (H + TILE_H - 1) / TILE_H;
+    const int64_t tpf = (int64_t)tx * ty;
+    int64_t step = LAUNCH_RECORDS;
+    if (sharpen) {
+        step = (1ll << 23) / tpf;
+        if (step < 1) return VRG_ERR_UNSUPPORTED;
+    }
+    for (int64_t f0 = 0; f0 < frames; f0 += step) {
+        const int64_t nf = frames - f0 < step ? frames - f0 : step;
+        const NoiseSplitK s = split_shifted(S, f0 * ppf * 3);
+        const typename IO::elem* src = reinterpret_cast<const typename IO::elem*>(in) + f0 * ppf;
+        typename IO::elem* dst = reinterpret_cast<typename IO::elem*>(out) + f0 * ppf;
+        if (sharpen) {
+            const uint32_t total = (uint32_t)(tpf * nf);
+            const uint32_t blocks = ((total + 7u) / 8u) * 8u;
+            hipLaunchKernelGGL((k_chain_tile<STAGES, IO>), dim3(blocks), dim3(256), 0, st, src, dst, H, W, tx, (int32_t)tpf, total, D, s);
+        } else {
+            hipLaunchKernelGGL((k_chain_pointwise<STAGES, IO>), dim3((uint32_t)((ppf + 255) / 256), (uint32_t)nf), dim3(256), 0, st,
+                               src, dst, (int32_t)ppf, D, s);
+        }
+        if (hipGetLastError() != hipSuccess) return VRG_ERR_LAUNCH;
+    }
+    return VRG_OK;
+}
+
+template <int STAGES>
+static int launch_stats_split(const float* in, int64_t frames, int32_t H, int32_t W, const ChainK& D, const NoiseSplitK& S, double* stats,
+                              void* scratch, hipStream_t st, float* lab_out) {
+    const int64_t ppf = (int64_t)H * W;
+    const int bpf = stats_blocks_per_frame(ppf);
+    double* partials = reinterpret_cast<double*>(scratch);
+    // (own loop: any frame may start a launch, nothing to align -- tests/test_gpu_split_noise.py crosses its seam)
+    for (int64_t f0 = 0; f0 < frames; f0 += LAUNCH_RECORDS) {
+        const int64_t nf = frames - f0 < LAUNCH_RECORDS ? frames - f0 : LAUNCH_RECORDS;
+        const NoiseSplitK s = split_shifted(S, f0 * ppf * 3);
+        const px3* src = reinterpret_cast<const px3*>(in) + f0 * ppf;
+        if (!stats) {                   // Lab image only
+            hipLaunchKernelGGL((k_lab_partials<STAGES, false>), dim3((uint32_t)bpf, (uint32_t)nf), dim3(256), 0, st, src, (int32_t)ppf, bpf, D,
+                               (double*)nullptr, reinterpret_cast<px3*>(lab_out) + f0 * ppf, s);
+        } else {
+            hipLaunchKernelGGL((k_lab_partials<STAGES>), dim3((uint32_t)bpf, (uint32_t)nf), dim3(256), 0, st, src, (int32_t)ppf, bpf, D,
+                               partials + f0 * bpf * 6, lab_out ? reinterpret_cast<px3*>(lab_out) + f0 * ppf : nullptr, s);
+            hipLaunchKernelGGL(k_lab_merge<STAGES>, dim3((uint32_t)nf), dim3(64), 0, st, src, (int32_t)ppf, bpf, D,
+                               partials + f0 * bpf * 6, stats + f0 * 9, s);
+        }
+        VRG_CHECK_LAUNCH();
+    }
+    return VRG_OK;
+}
+
+// The checks the split entry points share: the chain descriptor with its noise descriptor set aside (the table replaces it) and the table
+// itself against the launch's elements
+int fill_chain(const vrg_chain_desc* d, int32_t H, int32_t W, ChainK& D);
+static int fill_chain_split(const vrg_chain_desc* desc, const vrg_noise_split* split, int64_t frames, int32_t H, int32_t W, int allowed,
+                            ChainK& D, NoiseSplitK& S) {
+    if (!split || !(desc->stages & VRG_STAGE_GRAIN) || (desc->stages & ~31)) return VRG_ERR_BAD_ARG;
+    if (desc->stages & ~allowed) return VRG_ERR_UNSUPPORTED;
+    if ((int64_t)H * W > 0x7fffffff / 3) return VRG_ERR_UNSUPPORTED;
+    vrg_chain_desc d = *desc;
+    d.noise = vrg_noise_desc{0, 0, 0, 0, 0, 1, 256};
+    const int rc = fill_chain(&d, H, W, D);
+    if (rc) return rc;
+    S = make_split(split);
+    if (!split_covers(S, frames * D.noise.frame_elems)) return VRG_ERR_BAD_ARG;
     return VRG_OK;
 }
 
@@ -613,6 +693,72 @@ int vrg_fused_chain_u8(const uint8_t* in, uint8_t* out, int64_t frames, int32_t 
         case 2: return launch_chain<2, IoU8>(in, out, frames, height, width, D, sharpen, st);
         default: return launch_chain<3, IoU8>(in, out, frames, height, width, D, sharpen, st);
     }
+}
+
+}  // extern "C"
+
+// ---- the noise of a draw that torch splits (vrg_noise_split): never the march, produce or shared-Philox grain kernels ----
+template <class IO>
+static int fused_chain_split(const void* in, void* out, int64_t frames, int32_t height, int32_t width, const vrg_chain_desc* desc,
+                             const vrg_noise_split* split, int64_t elem_bytes, void* stream) {
+    if (!in || !out || !desc || frames < 0 || height <= 0 || width <= 0) return VRG_ERR_BAD_ARG;
+    {
+        const int64_t bytes = vrg_operand_bytes(frames, vrg_operand_bytes((int64_t)height * width, 3 * elem_bytes));
+        if (vrg_ranges_overlap(in, bytes, out, bytes)) return VRG_ERR_BAD_ARG;
+    }
+    ChainK D;
+    NoiseSplitK S;
+    if (frames == 0) return split && (desc->stages & VRG_STAGE_GRAIN) ? VRG_OK : VRG_ERR_BAD_ARG;
+    const int rc = fill_chain_split(desc, split, frames, height, width, VRG_STAGE_GRAIN | VRG_STAGE_LUT | VRG_STAGE_SHARPEN, D, S);
+    if (rc) return rc;
+    const bool sharpen = (desc->stages & VRG_STAGE_SHARPEN) != 0;
+    if (desc->stages & VRG_STAGE_LUT) return launch_chain_split<3, IO>(in, out, frames, height, width, D, S, sharpen, (hipStream_t)stream);
+    return launch_chain_split<1, IO>(in, out, frames, height, width, D, S, sharpen, (hipStream_t)stream);
+}
+
+extern "C" {
+
+int vrg_fused_chain_split_f32(const float* in, float* out, int64_t frames, int32_t height, int32_t width, const vrg_chain_desc* desc,
+                              const vrg_noise_split* split, void* stream) {
+    return fused_chain_split<IoF32>(in, out, frames, height, width, desc, split, 4, stream);
+}
+
+int vrg_fused_chain_split_u8(const uint8_t* in, uint8_t* out, int64_t frames, int32_t height, int32_t width, const vrg_chain_desc* desc,
+                             const vrg_noise_split* split, void* stream) {
+    return fused_chain_split<IoU8>(in, out, frames, height, width, desc, split, 1, stream);
+}
+
+int vrg_grain_split_f32(const float* in, float* out, int64_t frames, int32_t height, int32_t width, float intensity, float sat,
+                        float one_minus_sat, const vrg_noise_split* split, void* stream) {
+    // grain alone: element-wise, so in == out is fine as for vrg_grain_f32 (fused_chain_split's overlap rule is the stencil's)
+    if (!in || !out || !split || frames < 0 || height <= 0 || width <= 0) return VRG_ERR_BAD_ARG;
+    if (frames == 0) return VRG_OK;
+    vrg_chain_desc d{};
+    d.stages = VRG_STAGE_GRAIN;
+    d.intensity = intensity; d.sat = sat; d.one_minus_sat = one_minus_sat;
+    ChainK D;
+    NoiseSplitK S;
+    const int rc = fill_chain_split(&d, split, frames, height, width, VRG_STAGE_GRAIN, D, S);
+    if (rc) return rc;
+    return launch_chain_split<1, IoF32>(in, out, frames, height, width, D, S, false, (hipStream_t)stream);
+}
+
+int vrg_chain_stats_lab_split_f32(const float* in, float* lab_out, int64_t frames, int32_t height, int32_t width,
+                                  const vrg_chain_desc* desc, const vrg_noise_split* split, double* stats, void* scratch, void* stream) {
+    if (!in || !desc || !split || (!stats && !lab_out) || (stats && !scratch) || frames < 0 || height <= 0 || width <= 0) return VRG_ERR_BAD_ARG;
+    if (frames == 0) return VRG_OK;
+    if (desc->cm_math != VRG_CM_MATH_DEVICE && desc->cm_math != VRG_CM_MATH_FAST) return VRG_ERR_BAD_ARG;
+    vrg_chain_desc pre = *desc;
+    pre.stages &= (VRG_STAGE_GRAIN | VRG_STAGE_LUT);   // statistics are taken on the colour-match *input*
+    ChainK D;
+    NoiseSplitK S;
+    const int rc = fill_chain_split(&pre, split, frames, height, width, VRG_STAGE_GRAIN | VRG_STAGE_LUT, D, S);
+    if (rc) return rc;
+    const bool fast = desc->cm_math == VRG_CM_MATH_FAST;
+#define CALL(S_) launch_stats_split<S_>(in, frames, height, width, D, S, stats, scratch, (hipStream_t)stream, lab_out)
+    if (pre.stages & VRG_STAGE_LUT) return fast ? CALL(3 | VRG_STAGE_FASTMATH) : CALL(3);
+    return fast ? CALL(1 | VRG_STAGE_FASTMATH) : CALL(1);
+#undef CALL
 }
 
 }  // extern "C"

@@ -86,4 +86,75 @@ __device__ __forceinline__ void chain_pre(const ChainK& D, const FrameCtx& C, in
     chain_apply_stages<STAGES>(D, C, xin, n, o, PT);
 }
 
+// ---- the general form of the noise mapping: a draw that torch splits ------------------------------------------------------------------
+// The kernels of vrg_chain.hip take their noise source as a last argument: NoSplit (the chunks of ChainK::noise, the code above, and an
+// empty argument that leaves their instantiations as they were) or a NoiseSplitK, the leaves of one randn of more than 2^29 elements.
+// The leaves are not frame -- not even pixel -- aligned, so an element finds its leaf: element e of the launch lies in exactly one leaf
+// (start, size, G, off) and is torch_randn_element(seed, off, G, e - start).  That costs one Philox call per element like chain_pre above;
+// kernels that share a Philox call among four elements of ONE grid (the march, the produce pass, k_grain) have no such form.
+struct NoSplit {};
+__device__ __forceinline__ NoSplit noise_source() { return NoSplit{}; }
+__device__ __forceinline__ const NoiseSplitK& noise_source(const NoiseSplitK& s) { return s; }
+
+template <int STAGES>
+__device__ __forceinline__ FrameCtx frame_ctx(const ChainK& D, int64_t f, const NoSplit&) { return frame_ctx<STAGES>(D, f); }
+template <int STAGES, class MATH>
+__device__ __forceinline__ void chain_pre(const ChainK& D, const FrameCtx& C, int32_t p, const float xin[3], float o[3], const MATH& PT,
+                                          const NoSplit&) {
+    chain_pre<STAGES>(D, C, p, xin, o, PT);
+}
+
+struct SplitFrameCtx : FrameCtx {
+    int64_t base;                // element of the frame's first element inside the launch
+    uint32_t G;                  // one_leaf: the grid of the leaf that holds the whole frame (seed / off / elem0 are then that leaf's)
+    bool one_leaf;
+};
+
+// Resolved once per workgroup: does frame f lie inside ONE leaf?  Then seed / off / G / elem0 are workgroup-uniform and the pixel's
+// normals are drawn as for an ordinary chunk; otherwise every element looks its leaf up (chain_pre below).
+template <int STAGES>
+__device__ __forceinline__ SplitFrameCtx frame_ctx(const ChainK& D, int64_t f, const NoiseSplitK& S) {
+    SplitFrameCtx C;
+    static_cast<FrameCtx&>(C) = frame_ctx<STAGES & ~VRG_STAGE_GRAIN>(D, f);
+    C.base = f * D.noise.frame_elems;
+    const int first = split_leaf_of(S, C.base), last = split_leaf_of(S, C.base + D.noise.frame_elems - 1);
+    C.one_leaf = first == last;
+    NoiseLeafK L = S.leaf[0];
+#pragma unroll
+    for (int i = 1; i < NOISE_LEAVES_MAX; ++i)
+        if (i == first) L = S.leaf[i];          // (selects: a dynamic index would put the by-value table into scratch)
+    C.seed = S.seed;
+    C.off = L.off;
+    C.G = L.G;
+    C.elem0 = (uint64_t)(C.base - L.start);
+    return C;
+}
+
+// the normal of element e of the launch
+__device__ __forceinline__ float split_randn_element(const NoiseSplitK& S, int64_t e) {
+    NoiseLeafK L = S.leaf[0];
+#pragma unroll
+    for (int i = 1; i < NOISE_LEAVES_MAX; ++i)
+        if (i < S.count && S.leaf[i].start <= e) L = S.leaf[i];
+    return torch_randn_element32(S.seed, L.off, L.G, (uint32_t)(e - L.start));      // inside a leaf: below 2^32, no 64-bit divide
+}
+
+template <int STAGES, class MATH>
+__device__ __forceinline__ void chain_pre(const ChainK& D, const SplitFrameCtx& C, int32_t p, const float xin[3], float o[3], const MATH& PT,
+                                          const NoiseSplitK& S) {
+    float n[3] = {0.0f, 0.0f, 0.0f};
+    if (STAGES & VRG_STAGE_GRAIN) {
+        if (C.one_leaf) {
+            const uint32_t li = (uint32_t)C.elem0 + (uint32_t)p * 3u;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) n[c] = torch_randn_element32(C.seed, C.off, C.G, li + c);
+        } else {
+            const int64_t e = C.base + (int64_t)p * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) n[c] = split_randn_element(S, e + c);       // a leaf may begin inside the pixel
+        }
+    }
+    chain_apply_stages<STAGES>(D, C, xin, n, o, PT);
+}
+
 }  // namespace vrg

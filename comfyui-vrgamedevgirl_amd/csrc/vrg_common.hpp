@@ -91,6 +91,62 @@ struct NoiseK {
 VRG_HD uint64_t chunk_seed(const NoiseK& n, int64_t chunk_rel) { return n.seed0 + (uint64_t)(n.chunk0 + chunk_rel) * n.seed_stride; }
 VRG_HD uint64_t chunk_offset(const NoiseK& n, int64_t chunk_rel) { return n.off0 + (uint64_t)(n.chunk0 + chunk_rel) * n.off_stride; }
 
+// Device copy of vrg_noise_split: the leaves of ONE randn that torch splits (more than 2^29 elements) that a launch meets, by value in the
+// kernel arguments.  start = the leaf's first element relative to the launch's first element (negative: the leaf begins before it).
+constexpr int NOISE_LEAVES_MAX = VRG_NOISE_LEAVES_MAX;
+struct NoiseLeafK {
+    int64_t start;
+    uint32_t size, G;
+    uint64_t off;
+};
+struct NoiseSplitK {
+    uint64_t seed;
+    int32_t count;
+    NoiseLeafK leaf[NOISE_LEAVES_MAX];
+};
+
+// The leaf that holds element e of the launch: the last one that starts at or before it (the leaves are in memory order and without gaps,
+// split_covers).  An element outside the table takes the nearest leaf -- the caller's own range check decides what it does with it.
+VRG_HD int split_leaf_of(const NoiseSplitK& s, int64_t e) {
+    int at = 0;
+    for (int i = 1; i < NOISE_LEAVES_MAX; ++i)
+        if (i < s.count && s.leaf[i].start <= e) at = i;
+    return at;
+}
+
+// Is `s` a table for the elements [0, total) of a launch: 1 .. NOISE_LEAVES_MAX leaves that follow one another exactly (no overlap, no gap),
+// every grid a non-zero multiple of 256, the first at or before element 0 and the last ending at or after `total`?
+VRG_HD bool split_covers(const NoiseSplitK& s, int64_t total) {
+    if (s.count < 1 || s.count > NOISE_LEAVES_MAX || total < 1) return false;
+    if (s.leaf[0].start > 0 || s.leaf[0].start < -((int64_t)1 << 40)) return false;       // (no sum below can overflow)
+    for (int i = 0; i < s.count; ++i) {
+        const NoiseLeafK& l = s.leaf[i];
+        if (l.size == 0 || l.G == 0 || (l.G % 256u) != 0 || (l.off & 3u)) return false;
+        if (i > 0 && l.start != s.leaf[i - 1].start + (int64_t)s.leaf[i - 1].size) return false;
+    }
+    const NoiseLeafK& last = s.leaf[s.count - 1];
+    return last.start + (int64_t)last.size >= total;
+}
+
+// The table of a launch that starts `elems` elements further on
+VRG_HD NoiseSplitK split_shifted(const NoiseSplitK& s, int64_t elems) {
+    NoiseSplitK r = s;
+    for (int i = 0; i < NOISE_LEAVES_MAX; ++i) r.leaf[i].start -= elems;
+    return r;
+}
+
+inline NoiseSplitK make_split(const vrg_noise_split* d) {
+    NoiseSplitK s{};
+    s.seed = d->seed;
+    s.count = d->count;
+    for (int i = 0; i < NOISE_LEAVES_MAX; ++i) {
+        const bool used = i < d->count;
+        s.leaf[i] = NoiseLeafK{used ? d->leaves[i].start : 0, used ? d->leaves[i].size : 0u, used ? d->leaves[i].grid_threads : 0u,
+                               used ? d->leaves[i].offset : 0ull};
+    }
+    return s;
+}
+
 }  // namespace vrg
 
 #if defined(__HIPCC__) || defined(__HIP__)

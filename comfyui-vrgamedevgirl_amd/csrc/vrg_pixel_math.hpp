@@ -241,6 +241,13 @@ VRG_D float torch_randn_element(uint64_t seed, uint64_t offset, uint32_t G, uint
     const u32x4 r = philox_for(seed, idx, (offset >> 2) + (q >> 2));
     return normal_component(r, (int)(q & 3));
 }
+// The same for an element index that fits 32 bits (an element of a leaf of a split draw: at most 2^29 of them): no 64-bit divide
+VRG_D float torch_randn_element32(uint64_t seed, uint64_t offset, uint32_t G, uint32_t li) {
+    const uint32_t q = li / G;
+    const uint32_t idx = li - q * G;
+    const u32x4 r = philox_for(seed, idx, (offset >> 2) + (q >> 2));
+    return normal_component(r, (int)(q & 3));
+}
 
 // ------------------------------------------------------------------------------------------
 // Film grain (nodes.py:53-60)

@@ -85,9 +85,15 @@ class FastFilmGrain:
         frames = int(images.shape[0])
         step = batch_size if batch_size > 0 else max(frames, 1)
         primary = compute_device()
-        many = images.ndim == 4 and frames > 0 and images.shape[-1] == 3 and not ops.oversize_chunks(frames, _frame_numel(images), step)
+        many = images.ndim == 4 and frames > 0 and images.shape[-1] == 3
+        # RNG chunks torch itself splits (> 2^29 elements: batch_size 0 on a long batch) are counter-based noise like any other, and a piece
+        # of them is any range of whole frames (ops.slice_plans): such a batch streams in bounded pieces, defers and fuses.  Only a split
+        # chunk followed by a ragged tail chunk BELOW the limit keeps whole-chunk pieces: the tail is one ordinary draw.
+        split = many and ops.oversize_chunks(frames, _frame_numel(images), step)
+        if split and frames % step and not ops.oversize_chunks(frames % step, _frame_numel(images), 0):
+            many = False
         if not many:
-            # RNG chunks torch itself splits (> 2^29 elements), an empty batch, frames the kernels refuse: the generator is consumed inside
+            # an empty batch, frames the kernels refuse, the split-then-ordinary batch above: the generator is consumed inside
             # ops.film_grain, piece by piece, in submission order
             def run_now(gpu_frames, _first, out=None):
                 return ops.film_grain(gpu_frames, grain_intensity, saturation_mix, chunk_frames=step, out=out)
@@ -97,13 +103,14 @@ class FastFilmGrain:
         # the generator moves exactly as the reference's loop moves it whether the pieces run now, later (deferred graph fusion) or on
         # another GPU (VRGDG_DEVICES).
         plans = ops.plan_noise(frames, _frame_numel(images), step, primary)
+        pieces_of = 1 if split else step
 
         def run(gpu_frames, first, out=None):
             return ops.film_grain(gpu_frames, grain_intensity, saturation_mix, chunk_frames=step,
                                   plans=ops.slice_plans(plans, first, int(gpu_frames.shape[0])), out=out)
 
         fuse = {"I": grain_intensity, "s": saturation_mix, "step": step, "plans": plans}
-        return (_run_grouped(images, run, multiple_of=step, fn_for_device=lambda _device: run, kind="grain", fuse=fuse),)
+        return (_run_grouped(images, run, multiple_of=pieces_of, fn_for_device=lambda _device: run, kind="grain", fuse=fuse),)
 
 
 class ColorMatchToReference:

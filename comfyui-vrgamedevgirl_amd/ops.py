@@ -256,32 +256,131 @@ class NoisePlan:
                               grid_threads=s.grid_threads)
 
 
+@dataclass
+class SplitNoisePlan:
+    """Frames [first, first + frames) of a run of RNG chunks of `chunk_frames` frames that torch itself splits (more than
+    rng.MAX_CHUNK_NUMEL elements each, rng.reserve_split): chunk j of the run is call j of `stream`.  Counter-based noise needs no whole
+    chunks: any range of whole frames is a plan (slice_plans), and a frame finds the leaves it meets (split_launches)."""
+    chunk_frames: int
+    stream: rng.SplitStream
+    first: int = 0
+    frames: int = 0
+
+
 def oversize_chunks(frames: int, frame_numel: int, chunk_frames: int) -> bool:
     """Does the reference's chunk loop draw a torch.randn that ATen has to split (more than 2^29 elements)?"""
     step = min(chunk_frames if chunk_frames > 0 else frames, frames)
     return step * frame_numel > rng.MAX_CHUNK_NUMEL
 
 
-def plan_noise(frames: int, frame_numel: int, chunk_frames: int, device, generator=None):
+def plan_noise(frames: int, frame_numel: int, chunk_frames: int, device, generator=None, geom=None):
     """Reserve the generator range FastFilmGrain's chunk loop would consume (nodes.py:46-51).
-    Returns (plan for the full chunks or None, plan for the ragged tail chunk or None, n_full_chunks)."""
+    Returns (plan for the full chunks or None, plan for the ragged tail chunk or None, n_full_chunks).  A chunk of more than
+    rng.MAX_CHUNK_NUMEL elements (read now) is a draw torch splits: its plan is a SplitNoisePlan, and the generator moves as ATen moves it
+    -- per chunk the outer call's unused reservation, then the leaves."""
     step = chunk_frames if chunk_frames > 0 else frames
     step = min(step, frames)
     n_full, tail = divmod(frames, step)
-    main = tail_plan = None
-    if n_full:
-        main = NoisePlan(step, rng.reserve(step * frame_numel, n_full, device, generator))
-    if tail:
-        tail_plan = NoisePlan(tail, rng.reserve(tail * frame_numel, 1, device, generator))
+    limit = rng.MAX_CHUNK_NUMEL
+
+    def plan(chunk, n):
+        if chunk * frame_numel > limit:
+            return SplitNoisePlan(chunk, rng.reserve_split(chunk * frame_numel, device, generator, geom, n_chunks=n), 0, chunk * n)
+        return NoisePlan(chunk, rng.reserve(chunk * frame_numel, n, device, generator, geom))
+
+    main = plan(step, n_full) if n_full else None
+    tail_plan = plan(tail, 1) if tail else None
     return main, tail_plan, n_full
+
+
+def _plan_frames(plan, n_chunks: int) -> int:
+    return plan.frames if isinstance(plan, SplitNoisePlan) else n_chunks * plan.chunk_frames
+
+
+def _plan_segments(plans, frames: int, what: str) -> list:
+    """[(first frame, frames, plan)] of a call over `frames` frames under `plans` (plan_noise / slice_plans)"""
+    main, tail, n_full = plans
+    segments, done = [], 0
+    for plan, n in ((main, n_full), (tail, 1)):
+        if plan is not None:
+            segments.append((done, _plan_frames(plan, n), plan))
+            done += segments[-1][1]
+    if done != frames and any(isinstance(p, SplitNoisePlan) for p in (main, tail)):       # (a slice of a split batch is any frame range)
+        raise ValueError(f"{what}: the noise plans describe {done} frames, the call has {frames}")
+    return segments
+
+
+def split_launches(plan: SplitNoisePlan, frame_numel: int) -> list:
+    """The launches of a split plan: [(first frame of the plan, frames, seed, leaves)], each inside one chunk and meeting at most
+    rng.NOISE_LEAVES_MAX leaves -- `leaves` as rng.SplitStream.leaves_of gives them, relative to the launch's first element.  Halving stops
+    at pieces of at most `limit` elements, so a leaf holds at least (limit + 1) // 2 and a frame of fewer than `limit` meets at most 3; a
+    single frame that meets more than the maximum (more than 1.8 G elements at the real limit) comes back with leaves = None: that frame's
+    noise is written to memory (_film_grain_oversize)."""
+    out = []
+    step, s = plan.chunk_frames, plan.stream
+    f, end = plan.first, plan.first + plan.frames
+    while f < end:
+        chunk, lo = divmod(f, step)
+        hi_max = min(step, lo + end - f)
+        hi = lo + 1
+        leaves = s.leaves_of(chunk, lo * frame_numel, hi * frame_numel)
+        if len(leaves) > rng.NOISE_LEAVES_MAX:
+            out.append((f - plan.first, 1, s.seed, None))
+        else:
+            while hi < hi_max:
+                more = s.leaves_of(chunk, lo * frame_numel, (hi + 1) * frame_numel)
+                if len(more) > rng.NOISE_LEAVES_MAX:
+                    break
+                hi, leaves = hi + 1, more
+            out.append((f - plan.first, hi - lo, s.seed, leaves))
+        f += hi - lo
+    return out
+
+
+def _split_records(plan, frame_numel: int):
+    """[(first frame of the plan, frames, _hip.NoiseSplit)] for the launches of a split plan, [] for any other plan; None where a frame
+    meets more leaves than a launch takes"""
+    if not isinstance(plan, SplitNoisePlan):
+        return []
+    launches = split_launches(plan, frame_numel)
+    if any(leaves is None for _g0, _n, _seed, leaves in launches):
+        return None
+    return [(g0, n, _hip.NoiseSplit.of(seed, leaves)) for g0, n, seed, leaves in launches]
+
+
+def _slice_split_plans(plans, first_frame: int, frames: int):
+    main, tail, n_full = plans
+    main_len = _plan_frames(main, n_full) if main is not None else 0
+    tail_len = _plan_frames(tail, 1) if tail is not None else 0
+    end = first_frame + frames
+    if first_frame < 0 or frames < 0 or end > main_len + tail_len:
+        raise ValueError("a piece of a grain batch must lie inside the batch")
+    sub_main, sub_n = None, 0
+    if first_frame < main_len and frames:           # (main is a split plan: a split tail is shorter than its main chunk, which is then split too)
+        n = min(end, main_len) - first_frame
+        sub_main = SplitNoisePlan(main.chunk_frames, main.stream, main.first + first_frame, n)
+        sub_n = (sub_main.first + n - 1) // main.chunk_frames - sub_main.first // main.chunk_frames + 1
+    sub_tail = None
+    lo = max(first_frame, main_len) - main_len
+    if end - main_len > lo:
+        if isinstance(tail, SplitNoisePlan):
+            sub_tail = SplitNoisePlan(tail.chunk_frames, tail.stream, tail.first + lo, end - main_len - lo)
+        elif lo != 0 or end - main_len != tail_len:
+            raise ValueError("a piece of a grain batch must be made of whole noise chunks")
+        else:
+            sub_tail = tail
+    return sub_main, sub_tail, sub_n
 
 
 def slice_plans(plans, first_frame: int, frames: int):
     """The part of a whole-batch reservation (`plan_noise`) that covers frames [first_frame, first_frame + frames): what `plan_noise` would
     have returned for that piece had the pieces been reserved one after the other -- a batch's chunks are consecutive generator ranges, so
     reserving it at once (when the node is called) and slicing (when a piece runs) consumes the generator exactly as the reference's
-    chunk loop does.  `first_frame` must be a multiple of the chunk size."""
+    chunk loop does.  `first_frame` must be a multiple of the chunk size -- except under split plans (chunks torch itself splits), where
+    any range of whole frames is a piece, across chunks too.  Touches no generator."""
     main, tail, n_full = plans
+    if isinstance(main, SplitNoisePlan) or isinstance(tail, SplitNoisePlan):
+        return _slice_split_plans(plans, first_frame, frames)
     step = main.chunk_frames if main is not None else (tail.chunk_frames if tail is not None else 1)
     full_end = n_full * step if main is not None else 0
     if first_frame % step and first_frame < full_end:
@@ -323,32 +422,37 @@ def _grain_call(x, out, f0, nf, plan: NoisePlan, I32, S32, T32):
                                        _hip.current_stream()), "vrg_grain_f32")
 
 
-def _film_grain_oversize(x, out, grain_intensity, saturation_mix, chunk_frames, generator):
+def _film_grain_oversize(x, out, f0, plan: SplitNoisePlan, I32, S32, T32):
     """RNG chunks beyond 2^29 elements (batch_size 0 or >= 22 4K / >= 87 1080p frames): torch runs such a randn as several
-    kernels over 32-bit indexable sub-ranges, each with its own grid and generator offset (rng.reserve_split).  The
-    sub-ranges are not frame -- not even pixel -- aligned, so the chunk's noise is materialised leaf by leaf with the
-    stream kernel (bit-identical to torch.randn) and applied with the injected-noise grain kernel: three passes over
-    the chunk instead of one, for a case the reference handles at one tenth of the speed."""
-    F = x.shape[0]
+    kernels over 32-bit indexable sub-ranges ("leaves"), each with its own grid and generator offset (rng.reserve_split).  The
+    leaves are not frame -- not even pixel -- aligned, so every element looks its leaf up in a table of at most eight that rides in the
+    kernel arguments (vrg_grain_split_f32): one pass over frames [f0, f0 + plan.frames) of `x`, no noise in memory, one launch per group
+    of frames that meets at most eight leaves.  A single frame that meets more (1.8 G elements at the real limit) has its noise
+    written leaf by leaf with the stream kernel (bit-identical to torch.randn) and applied with the injected-noise grain kernel."""
     fe = x[0].numel()
-    step = min(chunk_frames if chunk_frames > 0 else F, F)
+    H, W = int(x.shape[1]), int(x.shape[2])
     lib = _hip.lib()
-    I32, S32, T32 = _f32(grain_intensity), _f32(saturation_mix), _f32(1.0 - saturation_mix)
-    noise = torch.empty((step * fe,), dtype=torch.float32, device=x.device)
-    for f0 in range(0, F, step):
-        nf = min(step, F - f0)
-        numel = nf * fe
-        if numel > rng.MAX_CHUNK_NUMEL:
-            split = rng.reserve_split(numel, x.device, generator)
-            seed, leaves = split.seed, split.leaves
-        else:           # ragged tail chunk below the limit: one ordinary randn
-            st = rng.reserve(numel, 1, x.device, generator)
-            seed, leaves = st.seed, [(0, numel, st.grid_threads, st.offset0)]
-        for start, size, G, off in leaves:
+    for g0, nf, seed, leaves in split_launches(plan, fe):
+        src = C.c_void_p(x.data_ptr() + 4 * (f0 + g0) * fe)
+        dst = C.c_void_p(out.data_ptr() + 4 * (f0 + g0) * fe)
+        if leaves is not None:
+            rec = _hip.NoiseSplit.of(seed, leaves)
+            _hip.check(lib.vrg_grain_split_f32(src, dst, nf, H, W, I32, S32, T32, C.byref(rec), _hip.current_stream()), "vrg_grain_split_f32")
+            continue
+        noise = torch.empty((fe,), dtype=torch.float32, device=x.device)
+        chunk, lo = divmod(plan.first + g0, plan.chunk_frames)
+        for start, size, G, off in plan.stream.leaves_of(chunk, lo * fe, (lo + 1) * fe):
+            # the leaf's elements inside the frame: whole Philox calls of the leaf are drawn into a buffer of their own where the leaf
+            # begins before the frame or ends behind it
+            a, b = max(start, 0), min(start + size, fe)
             d = _hip.NoiseDesc(seed0=seed, seed_stride=0, offset0=off, offset_stride=0, chunk0=0, chunk_frames=1, grid_threads=G)
-            _hip.check(lib.vrg_noise_f32(C.c_void_p(noise.data_ptr() + 4 * start), 1, size, C.byref(d), _hip.current_stream()), "vrg_noise_f32")
-        _hip.check(lib.vrg_grain_injected_f32(C.c_void_p(x.data_ptr() + 4 * f0 * fe), _hip.ptr(noise), C.c_void_p(out.data_ptr() + 4 * f0 * fe),
-                                              nf * fe // 3, I32, S32, T32, _hip.current_stream()), "vrg_grain_injected_f32")
+            if a == start and b == start + size:
+                _hip.check(lib.vrg_noise_f32(C.c_void_p(noise.data_ptr() + 4 * start), 1, size, C.byref(d), _hip.current_stream()), "vrg_noise_f32")
+            else:
+                whole = torch.empty((size,), dtype=torch.float32, device=x.device)
+                _hip.check(lib.vrg_noise_f32(_hip.ptr(whole), 1, size, C.byref(d), _hip.current_stream()), "vrg_noise_f32")
+                noise[a:b] = whole[a - start:b - start]
+        _hip.check(lib.vrg_grain_injected_f32(src, _hip.ptr(noise), dst, fe // 3, I32, S32, T32, _hip.current_stream()), "vrg_grain_injected_f32")
     return out
 
 
@@ -363,16 +467,14 @@ def film_grain(images: torch.Tensor, grain_intensity: float, saturation_mix: flo
     if F == 0:
         return out
     fe = H * W * 3
-    if plans is None and oversize_chunks(F, fe, chunk_frames):
-        return _film_grain_oversize(x, out, grain_intensity, saturation_mix, chunk_frames, generator)
-    main, tail, n_full = plans if plans is not None else plan_noise(F, fe, chunk_frames, x.device, generator)
+    if plans is None:
+        plans = plan_noise(F, fe, chunk_frames, x.device, generator)
     I32, S32, T32 = _f32(grain_intensity), _f32(saturation_mix), _f32(1.0 - saturation_mix)
-    done = 0
-    if main is not None:
-        _grain_call(x, out, 0, n_full * main.chunk_frames, main, I32, S32, T32)
-        done = n_full * main.chunk_frames
-    if tail is not None:
-        _grain_call(x, out, done, tail.chunk_frames, tail, I32, S32, T32)
+    for f0, nf, plan in _plan_segments(plans, F, "film_grain"):
+        if isinstance(plan, SplitNoisePlan):
+            _film_grain_oversize(x, out, f0, plan, I32, S32, T32)
+        else:
+            _grain_call(x, out, f0, nf, plan, I32, S32, T32)
     return out
 
 
@@ -2566,7 +2668,8 @@ def _chain_desc(spec: ChainSpec, plan: Optional[NoisePlan], keep, like: Optional
         I, s, _ = spec.grain
         stages |= _hip.STAGE_GRAIN
         d.intensity, d.sat, d.one_minus_sat = _f32(I), _f32(s), _f32(1.0 - s)
-        d.noise = plan.desc()
+        if isinstance(plan, NoisePlan):         # (a SplitNoisePlan travels beside the descriptor: _split_records)
+            d.noise = plan.desc()
     if spec.lut is not None:
         lut, strength = spec.lut
         mode, B, omB = blend_terms(strength)
@@ -2608,23 +2711,32 @@ def chain_stats(images: torch.Tensor, spec: ChainSpec, generator: Optional[torch
     fe = H * W * 3
     segments = [(0, F, None)]
     if spec.grain is not None:
-        main, tail, n_full = plans if plans is not None else plan_noise(F, fe, spec.grain[2], x.device, generator)
-        segments = []
-        if main is not None:
-            segments.append((0, n_full * main.chunk_frames, main))
-        if tail is not None:
-            segments.append((F - tail.chunk_frames, tail.chunk_frames, tail))
+        if plans is None:
+            plans = plan_noise(F, fe, spec.grain[2], x.device, generator)
+        segments = _plan_segments(plans, F, "chain_stats")
+        if any(_split_records(plan, fe) is None for _f0, _nf, plan in segments):
+            # a frame that meets more leaves than a launch takes (split_launches): grain with its noise in memory, then the rest
+            grained = film_grain(x, spec.grain[0], spec.grain[1], spec.grain[2], plans=plans)
+            import dataclasses
+            return chain_stats(grained, dataclasses.replace(spec, grain=None), lab_out=lab_out)
     stats = torch.empty((F, 3, 3), dtype=torch.float64, device=x.device)
     lib = _hip.lib()
     for f0, nf, plan in segments:
         keep = []
         d = _chain_desc(ChainSpec(grain=spec.grain, lut=spec.lut, variant=spec.variant, cm_math=spec.cm_math), plan, keep, x)
-        nbytes = int(lib.vrg_chain_stats_scratch_bytes(nf, H, W, C.byref(d)))
+        nbytes = int(lib.vrg_chain_stats_scratch_bytes(nf, H, W, C.byref(d))) if isinstance(plan, (NoisePlan, type(None))) else \
+            int(lib.vrg_lab_stats_scratch_bytes(nf))
         scratch = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.float64, device=x.device)
-        src = C.c_void_p(x.data_ptr() + f0 * fe * 4)
-        dst = C.c_void_p(lab_out.data_ptr() + f0 * fe * 4) if lab_out is not None else C.c_void_p(0)
-        _hip.check(lib.vrg_chain_stats_lab_f32(src, dst, nf, H, W, C.byref(d), C.c_void_p(stats.data_ptr() + f0 * 72),
-                                              _hip.ptr(scratch), _hip.current_stream()), "vrg_chain_stats_lab_f32")
+        for g0, n, rec in _split_records(plan, fe) or [(0, nf, None)]:
+            src = C.c_void_p(x.data_ptr() + (f0 + g0) * fe * 4)
+            dst = C.c_void_p(lab_out.data_ptr() + (f0 + g0) * fe * 4) if lab_out is not None else C.c_void_p(0)
+            sts = C.c_void_p(stats.data_ptr() + (f0 + g0) * 72)
+            if rec is None:
+                _hip.check(lib.vrg_chain_stats_lab_f32(src, dst, n, H, W, C.byref(d), sts, _hip.ptr(scratch), _hip.current_stream()),
+                           "vrg_chain_stats_lab_f32")
+            else:
+                _hip.check(lib.vrg_chain_stats_lab_split_f32(src, dst, n, H, W, C.byref(d), C.byref(rec), sts, _hip.ptr(scratch),
+                                                            _hip.current_stream()), "vrg_chain_stats_lab_split_f32")
     return stats
 
 
@@ -2657,33 +2769,30 @@ def fused_chain(images: torch.Tensor, spec: ChainSpec, generator: Optional[torch
     if F == 0:
         return out
     fe = H * W * 3
-    if spec.grain is not None and plans is not None and any(p is not None and p.chunk_frames * fe > rng.MAX_CHUNK_NUMEL for p in plans[:2]):
-        raise ValueError("fused_chain: a caller-supplied noise plan cannot describe an RNG chunk of more than 2^29 elements (torch splits "
-                         "such a randn into several kernels, rng.reserve_split); pass the generator instead of `plans`")
-    if spec.grain is not None and plans is None and oversize_chunks(F, fe, spec.grain[2]):
-        # RNG chunks that torch itself splits (see _film_grain_oversize): grain as its own pass, then the rest of the chain
-        import dataclasses
-        if u8:
-            # decoded uint8 frames: the same detour on the fp32 image (u8 -> f32 -> chain -> u8 equals the uint8 kernels byte for byte,
-            # tests/test_gpu_parity.py); costs two fp32 copies of the chunk on top of the noise buffer -- a > 0.5 G-element chunk of
-            # uint8 video is not a route the reference takes at speed either
-            res = fused_chain(frames_u8_to_f32(x), spec, generator=generator, kernel_events=kernel_events, cache_lab=cache_lab)
-            out.copy_(f32_to_frames_u8(res))
-            return out
-        grained = film_grain(x, spec.grain[0], spec.grain[1], spec.grain[2], generator=generator)
-        rest = dataclasses.replace(spec, grain=None)
-        if rest.lut is None and rest.colormatch is None and rest.sharpen is None:
-            out.copy_(grained)
-            return out
-        return fused_chain(grained, rest, out=out, kernel_events=kernel_events, lab_workspace=lab_workspace, cache_lab=cache_lab)
     segments = [(0, F, None)]
     if spec.grain is not None:
-        main, tail, n_full = plans if plans is not None else plan_noise(F, fe, spec.grain[2], x.device, generator)
-        segments = []
-        if main is not None:
-            segments.append((0, n_full * main.chunk_frames, main))
-        if tail is not None:
-            segments.append((F - tail.chunk_frames, tail.chunk_frames, tail))
+        if plans is None:
+            plans = plan_noise(F, fe, spec.grain[2], x.device, generator)
+        segments = _plan_segments(plans, F, "fused_chain")
+        # RNG chunks that torch itself splits (SplitNoisePlan) run inside the fused launches like any other: the kernels look every
+        # element's leaf up (vrg_fused_chain_split_*).  With a colour match the grain sits in pass 1, and pass 2 always starts from its
+        # Lab image: the recomputing form (cache_lab=False) gives the same bits and would need split forms of the colour-match kernels.
+        if any(isinstance(plan, SplitNoisePlan) for _f0, _nf, plan in segments):
+            cache_lab = True
+        if any(_split_records(plan, fe) is None for _f0, _nf, plan in segments):
+            # a single frame that meets more leaves than a launch takes (1.8 G elements at the real limit, split_launches): grain as its
+            # own pass with that frame's noise in memory (_film_grain_oversize), then the rest of the chain
+            import dataclasses
+            if u8:
+                res = fused_chain(frames_u8_to_f32(x), spec, plans=plans, kernel_events=kernel_events)
+                out.copy_(f32_to_frames_u8(res))
+                return out
+            grained = film_grain(x, spec.grain[0], spec.grain[1], spec.grain[2], plans=plans)
+            rest = dataclasses.replace(spec, grain=None)
+            if rest.lut is None and rest.colormatch is None and rest.sharpen is None:
+                out.copy_(grained)
+                return out
+            return fused_chain(grained, rest, out=out, kernel_events=kernel_events, lab_workspace=lab_workspace, cache_lab=cache_lab)
     lib = _hip.lib()
     st = _hip.current_stream()
     if spec.variant == 0:
@@ -2710,8 +2819,13 @@ def fused_chain(images: torch.Tensor, spec: ChainSpec, generator: Optional[torch
             if kernel_events is not None:
                 s0, s1 = HipEvent(), HipEvent()
                 s0.record()
-            _hip.check(lib.vrg_chain_stats_lab_f32(C.c_void_p(x.data_ptr() + f0 * fe * 4), C.c_void_p(lab_full.data_ptr() + f0 * fe * 4), nf, H, W,
-                                                  C.byref(d), None, None, st), "vrg_chain_stats_lab_f32")       # the Lab image only
+            for g0, n, rec in _split_records(plan, fe) or [(0, nf, None)]:           # the Lab image only
+                src, dst = C.c_void_p(x.data_ptr() + (f0 + g0) * fe * 4), C.c_void_p(lab_full.data_ptr() + (f0 + g0) * fe * 4)
+                if rec is None:
+                    _hip.check(lib.vrg_chain_stats_lab_f32(src, dst, n, H, W, C.byref(d), None, None, st), "vrg_chain_stats_lab_f32")
+                else:
+                    _hip.check(lib.vrg_chain_stats_lab_split_f32(src, dst, n, H, W, C.byref(d), C.byref(rec), None, None, st),
+                               "vrg_chain_stats_lab_split_f32")
             if kernel_events is not None:
                 s1.record()
                 kernel_events.append(("stats", s0, s1, nf))
@@ -2741,12 +2855,23 @@ def fused_chain(images: torch.Tensor, spec: ChainSpec, generator: Optional[torch
                 d.img_ms = img_ms_full.data_ptr() + f0 * 24
             else:
                 stats = torch.empty((nf, 3, 3), dtype=torch.float64, device=x.device)
-                nbytes = int(lib.vrg_chain_stats_scratch_bytes(nf, H, W, C.byref(d)))
+                nbytes = int(lib.vrg_chain_stats_scratch_bytes(nf, H, W, C.byref(d)))        # (at least vrg_lab_stats_scratch_bytes: the split form's)
                 scratch = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.float64, device=x.device)
                 if kernel_events is not None:
                     s0, s1 = HipEvent(), HipEvent()
                     s0.record()
-                if cache_lab:
+                if isinstance(plan, SplitNoisePlan):           # (cache_lab: set above)
+                    lab = lab_workspace[f0:f0 + nf] if lab_workspace is not None else torch.empty((nf, H, W, 3), dtype=torch.float32, device=x.device)
+                    if lab_workspace is not None and (lab_workspace.shape != x.shape or lab_workspace.dtype != torch.float32 or not lab_workspace.is_contiguous()):
+                        raise ValueError("lab_workspace must be a contiguous float32 tensor shaped like images")
+                    keep.append(lab)
+                    for g0, n, rec in _split_records(plan, fe):
+                        _hip.check(lib.vrg_chain_stats_lab_split_f32(C.c_void_p(x.data_ptr() + (f0 + g0) * fe * 4), C.c_void_p(lab.data_ptr() + g0 * fe * 4),
+                                                                    n, H, W, C.byref(d), C.byref(rec), C.c_void_p(stats.data_ptr() + g0 * 72),
+                                                                    _hip.ptr(scratch), st), "vrg_chain_stats_lab_split_f32")
+                    src = C.c_void_p(lab.data_ptr())
+                    d.stages = (d.stages & _hip.STAGE_SHARPEN) | _hip.STAGE_COLORMATCH | _hip.STAGE_FROM_LAB
+                elif cache_lab:
                     if lab_workspace is not None:
                         if lab_workspace.shape != x.shape or lab_workspace.dtype != torch.float32 or not lab_workspace.is_contiguous():
                             raise ValueError("lab_workspace must be a contiguous float32 tensor shaped like images")
@@ -2770,7 +2895,14 @@ def fused_chain(images: torch.Tensor, spec: ChainSpec, generator: Optional[torch
         if kernel_events is not None:
             e0, e1 = HipEvent(), HipEvent()
             e0.record()
-        if u8:
+        if isinstance(plan, SplitNoisePlan) and (d.stages & _hip.STAGE_GRAIN):
+            for g0, n, rec in _split_records(plan, fe):
+                a, b = C.c_void_p(src.value + g0 * fe * esize), C.c_void_p(dst.value + g0 * fe * esize)
+                if u8:
+                    _hip.check(lib.vrg_fused_chain_split_u8(a, b, n, H, W, C.byref(d), C.byref(rec), st), "vrg_fused_chain_split_u8")
+                else:
+                    _hip.check(lib.vrg_fused_chain_split_f32(a, b, n, H, W, C.byref(d), C.byref(rec), st), "vrg_fused_chain_split_f32")
+        elif u8:
             _hip.check(lib.vrg_fused_chain_u8(src, dst, nf, H, W, C.byref(d), st), "vrg_fused_chain_u8")
         else:
             _hip.check(lib.vrg_fused_chain_f32(src, dst, nf, H, W, C.byref(d), st), "vrg_fused_chain_f32")

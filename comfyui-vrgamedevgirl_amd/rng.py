@@ -82,32 +82,49 @@ def split_32bit(numel: int, start: int = 0):
     return split_32bit(first, start) + split_32bit(numel - first, start + first)
 
 
+#: leaves one kernel launch takes by value (include/vrgdg_hip.h: VRG_NOISE_LEAVES_MAX)
+NOISE_LEAVES_MAX = 8
+
+
 @dataclass
 class SplitStream:
-    """One oversize ``randn(numel)`` call: the leaves ATen launches, each with its own grid and generator offset."""
+    """Oversize ``randn(numel)`` calls of one size, one after the other: the leaves ATen launches for the first, each with its own grid
+    and generator offset; call j has the same leaves `offset_stride` further on in the generator."""
     seed: int
-    leaves: list            # [(start, size, grid_threads, offset), ...]
+    leaves: list            # [(start, size, grid_threads, offset), ...] of call 0, in memory order
     chunk_numel: int
+    offset_stride: int = 0  # what one call moves the generator by (its unused outer reservation + its leaves)
+
+    def leaves_of(self, chunk: int, lo: int, hi: int) -> list:
+        """The leaves of call `chunk` that elements [lo, hi) of it meet, `start` relative to element `lo` (negative where the leaf begins
+        before it), in memory order."""
+        if not 0 <= lo < hi <= self.chunk_numel:
+            raise ValueError("element range outside the draw")
+        shift = chunk * self.offset_stride
+        return [(start - lo, size, G, off + shift) for start, size, G, off in self.leaves if start < hi and start + size > lo]
 
 
-def reserve_split(numel: int, device, generator=None, geom: DeviceGeometry | None = None) -> SplitStream:
-    """Generator bookkeeping of ONE ``torch.randn(numel)`` with numel > 2^29, exactly as ATen's
+def reserve_split(numel: int, device, generator=None, geom: DeviceGeometry | None = None, n_chunks: int = 1) -> SplitStream:
+    """Generator bookkeeping of `n_chunks` successive ``torch.randn(numel)`` with numel > 2^29, exactly as ATen's
     ``distribution_nullary_kernel`` does it (DistributionTemplates.h:118-140): the outer call takes its Philox state --
     advancing the offset by the whole tensor's counter_offset, which is then never used -- before it notices that the
     iterator needs splitting, and every sub-iterator call takes (and advances by) its own."""
+    if n_chunks < 1:
+        raise ValueError("n_chunks must be positive")
     geom = geom or device_geometry(device)
     gen = _generator_for(device, generator)
     with _RESERVE_LOCK:
         seed = int(gen.initial_seed())
-        off = int(gen.get_offset())
+        off0 = off = int(gen.get_offset())
         off += counter_offset(numel, grid_threads(numel, geom))          # the outer call's unused reservation
         leaves = []
         for start, size in split_32bit(numel):
             G = grid_threads(size, geom)
             leaves.append((start, size, G, off))
             off += counter_offset(size, G)
-        gen.set_offset(off)
-    return SplitStream(seed=seed & 0xFFFFFFFFFFFFFFFF, leaves=leaves, chunk_numel=numel)
+        stride = off - off0
+        gen.set_offset(off0 + stride * n_chunks)
+    return SplitStream(seed=seed & 0xFFFFFFFFFFFFFFFF, leaves=leaves, chunk_numel=numel, offset_stride=stride)
 
 
 def _generator_for(device, generator):

@@ -80,6 +80,35 @@ typedef struct vrg_noise_desc {
     uint32_t grid_threads;  /* G */
 } vrg_noise_desc;
 
+/*
+ * Split noise: ONE `randn` of more than 2^29 elements, which ATen runs as several kernels over 32-bit indexable sub-ranges
+ * (TensorIteratorBase::with_32bit_indexing), every sub-range ("leaf") with a grid and a generator offset of its own.  A launch names the
+ * leaves its frames meet, in memory order and without gaps: `start` is the leaf's first element relative to the FIRST ELEMENT OF THE
+ * LAUNCH (negative where the leaf begins before it), and element e of the launch, start <= e < start + size, takes the value
+ * vrg_noise_desc describes for element e - start of a chunk drawn with `grid_threads` at `offset`.  The record travels in the
+ * kernel arguments: nothing is uploaded.  count in 1 .. VRG_NOISE_LEAVES_MAX, every grid_threads a non-zero multiple of 256, the leaves
+ * cover the launch's elements; anything else is VRG_ERR_BAD_ARG.
+ */
+#define VRG_NOISE_LEAVES_MAX 8
+typedef struct vrg_noise_leaf {
+    int64_t  start;
+    uint32_t size;
+    uint32_t grid_threads;
+    uint64_t offset;        /* multiple of 4 */
+} vrg_noise_leaf;
+typedef struct vrg_noise_split {
+    uint64_t seed;
+    int32_t  count;
+    int32_t  reserved;
+    vrg_noise_leaf leaves[VRG_NOISE_LEAVES_MAX];
+} vrg_noise_split;
+
+/* Film grain over frames whose noise is a split draw: vrg_grain_f32 with the noise of `split`.  Frames are whole frames of the draw, in
+ * any number; a frame may lie across leaves, and a leaf may begin or end inside a pixel. */
+int vrg_grain_split_f32(const float* in, float* out, int64_t frames, int32_t height, int32_t width,
+                        float intensity, float sat, float one_minus_sat,
+                        const vrg_noise_split* split, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * a1/a2  Film grain.  Replaces FastFilmGrain.apply_grain (nodes.py:41-66),
  * _apply_film_grain_tensor (VRGDG_LUTVideoTools.py:262-277) and _apply_seeded_grain
@@ -259,6 +288,17 @@ int64_t vrg_chain_stats_scratch_bytes(int64_t frames, int32_t height, int32_t wi
  * statistics (vrg_lab_stats_torch_f32 reduces `lab_out`). */
 int vrg_chain_stats_lab_f32(const float* in, float* lab_out, int64_t frames, int32_t height, int32_t width,
                             const vrg_chain_desc* desc, double* stats, void* scratch, void* stream);
+/* The same three with the grain stage's noise taken from `split` (vrg_noise_split) instead of desc->noise, which is ignored: desc->stages
+ * must hold VRG_STAGE_GRAIN.  Always the LDS-tile / point-wise kernels and the general statistics pass (the wave-march and
+ * shared-Philox kernels address one chunk with one grid); a colour-match stage in the apply pass is VRG_ERR_UNSUPPORTED -- pass 2 runs
+ * from the Lab image of vrg_chain_stats_lab_split_f32 through vrg_fused_chain_f32, which has no grain stage left.  `scratch` holds
+ * vrg_lab_stats_scratch_bytes(frames) bytes. */
+int vrg_fused_chain_split_f32(const float* in, float* out, int64_t frames, int32_t height, int32_t width,
+                              const vrg_chain_desc* desc, const vrg_noise_split* split, void* stream);
+int vrg_fused_chain_split_u8(const uint8_t* in, uint8_t* out, int64_t frames, int32_t height, int32_t width,
+                             const vrg_chain_desc* desc, const vrg_noise_split* split, void* stream);
+int vrg_chain_stats_lab_split_f32(const float* in, float* lab_out, int64_t frames, int32_t height, int32_t width,
+                                  const vrg_chain_desc* desc, const vrg_noise_split* split, double* stats, void* scratch, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * 13-slider Adjust of the video routes.
