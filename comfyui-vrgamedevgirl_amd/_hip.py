@@ -244,6 +244,15 @@ class AnchorDesc(Record):
                 ("h_ksize", C.c_int32), ("v_ksize", C.c_int32)]
 
 
+class GuidanceDesc(Record):
+    c_name = "vrg_guidance_desc"
+    _fields_ = [("rows", C.c_int64), ("row_len", C.c_int64), ("batch", C.c_int64), ("mode", C.c_int32), ("has_negative", C.c_int32),
+                ("has_perturbed", C.c_int32), ("cfg_star", C.c_int32), ("has_average", C.c_int32), ("has_momentum", C.c_int32),
+                ("has_threshold", C.c_int32), ("has_rescale", C.c_int32), ("want_negative", C.c_int32), ("cfg_m1", C.c_float),
+                ("eta", C.c_float), ("momentum", C.c_float), ("threshold", C.c_float), ("stg_scale", C.c_float), ("rescale", C.c_float),
+                ("one_minus_rescale", C.c_float)]
+
+
 class AreaCell(Record):          # one cell of the tables of vrg_area_taps / vrg_grid_taps / vrg_linear_taps
     c_name, c_header = "vrg::AreaCell", "comfyui-vrgamedevgirl_amd/csrc/vrg_area_math.hpp"
     _fields_ = [("first", C.c_int32), ("count", C.c_int32), ("w_first", C.c_float), ("w_mid", C.c_float), ("w_last", C.c_float)]
@@ -285,6 +294,8 @@ REFBATCH_BICUBIC, REFBATCH_BILINEAR, REFBATCH_AREA, REFBATCH_NEAREST_EXACT, REFB
 ASSEMBLE_MAX_SOURCES = 16       # include/vrgdg_hip.h: VRG_ASSEMBLE_MAX_SOURCES
 ASSEMBLE_BAR = 60               # include/vrgdg_hip.h: VRG_ASSEMBLE_BAR (rows of the label bar)
 ANCHOR_RGB, ANCHOR_BGR = 0, 1      # include/vrgdg_hip.h: VRG_ANCHOR_RGB / VRG_ANCHOR_BGR
+GUIDANCE_SPAN = 4096            # include/vrgdg_hip.h: VRG_GUIDANCE_SPAN (elements of a row one workgroup takes)
+GUIDANCE_CFG, GUIDANCE_APG = 0, 1      # include/vrgdg_hip.h: VRG_GUIDANCE_CFG / VRG_GUIDANCE_APG
 FACEFIX_STATS_WORDS = 12        # uint64 per frame (csrc/vrg_facefix_math.hpp: FF_STATS_WORDS)
 FACEFIX_PACKED_TILE = 256       # include/vrgdg_hip.h: VRG_FF_PACKED_TILE (box pixels of one workgroup)
 PIL_PACKED_TILE = 256           # include/vrgdg_hip.h: VRG_PIL_PACKED_TILE (box pixels of one workgroup of the packed far-face paste)
@@ -426,6 +437,12 @@ _SIGNATURES = {
     "vrg_anchor_check": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
     "vrg_anchor_frames_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, C.c_int32, C.c_int32, _P]),
     "vrg_anchor_store_u8": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
+    "vrg_guidance_check": (C.c_int, [C.POINTER(GuidanceDesc)]),
+    "vrg_guidance_scratch_bytes": (C.c_int64, [C.POINTER(GuidanceDesc)]),
+    "vrg_guidance_sums_f32": (C.c_int, [_P, _P, C.POINTER(GuidanceDesc), _P, C.c_int64, _P]),
+    "vrg_guidance_rows_f32": (C.c_int, [_P, _P, _P, _P, C.POINTER(GuidanceDesc), _P, C.c_int64, _P]),
+    "vrg_guidance_combine_f32": (C.c_int, [_P, _P, _P, _P, _P, _P, C.POINTER(GuidanceDesc), _P, C.c_int64, _P]),
+    "vrg_guidance_rescale_f32": (C.c_int, [_P, C.POINTER(GuidanceDesc), _P, C.c_int64, _P]),
 }
 
 # include/vrgdg_hip_debug.h: self-tests and probes -- for the test suite and the measurement tools, not part of the drop-in boundary

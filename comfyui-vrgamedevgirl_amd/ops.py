@@ -3998,3 +3998,141 @@ def anchor_store_bytes(images: torch.Tensor, bgr: bool = False, out: Optional[to
     _hip.check(_hip.lib().vrg_anchor_store_u8(_hip.ptr(x), _hip.ptr(dst), x.numel() // int(x.shape[3]), int(x.shape[3]),
                                               _hip.ANCHOR_BGR if bgr else _hip.ANCHOR_RGB, _hip.current_stream()), "vrg_anchor_store_u8")
     return dst
+
+
+# ---------------------------------------------------------------------------------------------
+# The guidance combine of the LTX Sigma Advanced guider (_LTXSigmaAdvancedGuider.predict_noise, CustomLTXNodes.py:436-563 of the
+# reference): CFG-star, CFG or APG, STG and the variance rescale between the model evaluations of a sampler step, in at most four
+# streaming launches and their finishers (csrc/vrg_guidance.hip); every sum is fp64 and every derived scalar stays on the device
+# ---------------------------------------------------------------------------------------------
+GUIDANCE_MODES = ("CFG", "APG")
+GUIDANCE_SPAN = _hip.GUIDANCE_SPAN      # elements of a row one workgroup takes
+
+
+@dataclass
+class GuidanceResult:
+    guided: torch.Tensor
+    negative: Optional[torch.Tensor] = None          # the CFG-star negative, where want_negative
+    average: Optional[torch.Tensor] = None           # the new running average, in APG mode with a momentum
+    launches: int = 0                                # kernels the call enqueued, the finishers included
+
+
+def _guidance_operand(t, name: str, like: Optional[torch.Tensor]) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"ltx_guidance: {name} must be a tensor")
+    if t.dtype != torch.float32:
+        raise ValueError(f"ltx_guidance: {name} must be float32, got {str(t.dtype).replace('torch.', '')}")
+    if t.ndim not in (4, 5):
+        raise ValueError(f"ltx_guidance: {name} must have 4 or 5 dimensions, got {t.ndim}")
+    if like is not None and tuple(t.shape) != tuple(like.shape):
+        raise ValueError(f"ltx_guidance: {name} is shaped {list(t.shape)}, positive {list(like.shape)}")
+    if like is not None and t.device != like.device:
+        raise ValueError(f"ltx_guidance: {name} lives on {t.device}, positive on {like.device}")
+    return t.detach()
+
+
+def guidance_desc(shape, *, has_negative: bool, has_perturbed: bool, cfg=1.0, stg_scale=0.0, rescale=0.0, cfg_star=False, mode="CFG", eta=1.0,
+                  norm_threshold=0.0, momentum=0.0, has_average=False, want_negative=False) -> "_hip.GuidanceDesc":
+    """The record of one call, no GPU needed: the layout of ``shape`` (rows of the last three dimensions, batches of shape[0]) and the
+    Python scalars, formed in double and rounded to fp32 once.  Without a negative the star, the mode and ``want_negative`` say nothing;
+    outside APG the threshold, the momentum and the average say nothing.  Checked by vrg_guidance_check."""
+    if mode not in GUIDANCE_MODES:
+        raise ValueError(f"ltx_guidance: mode must be one of {GUIDANCE_MODES}, got {mode!r}")
+    shape = tuple(int(v) for v in shape)
+    rows, row_len = math.prod(shape[:-3]), math.prod(shape[-3:])
+    if rows * row_len < 1:
+        raise ValueError(f"ltx_guidance: positive is empty ({list(shape)})")
+    if float(rescale) != 0.0 and rows * row_len < 2:
+        raise ValueError("ltx_guidance: positive has fewer than two elements, the rescale needs a standard deviation")
+    apg = bool(has_negative) and mode == "APG"
+    threshold = _f32(norm_threshold) if apg else 0.0
+    with_momentum = apg and float(momentum) != 0.0
+    desc = _hip.GuidanceDesc(rows=rows, row_len=row_len, batch=shape[0], mode=_hip.GUIDANCE_APG if mode == "APG" else _hip.GUIDANCE_CFG,
+                             has_negative=int(bool(has_negative)), has_perturbed=int(bool(has_perturbed)),
+                             cfg_star=int(bool(has_negative and cfg_star)), has_average=int(bool(with_momentum and has_average)),
+                             has_momentum=int(with_momentum), has_threshold=int(threshold > 0.0), has_rescale=int(float(rescale) != 0.0),
+                             want_negative=int(bool(has_negative and want_negative)), cfg_m1=_f32(float(cfg) - 1.0), eta=_f32(eta),
+                             momentum=_f32(momentum), threshold=threshold, stg_scale=_f32(stg_scale), rescale=_f32(rescale),
+                             one_minus_rescale=_f32(1.0 - float(rescale)))
+    _refuse(_host_lib().vrg_guidance_check(C.byref(desc)), "ltx_guidance", f"vrg_guidance_check refuses the record of {list(shape)}",
+            f"{list(shape)} is more than the launches take")
+    return desc
+
+
+class GuidancePlan:
+    """One call of ``ltx_guidance``: its record, its scratch buffer (partial sums and derived scalars, device memory) and its launches, every
+    one on the caller's current stream, in the order they are called here.  Nothing waits on the host."""
+
+    def __init__(self, desc: "_hip.GuidanceDesc", device):
+        self.desc = desc
+        self.bytes = int(_host_lib().vrg_guidance_scratch_bytes(C.byref(desc)))
+        self.scratch = torch.empty((self.bytes,), dtype=torch.uint8, device=device)
+        self.launches = 0        # kernels enqueued (the finishers included), for the benchmark tool
+
+    def _tail(self):
+        return C.byref(self.desc), _hip.ptr(self.scratch), self.bytes, _hip.current_stream()
+
+    @staticmethod
+    def _ptr(t):
+        return None if t is None else _hip.ptr(t)
+
+    def run_sums(self, positive, negative):
+        _hip.check(_hip.lib().vrg_guidance_sums_f32(_hip.ptr(positive), _hip.ptr(negative), *self._tail()), "vrg_guidance_sums_f32")
+        self.launches += 2
+
+    def run_rows(self, positive, negative, average, average_out):
+        _hip.check(_hip.lib().vrg_guidance_rows_f32(_hip.ptr(positive), _hip.ptr(negative), self._ptr(average), self._ptr(average_out),
+                                                    *self._tail()), "vrg_guidance_rows_f32")
+        self.launches += 2
+
+    def run_combine(self, positive, negative, perturbed, guidance, guided, negative_out):
+        _hip.check(_hip.lib().vrg_guidance_combine_f32(_hip.ptr(positive), self._ptr(negative), self._ptr(perturbed), self._ptr(guidance),
+                                                       _hip.ptr(guided), self._ptr(negative_out), *self._tail()), "vrg_guidance_combine_f32")
+        self.launches += 2 if self.desc.has_rescale else 1
+
+    def run_rescale(self, guided):
+        _hip.check(_hip.lib().vrg_guidance_rescale_f32(_hip.ptr(guided), *self._tail()), "vrg_guidance_rescale_f32")
+        self.launches += 1
+
+
+@_on_device
+def ltx_guidance(positive: torch.Tensor, negative: Optional[torch.Tensor] = None, perturbed: Optional[torch.Tensor] = None, *, cfg=1.0,
+                 stg_scale=0.0, rescale=0.0, cfg_star=False, mode="CFG", eta=1.0, norm_threshold=0.0, momentum=0.0,
+                 average: Optional[torch.Tensor] = None, want_negative=False) -> GuidanceResult:
+    """What the reference's LTX Sigma Advanced guider computes between its model evaluations, for device-resident fp32 latents of one
+    shape with 4 or 5 dimensions (rows = the last three dimensions, batches = shape[0]):
+
+    ``negative *= sum(p * n) / (sum(n * n) + 1e-8)`` per batch (``cfg_star``); ``p + (cfg - 1.0) * (p - n)`` (mode "CFG") or the APG
+    form -- ``g = p - n``, ``g = momentum * average + g`` (the new average; ``average=None``: g as it is), the per-row norm threshold,
+    the fp64 projection on ``p``, ``p + (cfg - 1.0) * (orth + eta * par)``; without a negative ``p``; ``+ stg_scale * (p - perturbed)``
+    where ``perturbed`` is given; ``* (rescale * std(p) / max(std(guided), 1e-12) + (1.0 - rescale))`` where ``rescale != 0``.
+
+    Returns ``GuidanceResult(guided, negative, average)``: ``guided`` always a fresh tensor, ``negative`` the CFG-star negative where
+    ``want_negative`` (and a negative is given), ``average`` the new running average in APG mode with ``momentum != 0``.  No output shares
+    memory with an input; no input is written (``average`` is read only).  All sums are fp64 and deterministic; the call never waits
+    for the device."""
+    p = _guidance_operand(positive, "positive", None)
+    n = None if negative is None else _guidance_operand(negative, "negative", p)
+    q = None if perturbed is None else _guidance_operand(perturbed, "perturbed", p)
+    a = None if average is None else _guidance_operand(average, "average", p)
+    desc = guidance_desc(p.shape, has_negative=n is not None, has_perturbed=q is not None, cfg=cfg, stg_scale=stg_scale, rescale=rescale,
+                         cfg_star=cfg_star, mode=mode, eta=eta, norm_threshold=norm_threshold, momentum=momentum, has_average=a is not None,
+                         want_negative=want_negative)
+    if not p.is_cuda:
+        raise ValueError(f"ltx_guidance: positive lives on {p.device}; the operator runs on the GPU and has no CPU form")
+    p, n, q = (None if t is None else t.contiguous() for t in (p, n, q))
+    a = a.contiguous() if desc.has_average else None
+    plan = GuidancePlan(desc, p.device)
+    guided = torch.empty_like(p)
+    negative_out = torch.empty_like(p) if desc.want_negative else None
+    average_out = torch.empty_like(p) if desc.has_momentum else None
+    _disjoint("ltx_guidance", [("guided", guided), ("the negative result", negative_out), ("the average result", average_out)],
+              [("positive", p), ("negative", n), ("perturbed", q), ("average", a)])
+    if desc.cfg_star:
+        plan.run_sums(p, n)
+    if desc.has_negative and desc.mode == _hip.GUIDANCE_APG:
+        plan.run_rows(p, n, a, average_out)
+    plan.run_combine(p, n, q, average_out, guided, negative_out)
+    if desc.has_rescale:
+        plan.run_rescale(guided)
+    return GuidanceResult(guided, negative_out, average_out, plan.launches)

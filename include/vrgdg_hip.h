@@ -1284,6 +1284,52 @@ int vrg_anchor_frames_f32(const uint8_t* src, int64_t src_bytes, const vrg_ancho
                           int64_t table_ints, float* out, int32_t out_h, int32_t out_w, void* stream);
 int vrg_anchor_store_u8(const float* in, uint8_t* out, int64_t pixels, int32_t channels, int32_t order, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The guidance combine of the LTX Sigma Advanced guider (_LTXSigmaAdvancedGuider.predict_noise of the reference's CustomLTXNodes.py,
+ * between its model evaluations): CFG-star, CFG or APG, STG and the variance rescale; csrc/vrg_guidance.hip, arithmetic and folds in
+ * csrc/vrg_guidance_math.hpp.  positive / negative / perturbed / average / guided / negative_out / average_out are fp32 tensors of ONE
+ * shape, contiguous, 4-byte aligned: rows * row_len elements, row = the last three dimensions, the rows of one batch entry adjacent
+ * (rows % batch == 0).  One record describes the call; Python scalars arrive rounded to fp32 once.
+ *
+ * The phases are separate launches on `stream`, in this order, each only where the record asks for it:
+ *   vrg_guidance_sums_f32     cfg_star: per batch sum(p * n), sum(n * n) -> alpha
+ *   vrg_guidance_rows_f32     APG with a negative: g = p - n' (+ momentum * average, stored to average_out where has_momentum), per row
+ *                             ||g||^2, ||p||^2, <g, p> -> the row's threshold scale and projection coefficient
+ *   vrg_guidance_combine_f32  guided (and negative_out = the CFG-star negative where want_negative); with has_rescale the moments of
+ *                             positive and guided -> the rescale factor
+ *   vrg_guidance_rescale_f32  has_rescale: guided *= factor, in place
+ * Every sum is fp64: lane, wave, LDS, one partial record per workgroup in `scratch` by vector stores, and a finishing launch that adds the
+ * records in a fixed order -- no atomics, no workgroup waits for another, the same inputs give the same bits.  Derived scalars stay in
+ * `scratch` (device memory, 8-byte aligned, vrg_guidance_scratch_bytes(desc) bytes, the same buffer for every phase of a call); nothing
+ * is read back.  A workgroup takes VRG_GUIDANCE_SPAN elements of one row: 16-byte accesses where every operand of the phase is on the
+ * 16-byte grid at the same element, 4-byte accesses elsewhere.  vrg_guidance_check refuses ON THE HOST what the launches refuse:
+ * VRG_ERR_BAD_ARG for sizes below 1, rows that do not divide into the batches, flags other than 0 / 1 or flags that contradict one
+ * another (a star, an average or want_negative without a negative; momentum / threshold outside APG), a threshold that is not positive,
+ * a rescale of fewer than two elements; VRG_ERR_UNSUPPORTED for more than 2^40 elements or 2^23 workgroups (every phase is one launch).  Outputs must not overlap
+ * inputs or one another (average_out and average included).
+ * ------------------------------------------------------------------------------------------- */
+#define VRG_GUIDANCE_SPAN 4096
+#define VRG_GUIDANCE_CFG 0
+#define VRG_GUIDANCE_APG 1
+
+typedef struct vrg_guidance_desc {
+    int64_t rows, row_len, batch;
+    int32_t mode;                  /* VRG_GUIDANCE_CFG / VRG_GUIDANCE_APG (read only with a negative) */
+    int32_t has_negative, has_perturbed, cfg_star, has_average, has_momentum, has_threshold, has_rescale, want_negative;
+    float cfg_m1;                  /* cfg - 1.0 */
+    float eta, momentum, threshold, stg_scale, rescale, one_minus_rescale;
+} vrg_guidance_desc;
+
+int vrg_guidance_check(const vrg_guidance_desc* desc);
+int64_t vrg_guidance_scratch_bytes(const vrg_guidance_desc* desc);      /* 0 for a record vrg_guidance_check refuses */
+int vrg_guidance_sums_f32(const float* positive, const float* negative, const vrg_guidance_desc* desc, void* scratch, int64_t scratch_bytes,
+                          void* stream);
+int vrg_guidance_rows_f32(const float* positive, const float* negative, const float* average, float* average_out,
+                          const vrg_guidance_desc* desc, void* scratch, int64_t scratch_bytes, void* stream);
+int vrg_guidance_combine_f32(const float* positive, const float* negative, const float* perturbed, const float* guidance, float* guided,
+                             float* negative_out, const vrg_guidance_desc* desc, void* scratch, int64_t scratch_bytes, void* stream);
+int vrg_guidance_rescale_f32(float* guided, const vrg_guidance_desc* desc, void* scratch, int64_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
