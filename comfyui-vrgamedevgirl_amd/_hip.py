@@ -443,6 +443,7 @@ _SIGNATURES = {
     "vrg_guidance_rows_f32": (C.c_int, [_P, _P, _P, _P, C.POINTER(GuidanceDesc), _P, C.c_int64, _P]),
     "vrg_guidance_combine_f32": (C.c_int, [_P, _P, _P, _P, _P, _P, C.POINTER(GuidanceDesc), _P, C.c_int64, _P]),
     "vrg_guidance_rescale_f32": (C.c_int, [_P, C.POINTER(GuidanceDesc), _P, C.c_int64, _P]),
+    "vrg_rgb24_frames_u8": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P]),
 }
 
 # include/vrgdg_hip_debug.h: self-tests and probes -- for the test suite and the measurement tools, not part of the drop-in boundary

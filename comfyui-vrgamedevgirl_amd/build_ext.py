@@ -23,11 +23,11 @@ DEBUG_LIB_PATH = os.path.join(PKG_DIR, "libvrgdg_hip_debug.so")
 STAMP = LIB_PATH + ".stamp"
 
 SOURCES = ("vrg_pointwise.hip", "vrg_stencil.hip", "vrg_chain.hip", "vrg_march.hip", "vrg_produce.hip", "vrg_apply_march.hip", "vrg_adjust.hip",
-           "vrg_collective.hip", "vrg_lut_tetra.hip", "vrg_torch_stats.hip", "vrg_resize.hip", "vrg_prepare.hip", "vrg_composite.hip", "vrg_crop.hip", "vrg_lanczos.hip", "vrg_cut.hip", "vrg_grid.hip", "vrg_thumbs.hip", "vrg_facefix.hip", "vrg_facefix_packed.hip", "vrg_farface.hip", "vrg_farface_packed.hip", "vrg_detect.hip", "vrg_sheet.hip", "vrg_thumb.hip", "vrg_msr.hip", "vrg_flf.hip", "vrg_refbatch.hip", "vrg_assemble.hip", "vrg_anchor.hip", "vrg_guidance.hip", "vrg_api.hip", "vrg_host.hip")
+           "vrg_collective.hip", "vrg_lut_tetra.hip", "vrg_torch_stats.hip", "vrg_resize.hip", "vrg_prepare.hip", "vrg_composite.hip", "vrg_crop.hip", "vrg_lanczos.hip", "vrg_cut.hip", "vrg_grid.hip", "vrg_thumbs.hip", "vrg_facefix.hip", "vrg_facefix_packed.hip", "vrg_farface.hip", "vrg_farface_packed.hip", "vrg_detect.hip", "vrg_sheet.hip", "vrg_thumb.hip", "vrg_msr.hip", "vrg_flf.hip", "vrg_refbatch.hip", "vrg_assemble.hip", "vrg_anchor.hip", "vrg_guidance.hip", "vrg_compare.hip", "vrg_api.hip", "vrg_host.hip")
 DEBUG_SOURCES = ("vrg_probe.hip",)
 HEADERS = ("vrg_common.hpp", "vrg_pixel_math.hpp", "vrg_chain_stages.hpp", "vrg_adjust_math.hpp", "vrg_pow_tables.inc",
            "vrg_ziv_log_table.inc", "vrg_produce_body.hpp", "vrg_apply_body.hpp", "vrg_tstats_body.hpp", "vrg_lanes.hpp", "vrg_tstats_config.hpp",
-           "vrg_resize_math.hpp", "vrg_composite_math.hpp", "vrg_lanczos_math.hpp", "vrg_lanczos_tile.hpp", "vrg_warp_math.hpp", "vrg_area_math.hpp", "vrg_grid_math.hpp", "vrg_area_walk.hpp", "vrg_thumbs_math.hpp", "vrg_facefix_math.hpp", "vrg_facefix_body.hpp", "vrg_facefix_packed_math.hpp", "vrg_detect_math.hpp", "vrg_pil_math.hpp", "vrg_farface_body.hpp", "vrg_pil_resample.hpp", "vrg_byte_mover.hpp", "vrg_grain_block.hpp", "vrg_sheet_math.hpp", "vrg_msr_math.hpp", "vrg_prepare_math.hpp", "vrg_flf_math.hpp", "vrg_refbatch_math.hpp", "vrg_assemble_math.hpp", "vrg_anchor_math.hpp", "vrg_guidance_math.hpp")
+           "vrg_resize_math.hpp", "vrg_composite_math.hpp", "vrg_lanczos_math.hpp", "vrg_lanczos_tile.hpp", "vrg_warp_math.hpp", "vrg_area_math.hpp", "vrg_grid_math.hpp", "vrg_area_walk.hpp", "vrg_thumbs_math.hpp", "vrg_facefix_math.hpp", "vrg_facefix_body.hpp", "vrg_facefix_packed_math.hpp", "vrg_detect_math.hpp", "vrg_pil_math.hpp", "vrg_farface_body.hpp", "vrg_pil_resample.hpp", "vrg_byte_mover.hpp", "vrg_grain_block.hpp", "vrg_sheet_math.hpp", "vrg_msr_math.hpp", "vrg_prepare_math.hpp", "vrg_flf_math.hpp", "vrg_refbatch_math.hpp", "vrg_assemble_math.hpp", "vrg_anchor_math.hpp", "vrg_guidance_math.hpp", "vrg_compare_math.hpp")
 
 # -ffp-contract=off : the reference performs one rounding per op; FMAs are written explicitly where
 #                     torch's own device code has them (Box-Muller).

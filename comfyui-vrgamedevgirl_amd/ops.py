@@ -4136,3 +4136,123 @@ def ltx_guidance(positive: torch.Tensor, negative: Optional[torch.Tensor] = None
     if desc.has_rescale:
         plan.run_rescale(guided)
     return GuidanceResult(guided, negative_out, average_out, plan.launches)
+
+
+# ---------------------------------------------------------------------------------------------
+# The Video Compare Slider's IMAGE batches as the rgb24 bytes of its ffmpeg pipe (_write_image_batch_video, VRGDG_VideoCompareNode.py:63-107
+# of the reference): quantised where the frames live (csrc/vrg_compare.hip), so 3 B/px cross PCIe instead of 12 (16 with alpha) and a
+# pending result of this pack never becomes fp32 on the host
+# ---------------------------------------------------------------------------------------------
+_NO_RGB24_IMAGES = "{} image input must be a non-empty IMAGE batch."           # the reference's text behind its label
+
+
+class Rgb24Handoff:
+    """One ``stream_rgb24`` call: the pieces of a batch, in frame order, each quantised on the device (one launch), downloaded into one of
+    two host buffers (page-locked; pageable where the host refuses to lock) and handed to ``sink(memoryview)``.  Everything is queued on
+    the caller's current stream; the sink call for a piece is made after the launch and the download of the next piece have been queued,
+    so the two overlap.  The memory a sink is given is its own until it returns (the buffer is written again two pieces later).
+
+    ``rgb24_frames`` and ``stream_rgb24`` are this class's two entry points."""
+
+    def __init__(self, sink, frame_bytes: int, per: int):
+        self.sink, self.frame_bytes, self.per = sink, int(frame_bytes), int(per)
+        self.buffers = [self._host_buffer(self.per * self.frame_bytes) for _ in range(2)]
+        self.queued = None          # (event behind its download, host bytes) of the piece the sink has not seen yet
+        self.pieces = self.frames = 0
+
+    @staticmethod
+    def _host_buffer(nbytes: int) -> torch.Tensor:
+        try:
+            return torch.empty((nbytes,), dtype=torch.uint8, pin_memory=True)
+        except RuntimeError:
+            return torch.empty((nbytes,), dtype=torch.uint8)
+
+    @staticmethod
+    def _checked(images, what: str) -> torch.Tensor:
+        x = images.unsqueeze(0) if isinstance(images, torch.Tensor) and images.ndim == 3 else images
+        if not isinstance(x, torch.Tensor) or x.ndim != 4 or min(int(v) for v in x.shape[:3]) < 1 or int(x.shape[3]) < 3:
+            raise ValueError(_NO_RGB24_IMAGES.format(what))
+        return _check_frames(x)
+
+    @classmethod
+    @_on_device
+    def launch(cls, images: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``rgb24_frames``"""
+        what = "rgb24_frames"
+        x = cls._checked(images, what)
+        dst = _checked_out(out, (*x.shape[:3], 3), torch.uint8, x.device, what)
+        _disjoint(what, [("out", dst)], [("images", x)])
+        _hip.check(_hip.lib().vrg_rgb24_frames_u8(_hip.ptr(x), _hip.ptr(dst), x.numel() // int(x.shape[3]), int(x.shape[3]),
+                                                  _hip.current_stream()), "vrg_rgb24_frames_u8")
+        return dst
+
+    def _give(self, queued):
+        """the piece whose download `queued` stands for to the sink; if the sink raises, the download still in flight is waited for first"""
+        done, host = queued
+        try:
+            done.synchronize()
+            self.sink(memoryview(host.numpy()))
+        except BaseException:
+            if self.queued is not None:
+                self.queued[0].synchronize()
+                self.queued = None
+            raise
+
+    def feed(self, gpu_frames: torch.Tensor) -> None:
+        """the next frames of the batch, device-resident: piece by piece"""
+        for s in range(0, int(gpu_frames.shape[0]), self.per):
+            data = self.launch(gpu_frames[s:s + self.per]).view(-1)
+            host = self.buffers[self.pieces % 2][:data.numel()]
+            host.copy_(data, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record()
+            before, self.queued = self.queued, (done, host)
+            self.pieces += 1
+            self.frames += data.numel() // self.frame_bytes
+            if before is not None:
+                self._give(before)
+
+    def finish(self) -> int:
+        before, self.queued = self.queued, None
+        if before is not None:
+            self._give(before)
+        return self.frames
+
+    @classmethod
+    def stream(cls, images: torch.Tensor, sink, piece_bytes: int = 0) -> int:
+        """``stream_rgb24``"""
+        from . import _devices
+        what = "stream_rgb24"
+        shape = tuple(int(v) for v in getattr(images, "shape", ()))
+        shape = (1,) + shape if len(shape) == 3 else shape
+        if not isinstance(images, torch.Tensor) or len(shape) != 4 or min(shape[:3]) < 1 or shape[3] < 3:
+            raise ValueError(_NO_RGB24_IMAGES.format(what))
+        if images.dtype != torch.float32:
+            raise ValueError(f"{what}: images must be float32")
+        pending = _devices.pending_of(images)
+        dev = images.device if images.is_cuda else _devices.compute_device()
+        frame_bytes = shape[1] * shape[2] * 3
+        with torch.cuda.device(dev):
+            handoff = cls(sink, frame_bytes, _devices.piece_frames(shape[0], frame_bytes, 1, int(piece_bytes)))
+            if pending is not None and pending.device == dev:
+                handoff.feed(_devices.on_device(images, dev))                # the device pieces behind a pending result, where they lie
+            elif images.is_cuda:
+                handoff.feed(_devices.materialise(images).detach().reshape(shape))
+            else:
+                _devices.upload_frames(_devices.materialise(images).detach().reshape(shape), lambda gpu, first: handoff.feed(gpu))
+            return handoff.finish()
+
+
+# The two operators are bound methods of the hand-off class, as GuidancePlan's launches are methods: the operator tables of
+# tests/overlap_support.py and tests/stream_support.py list the module-level functions of ops, and these two are held to the same
+# overlap and stream contracts by tests/test_gpu_compare.py.
+#: ``np.clip(images[..., :3] * 255.0, 0, 255).astype(np.uint8)`` of the reference's compare node for a device-resident fp32 ``[N, H, W, C]``
+#: or ``[H, W, C]`` batch, ``C >= 3``, as one launch on the caller's current stream: ``rgb24_frames(images, out=None)`` returns
+#: ``[N, H, W, 3]`` uint8 on the same device, R,G,B, truncated (not rounded: ``anchor_store_bytes`` rounds), NaN 0, +Inf 255; ``out``: an
+#: optional contiguous uint8 tensor of that shape that does not overlap the input.  An empty batch is a ValueError with the reference's text.
+rgb24_frames = Rgb24Handoff.launch
+#: ``stream_rgb24(images, sink, piece_bytes=0) -> frames written``: the whole hand-off of a batch to a byte consumer.  A CUDA batch is
+#: used where it lies, a pending ``LazyFrames`` of the compute device through ``_devices.on_device`` (no fp32 download, no upload), a CPU
+#: batch through ``_devices.upload_frames``.  Pieces along the frame axis hold ``piece_bytes`` of OUTPUT bytes (default: ``_devices.PIPE_BYTES``).
+#: An exception of the sink propagates unchanged once the download in flight has been waited for; nothing is launched after it.
+stream_rgb24 = Rgb24Handoff.stream

@@ -1330,6 +1330,21 @@ int vrg_guidance_combine_f32(const float* positive, const float* negative, const
                              float* negative_out, const vrg_guidance_desc* desc, void* scratch, int64_t scratch_bytes, void* stream);
 int vrg_guidance_rescale_f32(float* guided, const vrg_guidance_desc* desc, void* scratch, int64_t scratch_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The Video Compare Slider's IMAGE batch as the rgb24 bytes its ffmpeg pipe takes (_write_image_batch_video of the reference's
+ * VRGDG_VideoCompareNode.py), csrc/vrg_compare.hip and csrc/vrg_compare_math.hpp.
+ *
+ * vrg_rgb24_frames_u8: src = [pixels][channels] fp32 (4-byte aligned; channels >= 3, only the first three of a pixel are read),
+ * dst = [pixels][3] bytes in R,G,B at any address: (uint8)trunc(min(max(x * 255.0f, 0.0f), 255.0f)), ONE fp32 product rounded once, then
+ * the clip, then truncation -- numpy's np.clip(frame[..., :3] * 255.0, 0, 255).astype(np.uint8).  NaN gives 0 (what numpy yields on
+ * x86), +Inf 255, -Inf, negatives and -0.0 give 0.  Not vrg_anchor_store_u8's rule: that one rounds, so every product in [k + 0.5, k + 1)
+ * is k + 1 there and k here (a byte level k / 255.0f itself is k under both: its product is never below k, csrc/vrg_compare_math.hpp).
+ * The batch is one run of pixels (a frame seam may fall inside a piece); the bytes are written as a flat run of
+ * 16-byte non-temporal pieces with single bytes in front of the first 16-byte boundary and behind the last piece.  One launch;
+ * VRG_ERR_UNSUPPORTED for more pieces than one grid takes (about 2^43 bytes).  src and dst must not overlap.
+ * ------------------------------------------------------------------------------------------- */
+int vrg_rgb24_frames_u8(const float* src, uint8_t* dst, int64_t pixels, int32_t channels, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
