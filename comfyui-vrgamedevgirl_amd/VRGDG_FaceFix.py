@@ -26,13 +26,13 @@ aiohttp routes are out of scope.  The arithmetic is csrc/vrg_facefix_math.hpp; t
 from __future__ import annotations
 
 import ctypes as C
-import threading
 
 import numpy as np
 import torch
 
-from . import _hip, ops
+from . import _hip, _packed, ops
 from ._devices import compute_device
+from ._packed import frame_boxes as _boxes, frames_in as _frames_in, pack_boxes as _pack_boxes, peek as _peek
 
 NODE_CLASS_MAPPINGS = {}
 NODE_DISPLAY_NAME_MAPPINGS = {}
@@ -44,9 +44,9 @@ _BOX_DESC = _hip.record_dtype(_hip.FaceFixBoxDesc)
 _MASK_DESC = _hip.record_dtype(_hip.FaceFixMaskDesc)
 _FF_DESC = _hip.record_dtype(_hip.FaceFixDesc)
 
-_host = _hip.host_library       # the library for its HOST table functions (no GPU needed); far_face_repair imports the name
+_host = _hip.host_library       # the library for its HOST table functions (no GPU needed)
 _lanczos_taps = ops.lanczos4_taps
-_upload = _hip.upload_records   # records and the byte / int32 tables that go with them; far_face_repair imports the name
+_upload = _hip.upload_records   # records and the byte / int32 tables that go with them
 
 
 # ------------------------------------------------------------------------------------------------
@@ -105,71 +105,6 @@ def gauss_coeffs(feather: int) -> np.ndarray:
     coeffs = np.zeros(gauss_taps(feather), dtype=np.float32)
     _hip.check(_host().vrg_ff_gauss_coeffs(feather, C.c_void_p(coeffs.ctypes.data)), "vrg_ff_gauss_coeffs")
     return coeffs
-
-
-# ------------------------------------------------------------------------------------------------
-# frames in, frames out
-# ------------------------------------------------------------------------------------------------
-def _frames_in(frames, name):
-    """-> (uint8 [F,H,W,3] on the GPU, a function that hands a GPU batch back in the caller's form)"""
-    from .VRGDG_LUTVideoTools import _stack_frames, _unstack_frames
-    from .VRGDG_StandaloneVideoEnhancerNodes import DecodedFrames
-    if isinstance(frames, DecodedFrames):
-        return _check(frames.u8, name), DecodedFrames
-    if isinstance(frames, torch.Tensor):
-        x = _check(frames, name)
-        if x.is_cuda:
-            return x, lambda t: t
-        if x.shape[0] == 0:
-            return x.to(compute_device()), lambda t: t.cpu()
-        return _stack_frames(list(x.numpy())), lambda t: torch.from_numpy(np.stack(_unstack_frames(t))) if t.shape[0] else t.cpu()
-    arrays = list(frames)
-    if not arrays:
-        raise ValueError(f"{name} must not be empty")
-    return _stack_frames(arrays), lambda t: _unstack_frames(t) if t.shape[0] else []
-
-
-def _peek(frames, name):
-    """(frames, height, width) of a batch in any of the accepted forms, checked before anything is uploaded"""
-    t = getattr(frames, "u8", frames)
-    if isinstance(t, torch.Tensor):
-        _check(t, name)
-        return int(t.shape[0]), int(t.shape[1]), int(t.shape[2])
-    arrays = [np.asarray(f) for f in frames]
-    if not arrays:
-        raise ValueError(f"{name} must not be empty")
-    for a in arrays:
-        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[-1] != 3 or a.shape != arrays[0].shape:
-            raise ValueError(f"{name} must be HxWx3 uint8 arrays of one size")
-    return len(arrays), int(arrays[0].shape[0]), int(arrays[0].shape[1])
-
-
-def _check(t, name):
-    if t.ndim != 4 or t.shape[-1] != 3 or t.dtype != torch.uint8:
-        raise ValueError(f"{name} must be [frames, height, width, 3] uint8")
-    if t.shape[1] < 1 or t.shape[2] < 1:
-        raise ValueError(f"{name} must be at least 1 x 1")
-    return t if t.is_contiguous() else t.contiguous()
-
-
-def _boxes(crop_boxes, frames, height, width):
-    """one (left, top, w, h) or None per frame; a box without pixels raises the reference's ValueError (:947-948)"""
-    boxes = list(crop_boxes)
-    if len(boxes) != frames:
-        raise ValueError(f"crop_boxes must hold one box (or None) per frame: {len(boxes)} for {frames} frames")
-    out = []
-    for index, box in enumerate(boxes):
-        if box is None:
-            out.append(None)
-            continue
-        left, top, right, bottom = (int(v) for v in box)
-        w, h = right - left, bottom - top
-        if w <= 0 or h <= 0:
-            raise ValueError(f"Invalid crop box for frame {index}.")
-        if left < 0 or top < 0 or right > width or bottom > height:
-            raise ValueError(f"crop box of frame {index} does not lie inside the {width} x {height} frame")
-        out.append((left, top, w, h))
-    return out
 
 
 def _active(boxes, strengths=None):
@@ -343,10 +278,9 @@ class CompositePlan:
 # frames that stay on the host: only the boxes cross the bus (csrc/vrg_facefix_packed.hip)
 # ------------------------------------------------------------------------------------------------
 _PACKED_DESC = _hip.record_dtype(_hip.FaceFixPackedDesc)
-_transfer = threading.local()
 
 
-class PackedPlan:
+class PackedPlan(_packed.BoxPack):
     """Host integers of one packed call, one entry per ACTIVE frame (a box, and strength > 0 where strengths are given), in frame order:
     ``frames`` the frame indices, ``box_index`` each one's position among the frames that have a box, ``boxes`` (left, top, w, h),
     ``strengths`` (clamped; 1.0 without strengths), ``offsets`` the byte offset of the box's dense [h][w][3] block in the packed buffers,
@@ -355,13 +289,8 @@ class PackedPlan:
     frames and the small tables go up besides; a crop brings n * S * S * 3 bytes down).  ``frame_bytes`` = frames * H * W * 3."""
 
     def __init__(self, frames, box_index, boxes, strengths, n_boxes, frame_bytes):
-        self.frames, self.box_index, self.boxes, self.strengths, self.n_boxes, self.frame_bytes = frames, box_index, boxes, strengths, n_boxes, frame_bytes
-        sizes = [w * h * 3 for _, _, w, h in boxes]
-        self.offsets = [int(v) for v in np.cumsum([0] + sizes[:-1])] if sizes else []
-        tile = _hip.FACEFIX_PACKED_TILE
-        self.tile_prefix = np.concatenate([[0], np.cumsum([(w * h + tile - 1) // tile for _, _, w, h in boxes], dtype=np.int64)]).astype(np.int64)
-        self.tiles = int(self.tile_prefix[-1])
-        self.bytes_up = self.bytes_down = int(sum(sizes))
+        super().__init__(frames, boxes, frame_bytes)
+        self.box_index, self.strengths, self.n_boxes = box_index, strengths, n_boxes
 
 
 def packed_plan(frames, height, width, crop_boxes, strengths=None) -> PackedPlan:
@@ -376,38 +305,7 @@ def packed_plan(frames, height, width, crop_boxes, strengths=None) -> PackedPlan
 def last_transfer() -> dict:
     """The bytes the last packed call of this thread moved: ``bytes_up`` / ``bytes_down`` the boxes' pixels (the plan's counts; for a
     crop ``bytes_down`` is n * S * S * 3), ``enhanced_up`` the repaired frames, ``tables_up`` records and tables.  For tests and tools."""
-    return dict(getattr(_transfer, "value", None) or {"bytes_up": 0, "bytes_down": 0, "enhanced_up": 0, "tables_up": 0})
-
-
-def _host_arrays(frames, name, whole):
-    """-> one HxWx3 numpy view per frame of a CPU batch (a uint8 tensor or numpy frames), the caller's own memory"""
-    if hasattr(frames, "u8") or (isinstance(frames, torch.Tensor) and frames.is_cuda):
-        raise TypeError(f"{name} is on the GPU already: the packed route is for decoded frames on the host, use {whole}")
-    _peek(frames, name)
-    return list(frames.numpy()) if isinstance(frames, torch.Tensor) else [np.asarray(f) for f in frames]
-
-
-def _pack_boxes(arrays, plan, stage):
-    """every active box of ``arrays`` as a dense block at its offset of ``stage`` (a uint8 numpy array of at least plan.bytes_up)"""
-    for f, (left, top, w, h), offset in zip(plan.frames, plan.boxes, plan.offsets):
-        stage[offset:offset + w * h * 3].reshape(h, w, 3)[...] = arrays[f][top:top + h, left:left + w]
-
-
-def _paste_boxes(arrays, plan, results):
-    for f, (left, top, w, h), block in zip(plan.frames, plan.boxes, results):
-        arrays[f][top:top + h, left:left + w] = block
-
-
-def _staging(nbytes):
-    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, pin_memory=True)
-
-
-def _download(dev):
-    """a device tensor -> a page-locked host tensor of its shape, complete on return"""
-    host = torch.empty(dev.shape, dtype=dev.dtype, pin_memory=True)
-    host.copy_(dev, non_blocking=True)
-    torch.cuda.current_stream(dev.device).synchronize()
-    return host
+    return _packed.last_transfer("enhanced_up")
 
 
 def crop_frames_packed(frames_u8, crop_boxes, enhance_size):
@@ -417,13 +315,13 @@ def crop_frames_packed(frames_u8, crop_boxes, enhance_size):
     size = int(enhance_size)
     if size < 1:
         raise ValueError("enhance_size must be at least 1")
-    arrays = _host_arrays(frames_u8, "frames", "crop_frames")
+    arrays = _packed.host_arrays(frames_u8, "frames", "crop_frames")
     plan = packed_plan(*_peek(frames_u8, "frames"), crop_boxes)
     n, as_tensor = len(plan.frames), isinstance(frames_u8, torch.Tensor)
     if n == 0:
-        _transfer.value = None
+        _packed.note_transfer("enhanced_up")
         return torch.empty((0, size, size, 3), dtype=torch.uint8) if as_tensor else []
-    stage = _staging(plan.bytes_up)
+    stage = _packed.staging(plan.bytes_up)
     _pack_boxes(arrays, plan, stage.numpy())
     table, offsets = _tap_tables([(b[3], b[2]) for b in plan.boxes], lambda s: s, lambda s: (size, size))
     desc = np.zeros(n, dtype=_PACKED_DESC)
@@ -438,8 +336,8 @@ def crop_frames_packed(frames_u8, crop_boxes, enhance_size):
         out = torch.empty((n, size, size, 3), dtype=torch.uint8, device=device)
         _hip.check(_hip.lib().vrg_lanczos4_packed_u8(_hip.ptr(src), plan.bytes_up, _hip.ptr(dev_desc), n, _hip.ptr(out), size, size,
                                                      _hip.ptr(taps), len(table), _hip.current_stream()), "vrg_lanczos4_packed_u8")
-        host = _download(out)
-    _transfer.value = {"bytes_up": plan.bytes_up, "bytes_down": out.numel(), "enhanced_up": 0, "tables_up": table.nbytes + desc.nbytes}
+        host = _packed.download(out)
+    _packed.note_transfer("enhanced_up", bytes_up=plan.bytes_up, bytes_down=out.numel(), tables_up=table.nbytes + desc.nbytes)
     return host.clone() if as_tensor else list(host.numpy())
 
 
@@ -448,24 +346,25 @@ def composite_boxes_packed(originals_u8, enhanced_u8, crop_boxes, strengths, fea
     frames go up in one page-locked buffer, the composited boxes come down in one -> one ``[h, w, 3]`` array per active frame, in the
     order of ``packed_plan(...).frames`` (views of the download).  Nothing outside a box crosses the bus; no input is written."""
     feather, color_match = _blend_settings(feather, color_match)
-    arrays = _host_arrays(originals_u8, "originals", "composite_frames")
+    arrays = _packed.host_arrays(originals_u8, "originals", "composite_frames")
     F, H, W = _peek(originals_u8, "originals")
     plan = packed_plan(F, H, W, crop_boxes, strengths)
     n = len(plan.frames)
     if n == 0:
-        _transfer.value = None
+        _packed.note_transfer("enhanced_up")
         return []
-    enhanced = _host_arrays(enhanced_u8, "enhanced", "composite_frames")
+    enhanced = _packed.host_arrays(enhanced_u8, "enhanced", "composite_frames")
     EF, EH, EW = _peek(enhanced_u8, "enhanced")
     if EF not in (plan.n_boxes, F):
         raise ValueError(f"enhanced must hold one frame per box ({plan.n_boxes}) or per original frame ({F}), got {EF}")
     picks = plan.box_index if EF == plan.n_boxes else plan.frames
-    enh_bytes, enh_at = EH * EW * 3, -(-plan.bytes_up // 16) * 16
-    stage = _staging(enh_at + n * enh_bytes)
+    enh_bytes = EH * EW * 3
+    starts = _packed.staged_layout(plan.bytes_up, [enh_bytes] * n)
+    stage = _packed.staging(starts[-1])
     staged = stage.numpy()
     _pack_boxes(arrays, plan, staged)
-    for i, pick in enumerate(picks):                                        # the repaired frame of record i is frame i of the upload
-        staged[enh_at + i * enh_bytes:enh_at + (i + 1) * enh_bytes].reshape(EH, EW, 3)[...] = enhanced[pick]
+    for pick, start in zip(picks, starts):                                  # the repaired frame of record i is frame i of the upload
+        staged[start:start + enh_bytes].reshape(EH, EW, 3)[...] = enhanced[pick]
     spans, records, mask_offsets, mask_floats, largest, table, tap_offsets = _composite_tables(plan.boxes, (EH, EW), feather)
     desc = np.zeros(n, dtype=_PACKED_DESC)
     for i, ((_, _, w, h), offset, s) in enumerate(zip(plan.boxes, plan.offsets, plan.strengths)):
@@ -475,10 +374,9 @@ def composite_boxes_packed(originals_u8, enhanced_u8, crop_boxes, strengths, fea
                                            mask_floats, len(table), total, 0, 0), "vrg_ff_packed_check")
     device = compute_device()
     with torch.cuda.device(device):
-        dev = stage[:enh_at + n * enh_bytes].to(device, non_blocking=True)
-        src, enh = C.c_void_p(dev.data_ptr()), C.c_void_p(dev.data_ptr() + enh_at)
-        dev_desc = _upload(desc, device, trailing=(plan.tile_prefix,))
-        prefix = C.c_void_p(dev_desc.data_ptr() + desc.nbytes)
+        dev = stage[:starts[-1]].to(device, non_blocking=True)
+        src, enh = C.c_void_p(dev.data_ptr()), C.c_void_p(dev.data_ptr() + starts[0])
+        dev_desc, prefix = _packed.upload_with_prefix(desc, plan.tile_prefix, device)
         taps = _upload(table, device)
         masks = _run_masks(spans, records, mask_floats, largest, feather, device)
         face = torch.empty(total, dtype=torch.uint8, device=device)
@@ -491,18 +389,10 @@ def composite_boxes_packed(originals_u8, enhanced_u8, crop_boxes, strengths, fea
         _hip.check(lib.vrg_ff_packed_composite_u8(src, total, _hip.ptr(masks), mask_floats, _hip.ptr(dev_desc), prefix, n, plan.tiles,
                                                   _hip.ptr(face), total, _hip.ptr(stats), _hip.ptr(out), total, stream),
                    "vrg_ff_packed_composite_u8")
-        host = _download(out).numpy()
+        host = _packed.download(out).numpy()
     tables = desc.nbytes + plan.tile_prefix.nbytes + table.nbytes + spans.nbytes + records.nbytes + (4 * gauss_taps(feather) if feather > 0 else 0)
-    _transfer.value = {"bytes_up": plan.bytes_up, "bytes_down": plan.bytes_down, "enhanced_up": n * enh_bytes, "tables_up": tables}
-    return [host[offset:offset + w * h * 3].reshape(h, w, 3) for (_, _, w, h), offset in zip(plan.boxes, plan.offsets)]
-
-
-def _host_copy(dst, src):
-    """src -> dst, two numpy arrays of one shape: the threaded copy of vrg_host_copy where both are dense"""
-    if dst.flags.c_contiguous and src.flags.c_contiguous:
-        _hip.check(_host().vrg_host_copy(C.c_void_p(dst.ctypes.data), C.c_void_p(src.ctypes.data), src.nbytes, 0), "vrg_host_copy")
-    else:
-        dst[...] = src
+    _packed.note_transfer("enhanced_up", bytes_up=plan.bytes_up, bytes_down=plan.bytes_down, enhanced_up=n * enh_bytes, tables_up=tables)
+    return plan.blocks(host)
 
 
 def composite_frames_packed(originals_u8, enhanced_u8, crop_boxes, strengths, feather=DEFAULT_FEATHER, color_match=DEFAULT_COLOR_MATCH, *,
@@ -510,22 +400,10 @@ def composite_frames_packed(originals_u8, enhanced_u8, crop_boxes, strengths, fe
     """``composite_frames`` for frames on the host: ``composite_boxes_packed`` pasted into a host copy of ``originals_u8`` (the
     reference's ``original.copy()``; the result has the originals' form), or -- ``inplace=True`` -- into the caller's own frames, which
     are returned.  ``originals_u8`` is never written unless ``inplace=True``."""
-    arrays = _host_arrays(originals_u8, "originals", "composite_frames")
+    _packed.host_arrays(originals_u8, "originals", "composite_frames")       # frames on the GPU are refused before anything else
     plan = packed_plan(*_peek(originals_u8, "originals"), crop_boxes, strengths)
     results = composite_boxes_packed(originals_u8, enhanced_u8, crop_boxes, strengths, feather, color_match)
-    if inplace:
-        out, target = originals_u8, arrays
-    elif isinstance(originals_u8, torch.Tensor):
-        out = torch.empty(originals_u8.shape, dtype=torch.uint8)
-        if out.numel():
-            _host_copy(out.numpy(), originals_u8.numpy())
-        target = list(out.numpy())
-    else:
-        out = target = [np.empty(a.shape, dtype=np.uint8) for a in arrays]
-        for dst, src in zip(target, arrays):
-            _host_copy(dst, src)
-    _paste_boxes(target, plan, results)
-    return out
+    return _packed.paste_into_frames(originals_u8, plan, results, inplace)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -27,7 +27,7 @@ SOURCES = ("vrg_pointwise.hip", "vrg_stencil.hip", "vrg_chain.hip", "vrg_march.h
 DEBUG_SOURCES = ("vrg_probe.hip",)
 HEADERS = ("vrg_common.hpp", "vrg_pixel_math.hpp", "vrg_chain_stages.hpp", "vrg_adjust_math.hpp", "vrg_pow_tables.inc",
            "vrg_ziv_log_table.inc", "vrg_produce_body.hpp", "vrg_apply_body.hpp", "vrg_tstats_body.hpp", "vrg_lanes.hpp", "vrg_tstats_config.hpp",
-           "vrg_resize_math.hpp", "vrg_composite_math.hpp", "vrg_lanczos_math.hpp", "vrg_lanczos_tile.hpp", "vrg_warp_math.hpp", "vrg_area_math.hpp", "vrg_grid_math.hpp", "vrg_area_walk.hpp", "vrg_thumbs_math.hpp", "vrg_facefix_math.hpp", "vrg_facefix_body.hpp", "vrg_facefix_packed_math.hpp", "vrg_detect_math.hpp", "vrg_pil_math.hpp", "vrg_farface_body.hpp", "vrg_pil_resample.hpp", "vrg_byte_mover.hpp", "vrg_grain_block.hpp", "vrg_sheet_math.hpp", "vrg_msr_math.hpp", "vrg_prepare_math.hpp", "vrg_flf_math.hpp", "vrg_refbatch_math.hpp", "vrg_assemble_math.hpp", "vrg_anchor_math.hpp", "vrg_guidance_math.hpp", "vrg_compare_math.hpp")
+           "vrg_resize_math.hpp", "vrg_composite_math.hpp", "vrg_lanczos_math.hpp", "vrg_lanczos_tile.hpp", "vrg_warp_math.hpp", "vrg_area_math.hpp", "vrg_grid_math.hpp", "vrg_area_walk.hpp", "vrg_thumbs_math.hpp", "vrg_facefix_math.hpp", "vrg_facefix_body.hpp", "vrg_facefix_packed_math.hpp", "vrg_packed_tiles.hpp", "vrg_detect_math.hpp", "vrg_pil_math.hpp", "vrg_farface_body.hpp", "vrg_pil_resample.hpp", "vrg_byte_mover.hpp", "vrg_grain_block.hpp", "vrg_sheet_math.hpp", "vrg_msr_math.hpp", "vrg_prepare_math.hpp", "vrg_flf_math.hpp", "vrg_refbatch_math.hpp", "vrg_assemble_math.hpp", "vrg_anchor_math.hpp", "vrg_guidance_math.hpp", "vrg_compare_math.hpp")
 
 # -ffp-contract=off : the reference performs one rounding per op; FMAs are written explicitly where
 #                     torch's own device code has them (Box-Muller).

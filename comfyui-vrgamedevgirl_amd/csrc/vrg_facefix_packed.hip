@@ -1,13 +1,14 @@
 // vrg_facefix_packed.hip -- the Builder's Face Fix (csrc/vrg_facefix.hip) for frames that live on the host: only the boxes cross the bus.
-// gfx950 only.  Where a workgroup works and which records it follows: csrc/vrg_facefix_packed_math.hpp; what it does to a pixel, a byte
-// and its sums is csrc/vrg_facefix_body.hpp, the body of the whole-frame kernels, called with other addresses.
+// gfx950 only.  Where a workgroup works: csrc/vrg_packed_tiles.hpp, the tile map of both packed routes; which records it follows:
+// csrc/vrg_facefix_packed_math.hpp; what it does to a pixel, a byte and its sums is csrc/vrg_facefix_body.hpp, the body of the whole-frame
+// kernels, called with other addresses.
 //
 // Shape of the work.  The host gathers every box into one packed buffer ([box_h][box_w][3] blocks back to back) and uploads it with the
 // records and their tile prefix; the results come back packed the same way.  Each grid is one-dimensional.
 //   k_ffp_lanczos        prepare: thread = one output pixel of one record, lz_pixel on the box's block (row pitch = box_w, so the taps clamp
 //                        to the box by construction).  Every record has out_h * out_w pixels: the workgroup index divides into
 //                        (record, part); no table.
-//   k_ffp_resize_stats   finalize, first half: workgroup = one tile of 256 box pixels, found in the prefix table (ffp_find).  The repaired
+//   k_ffp_resize_stats   finalize, first half: workgroup = one tile of 256 box pixels, found in the prefix table (packed_tile_pixel).  The repaired
 //                        frame resized to the box into the byte scratch; with colour matching the selected count and six byte sums: lane
 //                        values -> wave butterfly -> LDS -> one 64-bit integer atomic per sum and workgroup, as k_ff_resize_stats.
 //                        The means and shifts of every record follow on the device: k_ff_finish of csrc/vrg_facefix.hip (ff_stats_end).
@@ -40,15 +41,12 @@ __global__ __launch_bounds__(256) void k_ffp_resize_stats(const uint8_t* __restr
                                                            const int64_t* __restrict__ prefix, const LzTap* __restrict__ taps,
                                                            uint8_t* __restrict__ bytes, unsigned long long* __restrict__ stats, FfpGeom g,
                                                            int32_t measure) {
-    const int64_t rec = ffp_find(prefix, g.n, (int64_t)blockIdx.x);
-    const vrg_ff_packed_desc d = desc[rec];                               // workgroup-uniform, and so is every return before the sums
-    if (!ffp_blend_ok(d, g, true) || (measure && !ffp_src_ok(d, g))) return;
-    int64_t p0;
-    int32_t count;
-    if (!ffp_place(d, prefix[rec], (int64_t)blockIdx.x, p0, count)) return;
+    int64_t rec, p;
+    vrg_ff_packed_desc d;                                                 // workgroup-uniform, and so is every return before the sums
+    const auto admits = [&](const vrg_ff_packed_desc& r) { return ffp_blend_ok(r, g, true) && (!measure || packed_src_ok(r, g.src_bytes)); };
+    if (!packed_tile_pixel(desc, prefix, g.n, admits, rec, d, p)) return;
     uint32_t acc[FF_STAT_SUMS] = {};
-    if ((int32_t)threadIdx.x < count) {
-        const int64_t p = p0 + threadIdx.x;
+    if (p >= 0) {
         const int32_t dy = (int32_t)(p / d.box_w), dx = (int32_t)(p - (int64_t)dy * d.box_w);
         ff_resize_pixel(enhanced + (int64_t)d.enhanced_index * g.enh_h * g.enh_w * 3, g.enh_h, g.enh_w, taps[d.taps_offset + dx],
                         taps[d.taps_offset + d.box_w + dy], bytes + d.bytes_offset + p * 3, masks + d.mask_offset + p,
@@ -61,15 +59,12 @@ __global__ __launch_bounds__(256) void k_ffp_composite(const uint8_t* __restrict
                                                         const vrg_ff_packed_desc* __restrict__ desc, const int64_t* __restrict__ prefix,
                                                         const uint8_t* __restrict__ bytes, const unsigned long long* __restrict__ stats,
                                                         uint8_t* __restrict__ out, FfpGeom g) {
-    const int64_t rec = ffp_find(prefix, g.n, (int64_t)blockIdx.x);
-    const vrg_ff_packed_desc d = desc[rec];                               // workgroup-uniform
-    if (!ffp_blocks_ok(d, g)) return;                                     // nowhere to read or to write
-    int64_t p0;
-    int32_t count;
-    if (!ffp_place(d, prefix[rec], (int64_t)blockIdx.x, p0, count) || (int32_t)threadIdx.x >= count) return;
-    const int64_t p = p0 + threadIdx.x;
-    const uint8_t* t = src + d.src_offset + p * 3;
-    uint8_t o[3] = {t[0], t[1], t[2]};
+    int64_t rec, p;
+    vrg_ff_packed_desc d;                                                 // workgroup-uniform
+    const auto admits = [&](const vrg_ff_packed_desc& r) { return packed_blocks_ok(r, g.src_bytes, g.out_bytes); };   // else nowhere to read or to write
+    if (!packed_tile_pixel(desc, prefix, g.n, admits, rec, d, p) || p < 0) return;
+    uint8_t o[3];
+    packed_pixel_load(src, d.src_offset, p, o);
     if (ffp_blend_ok(d, g, false)) {
         float shift[3];
         const bool matched = ff_read_record(stats + rec * FF_STATS_WORDS, shift);
@@ -78,28 +73,19 @@ __global__ __launch_bounds__(256) void k_ffp_composite(const uint8_t* __restrict
 #pragma unroll
         for (int c = 0; c < 3; ++c) o[c] = ff_composite_byte(o[c], fb[c], matched, shift[c], alpha, d.strength);
     }
-    uint8_t* dst = out + d.dst_offset + p * 3;
-    dst[0] = o[0]; dst[1] = o[1]; dst[2] = o[2];
+    packed_pixel_store(out, d.dst_offset, p, o);
 }
 
 }  // namespace vrg
 
 using namespace vrg;
 
-namespace {
-
-bool sizes_ok(int64_t n, int64_t src_bytes, int64_t a = 0, int64_t b = 0, int64_t c = 0, int64_t e = 0) {
-    return n >= 0 && src_bytes >= 0 && a >= 0 && b >= 0 && c >= 0 && e >= 0;
-}
-
-}  // namespace
-
 extern "C" {
 
 int vrg_ff_packed_check(const vrg_ff_packed_desc* desc_host, int64_t n, const int64_t* tile_prefix_host, int64_t src_bytes, int64_t out_bytes,
                         int64_t enhanced_frames, int64_t mask_floats, int64_t n_taps, int64_t capacity, int32_t out_h, int32_t out_w) {
     const bool crop = out_h > 0 || out_w > 0;
-    if (!sizes_ok(n, src_bytes, out_bytes, enhanced_frames, mask_floats, n_taps) || capacity < 0 || out_h < 0 || out_w < 0 ||
+    if (!packed_sizes_ok({n, src_bytes, out_bytes, enhanced_frames, mask_floats, n_taps}) || capacity < 0 || out_h < 0 || out_w < 0 ||
         (crop && (out_h < 1 || out_w < 1)))
         return VRG_ERR_BAD_ARG;
     if (n == 0) return VRG_OK;
@@ -107,15 +93,16 @@ int vrg_ff_packed_check(const vrg_ff_packed_desc* desc_host, int64_t n, const in
     const FfpGeom g{n, src_bytes, out_bytes, enhanced_frames, mask_floats, n_taps, capacity, 0, 0};
     for (int64_t i = 0; i < n; ++i) {
         const vrg_ff_packed_desc& d = desc_host[i];
-        if (crop ? !ffp_crop_ok(d, g, out_h, out_w) : !(ffp_blocks_ok(d, g) && ffp_blend_ok(d, g, true))) return VRG_ERR_BAD_ARG;
+        if (crop ? !ffp_crop_ok(d, g, out_h, out_w) : !(packed_blocks_ok(d, src_bytes, out_bytes) && ffp_blend_ok(d, g, true))) return VRG_ERR_BAD_ARG;
     }
-    if (tile_prefix_host && !ffp_prefix_ok(desc_host, n, tile_prefix_host)) return VRG_ERR_BAD_ARG;
+    const auto tiles_of = [&](int64_t i) { return packed_tiles(packed_box_pixels(desc_host[i])); };
+    if (tile_prefix_host && !tile_prefix_ok(n, tile_prefix_host, tiles_of)) return VRG_ERR_BAD_ARG;
     return VRG_OK;
 }
 
 int vrg_lanczos4_packed_u8(const uint8_t* src, int64_t src_bytes, const vrg_ff_packed_desc* desc, int64_t n, uint8_t* out, int32_t out_h,
                            int32_t out_w, const void* taps, int64_t n_taps, void* stream) {
-    if (!src || !out || src == out || !desc || !taps || (reinterpret_cast<uintptr_t>(taps) & 3u) != 0 || !sizes_ok(n, src_bytes, n_taps) ||
+    if (!src || !out || src == out || !desc || !taps || (reinterpret_cast<uintptr_t>(taps) & 3u) != 0 || !packed_sizes_ok({n, src_bytes, n_taps}) ||
         out_h < 1 || out_w < 1)
         return VRG_ERR_BAD_ARG;
     if (n == 0) return VRG_OK;
@@ -133,7 +120,7 @@ int vrg_ff_packed_resize_stats_u8(const uint8_t* src, int64_t src_bytes, const u
                                   int32_t enh_w, const float* masks, int64_t mask_floats, const vrg_ff_packed_desc* desc,
                                   const int64_t* tile_prefix, int64_t n, int64_t tiles, const void* taps, int64_t n_taps, uint8_t* bytes,
                                   int64_t capacity, void* stats, float color_match, void* stream) {
-    if (!sizes_ok(n, src_bytes, enhanced_frames, mask_floats, n_taps, capacity) || tiles < 0) return VRG_ERR_BAD_ARG;
+    if (!packed_sizes_ok({n, src_bytes, enhanced_frames, mask_floats, n_taps, capacity}) || tiles < 0) return VRG_ERR_BAD_ARG;
     if (n == 0) return VRG_OK;
     if (!src || !enhanced || !masks || !desc || !tile_prefix || (reinterpret_cast<uintptr_t>(tile_prefix) & 7u) != 0 || !taps ||
         (reinterpret_cast<uintptr_t>(taps) & 3u) != 0 || !bytes || !stats || (reinterpret_cast<uintptr_t>(stats) & 7u) != 0 || bytes == src ||
@@ -154,7 +141,7 @@ int vrg_ff_packed_resize_stats_u8(const uint8_t* src, int64_t src_bytes, const u
 int vrg_ff_packed_composite_u8(const uint8_t* src, int64_t src_bytes, const float* masks, int64_t mask_floats, const vrg_ff_packed_desc* desc,
                                const int64_t* tile_prefix, int64_t n, int64_t tiles, const uint8_t* bytes, int64_t capacity, const void* stats,
                                uint8_t* out, int64_t out_bytes, void* stream) {
-    if (!sizes_ok(n, src_bytes, mask_floats, capacity, out_bytes) || tiles < 0) return VRG_ERR_BAD_ARG;
+    if (!packed_sizes_ok({n, src_bytes, mask_floats, capacity, out_bytes}) || tiles < 0) return VRG_ERR_BAD_ARG;
     if (n == 0) return VRG_OK;
     if (!src || !masks || !desc || !tile_prefix || (reinterpret_cast<uintptr_t>(tile_prefix) & 7u) != 0 || !bytes || !stats ||
         (reinterpret_cast<uintptr_t>(stats) & 7u) != 0 || !out || out == src || out == bytes)

@@ -9,13 +9,12 @@
 // np_means_block strings them together with LDS and barriers on the device; tests/host_math/farface_packed_check.cpp runs the same three
 // with a loop for the lanes.
 //
-// The packed route (frames that stay on the host, only the boxes cross the bus): a workgroup of the paste is one TILE of PILP_TILE
-// consecutive box pixels, found in the prefix table the host uploads behind the records (ffp_find of csrc/vrg_facefix_packed_math.hpp,
-// the same table rule).  A kernel never trusts the table: the tile is checked against the record's own tile count (pilp_place) and every
-// span against the stated sizes (pilp_*_ok).  vrg_pil_packed_check applies the same rules on the host.
+// The packed route (frames that stay on the host, only the boxes cross the bus): where a workgroup of the paste works -- tiles, the prefix
+// table, the spans of a box's blocks -- is csrc/vrg_packed_tiles.hpp, shared with the Builder's route; here is the check only this route's
+// records have (pilp_blend_ok).  vrg_pil_packed_check applies the same rules on the host.
 #pragma once
 #include "vrg_common.hpp"
-#include "vrg_facefix_packed_math.hpp"
+#include "vrg_packed_tiles.hpp"
 #include "vrg_pil_math.hpp"
 
 namespace vrg {
@@ -101,58 +100,16 @@ VRG_HD uint8_t pil_face_byte(uint8_t original, uint8_t face, bool matched, float
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// the packed route: records, tiles
+// the packed route: what its records need besides the blocks
 // ---------------------------------------------------------------------------------------------------------------------------------
-constexpr int PILP_TILE = VRG_PIL_PACKED_TILE;
-static_assert(PILP_TILE == 256, "one tile = one workgroup of 256 threads, one pixel each");
-
 struct PilpGeom {
     int64_t n, src_bytes, rep_bytes, mask_bytes, out_bytes;
 };
 
-// pixels of a box; 0: no box (a side below 1, or 2^31 bytes and more)
-VRG_HD int64_t pilp_pixels(const vrg_pil_packed_desc& d) {
-    if (d.box_w < 1 || d.box_h < 1) return 0;
-    const int64_t px = (int64_t)d.box_w * d.box_h;
-    return px > FFP_MAX_BOX_BYTES / 3 ? 0 : px;
-}
-
-VRG_HD int64_t pilp_tiles(const vrg_pil_packed_desc& d) { return (pilp_pixels(d) + PILP_TILE - 1) / PILP_TILE; }
-
-// (record, tile) -> the pixels [p0, p0 + count) of the record's box; false: the tile is not one of this record's
-VRG_HD bool pilp_place(const vrg_pil_packed_desc& d, int64_t first_tile, int64_t tile, int64_t& p0, int32_t& count) {
-    const int64_t rel = tile - first_tile, px = pilp_pixels(d);
-    if (rel < 0 || rel >= pilp_tiles(d)) return false;
-    p0 = rel * PILP_TILE;
-    count = (int32_t)(px - p0 < PILP_TILE ? px - p0 : PILP_TILE);
-    return true;
-}
-
-// the box's original bytes lie inside `src`
-VRG_HD bool pilp_src_ok(const vrg_pil_packed_desc& d, const PilpGeom& g) {
-    const int64_t px = pilp_pixels(d);
-    return px > 0 && span_fits(d.src_offset, px * 3, g.src_bytes);
-}
-
-// what the paste needs to write anything at all: where the bytes come from and where they go
-VRG_HD bool pilp_blocks_ok(const vrg_pil_packed_desc& d, const PilpGeom& g) {
-    return pilp_src_ok(d, g) && span_fits(d.dst_offset, pilp_pixels(d) * 3, g.out_bytes);
-}
-
-// ... and to paste (and the means to measure): the resized crop and the mask
+// what the paste needs, beyond its blocks, to paste (and the means to measure): the resized crop and the mask
 VRG_HD bool pilp_blend_ok(const vrg_pil_packed_desc& d, const PilpGeom& g) {
-    const int64_t px = pilp_pixels(d);
+    const int64_t px = packed_box_pixels(d);
     return px > 0 && span_fits(d.mask_offset, px, g.mask_bytes) && span_fits(d.rep_offset, px * 3, g.rep_bytes);
-}
-
-// prefix[0 .. n] is the running sum of the records' tile counts
-inline bool pilp_prefix_ok(const vrg_pil_packed_desc* desc, int64_t n, const int64_t* prefix) {
-    int64_t want = 0;                                                     // at most n * 2^23
-    for (int64_t i = 0; i < n; ++i) {
-        if (prefix[i] != want) return false;
-        want += pilp_tiles(desc[i]);
-    }
-    return prefix[n] == want;
 }
 
 #if defined(__HIPCC__) || defined(__HIP__)

@@ -18,17 +18,6 @@ namespace vrg {
 
 typedef float rb_f4 __attribute__((ext_vector_type(4)));
 
-// the record tile `tile` belongs to: the last one whose first_tile is <= tile (records without tiles share a first_tile with their successor)
-__device__ inline int64_t rb_find(const vrg_refbatch_desc* __restrict__ desc, int64_t n, int32_t tile) {
-    int64_t lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi + 1) >> 1;
-        if (desc[mid].first_tile <= tile) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
 // (frame, first element) of this lane in record d; false: nothing to do
 __device__ inline bool rb_place(const vrg_refbatch_desc& d, int32_t tile, int64_t& frame, uint32_t& e, uint32_t& valid) {
     const int64_t rel = (int64_t)tile - d.first_tile;

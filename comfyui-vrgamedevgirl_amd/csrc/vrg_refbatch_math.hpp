@@ -28,6 +28,7 @@
 // tests/test_refbatch_host.py holds this header, compiled for the host, to torch itself run live.
 #pragma once
 #include "vrg_common.hpp"
+#include "vrg_packed_tiles.hpp"
 #include "vrg_resize_math.hpp"
 
 #include <algorithm>
@@ -67,6 +68,11 @@ VRG_HD uint8_t rb_quantise(float x) {
 VRG_HD int64_t rb_src_frame(const vrg_refbatch_desc& d) { return (int64_t)d.src_h * d.src_w * d.src_c; }
 VRG_HD int64_t rb_dst_frame(const vrg_refbatch_desc& d) { return (int64_t)d.dst_h * d.dst_w * d.dst_c; }
 VRG_HD int64_t rb_tiles(const vrg_refbatch_desc& d) { return (int64_t)d.frames * ((rb_dst_frame(d) + RB_TILE - 1) / RB_TILE); }
+
+// the record tile `tile` belongs to: the last one whose first_tile is <= tile -- tile_owner of csrc/vrg_packed_tiles.hpp over the records
+VRG_HD int64_t rb_find(const vrg_refbatch_desc* desc, int64_t n, int32_t tile) {
+    return tile_owner(n, tile, [&](int64_t i) { return desc[i].first_tile; });
+}
 
 // The rules of one record, which the launch and the kernel apply as well: VRG_OK, VRG_ERR_BAD_ARG or VRG_ERR_UNSUPPORTED
 VRG_HD int rb_desc_status(const vrg_refbatch_desc& d) {

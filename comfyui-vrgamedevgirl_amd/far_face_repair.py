@@ -28,16 +28,14 @@ from __future__ import annotations
 import ctypes as C
 import functools
 import math
-import threading
 from collections import namedtuple
 
 import numpy as np
 import torch
 
-from . import _hip, ops
+from . import _hip, _packed, ops
 from ._devices import compute_device
-from .VRGDG_FaceFix import (_boxes, _download, _frames_in, _host, _host_arrays, _host_copy, _pack_boxes, _paste_boxes, _peek, _staging,
-                            _upload)
+from ._packed import frame_boxes as _boxes, frames_in as _frames_in, peek as _peek
 
 NODE_CLASS_MAPPINGS = {}
 NODE_DISPLAY_NAME_MAPPINGS = {}
@@ -53,7 +51,8 @@ _MASK_DESC = _hip.record_dtype(_hip.PilMaskDesc)
 _BOX_DESC = _hip.record_dtype(_hip.PilBoxDesc)
 _THUMB_ENTRY = _hip.record_dtype(_hip.ThumbEntry)
 _PACKED_DESC = _hip.record_dtype(_hip.PilPackedDesc)
-_transfer = threading.local()
+_host = _hip.host_library       # the library for its HOST table functions (no GPU needed)
+_upload = _hip.upload_records   # records and the byte / int32 tables that go with them
 
 SHEET_CANVAS = (24, 24, 24)
 NO_FRAMES = "No frames were available for the contact sheet."
@@ -476,20 +475,7 @@ def masked_means(original, repaired, mask) -> dict:
 # ------------------------------------------------------------------------------------------------
 # frames that stay on the host: only the boxes cross the bus (csrc/vrg_farface_packed.hip)
 # ------------------------------------------------------------------------------------------------
-class PackedPlan:
-    """Host integers of one packed call, one entry per frame that has a box, in frame order: ``frames`` the frame indices, ``boxes``
-    (left, top, w, h), ``offsets`` the byte offset of the box's dense [h][w][3] block in the packed buffers, ``tile_prefix`` int64 [n + 1]:
-    0 and the running sum of ceil(w * h / 256), ``tiles`` its last entry.  ``bytes_up`` = ``bytes_down`` = the bytes of all boxes: what the
-    composite moves each way for the originals (the repaired crops and the small tables go up besides).  ``frame_bytes`` = frames * H * W * 3."""
-
-    def __init__(self, frames, boxes, frame_bytes):
-        self.frames, self.boxes, self.frame_bytes = frames, boxes, frame_bytes
-        sizes = [w * h * 3 for _, _, w, h in boxes]
-        self.offsets = [int(v) for v in np.cumsum([0] + sizes[:-1])] if sizes else []
-        tile = _hip.PIL_PACKED_TILE
-        self.tile_prefix = np.concatenate([[0], np.cumsum([(w * h + tile - 1) // tile for _, _, w, h in boxes], dtype=np.int64)]).astype(np.int64)
-        self.tiles = int(self.tile_prefix[-1])
-        self.bytes_up = self.bytes_down = int(sum(sizes))
+PackedPlan = _packed.BoxPack        # one entry per frame that has a box; the repaired crops and the small tables go up besides
 
 
 def packed_plan(frames, height, width, crop_boxes) -> PackedPlan:
@@ -504,7 +490,7 @@ def packed_plan(frames, height, width, crop_boxes) -> PackedPlan:
 def last_transfer() -> dict:
     """The bytes the last packed call of this thread moved: ``bytes_up`` / ``bytes_down`` the boxes' pixels (the plan's counts),
     ``repaired_up`` the repaired crops (and the saved masks), ``tables_up`` records and tables.  For tests and tools."""
-    return dict(getattr(_transfer, "value", None) or {"bytes_up": 0, "bytes_down": 0, "repaired_up": 0, "tables_up": 0})
+    return _packed.last_transfer("repaired_up")
 
 
 class PackedCompositePlan(CompositePlan):
@@ -522,8 +508,7 @@ class PackedCompositePlan(CompositePlan):
             desc[k] = (offset, offset, w, h, int(self.color_match), 0, mask_offsets[k], self.resize.offsets[k])
         _host_check(_host().vrg_pil_packed_check(C.c_void_p(desc.ctypes.data), len(desc), C.c_void_p(plan.tile_prefix.ctypes.data), total,
                                                  self.resize.dst_bytes, self.mask_bytes, total), "vrg_pil_packed_check")
-        self.desc = _upload(desc, device, trailing=(plan.tile_prefix,))
-        self.prefix = C.c_void_p(self.desc.data_ptr() + desc.nbytes)
+        self.desc, self.prefix = _packed.upload_with_prefix(desc, plan.tile_prefix, device)
         self.stats = torch.zeros(len(desc) * _hip.PIL_STATS_WORDS, dtype=torch.int32, device=device)
         self.out = torch.empty(total, dtype=torch.uint8, device=device)
         self.rep = self.masks = None
@@ -564,23 +549,21 @@ def composite_boxes_packed(originals_u8, repaired, crop_boxes, feather=DEFAULT_F
     buffer, the composited boxes come down in one -> one ``[h, w, 3]`` array per frame with a box, in the order of
     ``packed_plan(...).frames`` (views of the download).  ``repaired`` / ``masks`` as ``composite_frames`` takes them.  Nothing outside a
     box crosses the bus; no input is written.  Frames or crops on the GPU raise TypeError: ``composite_frames`` keeps them there."""
-    arrays = _host_arrays(originals_u8, "originals", "composite_frames")
+    arrays = _packed.host_arrays(originals_u8, "originals", "composite_frames")
     for values, name in ((repaired, "repaired"), (masks, "masks")):
         if values is not None and _on_gpu(values):
             raise TypeError(f"{name} is on the GPU already: the packed route is for decoded frames on the host, use composite_frames")
     feather, _, rep, mk = _prepare(originals_u8, repaired, crop_boxes, feather, masks)
     plan = packed_plan(*_peek(originals_u8, "originals"), crop_boxes)
     if not plan.frames:
-        _transfer.value = None
+        _packed.note_transfer("repaired_up")
         return []
     rep, mk = _host_images(rep), (_host_images(mk) if mk is not None else None)
-    sizes = [r.size for r in rep] + [m.size for m in mk or []]
-    rep_at = -(-plan.bytes_up // 16) * 16
-    starts = [int(v) for v in rep_at + np.cumsum([0] + sizes)]
-    mask_at = starts[len(rep)]
-    stage = _staging(starts[-1])
+    starts = _packed.staged_layout(plan.bytes_up, [r.size for r in rep] + [m.size for m in mk or []])
+    rep_at, mask_at = starts[0], starts[len(rep)]
+    stage = _packed.staging(starts[-1])
     staged = stage.numpy()
-    _pack_boxes(arrays, plan, staged)
+    _packed.pack_boxes(arrays, plan, staged)
     for image, start in zip(rep + (mk or []), starts):
         staged[start:start + image.size] = image.reshape(-1)
     device = compute_device()
@@ -591,31 +574,20 @@ def composite_boxes_packed(originals_u8, repaired, crop_boxes, feather=DEFAULT_F
         work.run_resize()
         work.run_masks()
         work.run_means()
-        host = _download(work.run_paste()).numpy()
-    _transfer.value = {"bytes_up": plan.bytes_up, "bytes_down": plan.bytes_down, "repaired_up": starts[-1] - rep_at, "tables_up": work.tables_up()}
-    return [host[offset:offset + w * h * 3].reshape(h, w, 3) for (_, _, w, h), offset in zip(plan.boxes, plan.offsets)]
+        host = _packed.download(work.run_paste()).numpy()
+    _packed.note_transfer("repaired_up", bytes_up=plan.bytes_up, bytes_down=plan.bytes_down, repaired_up=starts[-1] - rep_at,
+                          tables_up=work.tables_up())
+    return plan.blocks(host)
 
 
 def composite_frames_packed(originals_u8, repaired, crop_boxes, feather=DEFAULT_FEATHER, color_match=False, masks=None, *, inplace=False):
     """``composite_frames`` for frames on the host: ``composite_boxes_packed`` pasted into a host copy of ``originals_u8`` (the
     reference's ``original.copy()``; the result has the originals' form), or -- ``inplace=True`` -- into the caller's own frames, which
     are returned.  ``originals_u8`` is never written unless ``inplace=True``."""
-    arrays = _host_arrays(originals_u8, "originals", "composite_frames")
+    _packed.host_arrays(originals_u8, "originals", "composite_frames")       # frames on the GPU are refused before anything else
     plan = packed_plan(*_peek(originals_u8, "originals"), crop_boxes)
     results = composite_boxes_packed(originals_u8, repaired, crop_boxes, feather, color_match, masks)
-    if inplace:
-        out, target = originals_u8, arrays
-    elif isinstance(originals_u8, torch.Tensor):
-        out = torch.empty(originals_u8.shape, dtype=torch.uint8)
-        if out.numel():
-            _host_copy(out.numpy(), originals_u8.numpy())
-        target = list(out.numpy())
-    else:
-        out = target = [np.empty(a.shape, dtype=np.uint8) for a in arrays]
-        for dst, src in zip(target, arrays):
-            _host_copy(dst, src)
-    _paste_boxes(target, plan, results)
-    return out
+    return _packed.paste_into_frames(originals_u8, plan, results, inplace)
 
 
 # ------------------------------------------------------------------------------------------------

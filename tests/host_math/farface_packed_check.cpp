@@ -35,13 +35,6 @@ static void means_block(const Orig& orig, const uint8_t* rep, const uint8_t* mas
     np_finish(count, acc, strength, rec);
 }
 
-static vrg_pil_packed_desc box(int32_t box_w, int32_t box_h) {
-    vrg_pil_packed_desc d = {};
-    d.box_w = box_w;
-    d.box_h = box_h;
-    return d;
-}
-
 extern "C" {
 
 // a dense block: original, repaired [n][3]; mask [n]; stats: PIL_STATS_WORDS uint32
@@ -63,13 +56,14 @@ void hm_pilp_paste(const uint8_t* original, const uint8_t* repaired, const uint8
         for (int c = 0; c < 3; ++c) out[p * 3 + c] = pil_face_byte(original[p * 3 + c], repaired[p * 3 + c], matched, shift[c], mask[p]);
 }
 
-int64_t hm_pilp_tiles(int32_t box_w, int32_t box_h) { return pilp_tiles(box(box_w, box_h)); }
+// the tile map of csrc/vrg_packed_tiles.hpp, as k_pil_packed_paste calls it
+int64_t hm_pilp_tiles(int32_t box_w, int32_t box_h) { return packed_tiles(packed_box_pixels(box_w, box_h)); }
 
 // out: p0, count; -> 1 when `tile` is one of the record's
 int32_t hm_pilp_place(int32_t box_w, int32_t box_h, int64_t first_tile, int64_t tile, int64_t* out) {
     int64_t p0 = -1;
     int32_t count = -1;
-    const bool ok = pilp_place(box(box_w, box_h), first_tile, tile, p0, count);
+    const bool ok = tile_place(packed_box_pixels(box_w, box_h), first_tile, tile, p0, count);
     out[0] = p0;
     out[1] = count;
     return ok ? 1 : 0;

@@ -35,4 +35,7 @@ int hm_refbatch_quantise(const float* src_f32, int64_t src_floats, const vrg_ref
     return VRG_OK;
 }
 
+// the search of the kernels of csrc/vrg_refbatch.hip, as they call it: over the records' first_tile
+int64_t hm_rb_find(const vrg_refbatch_desc* desc, int64_t n, int32_t tile) { return rb_find(desc, n, tile); }
+
 }  // extern "C"

@@ -511,7 +511,7 @@ HOST_SYNCING = {
     "anchor_frames": "ops.py anchor_frames: table = _hip.upload_records(desc, dev, trailing=(tables,))",
     "facefix_builder_crop": "VRGDG_FaceFix.py crop_frames: taps, dev_desc = _upload(table, x.device), _upload(desc, x.device)",
     "facefix_builder_composite": "VRGDG_FaceFix.py CompositePlan.__init__: self.taps, self.desc = _upload(...); _run_masks: _upload(spans, device)",
-    "facefix_builder_packed": "VRGDG_FaceFix.py crop_frames_packed / composite_boxes_packed: _upload(...) and _download(out), which waits for the stream",
+    "facefix_builder_packed": "VRGDG_FaceFix.py crop_frames_packed / composite_boxes_packed: _upload(...), _packed.py upload_with_prefix(...) and download(out), which waits for the stream",
     "far_face_resize": "far_face_repair.py ResizePlan.__init__: self.tables = _upload(...), self.desc = _upload(desc, device)",
     "far_face_composite": "far_face_repair.py CompositePlan / ResizePlan / MaskPlan: _upload(...) of their records",
     "contact_sheet": "far_face_repair.py ThumbPlan.__init__: _upload(...) of the entries and tables",

@@ -93,8 +93,11 @@ def _table(counts):
     return np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
 
 
-@pytest.mark.parametrize("counts", ([1], [47], [1, 1, 1], [3, 1, 47, 2], [0, 0, 3, 1], [2, 0, 0, 5, 0, 1], [4, 2, 0, 0], [0, 5, 0], [0, 0, 1, 0, 0],
-                                    [1] * 700, [1, 2] * 350))
+# tile counts per record; tests/test_refbatch_host.py runs the same lists through the records' first_tile
+SEARCH_COUNTS = ([1], [47], [1, 1, 1], [3, 1, 47, 2], [0, 0, 3, 1], [2, 0, 0, 5, 0, 1], [4, 2, 0, 0], [0, 5, 0], [0, 0, 1, 0, 0], [1] * 700, [1, 2] * 350)
+
+
+@pytest.mark.parametrize("counts", SEARCH_COUNTS)
 def test_search_finds_first_and_last_tile_of_every_record(hm, counts):
     """tile counts of 0 repeat a prefix value: in front, in the middle, at the end of the table"""
     prefix, n = _table(counts), len(counts)

@@ -179,6 +179,29 @@ def test_sweep_composites(ff, sweep, feather, cm):
     assert np.array_equal(whole.numpy(), want)
 
 
+# ---- the tile map's seams in one call ------------------------------------------------------------------------------------------------------
+#: boxes at which the shared tile map (csrc/vrg_packed_tiles.hpp) can go wrong, one per frame of 32 x 300: a single pixel, 255 pixels (one
+#: short of a tile), 256 (exactly one), 257 x 1 (a tile plus one pixel), and a frame without a box -- five frames, since a frame has one box
+SEAM_H, SEAM_W = 32, 300
+SEAM_BOXES = [(7, 5, 8, 6), (20, 3, 35, 20), None, (100, 10, 116, 26), (30, 31, 287, 32)]
+
+
+@pytest.mark.parametrize("cm", (0.0, 0.65))
+def test_tile_seams_equal_the_whole_frame_route(ff, cm):
+    plan = ff.packed_plan(len(SEAM_BOXES), SEAM_H, SEAM_W, SEAM_BOXES, [1.0] * len(SEAM_BOXES))
+    assert [w * h for _, _, w, h in plan.boxes] == [1, 255, 256, 257] and list(plan.tile_prefix) == [0, 1, 2, 3, 5] and plan.frames == [0, 1, 3, 4]
+    originals = FS.make_frames("random", (len(SEAM_BOXES), SEAM_H, SEAM_W, 3), 6400)
+    enhanced = FS.make_frames("random", (4, 9, 7, 3), 6401)
+    got = ff.composite_frames_packed(torch.from_numpy(originals), torch.from_numpy(enhanced), SEAM_BOXES, [1.0] * len(SEAM_BOXES), 1, cm)
+    whole = ff.composite_frames(torch.from_numpy(originals).cuda(), torch.from_numpy(enhanced).cuda(), SEAM_BOXES, [1.0] * len(SEAM_BOXES), 1, cm)
+    assert np.array_equal(got.numpy(), whole.cpu().numpy())
+    assert np.array_equal(got[2].numpy(), originals[2]) and not np.array_equal(got.numpy(), originals)
+    for f, (left, top, w, h) in zip(plan.frames, plan.boxes):                # nothing outside a box was written
+        outside = np.ones((SEAM_H, SEAM_W), dtype=bool)
+        outside[top:top + h, left:left + w] = False
+        assert np.array_equal(got[f].numpy()[outside], originals[f][outside]), f
+
+
 def test_seven_hundred_small_boxes(ff):
     """700 frames of 6 x 6 with boxes of 2 x 2 and 3 x 3 in turn: one tile each, so the search runs over 700 equal steps"""
     n = 700

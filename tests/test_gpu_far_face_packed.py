@@ -170,6 +170,30 @@ def test_geometry_sweep(ffr, feather, cm):
         assert not np.array_equal(want[13], plain[13]) and np.array_equal(want[12], plain[12])
 
 
+# ---- the tile map's seams in one call ------------------------------------------------------------------------------------------------------
+#: boxes at which the shared tile map (csrc/vrg_packed_tiles.hpp) can go wrong, one per frame of 32 x 300: a single pixel, 255 pixels (one
+#: short of a tile), 256 (exactly one), 257 x 1 (a tile plus one pixel), and a frame without a box -- five frames, since a frame has one box.
+#: This route admits all four sizes.
+SEAM_H, SEAM_W = 32, 300
+SEAM_BOXES = [(7, 5, 8, 6), (20, 3, 35, 20), None, (100, 10, 116, 26), (30, 31, 287, 32)]
+
+
+@pytest.mark.parametrize("cm", (False, True), ids=("plain", "match"))
+def test_tile_seams_equal_the_whole_frame_route(ffr, cm):
+    plan = ffr.packed_plan(len(SEAM_BOXES), SEAM_H, SEAM_W, SEAM_BOXES)
+    assert [w * h for _, _, w, h in plan.boxes] == [1, 255, 256, 257] and list(plan.tile_prefix) == [0, 1, 2, 3, 5] and plan.frames == [0, 1, 3, 4]
+    originals = np.stack([S.random_image(9700 + f, SEAM_H, SEAM_W) for f in range(len(SEAM_BOXES))])
+    repaired = [S.random_image(9710 + k, h + 2, w + 3, 3, 0, 200) for k, (_, _, w, h) in enumerate(plan.boxes)]
+    got = ffr.composite_frames_packed(torch.from_numpy(originals), repaired, SEAM_BOXES, 1, cm)
+    whole = ffr.composite_frames(torch.from_numpy(originals).cuda(), repaired, SEAM_BOXES, 1, cm)
+    assert np.array_equal(got.numpy(), whole.cpu().numpy())
+    assert np.array_equal(got[2].numpy(), originals[2]) and not np.array_equal(got.numpy(), originals)
+    for f, (left, top, w, h) in zip(plan.frames, plan.boxes):                # nothing outside a box was written
+        outside = np.ones((SEAM_H, SEAM_W), dtype=bool)
+        outside[top:top + h, left:left + w] = False
+        assert np.array_equal(got[f].numpy()[outside], originals[f][outside]), f
+
+
 # ---- the means: 15 / 16 selected pixels, sums beyond 2^24 ------------------------------------------------------------------------------------
 def test_the_selection_boundary_on_saved_masks(ffr):
     frames, repaired, masks, boxes = [], [], [], []

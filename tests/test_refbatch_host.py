@@ -15,6 +15,7 @@ import torch
 
 import refbatch_support as S
 from conftest import PKG_NAME, ROOT
+from test_facefix_packed_host import SEARCH_COUNTS
 
 NEW_SYMBOLS = ("vrg_refbatch_check", "vrg_refbatch_f32", "vrg_refbatch_quantise_u8")
 
@@ -250,6 +251,26 @@ def test_abi_and_check_refusals(ops):
     assert lib.vrg_refbatch_f32(one, 8, null, 0, two, 1, 2 ** 31, three, 8, null) == 2
     assert lib.vrg_refbatch_quantise_u8(null, 0, null, 0, 0, null, 0, null) == 0
     assert lib.vrg_refbatch_quantise_u8(null, 8, two, 1, 1, three, 8, null) == 1 and lib.vrg_refbatch_quantise_u8(one, 8, two, 1, 1, null, 8, null) == 1
+
+
+@pytest.mark.parametrize("counts", SEARCH_COUNTS)
+def test_search_finds_first_and_last_tile_of_every_record(ops, host, counts):
+    """rb_find as the kernels of csrc/vrg_refbatch.hip call it -- tile_owner of csrc/vrg_packed_tiles.hpp through the first_tile of the
+    records -- on the tile-count lists of the packed routes' search: counts of 0 repeat a first_tile in front, in the middle, at the end"""
+    host.hm_rb_find.argtypes, host.hm_rb_find.restype = [C.c_void_p, C.c_int64, C.c_int32], C.c_int64
+    n, first = len(counts), np.concatenate([[0], np.cumsum(counts)])
+    desc = np.zeros(n, dtype=ops.REFBATCH_DESC)
+    desc["first_tile"] = first[:-1]
+
+    def find(tile):
+        return host.hm_rb_find(desc.ctypes.data, n, tile)
+
+    for rec, count in enumerate(counts):
+        if count:
+            assert find(int(first[rec])) == rec == find(int(first[rec]) + count - 1), (counts[:8], rec)
+    for tile in range(min(int(first[-1]), 64)):                              # every tile has the owner a linear walk finds
+        assert find(tile) == max(i for i in range(n) if first[i] <= tile and counts[i] > 0)
+    assert 0 <= find(int(first[-1]) + 5) < n                                 # a tile past the grid still names a record of the table
 
 
 def test_surfaces_paths_and_errors_equal_the_fixture(node, pkg):
